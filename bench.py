@@ -8,13 +8,23 @@ the rendered pixels (20 B/ray) so that every rank ends the step with all N
 views.  Weak scaling: N GPUs render N views.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement), extended with
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds per timed step, ...), extended with
   roofline      the distance-trunk kernel (78 % of the step) against the fp32 MFMA
                 peak, timed live with HIP events on its stream
+A plain run sets up, warms up, times --steps steps and prints that line.  With
+--full it then also measures and checks, outside the timed region:
+  psnr_vs_oracle_db, parity_sample   the HIP pixels against the CPU oracle (asserted)
+  value_incl_rng                     rays/s with the uniforms drawn inside the step
+  alt_operand_policy                 the same workload under split-fp16 operands
   cpu_baseline  the CPU oracle (oracle/, a C port of the reference) on the host
                 cores, on a bounded sample of the same workload (rank 0, N=1)
+--dump-outputs DIR writes what the last timed step returned (rendered colour,
+depth, transmittance per ray; for --workload train the loss and the updated
+parameters) as DIR/<name>.npy.  The inputs are seeded: equal arguments, equal inputs.
 """
 import argparse
 import json
@@ -246,6 +256,9 @@ def train_workload(args, dev, world=1, rank=0, use_dist=False):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:     # what the step leaves its caller: the loss and the parameters after the optimiser step
+        dump_outputs(args.dump_outputs, dict({"loss": loss.reshape(1)},
+                                             **{"param." + k: v for k, v in render.network_fine.named_parameters()}))
     pts = rays * (65 + 194) * world
     # forward GEMMs (Jacobian rows everywhere, as the reference trains) + dX + dW: 3 x 2 x 4 x 644 096 MACs per point, minus the
     # input gradients of the first layers of both trunks, which are never needed
@@ -395,12 +408,41 @@ def psnr_vs_oracle(render, ctx, cam, weights, R, T, calib, U, n_sample=256, lo=0
     return (10 * math.log10(1.0 / mse) if mse > 0 else float("inf")), worst, n_sample, margin
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000        # 64 MB in all, read strictly
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` ({name: tensor}) as path/<name>.npy in float32 (float64 stays float64).  Past 64 MB in all, every
+    array with the shared leading dimension keeps the same fixed, seeded sample of rows, and sample_rows.npy records which."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        n = max(v.shape[0] for v in arrays.values() if v.ndim)
+        per_row = 8 + sum(v.nbytes // n for v in arrays.values() if v.ndim and v.shape[0] == n)     # 8: the row's entry in sample_rows
+        fixed = sum(v.nbytes for v in arrays.values() if not (v.ndim and v.shape[0] == n))
+        keep = (DUMP_BUDGET_BYTES - fixed - 4096) // per_row
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: v[rows] if v.ndim and v.shape[0] == n else v for k, v in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: the parity sample "
+                         "against the CPU oracle (psnr_vs_oracle_db, asserted), the RNG-inclusive rates, the split-fp16 operand "
+                         "policy, the CPU baseline and (NEDDF_BENCH_PMC=1) the in-run PMC passes.  Off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32; "
+                         "a fixed row sample when the arrays exceed 64 MB in all)")
     ap.add_argument("--workload", choices=["c2", "c3", "c5", "train"], default="c2",
                     help="c2 = BASELINE configs[1] (headline, default; with --gpus N > 1 it is configs[3]: N views, rays sharded one "
                          "view per GPU, RCCL pixel gather); c3 = configs[2], 65 coarse + 129 importance samples; "
@@ -595,6 +637,13 @@ def main():
         assert full.shape[0] == n_total and torch.isfinite(full).all(), "gathered frame incomplete"
         off = slab_lo if strong else rank * n_rays
         assert torch.equal(full[off:off + n_local], state["last_packed"]), "the gathered frame does not hold this rank's pixels at its slab"
+    if args.dump_outputs and rank == 0:
+        if use_dist:        # what every rank ends the step with: the whole gathered frame, [n_total] rays
+            from neddf_amd.parallel import unpack_pixels
+            full = unpack_pixels(res.out if hasattr(res, "out") else res, keys)
+            dump_outputs(args.dump_outputs, {k: v.reshape(v.shape[0]) if v.shape[1] == 1 else v for k, v in full.items()})
+        else:
+            dump_outputs(args.dump_outputs, {k: res[k] for k in keys})
 
     if rank == 0:
         pts = n_local * samples_per_ray * args.steps              # field evaluations on this rank
@@ -686,7 +735,7 @@ def main():
                 line["roofline"]["traffic_breakdown"] = {k: (v * scale if k not in ("l2_hit_rate",) else v) for k, v in bd.items()}
             # NEDDF_BENCH_PMC=1: measured in this run (two extra passes over a one-slab probe, outside the timed region, ~1 min, while this
             # process keeps its context); default: the committed, calibrated table above
-            if os.environ.get("NEDDF_BENCH_PMC", "") == "1" and world == 1:
+            if args.full and os.environ.get("NEDDF_BENCH_PMC", "") == "1" and world == 1:
                 try:
                     m = measured_traffic(want, args.dtype, masked)
                     # the probe's launches must be of this run's size (one 65 536-ray slab = one launch at the default cap): per-point traffic
@@ -724,7 +773,8 @@ def main():
                                            "frac": ent["hbm_bytes_per_launch"] / (ms * 1e-3) / 8e12}
         except Exception:
             pass
-        if args.workload == "c2":
+        # --full: the parity sample against the oracle, the RNG-inclusive rates, the other operand policy, the CPU baseline
+        if args.full and args.workload == "c2":
             psnr, worst, ns, margin = psnr_vs_oracle(render, ctx, cam, weights, R, T, calib, U, lo=slab_lo)
             line["psnr_vs_oracle_db"] = psnr
             line["parity_sample"] = {"rays": ns, "max_abs_err": worst, "gate_margin": margin,
@@ -738,10 +788,10 @@ def main():
                 assert max(margin.values()) <= 1.0 and psnr > 120.0, "parity sample outside the 1e-4 + 1e-5 gate: %s, PSNR %.1f dB" % (margin, psnr)
             else:
                 assert psnr > 60.0, "bf16 parity sample: PSNR %.1f dB" % psnr
-        if world == 1 and args.workload == "c2":
+        if args.full and world == 1 and args.workload == "c2":
             # SURVEY 8d counts RNG generation/upload into rays/s; `value` keeps its inputs resident, these two add the draw
             line["value_incl_rng"] = rng_inclusive(render, cam, n_rays, dev)
-        if world == 1 and args.workload == "c2" and args.dtype == "f32":
+        if args.full and world == 1 and args.workload == "c2" and args.dtype == "f32":
             # supplementary: the same workload under the split-fp16 operand policy (fp32 data, fp32-level errors);
             # `value` above stays the exact fp32 MFMA path
             render.network_fine.weight_dtype = "f16_split"
@@ -755,7 +805,7 @@ def main():
                                           "value": n_rays * 2 / (time.perf_counter() - t1), "unit": "rays/s", "steps": 2,
                                           "parity": "same 1e-4 gates as the fp32 path (tests/test_gpu_c5.py)"}
             render.network_fine.weight_dtype = "fp32"
-        if world == 1 and not args.no_cpu_baseline and args.workload != "c5":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload != "c5":
             line["cpu_baseline"] = cpu_baseline(weights, render.bench_network_config, R, T, calib.astype(np.float32))
     if use_dist:
         torch.distributed.barrier()

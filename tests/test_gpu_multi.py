@@ -210,7 +210,7 @@ def test_bench_self_launch_two_ranks_shared_gpu():
     if torch.cuda.device_count() < 2:
         env["NEDDF_BENCH_SHARE_GPU"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = _bench_json(p.stdout)
     assert len(lines) == 1, p.stdout[-3000:]
@@ -409,7 +409,7 @@ def _bench_line(extra_args, extra_env):
     env.update(extra_env)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + extra_args,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"] + extra_args,
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     return _bench_json(p.stdout)[-1]
@@ -446,6 +446,39 @@ def test_bench_preflight_fails_fast_and_readably():
                        capture_output=True, text=True, timeout=300)
     assert p.returncode != 0 and "HIP device" in p.stderr and "--gpus %d" % n in p.stderr, p.stderr[-2000:]
     assert time.time() - t0 < 60.0      # (the first `import torch` of a fresh box is most of this)
+
+
+def test_bench_plain_run_dumps_what_it_timed(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps, prints the headline line without the --full extras, and --dump-outputs
+    writes the last step's frame: the same numbers this process renders from the same seeded inputs."""
+    import math
+    import bench
+    import neddf_amd
+    env = dict(os.environ, NEDDF_BENCH_PMC="0")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "NEDDF_BENCH_FORCE_DIST", "NEDDF_BENCH_SHARE_GPU"):
+        env.pop(k, None)
+    out = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs",
+                        str(out)], env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    line = _bench_json(p.stdout)[-1]
+    assert line["steps"] == 2 and line["unit"] == "rays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert abs(line["value"] * line["ms_per_step"] / 1e3 / 640000 - 1.0) < 1e-6, line
+    assert not {"psnr_vs_oracle_db", "value_incl_rng", "alt_operand_policy", "cpu_baseline"} & set(line), sorted(line)
+    got = {k: np.load(str(out / (k + ".npy"))) for k in ("color", "depth", "transmittance")}
+    assert sorted(os.listdir(str(out))) == ["color.npy", "depth.npy", "transmittance.npy"]
+    assert got["color"].shape == (640000, 3) and got["depth"].shape == got["transmittance"].shape == (640000,)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+    dev = torch.device("cuda:0")
+    render, _ = bench.build_render(dev)
+    fx = 0.5 * 800 / math.tan(0.5 * bench.CAMERA_ANGLE_X)
+    R, T = bench.view_pose(0)
+    cam = neddf_amd.Camera(neddf_amd.PinholeCalib(np.array([fx, fx, 400.0, 400.0])), None).to(dev)
+    cam.R, cam.T = torch.from_numpy(R).to(dev), torch.from_numpy(T).to(dev)
+    U = torch.rand(640000, 128, device=dev, generator=torch.Generator(device=dev).manual_seed(1234))
+    want = render.render_image_single_pass(800, 800, cam, 128, U=U)
+    for k, v in got.items():
+        assert np.array_equal(v, want[k].cpu().numpy()), (k, float(np.abs(v - want[k].cpu().numpy()).max()))
 
 
 _GUARD_WORKER = r"""

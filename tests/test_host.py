@@ -843,3 +843,26 @@ def test_documented_environment_switches_exist():
     assert len(lib_switches) <= 12, sorted(lib_switches)
     undocumented = sorted(u for u in used if u not in doc and u not in internal)
     assert not undocumented, "read by the library but missing from INTEGRATION.md: %s" % undocumented
+
+
+def test_bench_dump_outputs_stays_within_its_budget(tmp_path):
+    """bench.py --dump-outputs: float32 files; past the 64 MB budget every array of the shared leading dimension keeps the same
+    seeded sample of rows (recorded in sample_rows.npy), so two runs dump the same rows."""
+    import bench
+    g = torch.Generator().manual_seed(3)
+    n = 4 * 1000 * 1000
+    big = {"color": torch.rand(n, 3, generator=g), "depth": torch.rand(n, generator=g, dtype=torch.float64), "scale": torch.ones(2)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == ["color.npy", "depth.npy", "sample_rows.npy", "scale.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= bench.DUMP_BUDGET_BYTES
+    a = {f: np.load(str(tmp_path / "a" / f)) for f in files}
+    assert all(np.array_equal(a[f], np.load(str(tmp_path / "b" / f))) for f in files)
+    rows = a["sample_rows.npy"].astype(np.int64)
+    assert a["color.npy"].dtype == np.float32 and a["depth.npy"].dtype == np.float64 and len(np.unique(rows)) == rows.size > n // 2
+    assert np.array_equal(a["color.npy"], big["color"].numpy()[rows]) and np.array_equal(a["depth.npy"], big["depth"].numpy()[rows])
+    assert np.array_equal(a["scale.npy"], np.ones(2, np.float32))
+    small = {"color": torch.rand(10, 3, generator=g).to(torch.float16)}
+    bench.dump_outputs(str(tmp_path / "c"), small)
+    assert os.listdir(str(tmp_path / "c")) == ["color.npy"] and np.load(str(tmp_path / "c" / "color.npy")).dtype == np.float32

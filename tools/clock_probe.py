@@ -60,7 +60,7 @@ windows = {}
 for dt in ("f32", "f16_split", "bf16"):
     env = dict(os.environ, NEDDF_BENCH_PMC="0")
     t0 = time.time()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dtype", dt, "--steps", steps, "--warmup", "2", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dtype", dt, "--steps", steps, "--warmup", "2", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True)
     t1 = time.time()
     line = json.loads(p.stdout.strip().splitlines()[-1]) if p.returncode == 0 else {"error": p.stderr[-500:]}

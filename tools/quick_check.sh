@@ -2,7 +2,7 @@
 # (A/B of library variants: NEDDF_LIB_PATH=<variant .so> in front of the bench command, both runs in the SAME call -- boxes differ by +-2.5 %)
 O=gpurun_out/quick; mkdir -p $O
 run() { # name, args
-  python bench.py $2 --steps 3 --warmup 1 --no-cpu-baseline > $O/$1.json 2>$O/$1.err
+  python bench.py $2 --steps 3 --warmup 1 --no-cpu-baseline --full > $O/$1.json 2>$O/$1.err
   python - <<PY
 import json
 try:

@@ -9,7 +9,7 @@ export TMPDIR=/tmp PYTHONUNBUFFERED=1 NEDDF_BENCH_PMC=0 NEDDF_BENCH_PROBE=${NEDD
 for rep in 1 2; do
 for v in "$@"; do
   if [ "$v" = main ]; then unset NEDDF_LIB_PATH; else export NEDDF_LIB_PATH=$ROOT/neddf_amd/csrc/libneddf_hip_v_$v.so; fi
-  python bench.py --dtype $DTYPE --steps 4 --warmup 1 --no-cpu-baseline > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err || tail -5 $O/bench_${v}_$rep.err
+  python bench.py --dtype $DTYPE --steps 4 --warmup 1 --no-cpu-baseline --full > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err || tail -5 $O/bench_${v}_$rep.err
 done
 done
 unset NEDDF_LIB_PATH

@@ -4,20 +4,20 @@ ROOT=$PWD
 O=$ROOT/gpurun_out/${1:-r6prof}
 mkdir -p $O
 export TMPDIR=/tmp PYTHONUNBUFFERED=1
-NEDDF_BENCH_PMC=1 python bench.py --steps 8 --warmup 2 > $O/bench_c2_f32.json 2> $O/bench_c2_f32.err
+NEDDF_BENCH_PMC=1 python bench.py --steps 8 --warmup 2 --full > $O/bench_c2_f32.json 2> $O/bench_c2_f32.err
 export NEDDF_BENCH_PMC=0
 python bench.py --workload c3 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c3_f32.json 2>/dev/null
 python bench.py --workload c5 --steps 3 --warmup 1 > $O/bench_c5_bf16.json 2>/dev/null
-python bench.py --dtype f16_split --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_c2_f16_split.json 2>/dev/null
-NEDDF_BENCH_PMC=1 python bench.py --dtype bf16 --steps 4 --warmup 1 --no-cpu-baseline > $O/bench_c2_bf16.json 2>/dev/null
+python bench.py --dtype f16_split --steps 3 --warmup 1 --no-cpu-baseline --full > $O/bench_c2_f16_split.json 2>/dev/null
+NEDDF_BENCH_PMC=1 python bench.py --dtype bf16 --steps 4 --warmup 1 --no-cpu-baseline --full > $O/bench_c2_bf16.json 2>/dev/null
 python bench.py --workload train --steps 8 --warmup 3 > $O/bench_train_f32.json 2>/dev/null
 python bench.py --workload train --dtype f16_split --steps 8 --warmup 3 > $O/bench_train_f16_split.json 2>/dev/null
-NEDDF_BENCH_FORCE_DIST=1 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_c2_forced_collective.json 2>/dev/null
-NEDDF_BENCH_FORCE_DIST=1 python bench.py --scaling strong --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_c2_forced_collective_strong.json 2>/dev/null
+NEDDF_BENCH_FORCE_DIST=1 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --full > $O/bench_c2_forced_collective.json 2>/dev/null
+NEDDF_BENCH_FORCE_DIST=1 python bench.py --scaling strong --steps 3 --warmup 1 --no-cpu-baseline --full > $O/bench_c2_forced_collective_strong.json 2>/dev/null
 python tools/parity_report.py > $O/parity_report.json 2>/dev/null
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o b -- python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/prof_bench.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof16 -o b -- python $ROOT/bench.py --dtype bf16 --steps 3 --warmup 1 --no-cpu-baseline > $O/prof_bench_bf16.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o b -- python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --full > $O/prof_bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof16 -o b -- python $ROOT/bench.py --dtype bf16 --steps 3 --warmup 1 --no-cpu-baseline --full > $O/prof_bench_bf16.log 2>&1
 for dt in fp32 bf16; do
   export NEDDF_PROBE_DTYPE=$dt
   for c in FETCH_SIZE WRITE_SIZE; do

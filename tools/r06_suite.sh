@@ -9,4 +9,4 @@ tail -4 $O/pytest_gpu.txt
 NEDDF_GUARD=1 python -m pytest tests -m gpu -x -q > $O/pytest_gpu_guard.txt 2>&1
 tail -4 $O/pytest_gpu_guard.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -2 $O/smoke.txt
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.json
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.json
