@@ -41,6 +41,11 @@ struct Field {
     DdfArgs ddf{};
     ColArgs col{};
     NerfArgs nerf{};
+    // NeDDF in fp32: the same network with three-term bf16 products (operands 3), taken by the eval-minimal route's reverse-mode
+    // distance kernel and colour kernel (NEDDF_F32_PRODUCTS, neddf_capi.hip)
+    bool has3 = false;
+    DdfArgs ddf3{};
+    ColArgs col3{};
 };
 
 struct EventPair {

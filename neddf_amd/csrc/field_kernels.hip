@@ -1480,6 +1480,7 @@ static void launch_ddf_rev_w(const DdfArgs &a, int grid, hipStream_t s)
     constexpr int MT = WID <= 256 ? 2 : 1;
     if (a.operands == 2) launch_ddf_rev_t<MT, OpsF16SplitT<WID>>(a, grid, s);
     else if (a.operands == 1) launch_ddf_rev_t<MT, NEDDF_BF16_REV_OPS<WID>>(a, grid, s);
+    else if (a.operands == 3) launch_ddf_rev_t<MT, OpsF32x3T<WID>>(a, grid, s);      // fp32 data, three-term bf16 products
     else launch_ddf_rev_t<MT, OpsF32T<WID>>(a, grid, s);
 }
 
@@ -1499,7 +1500,8 @@ static void launch_col_w(const ColArgs &a, int grid, bool rows4, hipStream_t s)
     else if (a.operands == 1) {
         if constexpr (WID == 256) launch_col_g<2, 3, 4, OpsBF16>(a, grid, rows4, s);
         else launch_col_g<MT, 2, 4, OpsBF16T<WID>>(a, grid, rows4, s);
-    } else launch_col_g<MT, 2, 4, OpsF32T<WID>>(a, grid, rows4, s);
+    } else if (a.operands == 3) launch_col_g<MT, 2, 4, OpsF32x3T<WID>>(a, grid, rows4, s);
+    else launch_col_g<MT, 2, 4, OpsF32T<WID>>(a, grid, rows4, s);
 }
 
 void launch_col(const ColArgs &a, int grid, bool rows4, hipStream_t s)

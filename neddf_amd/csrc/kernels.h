@@ -76,7 +76,8 @@ struct DdfArgs {
     const float *w_ddf_out, *w_aux_out;   // [width] each
     float b_ddf_out, b_aux_out;
     float d_near, aux_grad_scale;
-    int operands;                         // 0 fp32 (32x32x2 f32 MFMA), 1 bf16, 2 split fp16 (three fp16 products per multiply-add), see tile_engine.h
+    int operands;                         // 0 fp32 (32x32x2 f32 MFMA), 1 bf16, 2 split fp16 (three fp16 products per multiply-add), 3 fp32 with
+                                          // three-term bf16 products (OpsF32x3T: reverse-mode distance + colour kernels only), see tile_engine.h
     int neus;                             // 1: NeuS sdf trunk (neus.py:118-145): plain PE, no heads, sdf = feature 0
     float neus_v10;                       // variance * 10
     float *scratch;                       // per-workgroup stash area

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -76,12 +77,35 @@ static inline float f16_value(uint16_t h)
     return (h & 0x8000) ? -v : v;
 }
 
+static inline float bf16_value(uint16_t b)
+{
+    const uint32_t u = (uint32_t)b << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+// w = hi + mid + lo in bf16 (tile_engine.h OpsF32x3T): each term the bf16 rounding of what the previous ones left.  Exact for every
+// finite fp32 w that bf16 does not round up to infinity -- checked here for every packed weight, not assumed
+static inline bool bf16x3_split(float w, uint16_t t[3])
+{
+    t[0] = bf16_bits(w);
+    const float r1 = w - bf16_value(t[0]);
+    t[1] = bf16_bits(r1);
+    const float r2 = r1 - bf16_value(t[1]);
+    t[2] = bf16_bits(r2);
+    return bf16_value(t[2]) == r2 && (double)bf16_value(t[0]) + (double)bf16_value(t[1]) + (double)bf16_value(t[2]) == (double)w;
+}
+
 // fragment-major packing, see kernels.h LayerW.  kmap (engine column -> reference weight row, -1 = zero) is padded to
 // a whole number of super-steps: 8 k-values for fp32 fragments (4 floats per lane half), 16 for bf16 (8 per lane half).
-static size_t pack_layer(std::vector<float> &blob, const Src &src, std::vector<int> kmap, int nout, int operands, int *ksteps_out)
+// (split_exact: cleared when a weight does not split exactly under operands 3)
+static size_t pack_layer(std::vector<float> &blob, const Src &src, std::vector<int> kmap, int nout, int operands, int *ksteps_out,
+                         bool *split_exact = nullptr)
 {
     // operands == 2 (split fp16): two fp16 planes of 2^10 w (h toward zero, m = remainder to nearest), 32 bytes per lane and super-step
-    const int step = operands ? 16 : 8, half = step / 2, tiles = nout / 32, planes = operands == 2 ? 2 : 1;     // nout: multiple of 32
+    // operands == 3 (fp32 as three bf16 terms): planes hi, mid, lo of the 32x32x16 fragment, 48 bytes per lane and super-step
+    const int step = operands ? 16 : 8, half = step / 2, tiles = nout / 32, planes = operands == 2 ? 2 : (operands == 3 ? 3 : 1);     // nout: multiple of 32
     while (kmap.size() % step) kmap.push_back(-1);
     const int ks = (int)kmap.size() / step;
     if (ksteps_out) *ksteps_out = ks;
@@ -98,7 +122,11 @@ static size_t pack_layer(std::vector<float> &blob, const Src &src, std::vector<i
                         int k = kmap[step * S + half * (lane >> 5) + r];
                         float v = (k < 0 || n >= src.cols) ? 0.f : src.at(k, n);
                         size_t frag = (((size_t)tile * ks + S) * 64 + lane);
-                        if (operands == 2) {
+                        if (operands == 3) {
+                            uint16_t t[3];
+                            if (!bf16x3_split(v, t) && split_exact) *split_exact = false;
+                            for (int pl = 0; pl < 3; ++pl) dst16[(frag * 3 + pl) * half + r] = t[pl];
+                        } else if (operands == 2) {
                             const float sv = v * 1024.0f;
                             uint16_t h = f16_bits(sv, true);
                             dst16[(frag * 2 + 0) * half + r] = h;
@@ -146,6 +174,21 @@ static void enc_map(std::vector<int> &m, int rank, int K, int base)
 
 
 
+// How fp32 NeDDF fields take their products on the eval-minimal route (reverse-mode distance kernel + colour kernel), read once:
+//   NEDDF_F32_PRODUCTS=split3 (default)  three-term bf16 splits on v_mfma_f32_32x32x16_bf16 (tile_engine.h OpsF32x3T): fp32-accurate
+//   NEDDF_F32_PRODUCTS=mfma              v_mfma_f32_32x32x2_f32, the exact-fp32 route of earlier versions, bit for bit
+// The forward-mode kernels (full outputs, NEDDF_DDF_REVERSE=0), NeRF, NeuS and the training kernels take the fp32 MFMA either way.
+static bool f32_products_split3()
+{
+    static const bool v = [] {
+        const char *e = getenv("NEDDF_F32_PRODUCTS");
+        if (e && *e && strcmp(e, "mfma") != 0 && strcmp(e, "split3") != 0)
+            fprintf(stderr, "neddf: NEDDF_F32_PRODUCTS=%s is neither 'split3' nor 'mfma'; taking split3\n", e);
+        return !e || strcmp(e, "mfma") != 0;
+    }();
+    return v;
+}
+
 static int build_neddf(neddf_ctx *ctx, Field &f, const float *const *W, const float *const *B, int n_tensors)
 {
     const neddf_field_desc &d = f.d;
@@ -161,99 +204,113 @@ static int build_neddf(neddf_ctx *ctx, Field &f, const float *const *W, const fl
     for (int i = 0; i < d.n_skips; ++i)
         if (d.skips[i] < 0 || d.skips[i] >= n_trunk - 1)
             return fail(ctx, NEDDF_EUNSUPPORTED, "NeDDF: skip index must address a trunk layer followed by another (the reference itself fails otherwise)");
+    // the argument blocks of one operand policy, their weights appended to `blob`; `resolve` sets their pointers once the blob is on the device
     std::vector<float> blob;
-    DdfArgs &a = f.ddf;
-    ColArgs &c = f.col;
-    a = DdfArgs{}; c = ColArgs{};
-    std::vector<size_t> o_wp(n_trunk), o_b(n_trunk), o_st;
-    std::vector<int> pe;
-    enc_map(pe, E, KH, 0);
-    a.n_layers = n_trunk; a.n_stash = 0;
-    for (int l = 0; l < n_trunk; ++l) {
-        bool wide = l > 0 && in_skips(d, l - 1);
-        int cin = l == 0 ? Cpe : (wide ? Wd + Cpe : Wd);
-        Src src{ W[l], cin, Wd, false };
-        std::vector<int> km;
-        a.layer[l].stash = -1;
-        if (l == 0) km = pe;
-        else km = hidden_map(Wd, WP, wide ? Cpe : 0);
-        o_wp[l] = pack_layer(blob, src, km, WP, operands, &a.layer[l].ksteps);
-        if (wide) {
-            if (a.n_stash >= kMaxStash) return fail(ctx, NEDDF_EUNSUPPORTED, "NeDDF: more than 4 skip connections");
-            o_st.push_back(pack_layer(blob, src, pe, WP, operands, &a.stash[a.n_stash].ksteps));
-            a.stash[a.n_stash].col0 = 0;
-            a.layer[l].stash = a.n_stash++;
+    auto pack = [&](int operands, DdfArgs &a, ColArgs &c, bool *exact, std::function<void(const float *)> &resolve) -> int {
+        a = DdfArgs{}; c = ColArgs{};
+        std::vector<size_t> o_wp(n_trunk), o_b(n_trunk), o_st;
+        std::vector<int> pe;
+        enc_map(pe, E, KH, 0);
+        a.n_layers = n_trunk; a.n_stash = 0;
+        for (int l = 0; l < n_trunk; ++l) {
+            bool wide = l > 0 && in_skips(d, l - 1);
+            int cin = l == 0 ? Cpe : (wide ? Wd + Cpe : Wd);
+            Src src{ W[l], cin, Wd, false };
+            std::vector<int> km;
+            a.layer[l].stash = -1;
+            if (l == 0) km = pe;
+            else km = hidden_map(Wd, WP, wide ? Cpe : 0);
+            o_wp[l] = pack_layer(blob, src, km, WP, operands, &a.layer[l].ksteps, exact);
+            if (wide) {
+                if (a.n_stash >= kMaxStash) return fail(ctx, NEDDF_EUNSUPPORTED, "NeDDF: more than 4 skip connections");
+                o_st.push_back(pack_layer(blob, src, pe, WP, operands, &a.stash[a.n_stash].ksteps, exact));
+                a.stash[a.n_stash].col0 = 0;
+                a.layer[l].stash = a.n_stash++;
+            }
+            o_b[l] = put(blob, B[l], Wd, WP);
         }
-        o_b[l] = put(blob, B[l], Wd, WP);
-    }
-    const int i_ddf = n_trunk + n_col, i_aux = i_ddf + 1, i_cout = i_ddf + 2;
-    size_t o_wddf = put(blob, W[i_ddf], Wd, WP), o_waux = put(blob, W[i_aux], Wd, WP);
-    a.b_ddf_out = B[i_ddf][0]; a.b_aux_out = B[i_aux][0];
-    // Reverse-mode distance gradient (ddf_rev_kernel): the transposes.  dL/dH_{l-1} = g_l x (hidden rows of W_l)^T is a dense
-    // product with B[k][n] = W_l[row0 + n][k]; the gradient of the encoding collects g_0 x W_0^T and g_skip x (encoding rows of
-    // W_skip)^T, 64 engine columns wide (same [sin half | cos half] order as the forward encoding in LDS)
-    std::vector<size_t> o_wT(n_trunk, 0);
-    size_t o_wT_pe0 = 0, o_wT_pes[kMaxStash] = { 0 };
-    a.skip_layer = -1;
-    {
-        const std::vector<int> kall = hidden_map(Wd, WP, 0);
-        // narrow transposes: column n of the engine's encoding layout is reference row pe[n] (or padding)
-        auto pack_pe_T = [&](const float *Wl) {
-            std::vector<float> tmp((size_t)Wd * 64, 0.f);           // [k][n] row-major, n < 64
-            for (int n = 0; n < (int)pe.size() && n < 64; ++n)
-                if (pe[n] >= 0)
-                    for (int k = 0; k < Wd; ++k) tmp[(size_t)k * 64 + n] = Wl[(size_t)pe[n] * Wd + k];
-            Src sn{ tmp.data(), Wd, 64, false };
-            return pack_layer(blob, sn, kall, 64, operands, nullptr);
+        const int i_ddf = n_trunk + n_col, i_aux = i_ddf + 1, i_cout = i_ddf + 2;
+        size_t o_wddf = put(blob, W[i_ddf], Wd, WP), o_waux = put(blob, W[i_aux], Wd, WP);
+        a.b_ddf_out = B[i_ddf][0]; a.b_aux_out = B[i_aux][0];
+        // Reverse-mode distance gradient (ddf_rev_kernel): the transposes.  dL/dH_{l-1} = g_l x (hidden rows of W_l)^T is a dense
+        // product with B[k][n] = W_l[row0 + n][k]; the gradient of the encoding collects g_0 x W_0^T and g_skip x (encoding rows of
+        // W_skip)^T, 64 engine columns wide (same [sin half | cos half] order as the forward encoding in LDS)
+        std::vector<size_t> o_wT(n_trunk, 0);
+        size_t o_wT_pe0 = 0, o_wT_pes[kMaxStash] = { 0 };
+        a.skip_layer = -1;
+        {
+            const std::vector<int> kall = hidden_map(Wd, WP, 0);
+            // narrow transposes: column n of the engine's encoding layout is reference row pe[n] (or padding)
+            auto pack_pe_T = [&](const float *Wl) {
+                std::vector<float> tmp((size_t)Wd * 64, 0.f);           // [k][n] row-major, n < 64
+                for (int n = 0; n < (int)pe.size() && n < 64; ++n)
+                    if (pe[n] >= 0)
+                        for (int k = 0; k < Wd; ++k) tmp[(size_t)k * 64 + n] = Wl[(size_t)pe[n] * Wd + k];
+                Src sn{ tmp.data(), Wd, 64, false };
+                return pack_layer(blob, sn, kall, 64, operands, nullptr, exact);
+            };
+            for (int l = 1; l < n_trunk; ++l) {
+                const bool wide = in_skips(d, l - 1);
+                // logical B[k][n] = W_l[(wide ? Cpe : 0) + n][k], W_l row-major [in][Wd]  ==  Src "transposed" with rows = Wd
+                Src st{ W[l] + (size_t)(wide ? Cpe : 0) * Wd, Wd, Wd, true };
+                o_wT[l] = pack_layer(blob, st, kall, WP, operands, nullptr, exact);
+                if (wide) { a.skip_layer = l; o_wT_pes[a.layer[l].stash] = pack_pe_T(W[l]); }
+            }
+            o_wT_pe0 = pack_pe_T(W[0]);
+        }
+        // colour trunk
+        std::vector<int> ka;
+        enc_map(ka, E, KH, 0);
+        enc_map(ka, Ed, KD, Cpe);
+        for (int k = 0; k < 3; ++k) ka.push_back(Cpe + Cdir + k);
+        std::vector<size_t> c_wp(n_col), c_b(n_col);
+        Src s0{ W[n_trunk], Cpe + Cdir + 3 + Wd, Wd, false };
+        size_t o_wa = pack_layer(blob, s0, ka, WP, operands, &c.ksteps_a, exact);
+        c.n_layers = n_col;
+        for (int l = 0; l < n_col; ++l) {
+            const std::vector<int> km = hidden_map(Wd, WP, l == 0 ? Cpe + Cdir + 3 : 0);
+            Src src{ W[n_trunk + l], l == 0 ? Cpe + Cdir + 3 + Wd : Wd, Wd, false };
+            c_wp[l] = pack_layer(blob, src, km, WP, operands, &c.layer[l].ksteps, exact);
+            c.layer[l].stash = -1;
+            c_b[l] = put(blob, B[n_trunk + l], Wd, WP);
+        }
+        size_t o_cout = put(blob, W[i_cout], (size_t)Wd * 3, (size_t)WP * 3);
+        for (int k = 0; k < 3; ++k) c.b_out[k] = B[i_cout][k];
+        resolve = [=, &a, &c](const float *base) {
+            for (int l = 0; l < n_trunk; ++l) { a.layer[l].wp = base + o_wp[l]; a.layer[l].bias = base + o_b[l]; }
+            for (int s = 0; s < a.n_stash; ++s) a.stash[s].wp = base + o_st[s];
+            a.w_ddf_out = base + o_wddf; a.w_aux_out = base + o_waux;
+            for (int l = 1; l < n_trunk; ++l) a.wT[l] = base + o_wT[l];
+            a.wT_pe0 = base + o_wT_pe0;
+            for (int st = 0; st < a.n_stash; ++st) a.wT_pe_skip[st] = base + o_wT_pes[st];
+            c.wp_a = base + o_wa;
+            for (int l = 0; l < n_col; ++l) { c.layer[l].wp = base + c_wp[l]; c.layer[l].bias = base + c_b[l]; }
+            c.w_out = base + o_cout;
         };
-        for (int l = 1; l < n_trunk; ++l) {
-            const bool wide = in_skips(d, l - 1);
-            // logical B[k][n] = W_l[(wide ? Cpe : 0) + n][k], W_l row-major [in][Wd]  ==  Src "transposed" with rows = Wd
-            Src st{ W[l] + (size_t)(wide ? Cpe : 0) * Wd, Wd, Wd, true };
-            o_wT[l] = pack_layer(blob, st, kall, WP, operands, nullptr);
-            if (wide) { a.skip_layer = l; o_wT_pes[a.layer[l].stash] = pack_pe_T(W[l]); }
-        }
-        o_wT_pe0 = pack_pe_T(W[0]);
+        a.ks_hidden = WP / (operands ? 16 : 8);
+        a.width = c.width = WP;
+        a.activation = c.activation = d.activation;
+        a.density_activation = d.density_activation;
+        a.d_near = d.d_near;
+        a.operands = c.operands = operands;
+        c.final_act = -1;
+        for (int k = 0; k < 6; ++k) { c.penalty_weight[k] = d.penalty_weight[k]; c.penalty_has[k] = d.penalty_has[k]; }
+        return 0;
+    };
+    std::function<void(const float *)> resolve, resolve3;
+    if (int rc = pack(operands, f.ddf, f.col, nullptr, resolve)) return rc;
+    // fp32 fields: the reverse-mode distance kernel and the colour kernel of the eval-minimal route take their products as three-term
+    // bf16 splits (operands 3, tile_engine.h OpsF32x3T) from a second packing of the same weights; the forward-mode kernels keep the first
+    f.has3 = false;
+    if (operands == NEDDF_DTYPE_F32 && f32_products_split3()) {
+        bool exact = true;
+        if (int rc = pack(3, f.ddf3, f.col3, &exact, resolve3)) return rc;
+        f.has3 = exact;
     }
-    // colour trunk
-    std::vector<int> ka;
-    enc_map(ka, E, KH, 0);
-    enc_map(ka, Ed, KD, Cpe);
-    for (int k = 0; k < 3; ++k) ka.push_back(Cpe + Cdir + k);
-    std::vector<size_t> c_wp(n_col), c_b(n_col);
-    Src s0{ W[n_trunk], Cpe + Cdir + 3 + Wd, Wd, false };
-    size_t o_wa = pack_layer(blob, s0, ka, WP, operands, &c.ksteps_a);
-    c.n_layers = n_col;
-    for (int l = 0; l < n_col; ++l) {
-        const std::vector<int> km = hidden_map(Wd, WP, l == 0 ? Cpe + Cdir + 3 : 0);
-        Src src{ W[n_trunk + l], l == 0 ? Cpe + Cdir + 3 + Wd : Wd, Wd, false };
-        c_wp[l] = pack_layer(blob, src, km, WP, operands, &c.layer[l].ksteps);
-        c.layer[l].stash = -1;
-        c_b[l] = put(blob, B[n_trunk + l], Wd, WP);
-    }
-    size_t o_cout = put(blob, W[i_cout], (size_t)Wd * 3, (size_t)WP * 3);
-    for (int k = 0; k < 3; ++k) c.b_out[k] = B[i_cout][k];
-
     if (int rc = ensure(ctx, f.blob, blob.size() * sizeof(float))) return rc;
     HIPCHK(hipMemcpy(f.blob.p, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
-    const float *base = (const float *)f.blob.p;
-    for (int l = 0; l < n_trunk; ++l) { a.layer[l].wp = base + o_wp[l]; a.layer[l].bias = base + o_b[l]; }
-    for (int s = 0; s < a.n_stash; ++s) a.stash[s].wp = base + o_st[s];
-    a.w_ddf_out = base + o_wddf; a.w_aux_out = base + o_waux;
-    for (int l = 1; l < n_trunk; ++l) a.wT[l] = base + o_wT[l];
-    a.wT_pe0 = base + o_wT_pe0;
-    for (int st = 0; st < a.n_stash; ++st) a.wT_pe_skip[st] = base + o_wT_pes[st];
-    a.ks_hidden = WP / (operands ? 16 : 8);
-    a.width = c.width = WP;
-    c.wp_a = base + o_wa;
-    for (int l = 0; l < n_col; ++l) { c.layer[l].wp = base + c_wp[l]; c.layer[l].bias = base + c_b[l]; }
-    c.w_out = base + o_cout;
-    a.activation = c.activation = d.activation;
-    a.density_activation = d.density_activation;
-    a.d_near = d.d_near;
-    a.operands = c.operands = operands;
-    c.final_act = -1;
-    for (int k = 0; k < 6; ++k) { c.penalty_weight[k] = d.penalty_weight[k]; c.penalty_has[k] = d.penalty_has[k]; }
+    resolve((const float *)f.blob.p);
+    if (f.has3) resolve3((const float *)f.blob.p);
     return 0;
 }
 
@@ -531,6 +588,8 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
     const char *rif = rays ? getenv("NEDDF_RAYS_IN_FIELD") : nullptr;
     const bool use_rays = rays && (!rif || atoi(rif) != 0) && reverse && f.d.kind == NEDDF_FIELD_NEDDF;
     if (rays && !use_rays) sample_now();
+    // fp32 products as three-term bf16 splits (f32_products_split3): the reverse-mode kernel and the colour kernel behind it only
+    const bool use3 = f.has3 && reverse && f.d.kind == NEDDF_FIELD_NEDDF;
     // Points per launch of the field kernels.  Every launch boundary drains the persistent grid (workgroups finish up to one tile
     // apart) and refills it: at 2^21 points a 65 536-ray x 128-sample call was four launch pairs, at 2^23 it is one -- fp32 +0.8 %,
     // split fp16 +0.7 %, bf16 +2.8 % (profiles/r04_launch_size.txt).  The hand-off buffers grow with it (1 088 B per point
@@ -562,7 +621,7 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
     if (int rc = ensure(ctx, ctx->sched, 2 * kSchedInts * sizeof(int))) return rc;
     for (int64_t off = 0; off < N; off += chunk) {
         const int64_t n = (N - off < chunk) ? N - off : chunk;
-        DdfArgs a = f.ddf;
+        DdfArgs a = use3 ? f.ddf3 : f.ddf;
         fill_enc(a.enc, f);
         a.pos = pos + off * 3; a.dir = dir + off * 3; a.var = var + off * 3; a.n_points = n;
         if (use_rays) {
@@ -608,7 +667,7 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
             STAGE(ctx, s, NEDDF_STAGE_DDF, launch_ddf(a, (int)(tiles < grid_cap_ddf ? tiles : grid_cap_ddf), s));
         }
         if (color || full) {
-            ColArgs c = f.col;
+            ColArgs c = use3 ? f.col3 : f.col;
             fill_enc(c.enc, f);
             c.pos = a.pos; c.dir = a.dir; c.var = a.var; c.n_points = n;
             c.rays = use_rays ? 1 : 0;
@@ -757,6 +816,7 @@ int neddf_set_field(neddf_ctx *ctx, int slot, const neddf_field_desc *desc, cons
     // on its stream by field_forward), not for the whole device -- other streams and other slots keep running
     if (f.last_use) HIPCHK(hipEventSynchronize(f.last_use));
     f.valid = false;
+    f.has3 = false;
     f.d = *desc;
     f.aux_grad_scale = 1.1f; f.distance_range_max = 2.0f;
     for (int i = 0; i < 10; ++i) f.lowpass[i] = 1.0f;

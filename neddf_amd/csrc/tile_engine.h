@@ -23,6 +23,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // `make exactact` (-DNEDDF_EXACT_ACT -> libneddf_hip_exactact.so) builds the fp32 and split-fp16 policies with the reference's
 // branch-exact tanhExp in the fused kernels too, so that the reduced-cost form stays A/B-testable on any network
@@ -67,7 +68,9 @@ struct OpsF32T {
     static constexpr bool kDeepPrefetch = false;
     static constexpr bool kEncInLds = false; // no LDS to spare next to two 67 KB tiles
     static constexpr bool kTransposed = false, kStashF16 = false;       // (see OpsBF16RT)
+    typedef frag mfrag;                      // A as the MFMAs take it (prep: what happens between the LDS read and the products)
     static __device__ __forceinline__ frag load_a(const act_t *p) { return *(const frag *)p; }
+    static __device__ __forceinline__ const mfrag &prep(const frag &a) { return a; }
     static __device__ __forceinline__ void zero(act_t *p) { *p = 0.f; }
     static __device__ __forceinline__ void put4(act_t *p, const f32x4v &v) { *(f32x4v *)p = v; }     // 4 consecutive columns
     static __device__ __forceinline__ void put(act_t *p, float v) { *p = v; }
@@ -104,7 +107,9 @@ struct OpsBF16T {
     static constexpr bool kDeepPrefetch = true;      // weight fragments two super-steps ahead (dense_pipeline3)
     static constexpr bool kEncInLds = true;          // the reverse-mode kernel keeps the encoding in a second LDS tile for its skip layers (a bf16 tile is 33 KB)
     static constexpr bool kTransposed = false, kStashF16 = false;
+    typedef frag mfrag;
     static __device__ __forceinline__ frag load_a(const act_t *p) { return *(const frag *)p; }
+    static __device__ __forceinline__ const mfrag &prep(const frag &a) { return a; }
     static __device__ __forceinline__ void zero(act_t *p) { *p = 0; }
     static __device__ __forceinline__ unsigned short cvt(float v)       // round to nearest even (v_cvt_pk_bf16_f32)
     {
@@ -251,6 +256,8 @@ struct OpsF16SplitT {
         a.h = *(const f16x8 *)p; a.m = *(const f16x8 *)(p + kPlane);
         return a;
     }
+    typedef afrag mfrag;
+    static __device__ __forceinline__ const mfrag &prep(const afrag &a) { return a; }
     static __device__ __forceinline__ f32x16 mfma(const afrag &a, const bfrag &b, const f32x16 &c, int r)
     {
         switch (r) {
@@ -261,6 +268,79 @@ struct OpsF16SplitT {
     }
 };
 typedef OpsF16SplitT<256> OpsF16Split;
+
+// fp32 data, fp32-accurate products on the bf16 matrix instructions.  An fp32 value splits EXACTLY into three bf16 terms,
+// a = a0 + a1 + a2 (a0 = bf16_rne(a), a1 = bf16_rne(a - a0), a2 = a - a0 - a1: every remainder is exact in fp32 and the last
+// one has at most 8 significant bits); bf16 has fp32's exponent range, so nothing is scaled and nothing saturates.  Every
+// product ai.bj is exact in fp32; the six with i + j <= 2 are kept, the three dropped ones together are below ~2^-26 |a||b|
+// (half an fp32 ulp of the product).  Six v_mfma_f32_32x32x16_bf16 per 16 k against eight v_mfma_f32_32x32x2_f32: 2.67x the
+// fp32 matrix rate, and unlike the fp32 MFMA the bf16 one issues beside vector work.
+// Everything that is not a product is OpsF32T's: the fp32 activation tile (kLd = WID + 4), the fp32 epilogues and stores, y'
+// stashed in fp32, the activation mode.  A is read as 8 fp32 k-values per lane (two ds_read_b128) and split in prep(), which
+// the engine calls ONCE per super-step and M-tile inside the product block (dense_mfma): both column tiles take the same
+// three terms, and the LDS read of the next super-step stays in flight across the split (44 vector instructions per
+// 12 MFMAs at MT = NT = 2).  B is three pre-split weight planes, 48 bytes per lane and super-step (neddf_capi.hip pack_layer,
+// operands 3): half the weight bytes per MFMA of the bf16 policy.
+// (neither `OpsBF16` nor `OpsF16Split` may appear in this name: the benchmark tells the dtypes apart by those substrings)
+struct f32x8frag {
+    f32x4v lo, hi;
+};
+struct bf16x8x3 {
+    bf16x8 t[3];         // hi, mid, lo term
+};
+
+template <int WID>
+struct OpsF32x3T : OpsF32T<WID> {
+    typedef float act_t;
+    typedef f32x8frag afrag;
+    typedef bf16x8x3 bfrag;
+    typedef bf16x8x3 mfrag;
+    static constexpr int kStep = 16;
+    static constexpr int kSub = 6;
+    static __device__ __forceinline__ afrag load_a(const act_t *p) { return { *(const f32x4v *)p, *(const f32x4v *)(p + 4) }; }
+    // v_cvt_pk_bf16_f32 rounds a PAIR to nearest even; the pair's terms come back to fp32 as the word's halves (lo << 16, hi & 0xffff0000).
+    // The empty asm keeps the packed word opaque: hipcc otherwise recognises the halves as the single conversions they equal and emits
+    // one conversion per value plus a shift (28 instead of 20 instructions per level and eight values)
+    static __device__ __forceinline__ unsigned cvt2(float x0, float x1, float &y0, float &y1)
+    {
+        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        unsigned w = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){ x0, x1 }, bf16x2));
+        asm("" : "+v"(w));
+        y0 = __builtin_bit_cast(float, w << 16);
+        y1 = __builtin_bit_cast(float, w & 0xffff0000u);
+        return w;
+    }
+    static __device__ __forceinline__ mfrag prep(const afrag &a)
+    {
+        const float x[8] = { a.lo[0], a.lo[1], a.lo[2], a.lo[3], a.hi[0], a.hi[1], a.hi[2], a.hi[3] };
+        u32x4 t0, t1, t2;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float h0, h1, m0, m1, d0, d1;
+            t0[i] = cvt2(x[2 * i], x[2 * i + 1], h0, h1);                        // a0 = rne(x)
+            const float r0 = x[2 * i] - h0, r1 = x[2 * i + 1] - h1;              // exact
+            t1[i] = cvt2(r0, r1, m0, m1);                                        // a1 = rne(x - a0)
+            t2[i] = cvt2(r0 - m0, r1 - m1, d0, d1);                              // a2 = x - a0 - a1: exact (at most 8 significant bits)
+            (void)d0; (void)d1;
+        }
+        mfrag m;
+        m.t[0] = __builtin_bit_cast(bf16x8, t0); m.t[1] = __builtin_bit_cast(bf16x8, t1); m.t[2] = __builtin_bit_cast(bf16x8, t2);
+        return m;
+    }
+    // the small terms first: a2.b0, a1.b1, a0.b2 (~2^-16 of the result), a1.b0, a0.b1 (~2^-8), a0.b0
+    static __device__ __forceinline__ f32x16 mfma(const mfrag &a, const bfrag &b, const f32x16 &c, int r)
+    {
+        switch (r) {
+        case 0: return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.t[2], b.t[0], c, 0, 0, 0);
+        case 1: return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.t[1], b.t[1], c, 0, 0, 0);
+        case 2: return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.t[0], b.t[2], c, 0, 0, 0);
+        case 3: return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.t[1], b.t[0], c, 0, 0, 0);
+        case 4: return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.t[0], b.t[1], c, 0, 0, 0);
+        default: return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.t[0], b.t[0], c, 0, 0, 0);
+        }
+    }
+};
 
 // the same policy over a narrow side tile (the encoding kept in LDS for the skip layers): 64 columns + 8 of padding per row, i.e. a row
 // stride of 36 dwords -- 16 rows x 16-byte fragments tile the 64 banks exactly
@@ -285,7 +365,6 @@ __device__ __forceinline__ const typename Ops::act_t *act_lane_ptr(const typenam
 // apart from the lane's slot, so the fragments are fetched as buffer loads -- a scalar resource (the wave's base), the
 // constant lane offset in a VGPR and the super-step's offset in an SGPR (`buffer_load_dwordx4 v, v_off, s[rsrc], s_off offen`)
 // -- instead of one 64-bit v_lshl_add_u64 per global load.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 struct WeightStream {
     __amdgpu_buffer_rsrc_t rsrc;    // base = the wave's first fragment, raw buffer without range clamp
     unsigned lane_off;              // lane * sizeof(fragment)
@@ -328,12 +407,15 @@ __device__ __forceinline__ void dense_load(typename Ops::afrag (&a)[MT], typenam
 template <int MT, int NT, class Ops = OpsF32>
 __device__ __forceinline__ void dense_mfma(f32x16 (&acc)[MT][NT], const typename Ops::afrag (&a)[MT], const typename Ops::bfrag (&b)[NT])
 {
+    typename Ops::mfrag m[MT];           // (the identity except under OpsF32x3T: once per M-tile, for all column tiles and terms)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) m[mt] = Ops::prep(a[mt]);
 #pragma unroll
     for (int r = 0; r < Ops::kSub; ++r)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) acc[mt][t] = Ops::mfma(a[mt], b[t], acc[mt][t], r);
+            for (int t = 0; t < NT; ++t) acc[mt][t] = Ops::mfma(m[mt], b[t], acc[mt][t], r);
 }
 
 // Software pipeline, ping-pong operand registers: the operands of super-step
