@@ -32,7 +32,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NEDDF_ABI_VERSION 5
+#define NEDDF_ABI_VERSION 6
 
 enum { NEDDF_OK = 0, NEDDF_EINVAL = -1, NEDDF_EHIP = -2, NEDDF_EUNSUPPORTED = -3, NEDDF_ENOFIELD = -4,
        NEDDF_ECOMM = -5,      /* RCCL reported an error (message in neddf_last_error) or is not loadable */
@@ -332,6 +332,30 @@ int neddf_composite_backward(neddf_ctx *ctx, const float *d_dists, const float *
                              int64_t n_rays, int S, float max_dist, const float *d_g_weight, const float *d_g_depth,
                              const float *d_g_color, const float *d_g_transmittance, float *d_g_density,
                              float *d_g_point_color, void *stream);
+
+/* ---- surface extraction (ABI v6; the reference meshes voxelize()'s cube with PyMCubes inside its Open3D viewer,
+ * neddf/scripts/fields_visualizer.py:528-566) -------------------------------------------------------------------
+ * Lattice: nx x ny x nz points between h_lo[3] and h_hi[3] (HOST doubles, x y z), coordinate i of an axis =
+ * (float)(lo + i * ((hi - lo) / (n - 1))) computed in double and the last one exactly hi: np.linspace's points, so that
+ * BaseNeuralField.voxelize (base_neuralfield.py:49-79) evaluates the same ones.  Volumes are [nz][ny][nx], x fastest. */
+enum { NEDDF_GRID_DISTANCE = 0, NEDDF_GRID_DENSITY = 1 };
+/* Field slot `slot`'s distance (NeuS: sdf) or density on the lattice, dir = (1, 0, 0) and var = 0 as voxelize passes them, under
+ * the slot's operand policy; written to d_volume [nz][ny][nx].  The lattice is evaluated in chunks of 2^23 points (the field
+ * kernels' launch size).  NEDDF_EINVAL for a dimension below 2, lo >= hi on an axis, or an output the field lacks (NeRF: distance). */
+int neddf_field_grid(neddf_ctx *ctx, int slot, int field, int nx, int ny, int nz, const double *h_lo, const double *h_hi, float *d_volume,
+                     void *stream);
+/* Marching cubes (Lorensen & Cline 1987, Bourke's corner / edge numbering; case table: neddf_amd/csrc/mc_tables.h) over a
+ * [nz][ny][nx] volume on the lattice above: an indexed mesh, one vertex per lattice edge the iso-surface crosses.
+ *   - a corner is inside when value < iso (NaN is outside); on the edge from lattice point g0 (value v0) to g1 (v1) the vertex is
+ *     g0 + t * (g1 - g0), t = (iso - v0) / (v1 - v0) in fp32 (t = 1/2 when that is NaN), the other two coordinates exact
+ *   - d_vertices [V][3] float (x, y, z in world units): ordered by the owning (lower) lattice point's linear index, then x, y, z edge
+ *   - d_triangles [T][3] int32: ordered by cell, then by table order; (p1 - p0) x (p2 - p0) points from the inside to the outside
+ *   - the output does not depend on timing (count / scan / write launches, no atomics)
+ * Two calls: with d_vertices or d_triangles NULL, or a cap below its count, only *h_n_vertices / *h_n_triangles are written;
+ * otherwise the mesh is too.  Synchronises `stream` once (to read the counts).  NEDDF_EUNSUPPORTED when V >= 2^31. */
+int neddf_marching_cubes(neddf_ctx *ctx, const float *d_volume, int nx, int ny, int nz, const double *h_lo, const double *h_hi, float iso,
+                         float *d_vertices, int64_t vertex_cap, int32_t *d_triangles, int64_t triangle_cap, int64_t *h_n_vertices,
+                         int64_t *h_n_triangles, void *stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

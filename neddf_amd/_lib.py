@@ -12,13 +12,14 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NEDDF_LIB_PATH selects another build of the same library (the sanitizer build, `make -C neddf_amd/csrc asan`)
 LIB_PATH = os.environ.get("NEDDF_LIB_PATH") or os.path.join(_HERE, "csrc", "libneddf_hip.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 FIELD_NEDDF, FIELD_NERF, FIELD_NEUS = 0, 1, 2
 ACT = {"ReLU": 0, "LeakyReLU": 1, "tanhExp": 2}
 DTYPE = {"fp32": 0, "bf16": 1, "f16_split": 2}
 SLOT_COARSE, SLOT_FINE, SLOT_GENERIC = 0, 1, 2
 OUT_MINIMAL, OUT_FULL = 0, 1
+GRID_FIELDS = {"distance": 0, "density": 1}        # NEDDF_GRID_*
 STAGES = ("ddf", "col", "nerf", "raygen", "ndc", "sample_coarse", "sampling", "composite", "penalty", "resample", "gather")
 COMM_ID_BYTES = 128
 UV_TYPES = {torch.float32: 0, torch.int64: 1, torch.int32: 2, torch.int16: 3}
@@ -28,6 +29,7 @@ PENALTY_KEYS = ("constraints_aux_grad", "constraints_dDdt", "range_distance", "r
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
 _i64 = C.c_int64
+_dp = C.POINTER(C.c_double)
 
 
 class NeddfError(RuntimeError):
@@ -105,6 +107,9 @@ SYMBOLS = [
     ("neddf_train_field_backward", C.c_int, [_vp, C.c_int, C.POINTER(_fp), C.POINTER(_fp), C.c_int, _i64, _vp, _vp, _vp, _vp,
                                              _vp, _vp, C.POINTER(_fp), C.POINTER(_fp), _vp]),
     ("neddf_composite_backward", C.c_int, [_vp, _vp, _vp, _vp, _i64, C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_field_grid", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _vp, _vp]),
+    ("neddf_marching_cubes", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_float, _vp, _i64, _vp, _i64,
+                                       C.POINTER(_i64), C.POINTER(_i64), _vp]),
 ]
 
 _lib = None
@@ -277,6 +282,43 @@ class Context:
                                                 _ptr(o["distance"]), _ptr(o["density"]), _ptr(o["color"]),
                                                 _ptr(o["fields_penalty"]), _ptr(o["aux_grad"]), self.stream()))
         return {k: v for k, v in o.items() if v is not None}
+
+    # ------------------------------------------------------------------ surface extraction
+    @staticmethod
+    def _bounds(lo, hi):
+        lo, hi = [float(x) for x in lo], [float(x) for x in hi]
+        if len(lo) != 3 or len(hi) != 3:
+            raise NeddfError("lo / hi must hold three values (x, y, z)")
+        return (C.c_double * 3)(*lo), (C.c_double * 3)(*hi)
+
+    def field_grid(self, slot, field, shape, lo, hi):
+        """`field` ("distance" / "density") of the field in `slot` on the lattice shape = (nx, ny, nz) between lo and hi
+        (np.linspace per axis) -> float32 [nz, ny, nx] on this context's device."""
+        if field not in GRID_FIELDS:
+            raise NeddfError("field_grid: field must be one of %s (got %r)" % (sorted(GRID_FIELDS), field))
+        nx, ny, nz = (int(n) for n in shape)
+        blo, bhi = self._bounds(lo, hi)
+        vol = torch.empty(max(nz, 0), max(ny, 0), max(nx, 0), device=self.device, dtype=torch.float32)
+        self.check(self.lib.neddf_field_grid(self.h, slot, GRID_FIELDS[field], nx, ny, nz, blo, bhi, _ptr(vol), self.stream()))
+        return vol
+
+    def marching_cubes(self, volume, iso, lo, hi):
+        """Indexed iso-surface of a contiguous float32 [nz, ny, nx] device volume on the lattice lo .. hi:
+        (vertices float32 [V, 3], triangles int32 [T, 3]), by a counting call and a writing call of exactly that size."""
+        nz, ny, nx = volume.shape
+        blo, bhi = self._bounds(lo, hi)
+        nv, nt = _i64(0), _i64(0)
+
+        def call(v, t):
+            self.check(self.lib.neddf_marching_cubes(self.h, _ptr(volume), nx, ny, nz, blo, bhi, float(iso), _ptr(v),
+                                                     0 if v is None else v.shape[0], _ptr(t), 0 if t is None else t.shape[0],
+                                                     C.byref(nv), C.byref(nt), self.stream()))
+        call(None, None)
+        verts = torch.empty(nv.value, 3, device=volume.device, dtype=torch.float32)
+        tris = torch.empty(nt.value, 3, device=volume.device, dtype=torch.int32)
+        if nv.value and nt.value:
+            call(verts, tris)
+        return verts, tris
 
     def composite(self, dists, dens, col, max_dist):
         require_device(dists, "dists")

@@ -188,6 +188,26 @@ void launch_integrate_penalty(const float *dists, const float *pen, int64_t n, i
 void launch_resample(const float *dists, float *weights, const float *U, int64_t n_rays, int n, int nf, int cat,
                      float *out, int64_t *ids, int *flag, int64_t group, int64_t offset, hipStream_t s);
 
+// Surface extraction (mesh_kernels.hip): a [nz][ny][nx] volume on the lattice lo .. hi (np.linspace per axis, x fastest)
+constexpr int kMcThreads = 256;          // lattice points per workgroup of the count / vertex / triangle kernels
+constexpr int kMcScanThreads = 1024;     // the one workgroup of the block-total scan
+struct McGrid {
+    const float *vol;                    // [nz][ny][nx] (NULL for grid_points_kernel)
+    int nx, ny, nz;
+    int64_t n;                           // nx * ny * nz
+    float iso;
+    double lo[3], hi[3];
+};
+static inline int64_t mc_blocks(int64_t n) { return (n + kMcThreads - 1) / kMcThreads; }
+void launch_grid_points(const McGrid &g, int64_t first, int64_t n, float *pos, float *dir, float *var, hipStream_t s);
+// per-block vertex / triangle totals (vblk / tblk [mc_blocks(n) + 1]) and the crossed-edge byte of every lattice point
+void launch_mc_count(const McGrid &g, unsigned char *mask, int64_t *vblk, int64_t *tblk, hipStream_t s);
+// block totals -> exclusive block bases in place; [nblocks] = the vertex / triangle count of the mesh
+void launch_mc_scan(int64_t *vblk, int64_t *tblk, int64_t nblocks, hipStream_t s);
+void launch_mc_vertices(const McGrid &g, const unsigned char *mask, const int64_t *vblk, int32_t *vbase, float *vertices, hipStream_t s);
+void launch_mc_triangles(const McGrid &g, const unsigned char *mask, const int64_t *tblk, const int32_t *vbase, int32_t *tris,
+                         hipStream_t s);
+
 void launch_linear_grad(const float *x, const float *J, int64_t n, int cin, int ldx, int cout_block, int ksteps, const float *wp,
                         const float *bias, float *y, float *G, int ldo, int nvalid, int accumulate, int grid, hipStream_t s);
 void launch_op_activation(int kind, const float *x, const float *J, int64_t N, int C, float *y, float *G, hipStream_t s);

@@ -751,7 +751,8 @@ void neddf_destroy(neddf_ctx *ctx)
         if (f.blob.p) (void)hipFree(f.blob.p);
         if (f.last_use) (void)hipEventDestroy(f.last_use);
     }
-    for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack, &ctx->ttmp, &ctx->tamax })
+    for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack, &ctx->ttmp, &ctx->tamax,
+                      &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk })
         if (b->p) (void)hipFree(b->base ? b->base : b->p);
     for (auto &e : ctx->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : ctx->pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -770,7 +771,7 @@ int neddf_debug_check_guards(neddf_ctx *ctx, int64_t *n_bands, int64_t *n_bad_by
     HIPCHK(hipDeviceSynchronize());
     std::vector<GuardBand> bands = ctx->carve_guards;
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack,
-                       &ctx->ttmp, &ctx->tamax })
+                       &ctx->ttmp, &ctx->tamax, &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk })
         if (b->base) {
             bands.push_back(GuardBand{ b->base, kGuardBytes });
             bands.push_back(GuardBand{ (char *)b->p + b->cap, kGuardBytes });
@@ -1189,6 +1190,89 @@ int neddf_get_stage_timings(neddf_ctx *ctx, float *ms, int *launches, int n_stag
     DeviceGuard guard_(ctx->device);
     for (int i = 0; i < n_stages; ++i) { ms[i] = 0.f; launches[i] = 0; }
     return drain_events(ctx, ms, launches);
+}
+
+// ---- surface extraction (no reference counterpart inside the library: fields_visualizer.py:528-566 meshes on the host) ----
+static bool lattice_ok(int nx, int ny, int nz, const double *lo, const double *hi)
+{
+    if (nx < 2 || ny < 2 || nz < 2) return false;
+    for (int a = 0; a < 3; ++a)
+        if (!(lo[a] < hi[a])) return false;      // NaN bounds fail too
+    return true;
+}
+
+static McGrid mc_grid(const float *vol, int nx, int ny, int nz, const double *lo, const double *hi, float iso)
+{
+    McGrid g{};
+    g.vol = vol; g.nx = nx; g.ny = ny; g.nz = nz;
+    g.n = (int64_t)nx * ny * nz;
+    g.iso = iso;
+    for (int a = 0; a < 3; ++a) { g.lo[a] = lo[a]; g.hi[a] = hi[a]; }
+    return g;
+}
+
+int neddf_field_grid(neddf_ctx *ctx, int slot, int field, int nx, int ny, int nz, const double *h_lo, const double *h_hi, float *d_volume,
+                     void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!h_lo || !h_hi || !d_volume) return fail(ctx, NEDDF_EINVAL, "field_grid: NULL bounds or volume");
+    if (!lattice_ok(nx, ny, nz, h_lo, h_hi)) return fail(ctx, NEDDF_EINVAL, "field_grid: every dimension must be >= 2 and lo < hi on every axis");
+    if (field != NEDDF_GRID_DISTANCE && field != NEDDF_GRID_DENSITY) return fail(ctx, NEDDF_EINVAL, "field_grid: field must be NEDDF_GRID_DISTANCE or NEDDF_GRID_DENSITY");
+    if (slot < 0 || slot >= NEDDF_NUM_SLOTS || !ctx->field[slot].valid) return fail(ctx, NEDDF_ENOFIELD, "no field in slot");
+    if (field == NEDDF_GRID_DISTANCE && ctx->field[slot].d.kind == NEDDF_FIELD_NERF)
+        return fail(ctx, NEDDF_EINVAL, "field_grid: a NeRF field has no distance output");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const McGrid g = mc_grid(nullptr, nx, ny, nz, h_lo, h_hi, 0.f);
+    // one chunk = one launch of field_forward at its own launch size (2^23 points): 302 MB of pos / dir / var
+    const int64_t chunk = g.n < ((int64_t)1 << 23) ? g.n : ((int64_t)1 << 23);
+    if (int rc = ensure(ctx, ctx->grid_pts, (size_t)chunk * 9 * sizeof(float))) return rc;
+    float *pos = (float *)ctx->grid_pts.p, *dir = pos + chunk * 3, *var = dir + chunk * 3;
+    for (int64_t off = 0; off < g.n; off += chunk) {
+        const int64_t n = g.n - off < chunk ? g.n - off : chunk;
+        launch_grid_points(g, off, n, pos, dir, var, s);
+        HIPCHK(hipGetLastError());
+        float *out = d_volume + off;
+        // no colour: the colour kernel and its hand-off are skipped (field_forward, a.features)
+        if (int rc = field_forward(ctx, slot, pos, dir, var, n, NEDDF_OUT_MINIMAL, field == NEDDF_GRID_DISTANCE ? out : nullptr,
+                                   field == NEDDF_GRID_DENSITY ? out : nullptr, nullptr, nullptr, nullptr, s)) return rc;
+    }
+    return 0;
+}
+
+int neddf_marching_cubes(neddf_ctx *ctx, const float *d_volume, int nx, int ny, int nz, const double *h_lo, const double *h_hi, float iso,
+                         float *d_vertices, int64_t vertex_cap, int32_t *d_triangles, int64_t triangle_cap, int64_t *h_n_vertices,
+                         int64_t *h_n_triangles, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!d_volume || !h_lo || !h_hi || !h_n_vertices || !h_n_triangles) return fail(ctx, NEDDF_EINVAL, "marching_cubes: NULL volume, bounds or count");
+    if (!lattice_ok(nx, ny, nz, h_lo, h_hi)) return fail(ctx, NEDDF_EINVAL, "marching_cubes: every dimension must be >= 2 and lo < hi on every axis");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const McGrid g = mc_grid(d_volume, nx, ny, nz, h_lo, h_hi, iso);
+    const int64_t nb = mc_blocks(g.n);
+    if (nb > 0x7fffffff) return fail(ctx, NEDDF_EUNSUPPORTED, "marching_cubes: lattice too large");
+    if (int rc = ensure(ctx, ctx->mc_mask, (size_t)g.n)) return rc;
+    if (int rc = ensure(ctx, ctx->mc_blk, (size_t)2 * (nb + 1) * sizeof(int64_t))) return rc;
+    unsigned char *mask = (unsigned char *)ctx->mc_mask.p;
+    int64_t *vblk = (int64_t *)ctx->mc_blk.p, *tblk = vblk + nb + 1;
+    launch_mc_count(g, mask, vblk, tblk, s);
+    launch_mc_scan(vblk, tblk, nb, s);
+    HIPCHK(hipGetLastError());
+    int64_t counts[2];
+    HIPCHK(hipMemcpyAsync(&counts[0], vblk + nb, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&counts[1], tblk + nb, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *h_n_vertices = counts[0];
+    *h_n_triangles = counts[1];
+    if (counts[0] >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "marching_cubes: 2^31 vertices or more (triangle indices are int32)");
+    if (!d_vertices || !d_triangles || vertex_cap < counts[0] || triangle_cap < counts[1]) return 0;     // the counting call
+    if (int rc = ensure(ctx, ctx->mc_vbase, (size_t)g.n * sizeof(int32_t))) return rc;
+    int32_t *vbase = (int32_t *)ctx->mc_vbase.p;
+    launch_mc_vertices(g, mask, vblk, vbase, d_vertices, s);
+    launch_mc_triangles(g, mask, tblk, vbase, d_triangles, s);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 }  // extern "C"

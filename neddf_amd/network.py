@@ -137,6 +137,44 @@ class BaseNeuralField(ABC, nn.Module):
             val = self.forward(Sampling(pos, d, torch.zeros_like(pos)))     # one call: no need to chunk on 288 GB
             return val[field_name].reshape(cube_resolution, cube_resolution, cube_resolution).cpu().numpy()
 
+    def _grid_fields(self):
+        """extract_mesh's field names -> the library's grid output."""
+        return {"distance": "distance", "density": "density"}
+
+    def extract_mesh(self, field_name: str = "distance", threshold: float = 0.0275, cube_range: float = 1.1,
+                     resolution: int = 64, timings: Optional[Dict[str, float]] = None):
+        """Triangle mesh of the `threshold` level set of `field_name` in the cube [-cube_range, cube_range]^3 sampled at
+        resolution^3 points -- the reference's generate_mesh (fields_visualizer.py:528-566: voxelize("distance", 1.1, 64),
+        mcubes.marching_cubes(voxel, 0.0275)) with the grid evaluation and marching cubes on the GPU.
+
+        field_name: "distance" (NeDDF), "sdf" (NeuS, use threshold=0.0), "density" (every kind).  The object is the low side
+        of a distance / sdf and the high side of a density; either way the triangles' normals (p1 - p0) x (p2 - p0) point out of it.
+        Returns (vertices float32 [V, 3], triangles int32 [T, 3]) on the field's device.  Vertices are in world coordinates;
+        the reference's .dae holds mcubes' index coordinates in voxelize's [y, z, x] order instead, mapped to the world by
+        (index - resolution / 2) * 2 * cube_range / resolution.  `timings` (a dict, optional) receives the wall time in seconds
+        of the grid evaluation ("grid") and of marching cubes ("mcubes"), each ending in a device synchronise."""
+        import time
+        from .mesh import marching_cubes
+        names = self._grid_fields()
+        if field_name not in names:
+            raise ValueError("extract_mesh: %s fields offer %s (got %r)" % (type(self).__name__, sorted(names), field_name))
+        lo, hi = (-float(cube_range),) * 3, (float(cube_range),) * 3
+        with torch.no_grad():
+            ctx = Context.get(self.device)
+            self.upload(ctx, self._slot)
+            t0 = time.perf_counter()
+            vol = ctx.field_grid(self._slot, names[field_name], (resolution,) * 3, lo, hi)
+            torch.cuda.synchronize(self.device)
+            t1 = time.perf_counter()
+            verts, tris = marching_cubes(vol, float(threshold), lo, hi)
+            if field_name == "density":                 # the object is above the threshold: turn the normals outward
+                tris = tris[:, [0, 2, 1]].contiguous()
+            torch.cuda.synchronize(self.device)
+            t2 = time.perf_counter()
+        if timings is not None:
+            timings["grid"], timings["mcubes"] = t1 - t0, t2 - t1
+        return verts, tris
+
     # ---- training at hidden widths other than 256 ---------------------------------------------------------------------
     # The training kernels are built for hidden width 256 (every field kind) and, on their per-layer route in 256 x 256 blocks,
     # 512 (csrc/train_capi.hip train_supported).  Any other width trains ZERO-PADDED to the next of the two: every parameter
@@ -396,6 +434,9 @@ class NeRF(BaseNeuralField):
     def set_iter(self, iter: int) -> None:
         self.lowpass_alpha = self.pe_pos.embed_dim if iter == -1 else self.lowpass_alpha_offset + 0.001 * iter
 
+    def _grid_fields(self):
+        return {"density": "density"}          # nerf.py:161-164: no distance output
+
 
 class NeuS(BaseNeuralField):
     """NeuS SDF field (neus.py:30-99 constructor keywords).  The reference takes the
@@ -504,6 +545,9 @@ class NeuS(BaseNeuralField):
 
     def set_iter(self, iter: int) -> None:      # base_neuralfield.py:14-22: no warm-up state
         pass
+
+    def _grid_fields(self):
+        return {"sdf": "distance", "density": "density"}
 
 
 # spellings used by BASELINE.json's north_star

@@ -18,6 +18,22 @@ import yaml
 from neddf_amd.config import instantiate
 
 
+def load_config(output_dir: Path) -> dict:
+    """The run's frozen `.hydra/config.yaml` with the test split selected (the reference's override)."""
+    conf = output_dir / ".hydra" / "config.yaml"
+    assert conf.is_file(), conf
+    cfg = yaml.safe_load(open(conf))
+    cfg["dataset"]["data_split"] = "test"
+    return cfg
+
+
+def load_trainer(cfg: dict, output_dir: Path, epoch: int):
+    """The trainer of `cfg` with the checkpoint `models/model_{epoch:05}.pth` of the run loaded."""
+    trainer = instantiate(cfg["trainer"], global_config=cfg, _recursive_=False)
+    trainer.load_pretrained_model(output_dir / "models/model_{:05}.pth".format(epoch))
+    return trainer
+
+
 def main(argv=None) -> None:
     parser = ArgumentParser()
     parser.add_argument("output_dir", type=Path, help="directory path where models and render are located")
@@ -27,10 +43,7 @@ def main(argv=None) -> None:
                              "torch seeds its default generator randomly per process)")
     args = parser.parse_args(argv)
     output_dir = args.output_dir.resolve()
-    conf = output_dir / ".hydra" / "config.yaml"
-    assert conf.is_file(), conf
-    cfg = yaml.safe_load(open(conf))
-    cfg["dataset"]["data_split"] = "test"
+    cfg = load_config(output_dir)
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     if world > 1:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -44,9 +57,8 @@ def main(argv=None) -> None:
         else:
             torch.distributed.init_process_group(backend)
         cfg["trainer"]["device"] = "cuda:%d" % local
-    trainer = instantiate(cfg["trainer"], global_config=cfg, _recursive_=False)
+    trainer = load_trainer(cfg, output_dir, args.epoch)
     trainer.writes_outputs = rank == 0
-    trainer.load_pretrained_model(output_dir / "models/model_{:05}.pth".format(args.epoch))
     save_dir = args.output_dir / "eval"
     if rank == 0:
         save_dir.mkdir(exist_ok=True)
