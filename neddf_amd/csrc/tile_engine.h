@@ -276,10 +276,10 @@ typedef OpsF16SplitT<256> OpsF16Split;
 // (half an fp32 ulp of the product).  Six v_mfma_f32_32x32x16_bf16 per 16 k against eight v_mfma_f32_32x32x2_f32: 2.67x the
 // fp32 matrix rate, and unlike the fp32 MFMA the bf16 one issues beside vector work.
 // Everything that is not a product is OpsF32T's: the fp32 activation tile (kLd = WID + 4), the fp32 epilogues and stores, y'
-// stashed in fp32, the activation mode.  A is read as 8 fp32 k-values per lane (two ds_read_b128) and split in prep(), which
-// the engine calls ONCE per super-step and M-tile inside the product block (dense_mfma): both column tiles take the same
-// three terms, and the LDS read of the next super-step stays in flight across the split (44 vector instructions per
-// 12 MFMAs at MT = NT = 2).  B is three pre-split weight planes, 48 bytes per lane and super-step (neddf_capi.hip pack_layer,
+// stashed in fp32, the activation mode.  A is read as 8 fp32 k-values per lane (two ds_read_b128) and split in prep(), ONCE
+// per super-step and M-tile (both column tiles take the same three terms; 44 vector instructions per 12 MFMAs at MT = NT = 2),
+// one super-step ahead: dense_mfma_split interleaves the split of super-step S + 1 with the MFMAs of S.  B is three
+// pre-split weight planes, 48 bytes per lane and super-step (neddf_capi.hip pack_layer,
 // operands 3): half the weight bytes per MFMA of the bf16 policy.
 // (neither `OpsBF16` nor `OpsF16Split` may appear in this name: the benchmark tells the dtypes apart by those substrings)
 struct f32x8frag {
@@ -297,6 +297,7 @@ struct OpsF32x3T : OpsF32T<WID> {
     typedef bf16x8x3 mfrag;
     static constexpr int kStep = 16;
     static constexpr int kSub = 6;
+    static constexpr int kPrepValu = 44;     // vector instructions of one prep() (dense_mfma_split spreads them over the MFMA gaps)
     static __device__ __forceinline__ afrag load_a(const act_t *p) { return { *(const f32x4v *)p, *(const f32x4v *)(p + 4) }; }
     // v_cvt_pk_bf16_f32 rounds a PAIR to nearest even; the pair's terms come back to fp32 as the word's halves (lo << 16, hi & 0xffff0000).
     // The empty asm keeps the packed word opaque: hipcc otherwise recognises the halves as the single conversions they equal and emits
@@ -512,12 +513,69 @@ __device__ __forceinline__ void dense_pipeline3(f32x16 (&acc)[MT][NT], typename 
     }
 }
 
+// Split policies (Ops::mfrag is not Ops::afrag: OpsF32x3T) split the NEXT super-step's A fragments in the gaps of this super-step's
+// MFMAs: the MFMAs of super-step S take the terms m (split one super-step earlier) while the vector ALU turns an (the LDS fragments of
+// S + 1, requested just before) into mn.  The schedule is fixed by hand: the first round of MFMAs (r = 0, MT x NT of them) covers the
+// LDS read of an, then every further MFMA carries at most kPrepValu * MT / (MFMAs left) split instructions -- 4 per gap at
+// MT = NT = 2, inside the 32-cycle gap of v_mfma_f32_32x32x16_bf16 (MI355X: 8 cycles of the MFMA's own issue + ~4 per VALU).  Without
+// it the split (kPrepValu per M-tile) ran serially in front of the MFMAs that use it.  Same prep(), same MFMA order per accumulator:
+// bit-identical to splitting in front of the products.
+template <class Ops>
+constexpr bool kSplitsA = !std::is_same<typename Ops::afrag, typename Ops::mfrag>::value;
+
+template <int MT, int NT, class Ops>
+__device__ __forceinline__ void dense_mfma_split(f32x16 (&acc)[MT][NT], const typename Ops::mfrag (&m)[MT], const typename Ops::bfrag (&b)[NT],
+                                                 const typename Ops::afrag (&an)[MT], typename Ops::mfrag (&mn)[MT])
+{
+#pragma unroll
+    for (int r = 0; r < Ops::kSub; ++r)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[mt][t] = Ops::mfma(m[mt], b[t], acc[mt][t], r);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) mn[mt] = Ops::prep(an[mt]);
+    constexpr int kMfma = Ops::kSub * MT * NT, kLead = MT * NT;
+    constexpr int kPer = (Ops::kPrepValu * MT + kMfma - kLead - 1) / (kMfma - kLead);
+#pragma unroll
+    for (int i = 0; i < kLead; ++i) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          // MFMA
+#pragma unroll
+    for (int i = kLead; i < kMfma; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                       // MFMA
+        __builtin_amdgcn_sched_group_barrier(0x002, kPer, 0);                                    // VALU (the split)
+    }
+}
+
 template <int MT, int NT, class Ops = OpsF32>
 __device__ __forceinline__ void dense_pipeline(f32x16 (&acc)[MT][NT], typename Ops::afrag (&a0)[MT], typename Ops::bfrag (&b0)[NT],
                                                const typename Ops::act_t *act_lane, const WeightStream &wl, int ksteps)
 {
     if constexpr (Ops::kDeepPrefetch) {
         dense_pipeline3<MT, NT, Ops>(acc, a0, b0, act_lane, wl, ksteps);
+        return;
+    }
+    if constexpr (kSplitsA<Ops>) {
+        typename Ops::afrag a1[MT];
+        typename Ops::bfrag b1[NT];
+        typename Ops::mfrag m0[MT], m1[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) m0[mt] = Ops::prep(a0[mt]);     // the first super-step's split is the only one in the open
+        const typename Ops::act_t *ap = act_lane;
+        for (int S = 0; S < ksteps; S += 2) {
+            const bool more = S + 1 < ksteps;
+            // (as below, A fragments up to two super-steps past the last are read and split, never used)
+            dense_load<MT, NT, Ops>(a1, b1, ap + Ops::kStep, wl, ksteps, more ? S + 1 : S);
+            __builtin_amdgcn_sched_barrier(0);
+            dense_mfma_split<MT, NT, Ops>(acc, m0, b0, a1, m1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) {
+                dense_load<MT, NT, Ops>(a0, b0, ap + 2 * Ops::kStep, wl, ksteps, S + 2 < ksteps ? S + 2 : S);
+                __builtin_amdgcn_sched_barrier(0);
+                dense_mfma_split<MT, NT, Ops>(acc, m1, b1, a0, m0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            ap += 2 * Ops::kStep;
+        }
         return;
     }
     typename Ops::afrag a1[MT];
