@@ -235,3 +235,60 @@ def random_train_render_config(seed):
     c["uv"] = c["uv"][:c["n"]]
     c["n_c"], c["n_f"] = 2 + c["n_c"] % 38, 1 + c["n_f"] % 60
     return c
+
+
+# ---------------------------------------------------------------- full-batch gradient checks (tests/golden/train_large.npz)
+# The NeRF field of the `relu250` records of train_nerf.npz (gen_goldens.gen_train_nerf, test_nerf_field_forward_backward): constructor
+# keywords, the keywords of its `nerf_state` and the iteration it is set to.
+NERF_RELU250 = dict(kw=dict(activation_type="ReLU", density_activation_type="ReLU"), state=dict(seed=11), iteration=500)
+
+FIELD_KEYS = {"neddf": ("distance", "density", "color", "fields_penalty", "aux_grad"), "nerf": ("density", "color"),
+              "neus": ("sdf", "density", "color")}
+
+# case -> (field kind, rays, samples per ray, seed of the points, seed of the upstream gradients, seed of the projection vectors,
+#          whole rows / columns stored per large matrix)
+TRAIN_LARGE_CASES = {
+    "bunny": ("neddf", 1024, 259, 9101, 9201, 9301, 16),
+    "bunny_ragged": ("neddf", 773, 259, 9102, 9202, 9302, 4),
+    "neddf512": ("neddf", 193, 259, 9103, 9203, 9303, 4),
+    "neddf192": ("neddf", 193, 259, 9104, 9204, 9304, 4),
+    "nerf": ("nerf", 507, 259, 9105, 9205, 9305, 4),
+    "neus": ("neus", 193, 259, 9106, 9206, 9306, 4),
+}
+
+
+def per_ray_upstream(keys, n_rays, n_samples, seed, lo=-7.0, hi=-3.0):
+    """Upstream gradients for every output key of a field: standard normal per element times ONE scale per ray, 10 ** uniform(lo, hi), and
+    exactly 0 for about one ray in 16 -- what a mean-over-rays loss with saturated and empty rays hands to the backward pass: neighbouring
+    64-row tiles of one gradient matrix differ by up to 10^4, some are all zero."""
+    rng = np.random.default_rng(seed)
+    scale = 10.0 ** rng.uniform(lo, hi, n_rays)
+    scale[rng.integers(0, 16, n_rays) == 0] = 0.0
+    ups = {}
+    for k in keys:
+        shape = (n_rays, n_samples) + ((3,) if k == "color" else ())
+        ups[k] = (rng.standard_normal(shape) * scale.reshape((n_rays,) + (1,) * (len(shape) - 1))).astype(np.float32)
+    return ups
+
+
+def train_large_inputs(case, kink_points=None):
+    """(pos, dir, var, upstream gradients by key) of one case of train_large.npz, from its seeds.  `kink_points`: flat indices of the
+    points whose upstream gradients are zero (the fixture's list of points on a ReLU kink, gen_goldens.gen_train_large)."""
+    kind, rays, samples, seed_pts, seed_ups = TRAIN_LARGE_CASES[case][:5]
+    pos, d, var = random_sampling(rays, samples, seed_pts, cone=True)
+    ups = per_ray_upstream(FIELD_KEYS[kind], rays, samples, seed_ups)
+    if kink_points is not None and len(kink_points):
+        for v in ups.values():
+            v.reshape((rays * samples,) + v.shape[2:])[kink_points] = 0.0
+    return pos, d, var, ups
+
+
+def input_digest(pos, d, var, ups):
+    """float64 sums of every input array (pos, dir, var, then the upstream gradients in key order) and the sha256 of their bytes."""
+    import hashlib
+    arrs = [pos, d, var] + [ups[k] for k in ups]
+    h = hashlib.sha256()
+    for a in arrs:
+        assert a.dtype == np.float32
+        h.update(np.ascontiguousarray(a).tobytes())
+    return np.array([np.sum(a, dtype=np.float64) for a in arrs]), h.hexdigest()

@@ -1387,6 +1387,173 @@ def gen_negbias():
     save("neddf_negbias_render_rays.npz", **r)
 
 
+def _cross_indices(length, hidden, count):
+    """`count` indices spread over [0, length) plus, where the axis is an input axis wider than the hidden width (a first or skip
+    layer: encoding and hidden units concatenated, in either order), the two indices on each side of both possible boundaries."""
+    idx = set(int(round(x)) for x in np.linspace(0, length - 1, count))
+    if length > hidden:
+        for b in (length - hidden, hidden):
+            idx.update((b - 1, b))
+    return np.array(sorted(i for i in idx if 0 <= i < length), np.int32)
+
+
+def _train_large_module(case, dtype):
+    """The reference module of one case of train_large.npz in `dtype`, its configuration (None for the shipped checkpoint)."""
+    torch.set_default_dtype(dtype)
+    try:
+        if case in ("bunny", "bunny_ragged"):
+            cfg = yaml.safe_load(open(os.path.join(REF, "pretrained/bunny_smoke/.hydra/config.yaml")))
+            kw = dict(cfg["network"], density_activation_type="ReLU")           # TRAIN_CFG of tests/test_gpu_train.py (see gen_train)
+            kw.pop("_target_")
+            net = NeDDF(**kw)
+            ck = torch.load(os.path.join(REF, "pretrained/bunny_smoke/models/model_02000.pth"), map_location="cpu")
+            sd = {k[len("network_fine."):]: v for k, v in ck.items() if k.startswith("network_fine.")}
+            it = 1500
+        elif case in ("neddf512", "neddf192"):
+            fx, seed = ("train_wide.npz", 37) if case == "neddf512" else ("train_widths.npz", 29)
+            kw = json.loads(str(np.load(os.path.join(HERE, fx))[case + "_config"]))
+            net = NeDDF(**kw)
+            sd = to_torch_sd(synth.neddf_state(kw["embed_pos_rank"], kw["embed_dir_rank"], kw["ddf_layer_count"], kw["ddf_layer_width"],
+                                               kw["col_layer_count"], kw["col_layer_width"], tuple(kw["skips"]), seed=seed))
+            it = 2500
+        elif case == "nerf":
+            kw = dict(synth.NERF_RELU250["kw"])
+            net = NeRF(**kw)
+            sd = to_torch_sd(synth.nerf_state(**synth.NERF_RELU250["state"]))
+            it = synth.NERF_RELU250["iteration"]
+        else:
+            kw = json.loads(str(np.load(os.path.join(HERE, "train_neus.npz"))["fb_tanhexp_config"]))
+            net = NeuS(**kw)
+            sd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth.neus_state(
+                kw["embed_pos_rank"], kw["embed_dir_rank"], kw["sdf_layer_count"], kw["sdf_layer_width"], kw["col_layer_count"],
+                kw["col_layer_width"], tuple(kw["skips"]), kw["init_variance"], seed=13).items()}
+            it = None
+        net.load_state_dict({k: v.to(dtype) for k, v in sd.items()})
+        if it is not None:
+            net.set_iter(it)
+        assert all(p_.dtype == dtype for p_ in net.parameters())
+        return net, kw
+    finally:
+        torch.set_default_dtype(torch.float32)
+
+
+def _sliced_gradients(net, dtype, pos, d, var, ups, step=4096):
+    """Parameter gradients of sum(output * upstream) over all points, accumulated over slices of `step` points (a parameter gradient
+    is a sum over points: no slice ever holds more than `step` points' activations)."""
+    torch.set_default_dtype(dtype)
+    try:
+        flat = [torch.from_numpy(a.reshape(-1, 1, 3)).to(dtype) for a in (pos, d, var)]
+        fups = {k: torch.from_numpy(v.reshape((-1, 1) + v.shape[2:])).to(dtype) for k, v in ups.items()}
+        net.zero_grad()
+        with torch.enable_grad():
+            for b in range(0, flat[0].shape[0], step):
+                o = net(Sampling(*(a[b:b + step].clone() for a in flat)))
+                sum((o[k] * fups[k][b:b + step]).sum() for k in fups).backward()
+        return {k: npy(p_.grad).astype(np.float64) for k, p_ in net.named_parameters()}
+    finally:
+        torch.set_default_dtype(torch.float32)
+
+
+def _kink_points(net, pos, d, var, margin=1e-5, step=4096):
+    """Flat indices of the points at which some linear layer's output (value rows) lies within `margin` of 0 in the fp64 run: the
+    pre-activations on whose sign a ReLU / LeakyReLU network's gradient depends discontinuously."""
+    torch.set_default_dtype(torch.float64)
+    hit, handles = [], []
+
+    def hook(mod, inp, out):
+        x = out[0] if isinstance(out, tuple) else out
+        hit[-1] |= (x.detach().abs() < margin).reshape(hit[-1].shape[0], -1).any(1)
+    try:
+        for m in net.modules():
+            if type(m).__name__ in ("Linear", "LinearGradLayer"):
+                handles.append(m.register_forward_hook(hook))
+        flat = [torch.from_numpy(a.reshape(-1, 1, 3)).double() for a in (pos, d, var)]
+        with torch.enable_grad():       # NeuS differentiates inside its forward
+            for b in range(0, flat[0].shape[0], step):
+                hit.append(torch.zeros(flat[0][b:b + step].shape[0], dtype=torch.bool))
+                net(Sampling(*(a[b:b + step].clone() for a in flat)))
+        return torch.cat(hit).numpy().nonzero()[0].astype(np.int32)
+    finally:
+        for h in handles:
+            h.remove()
+        torch.set_default_dtype(torch.float32)
+
+
+def gen_train_large():
+    """Parameter gradients at the training benchmark's batch size in DOUBLE precision (tests/test_gpu_train.py test_large_batch_*).  Per case
+    of synth.TRAIN_LARGE_CASES the reference module runs twice, in torch.float64 and in torch.float32 (same code, same weights), each in
+    slices of 4 096 points with `.grad` accumulating, on synth.train_large_inputs(case): seeded cone samples and upstream gradients on every
+    output with one scale per ray out of 10^-7 .. 10^-3 (one ray in 16: exactly 0).  The fixture holds no points, only a digest of them --
+    and, for the ReLU networks, a bit mask of the points that sit on a kink and whose upstream gradient is therefore zero (`kink_mask`).
+
+    Stored per parameter tensor from the fp64 run: norm and eight projections on seeded standard-normal vectors (`scalars`), the tensor itself when it has
+    at most 4 096 entries, else a cross of whole rows and whole columns (`rows_`, `cols_`: spread over the axis, plus both sides of the
+    encoding / hidden boundary of first and skip layers; every 32-wide k and n tile of the matrix lies on the cross).  `bunny` stores 16
+    rows and 16 columns per matrix; the other cases 4 and 4 (plus the boundary ones) -- 16 + 16 everywhere would be 2.3 MB of float32 against
+    the 1 MB a committed fixture may have; the eight projections see every entry in every case.  The last three columns of `scalars`: the
+    deviation of the fp32 reference run from the fp64 one in the same three measures (the tests' `ref32_*`).
+
+    Asserted here: the fp32 reference itself passes the test's gates (1e-4 norm, 3e-4 projections, 1e-4 entries) at tol = 0.5 against
+    its fp64 run, for every case and tensor.  A tensor that does not is listed under `loose_<case>` (and then gated at 2 x its ref32
+    deviation); more than two per case fail the generator."""
+    arrs, too_loose = {}, {}
+    for case, (kind, rays, samples, _, _, seed_proj, n_cross) in synth.TRAIN_LARGE_CASES.items():
+        import time
+        t0 = time.time()
+        net64, kw = _train_large_module(case, torch.float64)
+        pos, d, var, ups = synth.train_large_inputs(case)
+        # ReLU / LeakyReLU trunks: the gradient jumps where a pre-activation changes sign, and with (value, Jacobian) rows so do the
+        # outputs (measured on neddf512: the fp32 reference is 1e-7 from its fp64 run at the median point and 2e-3 at one in a thousand,
+        # and its summed gradients 1e-3).  Two correct fp32 evaluations may land on either side, so the points within 1e-5 of a kink
+        # (10x the fp32 error of a pre-activation) get a zero upstream gradient: they run through every kernel but decide nothing.
+        kink = _kink_points(net64, pos, d, var) if kw.get("activation_type", "ReLU") != "tanhExp" else np.zeros(0, np.int32)
+        pos, d, var, ups = synth.train_large_inputs(case, kink)
+        sums, sha = synth.input_digest(pos, d, var, ups)
+        g64 = _sliced_gradients(net64, torch.float64, pos, d, var, ups)
+        shapes = {k: tuple(p_.shape) for k, p_ in net64.named_parameters()}
+        del net64
+        net32, _ = _train_large_module(case, torch.float32)
+        g32 = _sliced_gradients(net32, torch.float32, pos, d, var, ups)
+        del net32
+        pre = case + "_"
+        hidden = max(set(s[-1] for s in shapes.values() if len(s) == 2), key=[s[-1] for s in shapes.values() if len(s) == 2].count)
+        arrs.update({pre + "config": np.array(json.dumps(kw)), pre + "param_names": np.array(json.dumps(list(g64))),
+                     pre + "points": np.array([rays, samples], np.int64), pre + "kink_mask": np.packbits(np.isin(np.arange(rays * samples), kink)), pre + "digest_sums": sums, pre + "digest_sha256": np.array(sha)})
+        proj = np.random.default_rng(seed_proj)
+        loose, scal = [], []
+        for k, a in g64.items():
+            b = g32[k]
+            assert a.shape == shapes[k] == b.shape and np.isfinite(a).all() and np.isfinite(b).all(), k
+            pv = proj.standard_normal((8,) + a.shape)
+            gn = float(np.linalg.norm(a))
+            assert gn > 0, k
+            pa, pb = (pv * a).reshape(8, -1).sum(1), (pv * b).reshape(8, -1).sum(1)
+            scal.append(np.concatenate([[gn], pa]))
+            if a.size <= 4096:
+                arrs[pre + "grad_" + k] = a.astype(np.float32)
+                sa, sb = a.reshape(-1), b.reshape(-1)
+            else:
+                rows, cols = _cross_indices(a.shape[0], hidden, n_cross), _cross_indices(a.shape[1], hidden, n_cross)
+                arrs.update({pre + "rows_" + k: rows, pre + "cols_" + k: cols, pre + "grows_" + k: a[rows].astype(np.float32),
+                             pre + "gcols_" + k: a[:, cols].astype(np.float32)})
+                sa, sb = np.concatenate([a[rows].reshape(-1), a[:, cols].reshape(-1)]), np.concatenate([b[rows].reshape(-1), b[:, cols].reshape(-1)])
+            dn, dp, de = abs(float(np.linalg.norm(b)) - gn) / gn, float(np.abs(pb - pa).max()) / gn, float(np.abs(sb - sa).max() / np.abs(sa).max())
+            scal[-1] = np.concatenate([scal[-1], [dn, dp, de]])
+            ok = dn <= 0.5 * 1e-4 and dp <= 0.5 * 3e-4 and de <= 0.5 * 1e-4
+            print("  %-14s %-24s |g| %.3e  fp32 reference vs fp64: norm %.2e  proj %.2e  entry %.2e%s" % (case, k, gn, dn, dp, de, "" if ok else "   LOOSE"))
+            if not ok:
+                loose.append(k)
+        too_loose.update({case: loose} if len(loose) > 2 else {})
+        arrs[pre + "scalars"] = np.stack(scal)       # per tensor, in the order of param_names: norm, 8 projections, ref32 norm / proj / entry
+        arrs["loose_" + case] = np.array(json.dumps(loose))
+        print("train_large %s: %d points (%d at a kink), %.0f s" % (case, rays * samples, kink.size, time.time() - t0), flush=True)
+    assert not too_loose, "more than two tensors of the fp32 reference miss the gates at tol 0.5 -- change the inputs: %s" % too_loose
+    arrs["cases"] = np.array(json.dumps(list(synth.TRAIN_LARGE_CASES)))
+    np.savez_compressed(os.path.join(HERE, "train_large.npz"), **arrs)
+    print("wrote train_large.npz (%.1f KB)" % (os.path.getsize(os.path.join(HERE, "train_large.npz")) / 1024))
+    assert os.path.getsize(os.path.join(HERE, "train_large.npz")) < 1000000
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "train_nerf":
         gen_train_nerf()
@@ -1434,6 +1601,10 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "fp64":
         gen_fp64()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "train_large":
+        from neddf.ray import Sampling  # noqa: F401
+        gen_train_large()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "fields":
         from neddf.ray import Sampling  # noqa: F401  (gen_bunny normally imports the reference first)
         gen_fields()
@@ -1476,4 +1647,5 @@ if __name__ == "__main__":
     gen_stages_random()
     gen_rays_random()
     gen_train_render_random()
+    gen_train_large()   # reads train_wide / train_widths / train_neus.npz written above
     gen_eval_harness()  # replaces cv2.imwrite / skimage / tensorboard stubs: keep it last
