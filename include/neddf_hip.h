@@ -32,7 +32,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define NEDDF_ABI_VERSION 6
+#define NEDDF_ABI_VERSION 7
 
 enum { NEDDF_OK = 0, NEDDF_EINVAL = -1, NEDDF_EHIP = -2, NEDDF_EUNSUPPORTED = -3, NEDDF_ENOFIELD = -4,
        NEDDF_ECOMM = -5,      /* RCCL reported an error (message in neddf_last_error) or is not loadable */
@@ -325,6 +325,38 @@ int neddf_train_field_backward(neddf_ctx *ctx, int slot, const float *const *d_W
                                int64_t n_points, const float *d_workspace, const float *d_g_distance,
                                const float *d_g_density, const float *d_g_color, const float *d_g_fields_penalty,
                                const float *d_g_aux_grad, float *const *d_gW, float *const *d_gB, void *stream);
+/* ---- pose gradients (ABI v7) --------------------------------------------------------------------------------------
+ * In the reference the rays come from camera.R / camera.T through differentiable torch ops, so a loss reaches Camera.params.
+ * These three entry points are that chain: field inputs, sampler, ray generation.  Reductions run in a fixed order (no
+ * floating-point atomics): the results are bitwise repeatable.
+ *
+ * neddf_train_field_backward plus the gradients of the forward's sample inputs, d_g_pos / d_g_dir / d_g_var ([n_points, 3],
+ * OVERWRITTEN, any may be NULL); d_pos / d_dir / d_var are the arrays the forward call was given.  Differentiates NeDDF.forward
+ * (neddf.py:186-257): embed_pos_scaled into distance layer 0 and every skip layer, embed_pos and embed_dir into colour layer 0
+ * (value and Jacobian rows, the second-derivative terms of the Jacobian rows included); norm_dir is detached and sample_pos_grad
+ * is the constant identity.  d_g_var is ZERO: Sampling.get_pe_weights (ray/sampling.py:44-71) runs with gradients disabled in the
+ * reference, which makes the cone weights constants of its autograd.  The parameter gradients are bit for bit those of
+ * neddf_train_field_backward.  The new products run on the fp32 MFMA path.  NeRF fields (nerf.py:139-159) take the same call with value
+ * rows only: embed_pos into layer 0 and after every skip layer, embed_dir into the colour head.  NEDDF_EUNSUPPORTED for NeuS (a
+ * third derivative of the sdf trunk) and for a field loaded under the split-fp16 operand policy. */
+int neddf_train_field_backward_inputs(neddf_ctx *ctx, int slot, const float *const *d_W, const float *const *d_B, int n_tensors,
+                                      int64_t n_points, const float *d_workspace, const float *d_pos, const float *d_dir,
+                                      const float *d_var, const float *d_g_distance, const float *d_g_density,
+                                      const float *d_g_color, const float *d_g_fields_penalty, const float *d_g_aux_grad,
+                                      float *const *d_gW, float *const *d_gB, float *d_g_pos, float *d_g_dir, float *d_g_var,
+                                      void *stream);
+/* Backward of neddf_sampling with respect to the ray (Ray.get_sampling_cones ray.py:128-194, get_sampling_points ray.py:88-126):
+ * pos = o + d t, dir = d, cone var = t_var d^2 + r_var (1 - d^2).  d_g_pos / d_g_dir / d_g_var [n_rays, S, 3] (any may be NULL)
+ * -> d_g_ray_dir, d_g_ray_orig [n_rays, 3].  The distances are not differentiated (the reference draws them under no_grad).
+ * radius < 0: point samples. */
+int neddf_sampling_backward(neddf_ctx *ctx, const float *d_g_pos, const float *d_g_dir, const float *d_g_var, const float *d_ray_dir,
+                            const float *d_dists, int64_t n_rays, int S, double radius, float *d_g_ray_dir, float *d_g_ray_orig,
+                            void *stream);
+/* Backward of neddf_raygen with respect to the pose (Camera.create_rays camera.py:155-171: ray_dir = R c(uv), ray_orig = T):
+ * d_g_RT[12] (DEVICE) = g_R [3][3] row-major = sum_b g_ray_dir[b] (x) c_b, then g_T [3] = sum_b g_ray_orig[b].  The intrinsics
+ * are not differentiated. */
+int neddf_raygen_backward(neddf_ctx *ctx, const void *d_uv, int uv_type, int64_t n, const neddf_camera *cam, const float *d_g_ray_dir,
+                          const float *d_g_ray_orig, float *d_g_RT, void *stream);
 /* Backward of integrate_volume_render (base_neural_render.py:148-171): gradients of weight [n_rays,S-1],
  * depth [n_rays], color [n_rays,3], transmittance [n_rays] (any may be NULL) -> d_g_density [n_rays,S],
  * d_g_point_color [n_rays,S,3]. */

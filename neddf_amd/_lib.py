@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NEDDF_LIB_PATH selects another build of the same library (the sanitizer build, `make -C neddf_amd/csrc asan`)
 LIB_PATH = os.environ.get("NEDDF_LIB_PATH") or os.path.join(_HERE, "csrc", "libneddf_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 FIELD_NEDDF, FIELD_NERF, FIELD_NEUS = 0, 1, 2
 ACT = {"ReLU": 0, "LeakyReLU": 1, "tanhExp": 2}
@@ -106,6 +106,10 @@ SYMBOLS = [
                                             _vp, _vp, _vp, _vp, _vp, _vp]),
     ("neddf_train_field_backward", C.c_int, [_vp, C.c_int, C.POINTER(_fp), C.POINTER(_fp), C.c_int, _i64, _vp, _vp, _vp, _vp,
                                              _vp, _vp, C.POINTER(_fp), C.POINTER(_fp), _vp]),
+    ("neddf_train_field_backward_inputs", C.c_int, [_vp, C.c_int, C.POINTER(_fp), C.POINTER(_fp), C.c_int, _i64, _vp, _vp, _vp, _vp,
+                                                    _vp, _vp, _vp, _vp, _vp, C.POINTER(_fp), C.POINTER(_fp), _vp, _vp, _vp, _vp]),
+    ("neddf_sampling_backward", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, C.c_int, C.c_double, _vp, _vp, _vp]),
+    ("neddf_raygen_backward", C.c_int, [_vp, _vp, C.c_int, _i64, C.POINTER(CameraDesc), _vp, _vp, _vp, _vp]),
     ("neddf_composite_backward", C.c_int, [_vp, _vp, _vp, _vp, _i64, C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("neddf_field_grid", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _vp, _vp]),
     ("neddf_marching_cubes", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_float, _vp, _i64, _vp, _i64,
@@ -464,8 +468,9 @@ class Context:
             _guard_check(ws._base[n_ws:], "the training workspace (forward)")
         return ws, distance, density, color, pen, aux
 
-    def train_field_backward(self, slot, weights, biases, N, ws, g_distance, g_density, g_color, g_penalty, g_aux):
-        """Returns (grad_weights, grad_biases) in the layout of `weights` / `biases`."""
+    def train_field_backward(self, slot, weights, biases, N, ws, g_distance, g_density, g_color, g_penalty, g_aux, inputs=None):
+        """Returns (grad_weights, grad_biases) in the layout of `weights` / `biases`.  `inputs` = the forward's (pos, dir, var):
+        additionally returns (g_pos, g_dir, g_var), each [N, 3] (neddf_train_field_backward_inputs)."""
         gs = [None if g is None else f32c(g) for g in (g_distance, g_density, g_color, g_penalty, g_aux)]
         # one zero fill for all gradients (the kernels accumulate into them): views into a flat buffer, 16-byte aligned pieces
         offs, at = [], 0
@@ -481,15 +486,58 @@ class Context:
         gw, gb = views[:len(weights)], views[len(weights):]
         wa, ba = self._dev_ptrs(weights, "weights"), self._dev_ptrs(biases, "biases")
         gwa, gba = self._dev_ptrs(gw, "weight gradients"), self._dev_ptrs(gb, "bias gradients")
-        self.check(self.lib.neddf_train_field_backward(self.h, slot, wa, ba, len(weights), N, _ptr(ws), _ptr(gs[0]), _ptr(gs[1]),
-                                                       _ptr(gs[2]), _ptr(gs[3]), _ptr(gs[4]), gwa, gba, self.stream()))
+        g_in = None
+        if inputs is None:
+            self.check(self.lib.neddf_train_field_backward(self.h, slot, wa, ba, len(weights), N, _ptr(ws), _ptr(gs[0]), _ptr(gs[1]),
+                                                           _ptr(gs[2]), _ptr(gs[3]), _ptr(gs[4]), gwa, gba, self.stream()))
+        else:
+            pos, dir, var = (f32c(t).reshape(-1, 3) for t in inputs)
+            if pos.shape[0] != N or dir.shape[0] != N or var.shape[0] != N:
+                raise NeddfError("input gradients: pos / dir / var must be the forward call's [N, 3] tensors")
+            g_in = tuple(torch.empty(N, 3, device=pos.device, dtype=torch.float32) for _ in range(3))
+            self.check(self.lib.neddf_train_field_backward_inputs(self.h, slot, wa, ba, len(weights), N, _ptr(ws), _ptr(pos), _ptr(dir),
+                                                                  _ptr(var), _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), _ptr(gs[3]),
+                                                                  _ptr(gs[4]), gwa, gba, _ptr(g_in[0]), _ptr(g_in[1]), _ptr(g_in[2]),
+                                                                  self.stream()))
         if _GUARD:
             for i, (o, t) in enumerate(zip(offs, list(weights) + list(biases))):
                 e = o + ((t.numel() + 3) & ~3)
                 _guard_check(flat[e:e + gap], "gradient tensor %d" % i)
             if ws._base is not None:
                 _guard_check(ws._base[ws.numel():], "the training workspace (backward)")
+        if g_in is not None:
+            return gw, gb, g_in
         return gw, gb
+
+    def sampling_backward(self, g_pos, g_dir, g_var, ray_dir, dists, ray_radius):
+        """Backward of `sampling` with respect to the ray: [B, S, 3] sample gradients (any may be None) -> g_ray_dir, g_ray_orig [B, 3]."""
+        require_device(dists, "dists")
+        ray_dir, dists = f32c(ray_dir), f32c(dists)
+        B, S = dists.shape
+        gs = [None if g is None else f32c(g) for g in (g_pos, g_dir, g_var)]
+        for g in gs:
+            if g is not None and g.numel() != B * S * 3:
+                raise NeddfError("sampling_backward: sample gradients must be [B, S, 3]")
+        g_rd = torch.empty(B, 3, device=dists.device, dtype=torch.float32)
+        g_ro = torch.empty_like(g_rd)
+        radius = -1.0 if ray_radius is None else float(ray_radius)
+        self.check(self.lib.neddf_sampling_backward(self.h, _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), _ptr(ray_dir), _ptr(dists), B, S,
+                                                    radius, _ptr(g_rd), _ptr(g_ro), self.stream()))
+        return g_rd, g_ro
+
+    def raygen_backward(self, uv, cam, g_ray_dir, g_ray_orig):
+        """Backward of `raygen` with respect to the pose: g_R [3, 3], g_T [3] (device tensors)."""
+        require_device(uv, "uv")
+        if uv.dtype not in UV_TYPES:
+            uv = uv.to(torch.float32)
+        uv = uv.contiguous()
+        g_rd, g_ro = f32c(g_ray_dir), f32c(g_ray_orig)
+        if g_rd.shape != (uv.shape[0], 3) or g_ro.shape != (uv.shape[0], 3):
+            raise NeddfError("raygen_backward: ray gradients must be [B, 3]")
+        out = torch.empty(12, device=uv.device, dtype=torch.float32)
+        self.check(self.lib.neddf_raygen_backward(self.h, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0], C.byref(cam), _ptr(g_rd),
+                                                  _ptr(g_ro), _ptr(out), self.stream()))
+        return out[:9].view(3, 3), out[9:]
 
     def composite_backward(self, dists, density, color, max_dist, g_weight, g_depth, g_color, g_trans):
         dists, density, color = f32c(dists), f32c(density), f32c(color)

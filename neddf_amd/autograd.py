@@ -7,6 +7,11 @@ The reference trains through torch autograd over its with_grad modules
 forward and backward are HIP kernels behind the C ABI
 (neddf_train_field_forward / _backward, neddf_composite / _composite_backward);
 torch only carries the small per-ray tensors between them and into the losses.
+
+Pose gradients (opt-in, `render.pose_gradients = True`): the reference builds its rays from camera.R / camera.T with
+differentiable torch ops, so its loss reaches Camera.params.  Here that chain is three more nodes over HIP kernels --
+FieldFunction's input gradients, SamplingFunction, RayFunction -- and torch carries g_R / g_T through Rodrigues
+(Camera.update_transform) to the six pose parameters.
 """
 from typing import Tuple
 
@@ -19,8 +24,11 @@ from ._lib import Context
 class FieldFunction(torch.autograd.Function):
     """NeDDF.forward (neddf.py:162-309) on [N,3] samples -> distance, density, color, fields_penalty, aux_grad.
 
-    Gradients flow to the parameters only: sample positions come out of the
-    (non-differentiable) sampler, exactly as in the reference's render_rays."""
+    Gradients flow to the parameters and, when pos / dir / var require them, to the sample inputs
+    (neddf_train_field_backward_inputs): in the reference the samplers are differentiable torch ops, so the loss reaches the
+    rays and the camera pose through them.  The gradient of var is zero, as in the reference (get_pe_weights runs with
+    gradients disabled, sampling.py:55).  Inputs that do not require a gradient cost nothing: the parameter-only kernel
+    path runs, bit for bit as before."""
 
     @staticmethod
     def forward(ctx, hip: Context, slot: int, iter_state, n_tensors: int, pos: Tensor, dir: Tensor, var: Tensor,
@@ -30,17 +38,26 @@ class FieldFunction(torch.autograd.Function):
         hip.set_iter(slot, *iter_state)
         ws, distance, density, color, penalty, aux = hip.train_field_forward(slot, weights, biases, pos, dir, var)
         ctx.hip, ctx.slot, ctx.iter_state, ctx.n_tensors, ctx.n_points = hip, slot, iter_state, n_tensors, distance.shape[0]
-        ctx.save_for_backward(ws, *params)
+        ctx.input_grads = any(ctx.needs_input_grad[4:7])
+        ctx.save_for_backward(ws, *((pos, dir, var) if ctx.input_grads else ()), *params)
         return distance, density, color, penalty, aux
 
     @staticmethod
     def backward(ctx, g_distance, g_density, g_color, g_penalty, g_aux):
         ws, *params = ctx.saved_tensors
+        inputs = None
+        if ctx.input_grads:
+            inputs, params = tuple(t.detach() for t in params[:3]), params[3:]
         n = ctx.n_tensors
         weights = [p.detach() for p in params[:n]]
         biases = [p.detach() for p in params[n:]]
         ctx.hip.set_iter(ctx.slot, *ctx.iter_state)
         with torch.cuda.device(ws.device):
+            if ctx.input_grads:
+                gw, gb, g_in = ctx.hip.train_field_backward(ctx.slot, weights, biases, ctx.n_points, ws, g_distance, g_density,
+                                                            g_color, g_penalty, g_aux, inputs=inputs)
+                g_in = tuple(g.view(t.shape) if need else None for g, t, need in zip(g_in, inputs, ctx.needs_input_grad[4:7]))
+                return (None,) * 4 + g_in + tuple(gw) + tuple(gb)
             gw, gb = ctx.hip.train_field_backward(ctx.slot, weights, biases, ctx.n_points, ws, g_distance, g_density, g_color,
                                                   g_penalty, g_aux)
         return (None,) * 7 + tuple(gw) + tuple(gb)
@@ -59,17 +76,26 @@ class RadianceFieldFunction(torch.autograd.Function):
         hip.set_iter(slot, *iter_state)
         ws, _, density, color, _, _ = hip.train_field_forward(slot, weights, biases, pos, dir, var, radiance_only=True)
         ctx.hip, ctx.slot, ctx.iter_state, ctx.n_tensors, ctx.n_points = hip, slot, iter_state, n_tensors, density.shape[0]
-        ctx.save_for_backward(ws, *params)
+        ctx.input_grads = any(ctx.needs_input_grad[4:7])        # as FieldFunction: gradients of pos / dir (var: zero)
+        ctx.save_for_backward(ws, *((pos, dir, var) if ctx.input_grads else ()), *params)
         return density, color
 
     @staticmethod
     def backward(ctx, g_density, g_color):
         ws, *params = ctx.saved_tensors
+        inputs = None
+        if ctx.input_grads:
+            inputs, params = tuple(t.detach() for t in params[:3]), params[3:]
         n = ctx.n_tensors
         weights = [p.detach() for p in params[:n]]
         biases = [p.detach() for p in params[n:]]
         ctx.hip.set_iter(ctx.slot, *ctx.iter_state)
         with torch.cuda.device(ws.device):
+            if ctx.input_grads:
+                gw, gb, g_in = ctx.hip.train_field_backward(ctx.slot, weights, biases, ctx.n_points, ws, None, g_density, g_color, None,
+                                                            None, inputs=inputs)
+                g_in = tuple(g.view(t.shape) if need else None for g, t, need in zip(g_in, inputs, ctx.needs_input_grad[4:7]))
+                return (None,) * 4 + g_in + tuple(gw) + tuple(gb)
             gw, gb = ctx.hip.train_field_backward(ctx.slot, weights, biases, ctx.n_points, ws, None, g_density, g_color, None, None)
         return (None,) * 7 + tuple(gw) + tuple(gb)
 
@@ -82,6 +108,8 @@ class SdfFieldFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hip: Context, slot: int, n_tensors: int, pos: Tensor, dir: Tensor, *params: Tensor) -> Tuple[Tensor, ...]:
+        if any(ctx.needs_input_grad[3:5]):
+            raise NotImplementedError("pose gradients through a NeuS field need a third derivative of the sdf trunk: not implemented")
         weights = [p.detach() for p in params[:n_tensors]]
         biases = [p.detach() for p in params[n_tensors:]]
         ws, sdf, density, color, _, _ = hip.train_field_forward(slot, weights, biases, pos, dir, torch.zeros_like(pos),
@@ -119,3 +147,41 @@ class CompositeFunction(torch.autograd.Function):
             g_density, g_point_color = ctx.hip.composite_backward(dists, densities, colors, ctx.max_dist, g_weight, g_depth,
                                                                   g_color, g_trans)
         return None, None, None, g_density, g_point_color
+
+
+class SamplingFunction(torch.autograd.Function):
+    """Ray.get_sampling_cones (ray.py:128-194) / get_sampling_points (ray.py:88-126) with the ray differentiable:
+    (ray_dir, ray_orig) [B,3] -> (pos, dir, var) [B,S,3].  The distances are not differentiated, as in the reference (stratified
+    uniforms and sample_pdf output under no_grad)."""
+
+    @staticmethod
+    def forward(ctx, hip: Context, ray_dir: Tensor, ray_orig: Tensor, dists: Tensor, radius):
+        pos, d, var = hip.sampling(ray_dir, ray_orig, dists, radius)
+        ctx.hip, ctx.radius = hip, radius
+        ctx.save_for_backward(ray_dir, dists)
+        return pos, d, var
+
+    @staticmethod
+    def backward(ctx, g_pos, g_dir, g_var):
+        ray_dir, dists = ctx.saved_tensors
+        with torch.cuda.device(dists.device):
+            g_rd, g_ro = ctx.hip.sampling_backward(g_pos, g_dir, g_var, ray_dir, dists, ctx.radius)
+        return None, g_rd, g_ro, None, None
+
+
+class RayFunction(torch.autograd.Function):
+    """Camera.create_rays (camera.py:155-171) with the pose differentiable: (R [3,3], T [3]) -> (ray_dir, ray_orig) [B,3].
+    `cam` is the POD descriptor built from the same R and T; the intrinsics are not differentiated."""
+
+    @staticmethod
+    def forward(ctx, hip: Context, uv: Tensor, cam, R: Tensor, T: Tensor):
+        rd, ro = hip.raygen(uv, cam)
+        ctx.hip, ctx.cam = hip, cam
+        ctx.save_for_backward(uv)
+        return rd, ro
+
+    @staticmethod
+    def backward(ctx, g_rd, g_ro):
+        with torch.cuda.device(g_rd.device):
+            g_R, g_T = ctx.hip.raygen_backward(ctx.saved_tensors[0], ctx.cam, g_rd, g_ro)
+        return None, None, None, g_R, g_T

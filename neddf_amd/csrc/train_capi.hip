@@ -10,6 +10,7 @@
 #include "train_kernels.h"
 
 #include <stdlib.h>
+#include <string.h>
 
 namespace {
 
@@ -223,8 +224,15 @@ int nerf_forward(neddf_ctx *ctx, int slot, const float *const *W, const float *c
     return 0;
 }
 
+// the forward's sample inputs and the input-gradient outputs of neddf_train_field_backward_inputs (NULL: parameter gradients only --
+// then not one launch, allocation or byte of the pass below differs from what it was before these outputs existed)
+struct InputGrads {
+    const float *pos, *dir, *var;
+    float *g_pos, *g_dir, *g_var;
+};
+
 int nerf_backward(neddf_ctx *ctx, int slot, const float *const *W, int n_tensors, int64_t N, float *ws, const float *g_density,
-                  const float *g_color, float *const *gW, float *const *gB, hipStream_t s)
+                  const float *g_color, float *const *gW, float *const *gB, const InputGrads *ig, hipStream_t s)
 {
     NerfPlan p;
     if (int rc = make_nerf_plan(ctx, slot, N, n_tensors, p)) return rc;
@@ -232,9 +240,24 @@ int nerf_backward(neddf_ctx *ctx, int slot, const float *const *W, int n_tensors
     const int act = f.d.activation, cus = ctx->cus, WH = p.WH, NBK = WH / kWidth, HC = p.HC;
     const int sp = f.d.weight_dtype == NEDDF_DTYPE_F16_SPLIT;
     if (int rc = ensure(ctx, ctx->tpack, 2 * kPackFloats * sizeof(float))) return rc;
-    if (int rc = ensure(ctx, ctx->ttmp, (size_t)N * (2 * WH + 2 * kLdNarrow) * sizeof(float))) return rc;
+    // input gradients (ig): this route reuses dA / dB from layer to layer, so the gradient matrices of the layers that read an encoding
+    // (the colour head's first layer, layer 0, the layers after a skip) are copied aside as they appear, for launch_enc_input_grad
+    int n_keep = 0;
+    if (ig) {
+        n_keep = 2;
+        for (int l = 1; l < p.n; ++l) n_keep += in_skips(f.d, l - 1) ? 1 : 0;
+    }
+    if (int rc = ensure(ctx, ctx->ttmp, (size_t)N * ((2 + n_keep) * WH + 2 * kLdNarrow) * sizeof(float))) return rc;
     float *wp = (float *)ctx->tpack.p;
     float *dA = (float *)ctx->ttmp.p, *dB = dA + (size_t)N * WH, *GC = dB + (size_t)N * WH, *GD = GC + (size_t)N * kLdNarrow;
+    float *keep_at = GD + (size_t)N * kLdNarrow;
+    EncGradArgs eg{};
+    auto keep = [&](const float *dZ, int ld, int nk, const float *Wseg, int64_t sk, int ncols, int col0) -> int {
+        HIPCHK(hipMemcpyAsync(keep_at, dZ, (size_t)N * ld * sizeof(float), hipMemcpyDeviceToDevice, s));
+        eg.seg[eg.n_seg++] = EncGradSeg{ keep_at, 0, 1, ld, nk, Wseg, 1, sk, ncols, col0, 1 };
+        keep_at += (size_t)N * ld;
+        return 0;
+    };
     const float *PE = ws + p.o_pe, *Ed = ws + p.o_ed, *Hlast = ws + p.o_h[p.n - 1];
     HIPCHK(hipMemsetAsync(GC, 0, (size_t)N * 2 * kLdNarrow * sizeof(float), s));      // GC and GD
     if (g_color) launch_copy3(g_color, 3, GC, kLdNarrow, N, s);
@@ -246,6 +269,7 @@ int nerf_backward(neddf_ctx *ctx, int slot, const float *const *W, int n_tensors
     if (int rc = amax_begin(ctx, sp, am, s)) return rc;
     float *mA = am.take();          // max |dA| of the gradient matrix currently in dA
     launch_narrow_backward_act(GC, kLdNarrow, N, c1, nullptr, 0, NEDDF_ACT_RELU, 1, ws + p.o_zc, dA, kWidth, s, mA);
+    if (ig) if (int rc = keep(dA, kWidth, HC, W[p.i_c0] + WH, p.in_c0, p.Cdir, p.Cpe)) return rc;       // embed_dir columns of the colour head
     {
         float *wc[3] = { gW[p.i_c1], gW[p.i_c1] + HC, gW[p.i_c1] + 2 * HC }, *bc[3] = { gB[p.i_c1], gB[p.i_c1] + 1, gB[p.i_c1] + 2 };
         launch_narrow_dw(ws + p.o_hc, kWidth, GC, kLdNarrow, N, 3, wc, 1, bc, 1, HC, s);
@@ -280,6 +304,7 @@ int nerf_backward(neddf_ctx *ctx, int slot, const float *const *W, int n_tensors
     for (int l = p.n - 1; l >= 0; --l) {
         const bool wide = l > 0 && in_skips(f.d, l - 1);
         const int in_total = l == 0 ? p.Cpe : (wide ? WH + p.Cpe : WH);
+        if (ig && (l == 0 || wide)) if (int rc = keep(dA, WH, WH, W[l] + (l == 0 ? 0 : WH), in_total, p.Cpe, 0)) return rc;
         if (l == 0) {
             dw_blocks(PE, kLdPe, p.Cpe, gW[0], in_total, 0, gB[0]);
             break;
@@ -298,6 +323,13 @@ int nerf_backward(neddf_ctx *ctx, int slot, const float *const *W, int n_tensors
             }
         float *t = dA; dA = dB; dB = t;
         mA = mB;
+    }
+    if (ig) {
+        eg.N = N;
+        fill_enc(eg.enc, f);
+        eg.pos = ig->pos; eg.dir = ig->dir; eg.var = ig->var;
+        eg.g_pos = ig->g_pos; eg.g_dir = ig->g_dir; eg.g_var = ig->g_var;
+        launch_enc_input_grad(eg, s);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -721,18 +753,31 @@ int neddf_train_field_forward(neddf_ctx *ctx, int slot, const float *const *W, c
     return 0;
 }
 
-int neddf_train_field_backward(neddf_ctx *ctx, int slot, const float *const *W, const float *const *B, int n_tensors, int64_t N,
-                               const float *ws_, const float *g_distance, const float *g_density, const float *g_color,
-                               const float *g_penalty, const float *g_aux_grad, float *const *gW, float *const *gB, void *stream)
+static int field_backward(neddf_ctx *ctx, int slot, const float *const *W, const float *const *B, int n_tensors, int64_t N,
+                          const float *ws_, const float *g_distance, const float *g_density, const float *g_color,
+                          const float *g_penalty, const float *g_aux_grad, float *const *gW, float *const *gB, const InputGrads *ig, void *stream)
 {
     if (!ctx) return NEDDF_EINVAL;
     if (N <= 0) return 0;
     if (!W || !B || !ws_ || !gW || !gB) return fail(ctx, NEDDF_EINVAL, "null argument");
+    if (ig && (!ig->pos || !ig->dir || !ig->var)) return fail(ctx, NEDDF_EINVAL, "input gradients need the forward's pos, dir and var");
     DeviceGuard guard_(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     float *ws = const_cast<float *>(ws_);
+    if (ig) {
+        if (slot < 0 || slot >= NEDDF_NUM_SLOTS || !ctx->field[slot].valid) return fail(ctx, NEDDF_ENOFIELD, "no field in slot");
+        const Field &fi = ctx->field[slot];
+        if (fi.d.kind == NEDDF_FIELD_NEUS)
+            return fail(ctx, NEDDF_EUNSUPPORTED, "input gradients of a NeuS field need a third derivative of the sdf trunk: not implemented");
+        if (fi.d.kind != NEDDF_FIELD_NEDDF && fi.d.kind != NEDDF_FIELD_NERF)
+            return fail(ctx, NEDDF_EUNSUPPORTED, "input gradients: unknown field kind");
+        if (fi.d.weight_dtype == NEDDF_DTYPE_F16_SPLIT)
+            return fail(ctx, NEDDF_EUNSUPPORTED, "input gradients run on the fp32 MFMA path: load the field with fp32 operands");
+        if (6 * fi.d.embed_pos_rank > 64 || 6 * (fi.d.embed_pos_rank + fi.d.embed_dir_rank) > 128)
+            return fail(ctx, NEDDF_EUNSUPPORTED, "input gradients take embed_pos_rank <= 10 and embed_pos_rank + embed_dir_rank <= 21");
+    }
     if (slot >= 0 && slot < NEDDF_NUM_SLOTS && ctx->field[slot].valid && ctx->field[slot].d.kind == NEDDF_FIELD_NERF)
-        return nerf_backward(ctx, slot, W, n_tensors, N, ws, g_density, g_color, gW, gB, s);
+        return nerf_backward(ctx, slot, W, n_tensors, N, ws, g_density, g_color, gW, gB, ig, s);
     if (slot >= 0 && slot < NEDDF_NUM_SLOTS && ctx->field[slot].valid && ctx->field[slot].d.kind == NEDDF_FIELD_NEUS)
         return neus_backward(ctx, slot, W, n_tensors, N, ws, g_distance, g_density, g_color, gW, gB, s);
     Plan p;
@@ -868,13 +913,38 @@ int neddf_train_field_backward(neddf_ctx *ctx, int slot, const float *const *W, 
         }
         if (dwj.overflow) return fail(ctx, NEDDF_EUNSUPPORTED, "more weight-gradient products than DwJobs holds (train_kernels.h kMaxDwJobs)");
         flush_dw();
+        if (ig) {       // every dZ of the pass is still in its own matrix: the encoding segments' input gradients read them in place
+            EncGradArgs e{};
+            e.N = N; e.enc = a.enc;
+            e.pos = ig->pos; e.dir = ig->dir; e.var = ig->var;
+            e.g_pos = ig->g_pos; e.g_dir = ig->g_dir; e.g_var = ig->g_var;
+            for (int l = 0; l < nT; ++l)
+                if (l == 0 || in_skips(f.d, l - 1)) e.seg[e.n_seg++] = EncGradSeg{ dZt(l), 1, 4, WH, WH, W[l], WH, 1, p.Cpe, 0, 0 };
+            e.seg[e.n_seg++] = EncGradSeg{ dZc(0), 1, 4, WH, WH, W[nT], WH, 1, p.Cpe + p.Cdir, 0, 1 };
+            launch_enc_input_grad(e, s);
+        }
         HIPCHK(hipGetLastError());
         return 0;
     }
+    // per-layer route: dA / dB are reused from layer to layer, so the gradient matrices the input gradients need (layer 0, the skip
+    // layers, colour layer 0) are copied aside as they appear
+    int n_keep = 0;
+    if (ig) {
+        n_keep = 2;
+        for (int l = 1; l < p.n_trunk; ++l) n_keep += in_skips(f.d, l - 1) ? 1 : 0;
+    }
     if (int rc = ensure(ctx, ctx->tpack, 2 * kPackFloats * sizeof(float))) return rc;
-    if (int rc = ensure(ctx, ctx->ttmp, (size_t)p.R * (2 * WH + 2 * kLdNarrow) * sizeof(float))) return rc;
+    if (int rc = ensure(ctx, ctx->ttmp, (size_t)p.R * ((2 + n_keep) * WH + 2 * kLdNarrow) * sizeof(float))) return rc;
     float *wp = (float *)ctx->tpack.p;
     float *dA = (float *)ctx->ttmp.p, *dB = dA + (size_t)p.R * WH, *GZH = dB + (size_t)p.R * WH, *GCR = GZH + (size_t)p.R * kLdNarrow;
+    float *keep_at = GCR + (size_t)p.R * kLdNarrow;
+    EncGradArgs eg{};
+    auto keep = [&](const float *dZ, const float *Wl, int ncols, int target) -> int {      // copy dZ aside and register its segment
+        HIPCHK(hipMemcpyAsync(keep_at, dZ, (size_t)p.R * WH * sizeof(float), hipMemcpyDeviceToDevice, s));
+        eg.seg[eg.n_seg++] = EncGradSeg{ keep_at, 0, 4, WH, WH, Wl, WH, 1, ncols, 0, target };
+        keep_at += (size_t)p.R * WH;
+        return 0;
+    };
     const float *PEs = ws + p.o_pes;
     TrainPointArgs a;
     point_args(a, f, p, ws);
@@ -945,6 +1015,7 @@ int neddf_train_field_backward(neddf_ctx *ctx, int slot, const float *const *W, 
         } else {
             dw_blocks(ws + p.o_xa, p.ldxa, p.Ca, gWl, 0, gBl, mA);
             dw_blocks(Hlast, WH, WH, gWl, p.Ca, nullptr, mA);
+            if (ig) if (int rc = keep(dA, Wl, p.Cpe + p.Cdir, 1)) return rc;
             // the small colour inputs (encodings, detached normal) carry no parameters: only the feature segment propagates
             gemm_bw(Wl, p.Ca, -1, nullptr, mA, nullptr);
         }
@@ -963,6 +1034,7 @@ int neddf_train_field_backward(neddf_ctx *ctx, int slot, const float *const *W, 
     // distance trunk
     for (int l = p.n_trunk - 1; l >= 0; --l) {
         const bool wide = l > 0 && in_skips(f.d, l - 1);
+        if (ig && (l == 0 || wide)) if (int rc = keep(dA, W[l], p.Cpe, 0)) return rc;
         if (l == 0) {
             dw_blocks(PEs, kLdPe, p.Cpe, gW[0], 0, gB[0], mA);
             break;
@@ -976,6 +1048,61 @@ int neddf_train_field_backward(neddf_ctx *ctx, int slot, const float *const *W, 
         float *t = dA; dA = dB; dB = t;
         mA = mB;
     }
+    if (ig) {
+        eg.N = N; eg.enc = a.enc;
+        eg.pos = ig->pos; eg.dir = ig->dir; eg.var = ig->var;
+        eg.g_pos = ig->g_pos; eg.g_dir = ig->g_dir; eg.g_var = ig->g_var;
+        launch_enc_input_grad(eg, s);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_train_field_backward(neddf_ctx *ctx, int slot, const float *const *W, const float *const *B, int n_tensors, int64_t N,
+                               const float *ws_, const float *g_distance, const float *g_density, const float *g_color,
+                               const float *g_penalty, const float *g_aux_grad, float *const *gW, float *const *gB, void *stream)
+{
+    return field_backward(ctx, slot, W, B, n_tensors, N, ws_, g_distance, g_density, g_color, g_penalty, g_aux_grad, gW, gB, nullptr, stream);
+}
+
+// NeDDF.forward's dependence on its sample inputs (neddf.py:186-257; PositionalEncodingGradLayer.forward
+// with_grad/positional_encoding.py:65-87, Sampling.get_pe_weights ray/sampling.py:44-71, LinearGradFunction.backward
+// with_grad/linear.py:72-75): the pass above, then the encoding segments' input gradients (pose_kernels.hip)
+int neddf_train_field_backward_inputs(neddf_ctx *ctx, int slot, const float *const *W, const float *const *B, int n_tensors, int64_t N,
+                                      const float *ws_, const float *pos, const float *dir, const float *var, const float *g_distance,
+                                      const float *g_density, const float *g_color, const float *g_penalty, const float *g_aux_grad,
+                                      float *const *gW, float *const *gB, float *g_pos, float *g_dir, float *g_var, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    const InputGrads ig{ pos, dir, var, g_pos, g_dir, g_var };
+    return field_backward(ctx, slot, W, B, n_tensors, N, ws_, g_distance, g_density, g_color, g_penalty, g_aux_grad, gW, gB, &ig, stream);
+}
+
+// Ray.get_sampling_cones (ray.py:128-194) / get_sampling_points (ray.py:88-126) differentiated with respect to the ray
+int neddf_sampling_backward(neddf_ctx *ctx, const float *g_pos, const float *g_dir, const float *g_var, const float *rd, const float *dists,
+                            int64_t n, int S, double radius, float *g_rd, float *g_ro, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (n <= 0) return 0;
+    if (!rd || !dists || !g_rd || !g_ro || S < 1) return fail(ctx, NEDDF_EINVAL, "sampling_backward: bad argument");
+    if (radius >= 0.0 && S < 2) return fail(ctx, NEDDF_EINVAL, "cone sampling needs at least 2 samples");
+    DeviceGuard guard_(ctx->device);
+    launch_sampling_backward(g_pos, g_dir, g_var, rd, dists, n, S, radius, g_rd, g_ro, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Camera.create_rays (camera.py:155-171, pinhole_calib.py:51-74) differentiated with respect to R and T
+int neddf_raygen_backward(neddf_ctx *ctx, const void *uv, int uv_type, int64_t n, const neddf_camera *cam, const float *g_rd,
+                          const float *g_ro, float *g_RT, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!uv || !cam || !g_rd || !g_ro || !g_RT || n < 0) return fail(ctx, NEDDF_EINVAL, "raygen_backward: bad argument");
+    if (uv_type < 0 || uv_type > 3) return fail(ctx, NEDDF_EINVAL, "bad uv_type");
+    DeviceGuard guard_(ctx->device);
+    CameraArg c;
+    memcpy(c.R, cam->R, sizeof(c.R)); memcpy(c.T, cam->T, sizeof(c.T)); memcpy(c.calib, cam->calib, sizeof(c.calib));
+    launch_raygen_backward(uv, uv_type, n, c, g_rd, g_ro, g_RT, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -227,4 +227,32 @@ void launch_composite_backward(const float *dists, const float *dens, const floa
                                const float *g_weight, const float *g_depth, const float *g_color, const float *g_trans, float *g_dens,
                                float *g_col, hipStream_t s);
 
+// ---- pose gradients (pose_kernels.hip) ---------------------------------------------------------------------------------
+// Input gradients of a field: the products dZ_l x (encoding rows of W_l)^T of every layer that reads an encoding, fused with the
+// backward of the encodings.  One segment per such layer; the dZ matrices are what the backward pass leaves behind:
+//   NeDDF  [4N, nk] on (value, Jacobian) row groups, point-major (ld = nk) or row-major (rows = 4), W [in, nk]: sj = nk, sk = 1
+//   NeRF   [N, ld] value rows (rows = 1; the Jacobian rows of the tile are zero), nn.Linear W [out, in]: sj = 1, sk = in
+struct EncGradSeg {
+    const float *dZ; int point_major, rows, ld, nk;       // nk: features (a multiple of 32)
+    const float *W; int64_t sj, sk;       // encoding column j of the segment, feature k: W[j * sj + k * sk] (W already points at the segment)
+    int ncols, col0;                      // the segment's columns are col0 .. col0 + ncols of the target's accumulator tile
+    int target;                           // 0: embed_pos_scaled columns (6E <= 64); 1: [embed_pos | embed_dir] columns (<= 128)
+};
+constexpr int kMaxEncGradSegs = kMaxLayers + 1;
+struct EncGradArgs {
+    int64_t N;
+    EncodeDesc enc;
+    const float *pos, *dir, *var;         // [N, 3] each: the forward's inputs (sin / cos / weights are recomputed)
+    int n_seg;
+    EncGradSeg seg[kMaxEncGradSegs];
+    float *g_pos, *g_dir, *g_var;         // [N, 3] each, any may be NULL
+};
+void launch_enc_input_grad(const EncGradArgs &a, hipStream_t s);
+// g_ray_dir / g_ray_orig [n, 3] from the sample gradients [n, S, 3] (any of the three may be NULL); radius < 0: point samples
+void launch_sampling_backward(const float *g_pos, const float *g_dir, const float *g_var, const float *rd, const float *dists, int64_t n, int S,
+                              double radius, float *g_rd, float *g_ro, hipStream_t s);
+// out[12] = g_R[9] (row-major) | g_T[3]
+void launch_raygen_backward(const void *uv, int uv_type, int64_t n, const CameraArg &cam, const float *g_rd, const float *g_ro, float *out,
+                            hipStream_t s);
+
 }  // namespace neddf

@@ -328,9 +328,12 @@ class NeDDF(BaseNeuralField):
         desc, ws, bs = self._train_tensors(ws, bs)
         self.upload(ctx, self._slot, weights=False, train=(desc, ws, bs) if self._train_layout() is not None else None)
         B, S = pos.shape[0], pos.shape[1]
+        # sample tensors that carry a graph (NeRFRender(pose_gradients=True)) keep it: FieldFunction then returns their gradients
+        def leaf(t):
+            return t if t.requires_grad else t.detach()
         distance, density, color, penalty, aux = FieldFunction.apply(
-            ctx, self._slot, self._iter_state(), len(ws), pos.detach(), sampling.sample_dir.detach(),
-            sampling.diag_variance.detach(), *ws, *bs)
+            ctx, self._slot, self._iter_state(), len(ws), leaf(pos), leaf(sampling.sample_dir),
+            leaf(sampling.diag_variance), *ws, *bs)
         return {"distance": distance.view(B, S), "density": density.view(B, S), "color": color.view(B, S, 3),
                 "fields_penalty": penalty.view(B, S), "aux_grad": aux.view(B, S)}
 
@@ -426,8 +429,10 @@ class NeRF(BaseNeuralField):
             desc, ws, bs = self._train_tensors(ws, bs)
             self.upload(ctx, self._slot, weights=False, train=(desc, ws, bs) if self._train_layout() is not None else None)
             B, S = pos.shape[0], pos.shape[1]
-            density, color = RadianceFieldFunction.apply(ctx, self._slot, self._iter_state(), len(ws), pos.detach(),
-                                                         sampling.sample_dir.detach(), sampling.diag_variance.detach(), *ws, *bs)
+            def leaf(t):        # sample tensors that carry a graph (pose gradients) keep it
+                return t if t.requires_grad else t.detach()
+            density, color = RadianceFieldFunction.apply(ctx, self._slot, self._iter_state(), len(ws), leaf(pos),
+                                                         leaf(sampling.sample_dir), leaf(sampling.diag_variance), *ws, *bs)
             return {"density": density.view(B, S), "color": color.view(B, S, 3)}
         return self._run(sampling, OUT_MINIMAL, ("density", "color"))
 
@@ -538,6 +543,8 @@ class NeuS(BaseNeuralField):
             desc, ws, bs = self._train_tensors(ws, bs)
             self.upload(ctx, self._slot, weights=False, train=(desc, ws, bs) if self._train_layout() is not None else None)
             B, S = pos.shape[0], pos.shape[1]
+            if pos.requires_grad or sampling.sample_dir.requires_grad:
+                raise NotImplementedError("pose gradients through a NeuS field need a third derivative of the sdf trunk: not implemented")
             sdf, density, color = SdfFieldFunction.apply(ctx, self._slot, len(ws), pos.detach(), sampling.sample_dir.detach(), *ws, *bs)
             return {"sdf": sdf.view(B, S), "density": density.view(B, S), "color": color.view(B, S, 3)}
         o = self._run(sampling, OUT_MINIMAL, ("distance", "density", "color"))

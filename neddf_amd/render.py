@@ -35,6 +35,15 @@ class BaseNeuralRender(nn.Module):
         self.iteration = iter
 
 
+def render_from_config(render_config: Any, **kwargs: Any) -> "NeRFRender":
+    """instantiate() a render configuration; the key `pose_gradients` (not a reference keyword) becomes the attribute."""
+    cfg = dict(render_config)
+    pose = bool(cfg.pop("pose_gradients", False))
+    render = instantiate(cfg, **kwargs)
+    render.pose_gradients = pose
+    return render
+
+
 class NeRFRender(BaseNeuralRender):
     """nerf_render.py:40-81.  Extra (non-reference) attributes:
 
@@ -47,7 +56,15 @@ class NeRFRender(BaseNeuralRender):
                    rays of an ndc_width x ndc_height view with near plane ndc_near (original NeRF paper, appendix C;
                    the reference has no such mode).  dist_near / dist_far are then NDC depths (0 and 1) and the fields
                    still receive the world-space viewing direction.  Use sampling_type="point" with it.
+    pose_gradients (attribute, set after construction or through `render.pose_gradients` of a run configuration -- see
+                   render_from_config; the constructor keeps the reference's keywords)
+                   False (default): render_rays under autograd differentiates the network parameters only; True: ray
+                   generation and the samplers join the graph as in the reference (camera.py:155-171, ray.py:88-194 are
+                   differentiable torch there), so loss.backward() fills camera.params.grad.  NeDDF and NeRF fields with fp32
+                   operands and world-space rays; NeuS, NDC rays and split-fp16 operands raise.  The intrinsics get no gradient.
     """
+
+    pose_gradients = False
 
     def __init__(self, network_config: Any, sample_coarse: int = 128, sample_fine: int = 128, dist_near: float = 2.0,
                  dist_far: float = 6.0, max_dist: float = 6.0, use_coarse_network: bool = True,
@@ -188,6 +205,8 @@ class NeRFRender(BaseNeuralRender):
         U_c = self._rand(B, self.sample_coarse + 1, uv.device)
         U_f = self._rand(B, self.sample_fine + 1, uv.device)
         radius = p.ray_radius if p.cone_sampling else None
+        if self.pose_gradients:
+            return self._render_rays_with_pose_grad(ctx, uv, camera, p, radius, U_c, U_f)
         with torch.no_grad():
             cam = camera.descriptor()
             rd, ro = ctx.raygen(uv, cam)
@@ -207,6 +226,44 @@ class NeRFRender(BaseNeuralRender):
             # sanitises the coarse weights in place, as the reference does under set_grad_enabled(False)
             dists_f = ctx.importance_resample(dists_c, integ_c["weight"].detach(), U_f, True)
             smp_f = Sampling(*ctx.sampling(rd, ro, dists_f, radius, view))
+        val_f = self.network_fine(smp_f)
+        integ = self.integrate_volume_render(dists_f, val_f["density"], val_f["color"])
+        for key in val_f:
+            if "penalty" in key:
+                delta = dists_f[:, 1:] - dists_f[:, :-1]
+                integ[key] = torch.sum(delta * val_f[key].reshape(B, -1)[:, :-1], dim=1)
+        for key in list(integ_c):
+            integ["{}_coarse".format(key)] = integ_c[key]
+        return integ
+
+    def _render_rays_with_pose_grad(self, ctx: Context, uv: Tensor, camera: Camera, p: RenderParams, radius, U_c: Tensor,
+                                    U_f: Tensor) -> Dict[str, Tensor]:
+        """_render_rays_with_grad with ray generation and both samplers as autograd nodes (autograd.py RayFunction,
+        SamplingFunction): the same kernels, draws and outputs, and camera.R / camera.T (differentiable results of
+        Camera.update_transform) receive their gradients."""
+        from .autograd import RayFunction, SamplingFunction
+        from .ray import Sampling
+        if p.ndc_rays:
+            raise NotImplementedError("pose_gradients: NDC rays (ray_space='ndc') are not differentiated")
+        from .network import NeuS
+        if isinstance(self.network_coarse, NeuS) or isinstance(self.network_fine, NeuS):
+            raise NotImplementedError("pose_gradients through a NeuS field need a third derivative of the sdf trunk: not implemented")
+        # (the intrinsics are not differentiated: PinholeCalib.params reaches the kernels as plain numbers and receives no gradient;
+        # NeRFTrainer refuses to put it into the optimiser together with the poses)
+        B = uv.shape[0]
+        rd, ro = RayFunction.apply(ctx, uv, camera.descriptor(), camera.R, camera.T)
+        with torch.no_grad():
+            dists_c = ctx.sample_coarse(U_c, self.dist_near, self.dist_far)
+        smp_c = Sampling(*SamplingFunction.apply(ctx, rd, ro, dists_c, radius))
+        val_c = self.network_coarse(smp_c)
+        integ_c = self.integrate_volume_render(dists_c, val_c["density"], val_c["color"])
+        for key in val_c:
+            if "penalty" in key:
+                delta = dists_c[:, 1:] - dists_c[:, :-1]
+                integ_c[key] = torch.sum(delta * val_c[key].reshape(B, -1)[:, :-1], dim=1)
+        with torch.no_grad():
+            dists_f = ctx.importance_resample(dists_c, integ_c["weight"].detach(), U_f, True)
+        smp_f = Sampling(*SamplingFunction.apply(ctx, rd, ro, dists_f, radius))
         val_f = self.network_fine(smp_f)
         integ = self.integrate_volume_render(dists_f, val_f["density"], val_f["color"])
         for key in val_f:

@@ -17,6 +17,7 @@ from .dataset import imwrite_bgr
 from .logger import ScalarLog
 from .metrics import peak_signal_noise_ratio, structural_similarity
 from .parallel import average_gradients, render_image_sharded
+from .render import render_from_config
 
 
 def _get(cfg: Any, key: str) -> Any:
@@ -125,18 +126,29 @@ class BaseTrainer:
 
 
 class NeRFTrainer(BaseTrainer):
-    """nerf_trainer.py:23-140"""
+    """nerf_trainer.py:23-140.  Two keywords the reference does not have: optimize_cameras (default False) puts every view's
+    Camera.params -- the SE(3) perturbation of its dataset pose -- into Adam as a second parameter group and switches the
+    render's pose_gradients on; camera_lr is that group's learning rate.  The reference leaves the pose parameters out of its
+    optimiser, so it has no value to follow: 1e-3 is the step of published joint pose / field optimisation (BARF, Lin et al.
+    2021, train their poses at 1e-3), twice the field's 5e-4 here, and decays with the same scheduler."""
 
-    def __init__(self, **kwargs: Any) -> None:
+    def __init__(self, optimize_cameras: bool = False, camera_lr: float = 1e-3, **kwargs: Any) -> None:
         super().__init__(**kwargs)
-        self.neural_render = instantiate(_get(self.config, "render"), network_config=to_plain(_get(self.config, "network")),
-                                         _recursive_=False).to(self.device)
+        self.optimize_cameras, self.camera_lr = bool(optimize_cameras), float(camera_lr)
+        self.neural_render = render_from_config(to_plain(_get(self.config, "render")), network_config=to_plain(_get(self.config, "network")),
+                                                _recursive_=False).to(self.device)
         if getattr(self.neural_render, "ray_space", "world") == "ndc":      # forward-facing data: NDC of the full image
             self.neural_render.ndc_width, self.neural_render.ndc_height = self.dataset.image_width, self.dataset.image_height
         self.optimizer = torch.optim.Adam(self.neural_render.get_parameters_list(), lr=self.optimizer_lr,
                                           weight_decay=self.optimizer_weight_decay)
+        if self.optimize_cameras:
+            self.neural_render.pose_gradients = True
+            self.optimizer.add_param_group({"params": self.camera_parameters(), "lr": self.camera_lr, "weight_decay": 0.0})
         self.scheduler = torch.optim.lr_scheduler.ExponentialLR(self.optimizer, gamma=self.scheduler_lr)
         self.logger = None      # created by the first training step: evaluation runs leave no ./log behind
+
+    def camera_parameters(self) -> List[torch.nn.Parameter]:
+        return [c.params for c in self.cameras]
 
     def run_train(self) -> None:
         """nerf_trainer.py:47-79: epochs over a random permutation of the frames, outputs under the working directory
@@ -191,6 +203,14 @@ class NeRFTrainer(BaseTrainer):
                 total.backward()
             # data-parallel runs (scripts/run.py under torchrun: per-rank seed and device): one all-reduce of the gradients
             average_gradients(self.neural_render.get_parameters_list())
+            if self.optimize_cameras:       # (every rank passes the same list; the ranks visit different views per step)
+                average_gradients(self.camera_parameters())
+                # the all-reduce hands every camera a gradient tensor, zeros for the views no rank visited; Adam would then step
+                # those too (a view visited once would keep drifting on its decaying first moment).  As in a single-rank run a
+                # view nobody visited has no gradient: same decision on every rank, since the averaged values are the same
+                for p in self.camera_parameters():
+                    if p.grad is not None and not bool(p.grad.any()):
+                        p.grad = None
             self.optimizer.step()
             mse = float(torch.mean(torch.square(rendered["color"].detach() - targets["color"])).item())
             loss_value = float(total.item())
