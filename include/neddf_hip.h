@@ -175,6 +175,24 @@ int neddf_rays_to_ndc(neddf_ctx *ctx, const float *d_ray_dir, const float *d_ray
 int neddf_field_forward(neddf_ctx *ctx, int slot, const float *d_pos, const float *d_dir, const float *d_var,
                         int64_t n_points, int out_mode, float *d_distance, float *d_density, float *d_color,
                         float *d_fields_penalty, float *d_aux_grad, void *stream);
+/* ---- surface normals (additive to ABI v7: new functions only) ----------------------------------------------------
+ * neddf_field_forward plus the two quantities the distance trunk hands to the colour trunk, each [N,3], each nullable:
+ *   d_distance_grad  NeDDF: distance_grad, the position gradient of the distance (neddf.py:223); NeuS: `gradients`, the
+ *                    position gradient of the sdf that the reference takes with torch.autograd.grad (neus.py:135-143)
+ *   d_normal         what the colour trunk receives: NeDDF norm_dir = distance_grad / (|distance_grad| + 1e-7) (neddf.py:235,241);
+ *                    NeuS the sdf gradient itself, NOT normalised (neus.py:144-145 concatenates `gradients` as they are)
+ * Both are read back from the per-point record the distance kernel leaves for the colour kernel, under every operand policy and
+ * both output modes (NEDDF_OUT_MINIMAL: reverse-mode gradient, NEDDF_OUT_FULL: forward-mode Jacobian rows); the other outputs are
+ * those of neddf_field_forward bit for bit.  NEDDF_EUNSUPPORTED for NeRF fields (no distance, no sdf: nerf.py:107-165). */
+int neddf_field_forward_surface(neddf_ctx *ctx, int slot, const float *d_pos, const float *d_dir, const float *d_var,
+                                int64_t n_points, int out_mode, float *d_distance, float *d_density, float *d_color,
+                                float *d_fields_penalty, float *d_aux_grad, float *d_distance_grad, float *d_normal, void *stream);
+/* The normal render target: d_out_normal[b] = sum_j weight[b,j] * d_normals[b,j] over the S-1 intervals and with the weights of
+ * neddf_composite (base_neural_render.py:148-160, where color is integrated the same way).  d_normals [n_rays,S,3].  Not
+ * normalised: its length is at most 1 - transmittance for unit normals, the background is the zero vector.  One wave per ray,
+ * fp64 multiplicative wave scan, fixed reduction order: bitwise repeatable. */
+int neddf_composite_normal(neddf_ctx *ctx, const float *d_dists, const float *d_density, const float *d_normals, int64_t n_rays, int S,
+                           float *d_out_normal, void *stream);
 /* BaseNeuralRender.integrate_volume_render (base_neural_render.py:117-172).
  * d_weight [n_rays,S-1] may be NULL.  *d_nan_flag (int, may be NULL) is set to 1
  * if any weight is NaN (the reference asserts, :155). */
@@ -245,6 +263,17 @@ int neddf_render_rays(neddf_ctx *ctx, const void *d_uv, int uv_type, int64_t n_r
 int neddf_render_rays_single(neddf_ctx *ctx, int slot, const void *d_uv, int uv_type, int64_t n_rays,
                              const neddf_camera *h_cam, const neddf_render_params *params, int S1,
                              const float *d_U, const neddf_render_outputs *out, void *stream);
+
+/* neddf_render_rays / neddf_render_rays_single with the normal target: d_normal [n_rays,3] (fine pass) and d_normal_coarse
+ * [n_rays,3] (coarse pass), either may be NULL; per sample the field's d_normal of neddf_field_forward_surface, integrated as by
+ * neddf_composite_normal.  Every output of `out` is what the plain call writes, bit for bit.  NEDDF_EUNSUPPORTED when a requested
+ * normal would come from a NeRF field. */
+int neddf_render_rays_surface(neddf_ctx *ctx, const void *d_uv, int uv_type, int64_t n_rays, const neddf_camera *h_cam,
+                              const neddf_render_params *params, const float *d_U_coarse, const float *d_U_fine,
+                              const neddf_render_outputs *out, float *d_normal, float *d_normal_coarse, void *stream);
+int neddf_render_rays_single_surface(neddf_ctx *ctx, int slot, const void *d_uv, int uv_type, int64_t n_rays,
+                                     const neddf_camera *h_cam, const neddf_render_params *params, int S1,
+                                     const float *d_U, const neddf_render_outputs *out, float *d_normal, void *stream);
 
 /* Stage timing: hipEvent pairs recorded on the launch stream around every stage kernel launched through this ctx while
  * timing is enabled (neddf_set_timing), drained by either getter (both synchronise on the recorded events).
@@ -388,6 +417,14 @@ int neddf_field_grid(neddf_ctx *ctx, int slot, int field, int nx, int ny, int nz
 int neddf_marching_cubes(neddf_ctx *ctx, const float *d_volume, int nx, int ny, int nz, const double *h_lo, const double *h_hi, float iso,
                          float *d_vertices, int64_t vertex_cap, int32_t *d_triangles, int64_t triangle_cap, int64_t *h_n_vertices,
                          int64_t *h_n_triangles, void *stream);
+
+/* Geometric vertex normals of an indexed mesh (no reference counterpart: its .dae export carries none): d_normals[v] = the
+ * normalised sum, over the triangles that hold v, of (p1 - p0) x (p2 - p0) -- weighted by area, pointing where the triangles'
+ * orientation points (out of the object for neddf_marching_cubes' meshes).  Cross products in fp32, sums in 64-bit fixed point with
+ * integer atomics (exact, so the result does not depend on timing), normalisation in fp64; a sum shorter than 1e-20 gives (0,0,0).
+ * Triangles with an index outside [0, n_vertices) or a non-finite cross product are ignored. */
+int neddf_mesh_vertex_normals(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles,
+                              int64_t n_triangles, float *d_normals, void *stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -114,6 +114,13 @@ SYMBOLS = [
     ("neddf_field_grid", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _vp, _vp]),
     ("neddf_marching_cubes", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_float, _vp, _i64, _vp, _i64,
                                        C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    ("neddf_field_forward_surface", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_composite_normal", C.c_int, [_vp, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),
+    ("neddf_render_rays_surface", C.c_int, [_vp, _vp, C.c_int, _i64, C.POINTER(CameraDesc), C.POINTER(RenderParams), _vp, _vp,
+                                            C.POINTER(RenderOutputs), _vp, _vp, _vp]),
+    ("neddf_render_rays_single_surface", C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, C.POINTER(CameraDesc),
+                                                   C.POINTER(RenderParams), C.c_int, _vp, C.POINTER(RenderOutputs), _vp, _vp]),
+    ("neddf_mesh_vertex_normals", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
 ]
 
 _lib = None
@@ -287,6 +294,44 @@ class Context:
                                                 _ptr(o["fields_penalty"]), _ptr(o["aux_grad"]), self.stream()))
         return {k: v for k, v in o.items() if v is not None}
 
+    def field_forward_surface(self, slot, pos, dir, var, out_mode, want):
+        """field_forward plus "distance_grad" / "normal" [N, 3] (neddf_field_forward_surface); NeRF fields raise."""
+        require_device(pos, "sample_pos")
+        pos, dir, var = f32c(pos), f32c(dir), f32c(var)
+        N = pos.numel() // 3
+        dev = pos.device
+        wide = ("color", "distance_grad", "normal")
+        o = {k: (torch.empty(N * (3 if k in wide else 1), device=dev, dtype=torch.float32) if k in want else None)
+             for k in ("distance", "density", "color", "fields_penalty", "aux_grad", "distance_grad", "normal")}
+        self.check(self.lib.neddf_field_forward_surface(self.h, slot, _ptr(pos), _ptr(dir), _ptr(var), N, out_mode,
+                                                        _ptr(o["distance"]), _ptr(o["density"]), _ptr(o["color"]),
+                                                        _ptr(o["fields_penalty"]), _ptr(o["aux_grad"]), _ptr(o["distance_grad"]),
+                                                        _ptr(o["normal"]), self.stream()))
+        return {k: v for k, v in o.items() if v is not None}
+
+    def composite_normal(self, dists, dens, normals):
+        """sum_j weight[b, j] * normals[b, j] with composite()'s weights: [B, 3] (neddf_composite_normal)."""
+        require_device(dists, "dists")
+        dists, dens, normals = f32c(dists), f32c(dens), f32c(normals)
+        B, S = dists.shape
+        if dens.numel() != B * S or normals.numel() != B * S * 3:
+            raise NeddfError("composite_normal: density [B, S] and normals [B, S, 3] expected")
+        out = torch.empty(B, 3, device=dists.device, dtype=torch.float32)
+        self.check(self.lib.neddf_composite_normal(self.h, _ptr(dists), _ptr(dens), _ptr(normals), B, S, _ptr(out), self.stream()))
+        return out
+
+    def mesh_vertex_normals(self, vertices, triangles):
+        """Area-weighted geometric vertex normals [V, 3] of an indexed device mesh (neddf_mesh_vertex_normals)."""
+        require_device(vertices, "vertices")
+        require_device(triangles, "triangles")
+        v = f32c(vertices)
+        t = triangles.contiguous() if triangles.dtype == torch.int32 else triangles.to(torch.int32).contiguous()
+        if v.dim() != 2 or v.shape[1] != 3 or t.dim() != 2 or t.shape[1] != 3:
+            raise NeddfError("mesh_vertex_normals: vertices [V, 3] and triangles [T, 3] expected")
+        out = torch.empty_like(v)
+        self.check(self.lib.neddf_mesh_vertex_normals(self.h, _ptr(v), v.shape[0], _ptr(t), t.shape[0], _ptr(out), self.stream()))
+        return out
+
     # ------------------------------------------------------------------ surface extraction
     @staticmethod
     def _bounds(lo, hi):
@@ -359,15 +404,27 @@ class Context:
         return (out, ids) if want_ids else out
 
     def render_rays(self, uv, cam, params, U_coarse, U_fine, outputs, single_slot=None):
-        """outputs: dict name -> preallocated device tensor (subset of RenderOutputs fields)."""
+        """outputs: dict name -> preallocated device tensor (subset of RenderOutputs fields, plus "normal" / "normal_coarse"
+        [B, 3]: with either present the call goes through the *_surface entry points)."""
         require_device(uv, "uv")
         if uv.dtype not in UV_TYPES:
             uv = uv.to(torch.float32)
         uv = uv.contiguous()
         ro = RenderOutputs()
+        outputs = dict(outputs)
+        normal, normal_coarse = outputs.pop("normal", None), outputs.pop("normal_coarse", None)
         for k, t in outputs.items():
             setattr(ro, k, t.data_ptr())
-        if single_slot is None:
+        if normal is not None or normal_coarse is not None:
+            if single_slot is None:
+                self.check(self.lib.neddf_render_rays_surface(self.h, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0], C.byref(cam),
+                                                              C.byref(params), _ptr(U_coarse), _ptr(U_fine), C.byref(ro),
+                                                              _ptr(normal), _ptr(normal_coarse), self.stream()))
+            else:
+                self.check(self.lib.neddf_render_rays_single_surface(self.h, single_slot, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0],
+                                                                     C.byref(cam), C.byref(params), U_coarse.shape[1], _ptr(U_coarse),
+                                                                     C.byref(ro), _ptr(normal), self.stream()))
+        elif single_slot is None:
             self.check(self.lib.neddf_render_rays(self.h, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0], C.byref(cam),
                                                   C.byref(params), _ptr(U_coarse), _ptr(U_fine), C.byref(ro), self.stream()))
         else:

@@ -97,6 +97,7 @@ struct neddf_ctx {
     DevBuf tamax;                // training step: max |dZ| of every gradient matrix of a backward pass (split-fp16 operand range)
     DevBuf grid_pts;             // neddf_field_grid: pos / dir / var of one chunk of the lattice
     DevBuf mc_mask, mc_vbase, mc_blk;         // neddf_marching_cubes: crossed-edge byte and first vertex id per lattice point, block bases
+    DevBuf mc_nacc;              // neddf_mesh_vertex_normals: 64-bit fixed-point sums [3 V] + the scale word
     std::vector<GuardBand> carve_guards;      // NEDDF_GUARD=1: the bands behind the carves of the last render call
     bool timing = false;
     std::vector<EventPair> events;

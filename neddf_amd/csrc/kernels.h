@@ -184,6 +184,10 @@ void launch_ndc(const float *rd, const float *ro, int64_t n, float width, float 
                 float *no, hipStream_t s);
 void launch_composite(const float *dists, const float *dens, const float *col, int64_t n, int S, float max_dist,
                       float *w, float *depth, float *color, float *trans, int *nan_flag, hipStream_t s);
+// sum_j weight[b, j] * nrm[b, j] with launch_composite's weights (render_kernels.hip composite_normal_kernel); nrm [n, S, 3], normal [n, 3]
+void launch_composite_normal(const float *dists, const float *dens, const float *nrm, int64_t n, int S, float *normal, hipStream_t s);
+// [n, 3] position gradient / normal out of the per-point record of a distance-trunk launch (either may be NULL)
+void launch_surface_gather(const float *ptaux, int64_t n, int neus, float *dgrad, float *normal, hipStream_t s);
 void launch_integrate_penalty(const float *dists, const float *pen, int64_t n, int S, float *out, hipStream_t s);
 void launch_resample(const float *dists, float *weights, const float *U, int64_t n_rays, int n, int nf, int cat,
                      float *out, int64_t *ids, int *flag, int64_t group, int64_t offset, hipStream_t s);
@@ -207,6 +211,8 @@ void launch_mc_scan(int64_t *vblk, int64_t *tblk, int64_t nblocks, hipStream_t s
 void launch_mc_vertices(const McGrid &g, const unsigned char *mask, const int64_t *vblk, int32_t *vbase, float *vertices, hipStream_t s);
 void launch_mc_triangles(const McGrid &g, const unsigned char *mask, const int64_t *tblk, const int32_t *vbase, int32_t *tris,
                          hipStream_t s);
+// geometric vertex normals of an indexed mesh; acc: workspace of (3 V + 1) 64-bit words
+void launch_mesh_normals(const float *vertices, int64_t V, const int32_t *tris, int64_t T, unsigned long long *acc, float *normals, hipStream_t s);
 
 void launch_linear_grad(const float *x, const float *J, int64_t n, int cin, int ldx, int cout_block, int ksteps, const float *wp,
                         const float *bias, float *y, float *G, int ldo, int nvalid, int accumulate, int grid, hipStream_t s);

@@ -7,6 +7,8 @@
 //   mc_scan_kernel       one workgroup: exclusive scans of the block totals (in place, the grand totals behind them)
 //   mc_vertex_kernel     per point: its first vertex id (block scan + block base), the vertices of its crossed edges
 //   mc_triangle_kernel   per cell: its first triangle id (block scan + block base), the triangles of its case
+//   mesh_normal_*        geometric vertex normals of an indexed mesh: area-weighted sums of the incident triangles' cross products,
+//                        accumulated in 64-bit fixed point with INTEGER atomics (exact, hence order-independent), then normalised
 //
 // Placement is decided by count -> scan -> write launches only: no atomics, no exchange between workgroups inside a launch,
 // so the output is the same on every run (tests/mesh_check.py restates it in numpy bit for bit).  A corner is inside when
@@ -178,6 +180,93 @@ __global__ void __launch_bounds__(kMcThreads) mc_triangle_kernel(McGrid g, const
         const int axis = own >> 3;
         tris[3 * first + e] = vbase[q] + (int32_t)__popc(mask[q] & ((1 << axis) - 1));
     }
+}
+
+// ---- geometric vertex normals ------------------------------------------------------------------------------------------------
+// n_v = normalise(sum over the triangles t that hold v of (p1 - p0) x (p2 - p0)): the cross product's length is twice the triangle's
+// area, so the sum is area-weighted.  The cross product is taken in fp32 (differences, then products and one subtraction per
+// component, no fma: the file is compiled with -ffp-contract=off), scaled by a power of two that puts the largest component of the
+// whole mesh at 2^52 and rounded to an integer: below 2^-52 of the largest triangle a contribution is dropped, everything above is
+// exact, and integer sums do not depend on the order the atomics land in.  Triangles with a vertex index outside [0, V) or a
+// non-finite cross product contribute nothing.
+__device__ __forceinline__ bool tri_cross(const float *v, const int32_t *tris, int64_t t, int64_t V, int32_t id[3], float c[3])
+{
+    id[0] = tris[3 * t]; id[1] = tris[3 * t + 1]; id[2] = tris[3 * t + 2];
+    for (int k = 0; k < 3; ++k)
+        if (id[k] < 0 || id[k] >= V) return false;
+    const float *p0 = v + 3 * (int64_t)id[0], *p1 = v + 3 * (int64_t)id[1], *p2 = v + 3 * (int64_t)id[2];
+    const float a0 = p1[0] - p0[0], a1 = p1[1] - p0[1], a2 = p1[2] - p0[2];
+    const float b0 = p2[0] - p0[0], b1 = p2[1] - p0[1], b2 = p2[2] - p0[2];
+    c[0] = a1 * b2 - a2 * b1;
+    c[1] = a2 * b0 - a0 * b2;
+    c[2] = a0 * b1 - a1 * b0;
+    const float m = fmaxf(fabsf(c[0]), fmaxf(fabsf(c[1]), fabsf(c[2])));
+    return m < INFINITY && c[0] == c[0] && c[1] == c[1] && c[2] == c[2];
+}
+
+// largest |component| of any cross product, as the bit pattern of a non-negative float (ordered like the value: an integer max)
+__global__ void __launch_bounds__(kMcThreads) mesh_normal_max_kernel(const float *v, int64_t V, const int32_t *tris, int64_t T, unsigned *maxbits)
+{
+    const int64_t t = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    if (t >= T) return;
+    int32_t id[3];
+    float c[3];
+    if (!tri_cross(v, tris, t, V, id, c)) return;
+    const float m = fmaxf(fabsf(c[0]), fmaxf(fabsf(c[1]), fabsf(c[2])));
+    atomicMax(maxbits, __float_as_uint(m));
+}
+
+// 2^(52 - e) with 2^e <= max < 2^(e+1) (frexp's exponent minus one); max = 0 (or a subnormal scale overflow) is handled by the callers
+__device__ __forceinline__ double mesh_normal_scale(unsigned maxbits)
+{
+    int e;
+    (void)frexpf(__uint_as_float(maxbits), &e);
+    return ldexp(1.0, 53 - e);
+}
+
+__global__ void __launch_bounds__(kMcThreads) mesh_normal_accum_kernel(const float *v, int64_t V, const int32_t *tris, int64_t T,
+                                                                       const unsigned *maxbits, unsigned long long *acc)
+{
+    const int64_t t = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    if (t >= T || *maxbits == 0) return;
+    int32_t id[3];
+    float c[3];
+    if (!tri_cross(v, tris, t, V, id, c)) return;
+    const double scale = mesh_normal_scale(*maxbits);
+    for (int d = 0; d < 3; ++d) {
+        const long long q = (long long)rint((double)c[d] * scale);      // |q| <= 2^53
+        if (!q) continue;
+        for (int k = 0; k < 3; ++k) atomicAdd(acc + 3 * (int64_t)id[k] + d, (unsigned long long)q);     // two's complement: signed sums
+    }
+}
+
+__global__ void __launch_bounds__(kMcThreads) mesh_normal_finish_kernel(int64_t V, const unsigned *maxbits, const unsigned long long *acc,
+                                                                        float *normals)
+{
+    const int64_t i = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    if (i >= V) return;
+    float out[3] = { 0.f, 0.f, 0.f };
+    if (*maxbits) {
+        const double inv = 1.0 / mesh_normal_scale(*maxbits);
+        const double x = (double)(long long)acc[3 * i] * inv, y = (double)(long long)acc[3 * i + 1] * inv, z = (double)(long long)acc[3 * i + 2] * inv;
+        const double len = sqrt(x * x + y * y + z * z);
+        if (len >= 1e-20) { out[0] = (float)(x / len); out[1] = (float)(y / len); out[2] = (float)(z / len); }
+    }
+    normals[3 * i] = out[0]; normals[3 * i + 1] = out[1]; normals[3 * i + 2] = out[2];
+}
+
+// acc: [3 V] 64-bit words followed by one 32-bit word (the max), zeroed here
+void launch_mesh_normals(const float *vertices, int64_t V, const int32_t *tris, int64_t T, unsigned long long *acc, float *normals, hipStream_t s)
+{
+    if (V <= 0) return;
+    unsigned *maxbits = (unsigned *)(acc + 3 * V);
+    (void)hipMemsetAsync(acc, 0, (size_t)(3 * V + 1) * sizeof(unsigned long long), s);
+    if (T > 0) {
+        const unsigned tb = (unsigned)((T + kMcThreads - 1) / kMcThreads);
+        hipLaunchKernelGGL(mesh_normal_max_kernel, dim3(tb), dim3(kMcThreads), 0, s, vertices, V, tris, T, maxbits);
+        hipLaunchKernelGGL(mesh_normal_accum_kernel, dim3(tb), dim3(kMcThreads), 0, s, vertices, V, tris, T, maxbits, acc);
+    }
+    hipLaunchKernelGGL(mesh_normal_finish_kernel, dim3((unsigned)((V + kMcThreads - 1) / kMcThreads)), dim3(kMcThreads), 0, s, V, maxbits, acc, normals);
 }
 
 void launch_grid_points(const McGrid &g, int64_t first, int64_t n, float *pos, float *dir, float *var, hipStream_t s)

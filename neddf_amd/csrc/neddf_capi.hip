@@ -539,11 +539,14 @@ struct UseMark {
 // the sampling kernel when the route cannot take its points from the rays, untouched when it can (kernels.h RaySrc)
 static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float *dir, const float *var, int64_t N,
                          int out_mode, float *distance, float *density, float *color, float *penalty, float *aux,
-                         hipStream_t s, const RaySrc *rays = nullptr)
+                         hipStream_t s, const RaySrc *rays = nullptr, float *dgrad = nullptr, float *normal = nullptr)
 {
     if (slot < 0 || slot >= NEDDF_NUM_SLOTS || !ctx->field[slot].valid) return fail(ctx, NEDDF_ENOFIELD, "no field in slot");
     if (N <= 0) return 0;
     Field &f = ctx->field[slot];
+    // dgrad / normal [N, 3] (the surface entry points): read back from the per-point record after each distance-trunk launch
+    if ((dgrad || normal) && f.d.kind == NEDDF_FIELD_NERF)
+        return fail(ctx, NEDDF_EUNSUPPORTED, "a NeRF field has no distance or sdf: no gradient and no normal (nerf.py:107-165)");
     UseMark mark{ ctx, f, s };
     const int dt = f.d.weight_dtype;
     const int wid = f.d.kind == NEDDF_FIELD_NERF ? f.nerf.width : f.ddf.width;        // engine width
@@ -586,7 +589,8 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
     // sampling tensors (the A/B partner: tests/test_gpu_parity.py holds both routes bit-identical)
     // (read per call, a few times per frame: the bit-identity test flips it inside one process)
     const char *rif = rays ? getenv("NEDDF_RAYS_IN_FIELD") : nullptr;
-    const bool use_rays = rays && (!rif || atoi(rif) != 0) && reverse && f.d.kind == NEDDF_FIELD_NEDDF;
+    // (a rays-sourced launch parks the sample position in the record's gradient slots, kernels.h PA_R_POS: not when the gradient is asked for)
+    const bool use_rays = rays && (!rif || atoi(rif) != 0) && reverse && f.d.kind == NEDDF_FIELD_NEDDF && !dgrad;
     if (rays && !use_rays) sample_now();
     // fp32 products as three-term bf16 splits (f32_products_split3): the reverse-mode kernel and the colour kernel behind it only
     const bool use3 = f.has3 && reverse && f.d.kind == NEDDF_FIELD_NEDDF;
@@ -666,6 +670,8 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
             const int64_t tiles = (n + ddf_points_per_tile(dt, wid) - 1) / ddf_points_per_tile(dt, wid);
             STAGE(ctx, s, NEDDF_STAGE_DDF, launch_ddf(a, (int)(tiles < grid_cap_ddf ? tiles : grid_cap_ddf), s));
         }
+        if (dgrad || normal)
+            launch_surface_gather(a.ptaux, n, f.d.kind == NEDDF_FIELD_NEUS, dgrad ? dgrad + off * 3 : nullptr, normal ? normal + off * 3 : nullptr, s);
         if (color || full) {
             ColArgs c = use3 ? f.col3 : f.col;
             fill_enc(c.enc, f);
@@ -752,7 +758,7 @@ void neddf_destroy(neddf_ctx *ctx)
         if (f.last_use) (void)hipEventDestroy(f.last_use);
     }
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack, &ctx->ttmp, &ctx->tamax,
-                      &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk })
+                      &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc })
         if (b->p) (void)hipFree(b->base ? b->base : b->p);
     for (auto &e : ctx->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : ctx->pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -771,7 +777,7 @@ int neddf_debug_check_guards(neddf_ctx *ctx, int64_t *n_bands, int64_t *n_bad_by
     HIPCHK(hipDeviceSynchronize());
     std::vector<GuardBand> bands = ctx->carve_guards;
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack,
-                       &ctx->ttmp, &ctx->tamax, &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk })
+                       &ctx->ttmp, &ctx->tamax, &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc })
         if (b->base) {
             bands.push_back(GuardBand{ b->base, kGuardBytes });
             bands.push_back(GuardBand{ (char *)b->p + b->cap, kGuardBytes });
@@ -911,6 +917,29 @@ int neddf_field_forward(neddf_ctx *ctx, int slot, const float *pos, const float 
     return field_forward(ctx, slot, pos, dir, var, N, out_mode, distance, density, color, penalty, aux, (hipStream_t)stream);
 }
 
+int neddf_field_forward_surface(neddf_ctx *ctx, int slot, const float *pos, const float *dir, const float *var, int64_t N, int out_mode,
+                                float *distance, float *density, float *color, float *penalty, float *aux, float *dgrad, float *normal,
+                                void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (N <= 0) return 0;
+    if (!pos || !dir || !var) return NEDDF_EINVAL;
+    DeviceGuard guard_(ctx->device);
+    if (slot >= 0 && slot < NEDDF_NUM_SLOTS && ctx->field[slot].valid && ctx->field[slot].d.kind == NEDDF_FIELD_NERF)
+        return fail(ctx, NEDDF_EUNSUPPORTED, "field_forward_surface: a NeRF field has no distance or sdf, hence no gradient and no normal");
+    return field_forward(ctx, slot, pos, dir, var, N, out_mode, distance, density, color, penalty, aux, (hipStream_t)stream, nullptr, dgrad, normal);
+}
+
+int neddf_composite_normal(neddf_ctx *ctx, const float *dists, const float *dens, const float *nrm, int64_t n, int S, float *normal,
+                           void *stream)
+{
+    if (!ctx || !dists || !dens || !nrm || !normal || S < 2) return NEDDF_EINVAL;
+    DeviceGuard guard_(ctx->device);
+    STAGE(ctx, (hipStream_t)stream, NEDDF_STAGE_COMPOSITE, launch_composite_normal(dists, dens, nrm, n, S, normal, (hipStream_t)stream));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int neddf_composite(neddf_ctx *ctx, const float *dists, const float *dens, const float *col, int64_t n, int S, float max_dist,
                     float *w, float *depth, float *color, float *trans, int *nan_flag, void *stream)
 {
@@ -971,7 +1000,8 @@ static size_t carve_bytes(size_t n_floats)
 
 static int render_pass(neddf_ctx *ctx, int slot, const float *rd, const float *ro, const float *view, const float *dists, int64_t B, int S,
                        const neddf_render_params *rp, float *pos, float *dir, float *var, float *dens, float *col, float *pen,
-                       float *w_out, float *depth, float *color, float *trans, float *pen_out, int *nan_flag, hipStream_t s)
+                       float *w_out, float *depth, float *color, float *trans, float *pen_out, int *nan_flag, hipStream_t s,
+                       float *nrm = nullptr, float *normal_out = nullptr)      // nrm [B, S, 3] workspace, normal_out [B, 3] (the normal target)
 {
     RaySrc rays;
     rays.rd = rd; rays.ro = ro; rays.view = view; rays.dists = dists; rays.S = S;
@@ -983,15 +1013,16 @@ static int render_pass(neddf_ctx *ctx, int slot, const float *rd, const float *r
     // densities only -- the colour trunk is skipped (the reference evaluates and discards it)
     const bool want_col = depth || color || trans || want_pen;
     int rc = field_forward(ctx, slot, pos, dir, var, B * S, want_pen ? NEDDF_OUT_FULL : NEDDF_OUT_MINIMAL, nullptr, dens, want_col ? col : nullptr,
-                           want_pen ? pen : nullptr, nullptr, s, &rays);
+                           want_pen ? pen : nullptr, nullptr, s, &rays, nullptr, normal_out ? nrm : nullptr);
     if (rc) return rc;
     STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite(dists, dens, want_col ? col : nullptr, B, S, rp->max_dist, w_out, depth, color, trans, nan_flag, s));
+    if (normal_out) STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite_normal(dists, dens, nrm, B, S, normal_out, s));
     if (want_pen) STAGE(ctx, s, NEDDF_STAGE_PENALTY, launch_integrate_penalty(dists, pen, B, S, pen_out, s));
     return 0;
 }
 
-int neddf_render_rays(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, const neddf_camera *cam, const neddf_render_params *rp,
-                      const float *Uc, const float *Uf, const neddf_render_outputs *out, void *stream)
+static int render_rays_impl(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, const neddf_camera *cam, const neddf_render_params *rp,
+                            const float *Uc, const float *Uf, const neddf_render_outputs *out, float *normal, float *normal_coarse, void *stream)
 {
     if (!ctx) return NEDDF_EINVAL;
     if (B <= 0) return 0;           // empty batch: nothing to do (pointers of empty tensors may be NULL)
@@ -1003,6 +1034,7 @@ int neddf_render_rays(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, co
     size_t need = 2 * carve_bytes(B * 3) + carve_bytes(B * Sc1) + carve_bytes(B * S2) + 3 * carve_bytes(B * S2 * 3) +
                   2 * carve_bytes(B * S2) + carve_bytes(B * S2 * 3) + carve_bytes(B * (Sc1 - 1)) + carve_bytes(B * (S2 - 1)) +
                   8 * carve_bytes(B * 3);
+    if (normal || normal_coarse) need += carve_bytes(B * S2 * 3);       // the per-sample normals of one pass
     // the arena is also used by field_forward as a colour sink only when colour is not requested; never the case here
     if (int rc = ensure(ctx, ctx->arena, need)) return rc;
     ctx->carve_guards.clear();
@@ -1021,6 +1053,7 @@ int neddf_render_rays(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, co
     float *depth = out->depth ? out->depth : cv.take(B);
     float *color = out->color ? out->color : cv.take(B * 3);
     float *trans = out->transmittance ? out->transmittance : cv.take(B);
+    float *nrm = (normal || normal_coarse) ? cv.take(B * S2 * 3) : nullptr;
     int *flags = (int *)ctx->flags.p;
     int *nan_flag = out->nan_flag ? out->nan_flag : flags;
 
@@ -1033,7 +1066,7 @@ int neddf_render_rays(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, co
     }
     STAGE(ctx, s, NEDDF_STAGE_SAMPLE_COARSE, launch_sample_coarse(Uc, B, Sc1, rp->dist_near, rp->dist_far, dc, s));
     int rc = render_pass(ctx, NEDDF_SLOT_COARSE, rd, ro, view, dc, B, Sc1, rp, pos, dir, var, dens, col, pen, wc, depth_c, color_c,
-                         trans_c, out->fields_penalty_coarse, nan_flag, s);
+                         trans_c, out->fields_penalty_coarse, nan_flag, s, nrm, normal_coarse);
     if (rc) return rc;
     // the reference takes the NaN-fallback decision of sample_pdf per render_rays call, i.e. per `chunk` rays of render_image
     const int64_t group = rp->nan_group > 0 ? rp->nan_group : B;
@@ -1041,14 +1074,28 @@ int neddf_render_rays(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, co
     if (int rc = ensure(ctx, ctx->rflags, (size_t)((B + goff + group - 1) / group) * sizeof(int))) return rc;
     STAGE(ctx, s, NEDDF_STAGE_RESAMPLE, launch_resample(dc, wc, Uf, B, Sc1, Sf1, 1, df, nullptr, (int *)ctx->rflags.p, group, goff, s));
     rc = render_pass(ctx, NEDDF_SLOT_FINE, rd, ro, view, df, B, S2, rp, pos, dir, var, dens, col, pen, out->weight, depth, color, trans,
-                     out->fields_penalty, nan_flag, s);
+                     out->fields_penalty, nan_flag, s, nrm, normal);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-int neddf_render_rays_single(neddf_ctx *ctx, int slot, const void *uv, int uv_type, int64_t B, const neddf_camera *cam,
-                             const neddf_render_params *rp, int S1, const float *U, const neddf_render_outputs *out, void *stream)
+int neddf_render_rays(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, const neddf_camera *cam, const neddf_render_params *rp,
+                      const float *Uc, const float *Uf, const neddf_render_outputs *out, void *stream)
+{
+    return render_rays_impl(ctx, uv, uv_type, B, cam, rp, Uc, Uf, out, nullptr, nullptr, stream);
+}
+
+int neddf_render_rays_surface(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, const neddf_camera *cam, const neddf_render_params *rp,
+                              const float *Uc, const float *Uf, const neddf_render_outputs *out, float *normal, float *normal_coarse,
+                              void *stream)
+{
+    return render_rays_impl(ctx, uv, uv_type, B, cam, rp, Uc, Uf, out, normal, normal_coarse, stream);
+}
+
+static int render_rays_single_impl(neddf_ctx *ctx, int slot, const void *uv, int uv_type, int64_t B, const neddf_camera *cam,
+                                   const neddf_render_params *rp, int S1, const float *U, const neddf_render_outputs *out, float *normal,
+                                   void *stream)
 {
     if (!ctx) return NEDDF_EINVAL;
     if (B <= 0) return 0;
@@ -1058,6 +1105,7 @@ int neddf_render_rays_single(neddf_ctx *ctx, int slot, const void *uv, int uv_ty
     if (slot < 0 || slot >= NEDDF_NUM_SLOTS || !ctx->field[slot].valid) return fail(ctx, NEDDF_ENOFIELD, "no field in slot");
     size_t need = 2 * carve_bytes(B * 3) + carve_bytes(B * S1) + 3 * carve_bytes(B * S1 * 3) + 2 * carve_bytes(B * S1) +
                   carve_bytes(B * S1 * 3) + 5 * carve_bytes(B * 3);
+    if (normal) need += carve_bytes(B * S1 * 3);
     if (int rc = ensure(ctx, ctx->arena, need)) return rc;
     ctx->carve_guards.clear();
     Carver cv{ (char *)ctx->arena.p, ctx, s };
@@ -1068,6 +1116,7 @@ int neddf_render_rays_single(neddf_ctx *ctx, int slot, const void *uv, int uv_ty
     float *depth = out->depth ? out->depth : cv.take(B);
     float *color = out->color ? out->color : cv.take(B * 3);
     float *trans = out->transmittance ? out->transmittance : cv.take(B);
+    float *nrm = normal ? cv.take(B * S1 * 3) : nullptr;
     int *nan_flag = out->nan_flag ? out->nan_flag : (int *)ctx->flags.p;
     STAGE(ctx, s, NEDDF_STAGE_RAYGEN, launch_raygen(uv, uv_type, B, cam_arg(cam), rd, ro, s));
     const float *view = nullptr;
@@ -1078,10 +1127,23 @@ int neddf_render_rays_single(neddf_ctx *ctx, int slot, const void *uv, int uv_ty
     }
     STAGE(ctx, s, NEDDF_STAGE_SAMPLE_COARSE, launch_sample_coarse(U, B, S1, rp->dist_near, rp->dist_far, dc, s));
     int rc = render_pass(ctx, slot, rd, ro, view, dc, B, S1, rp, pos, dir, var, dens, col, pen, out->weight, depth, color, trans,
-                         out->fields_penalty, nan_flag, s);
+                         out->fields_penalty, nan_flag, s, nrm, normal);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+int neddf_render_rays_single(neddf_ctx *ctx, int slot, const void *uv, int uv_type, int64_t B, const neddf_camera *cam,
+                             const neddf_render_params *rp, int S1, const float *U, const neddf_render_outputs *out, void *stream)
+{
+    return render_rays_single_impl(ctx, slot, uv, uv_type, B, cam, rp, S1, U, out, nullptr, stream);
+}
+
+int neddf_render_rays_single_surface(neddf_ctx *ctx, int slot, const void *uv, int uv_type, int64_t B, const neddf_camera *cam,
+                                     const neddf_render_params *rp, int S1, const float *U, const neddf_render_outputs *out, float *normal,
+                                     void *stream)
+{
+    return render_rays_single_impl(ctx, slot, uv, uv_type, B, cam, rp, S1, U, out, normal, stream);
 }
 
 int neddf_op_activation(neddf_ctx *ctx, int op, const float *x, const float *J, int64_t N, int C, float *y, float *G, void *stream)
@@ -1271,6 +1333,21 @@ int neddf_marching_cubes(neddf_ctx *ctx, const float *d_volume, int nx, int ny, 
     int32_t *vbase = (int32_t *)ctx->mc_vbase.p;
     launch_mc_vertices(g, mask, vblk, vbase, d_vertices, s);
     launch_mc_triangles(g, mask, tblk, vbase, d_triangles, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_mesh_vertex_normals(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                              float *d_normals, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (n_vertices < 0 || n_triangles < 0) return fail(ctx, NEDDF_EINVAL, "mesh_vertex_normals: negative count");
+    if (n_vertices == 0) return 0;
+    if (!d_vertices || !d_normals || (n_triangles > 0 && !d_triangles)) return fail(ctx, NEDDF_EINVAL, "mesh_vertex_normals: NULL vertices, triangles or normals");
+    if (n_vertices >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "mesh_vertex_normals: 2^31 vertices or more (triangle indices are int32)");
+    DeviceGuard guard_(ctx->device);
+    if (int rc = ensure(ctx, ctx->mc_nacc, (size_t)(3 * n_vertices + 1) * sizeof(unsigned long long))) return rc;
+    launch_mesh_normals(d_vertices, n_vertices, d_triangles, n_triangles, (unsigned long long *)ctx->mc_nacc.p, d_normals, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -212,6 +212,72 @@ void launch_composite(const float *dists, const float *dens, const float *col, i
                        depth, color, trans, nan_flag);
 }
 
+// Normal render target: normal[b] = sum_j weight[b, j] * n[b, j] over the S - 1 intervals of composite_kernel, with composite_kernel's
+// own weights -- the same expressions in the same order (one wavefront per ray, the fp64 multiplicative wave scan, wave_sum's fixed
+// butterfly), so the weights are its weights bit for bit and two runs agree bitwise.  A kernel of its own: composite_kernel, and with
+// it colour / depth / transmittance / weight, is untouched by the target.  nrm [n, S, 3]: what the field hands to its colour trunk.
+__global__ __launch_bounds__(256) void composite_normal_kernel(const float *dists, const float *dens, const float *nrm, int64_t n,
+                                                               int S, float *normal)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (b >= n) return;
+    const float *d = dists + b * S, *r = dens + b * S, *c = nrm + b * S * 3;
+    double carry = 1.0;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (int base = 0; base < S - 1; base += 64) {
+        int j = base + lane;
+        bool on = j < S - 1;
+        float dj = on ? d[j] : 0.f;
+        float delta = on ? d[j + 1] - dj : 0.f;
+        float o = on ? 1.0f - expf(-r[j] * delta) : 0.f;
+        double aj = on ? (double)(1.0f - o + 1e-7f) : 1.0;
+        double incl = wave_scan_mul(aj, lane) * carry;
+        double excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = carry;
+        float tprev = (float)excl;
+        float w = o * tprev;
+        if (on) {
+            s0 += w * c[3 * j + 0];
+            s1 += w * c[3 * j + 1];
+            s2 += w * c[3 * j + 2];
+        }
+        carry = __shfl(incl, 63, 64);
+    }
+    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
+    if (lane == 0) { normal[3 * b + 0] = s0; normal[3 * b + 1] = s1; normal[3 * b + 2] = s2; }
+}
+
+void launch_composite_normal(const float *dists, const float *dens, const float *nrm, int64_t n, int S, float *normal, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(composite_normal_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dists, dens, nrm, n, S, normal);
+}
+
+// The position gradient and the normal of the distance trunk, read back from the per-point record it leaves for the colour kernel
+// (kernels.h PA_*): normal = slots PA_N0..2 -- NeDDF: g / (|g| + 1e-7) (neddf.py:241), NeuS: the sdf gradient itself, which is what
+// neus.py:144-145 concatenates into the colour input -- and the gradient = PA_DG0..2 (NeDDF) or PA_N0..2 (NeuS).  Not valid for the
+// gradient of a rays-sourced launch (PA_R_POS lives in PA_DG*): the host never asks for it there.
+__global__ __launch_bounds__(256) void surface_gather_kernel(const float *ptaux, int64_t n, int neus, float *dgrad, float *normal)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float *pa = ptaux + i * kPtAux;
+    const float n0 = pa[PA_N0], n1 = pa[PA_N1], n2 = pa[PA_N2];
+    if (normal) { normal[3 * i + 0] = n0; normal[3 * i + 1] = n1; normal[3 * i + 2] = n2; }
+    if (dgrad) {
+        dgrad[3 * i + 0] = neus ? n0 : pa[PA_DG0];
+        dgrad[3 * i + 1] = neus ? n1 : pa[PA_DG1];
+        dgrad[3 * i + 2] = neus ? n2 : pa[PA_DG2];
+    }
+}
+
+void launch_surface_gather(const float *ptaux, int64_t n, int neus, float *dgrad, float *normal, hipStream_t s)
+{
+    if (n <= 0 || (!dgrad && !normal)) return;
+    hipLaunchKernelGGL(surface_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ptaux, n, neus, dgrad, normal);
+}
+
 // penalty line integral nerf_render.py:153-159
 __global__ __launch_bounds__(256) void integrate_penalty_kernel(const float *dists, const float *pen, int64_t n, int S, float *out)
 {

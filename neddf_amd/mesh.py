@@ -29,22 +29,60 @@ def marching_cubes(volume, iso, lo=(-1.0, -1.0, -1.0), hi=(1.0, 1.0, 1.0)):
     return Context.get(volume.device).marching_cubes(volume.contiguous(), iso, lo, hi)
 
 
-def write_ply(path, vertices, triangles):
-    """Binary little-endian PLY: vertex (float x, y, z), face (list uchar int vertex_indices)."""
-    v = np.ascontiguousarray(vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else vertices, dtype="<f4")
-    t = np.ascontiguousarray(triangles.detach().cpu().numpy() if isinstance(triangles, torch.Tensor) else triangles, dtype="<i4")
+def vertex_normals(vertices, triangles):
+    """Geometric vertex normals float32 [V, 3] of an indexed device mesh: the normalised, area-weighted sum of the incident
+    triangles' cross products (p1 - p0) x (p2 - p0); a vertex whose sum vanishes gets (0, 0, 0).  Independent of timing
+    (include/neddf_hip.h neddf_mesh_vertex_normals)."""
+    if not isinstance(vertices, torch.Tensor) or not vertices.is_cuda:
+        raise NeddfError("vertex_normals: the mesh must live on a HIP device")
+    return Context.get(vertices.device).mesh_vertex_normals(vertices, triangles)
+
+
+def _host(a, dtype):
+    return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=dtype)
+
+
+def write_ply(path, vertices, triangles, normals=None, colors=None):
+    """Binary little-endian PLY: vertex (float x, y, z), face (list uchar int vertex_indices).
+    normals [V, 3] append `property float nx, ny, nz`; colors [V, 3] -- floats in [0, 1] in the field's channel order, which is the
+    dataset's B, G, R -- append `property uchar red, green, blue`: swapped to R, G, B, times 255, rounded half to even, clamped to
+    [0, 255].  With both None the file is the plain 12-bytes-per-vertex one."""
+    v = _host(vertices, "<f4")
+    t = _host(triangles, "<i4")
     if v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
         raise ValueError("write_ply: vertices [V, 3] and triangles [T, 3] expected (got %s, %s)" % (v.shape, t.shape))
-    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-            "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(v), len(t)))
+    fields, props = [("p", "<f4", (3,))], "property float x\nproperty float y\nproperty float z\n"
+    extra = {}
+    if normals is not None:
+        extra["n"] = _host(normals, "<f4")
+        fields.append(("n", "<f4", (3,)))
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+    if colors is not None:
+        c = _host(colors, np.float64)
+        extra["c"] = np.clip(np.rint(np.nan_to_num(c[..., ::-1]) * 255.0), 0, 255).astype(np.uint8)       # np.rint: half to even; NaN -> 0
+        fields.append(("c", "u1", (3,)))
+        props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    for k, a in extra.items():
+        if a.shape != v.shape:
+            raise ValueError("write_ply: normals / colors must be [V, 3] like the vertices (got %s)" % (a.shape,))
+    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n%s"
+            "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(v), props, len(t)))
+    if extra:
+        rec = np.empty(len(v), dtype=np.dtype(fields))
+        rec["p"] = v
+        for k, a in extra.items():
+            rec[k] = a
+        vbytes = rec.tobytes()
+    else:
+        vbytes = v.tobytes()
     faces = np.empty(len(t), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
     faces["n"] = 3
     faces["i"] = t
     with open(path, "wb") as fh:
         fh.write(head.encode("ascii"))
-        fh.write(v.tobytes())
+        fh.write(vbytes)
         fh.write(faces.tobytes())
     return path
 
 
-__all__ = ["marching_cubes", "write_ply"]
+__all__ = ["marching_cubes", "vertex_normals", "write_ply"]

@@ -142,7 +142,7 @@ class BaseNeuralField(ABC, nn.Module):
         return {"distance": "distance", "density": "density"}
 
     def extract_mesh(self, field_name: str = "distance", threshold: float = 0.0275, cube_range: float = 1.1,
-                     resolution: int = 64, timings: Optional[Dict[str, float]] = None):
+                     resolution: int = 64, timings: Optional[Dict[str, float]] = None, normals=False, colors: bool = False):
         """Triangle mesh of the `threshold` level set of `field_name` in the cube [-cube_range, cube_range]^3 sampled at
         resolution^3 points -- the reference's generate_mesh (fields_visualizer.py:528-566: voxelize("distance", 1.1, 64),
         mcubes.marching_cubes(voxel, 0.0275)) with the grid evaluation and marching cubes on the GPU.
@@ -152,9 +152,23 @@ class BaseNeuralField(ABC, nn.Module):
         Returns (vertices float32 [V, 3], triangles int32 [T, 3]) on the field's device.  Vertices are in world coordinates;
         the reference's .dae holds mcubes' index coordinates in voxelize's [y, z, x] order instead, mapped to the world by
         (index - resolution / 2) * 2 * cube_range / resolution.  `timings` (a dict, optional) receives the wall time in seconds
-        of the grid evaluation ("grid") and of marching cubes ("mcubes"), each ending in a device synchronise."""
+        of the grid evaluation ("grid") and of marching cubes ("mcubes"), each ending in a device synchronise.
+
+        normals (not in the reference, whose export carries none): False, True / "field" or "geometric".  "field": the field's
+        own normal at every vertex (forward_surface with var = 0), normalised to unit length -- NeDDF and NeuS; it points
+        towards increasing distance, i.e. out of the object like the triangles.  "geometric": the area-weighted mean of the
+        incident triangles' normals (mesh.vertex_normals).  True takes "field" where the field has one and "geometric" for NeRF.
+        colors: the colour trunk at every vertex seen straight on, dir = -normal (for NeRF fields the geometric normal), float32
+        [V, 3] in the field's channel order (the dataset's B, G, R).  With either option the result is a tuple
+        (vertices, triangles[, normals][, colors]); "normals" / "colors" in `timings` receive their wall time."""
         import time
-        from .mesh import marching_cubes
+        from .mesh import marching_cubes, vertex_normals
+        if normals is True:
+            normals = "field" if self._has_surface() else "geometric"
+        if normals not in (False, None, "field", "geometric"):
+            raise ValueError("extract_mesh: normals must be False, True, 'field' or 'geometric' (got %r)" % (normals,))
+        if normals == "field" and not self._has_surface():
+            raise ValueError("extract_mesh: %s fields have no field normal; use normals='geometric'" % type(self).__name__)
         names = self._grid_fields()
         if field_name not in names:
             raise ValueError("extract_mesh: %s fields offer %s (got %r)" % (type(self).__name__, sorted(names), field_name))
@@ -171,9 +185,65 @@ class BaseNeuralField(ABC, nn.Module):
                 tris = tris[:, [0, 2, 1]].contiguous()
             torch.cuda.synchronize(self.device)
             t2 = time.perf_counter()
+            out = [verts, tris]
+            nrm = None
+            if normals or colors:
+                kind = normals or ("field" if self._has_surface() else "geometric")
+                if verts.shape[0] == 0:
+                    nrm = torch.empty_like(verts)
+                elif kind == "field":
+                    view = torch.tensor([1.0, 0.0, 0.0], device=verts.device).expand_as(verts).contiguous()     # voxelize's; the normal ignores it
+                    nrm = self.forward_surface(Sampling(verts[None], view[None], torch.zeros_like(verts)[None]), want=("normal",))["normal"][0]
+                    nrm = nrm / nrm.norm(dim=1, keepdim=True).clamp_min(1e-20)
+                else:
+                    nrm = vertex_normals(verts, tris)
+                if normals:
+                    out.append(nrm)
+            torch.cuda.synchronize(self.device)
+            t3 = time.perf_counter()
+            if colors:
+                if verts.shape[0] == 0:
+                    out.append(torch.empty_like(verts))
+                else:
+                    smp = Sampling(verts[None], (-nrm)[None].contiguous(), torch.zeros_like(verts)[None])
+                    out.append(self._run(smp, OUT_MINIMAL, ("color",))["color"][0])
+            torch.cuda.synchronize(self.device)
+            t4 = time.perf_counter()
         if timings is not None:
             timings["grid"], timings["mcubes"] = t1 - t0, t2 - t1
-        return verts, tris
+            if normals:
+                timings["normals"] = t3 - t2
+            if colors:
+                timings["colors"] = t4 - t3
+        return tuple(out) if (normals or colors) else (verts, tris)
+
+    def _has_surface(self) -> bool:
+        """True for fields with a distance / sdf trunk, whose position gradient is the surface normal (NeDDF, NeuS)."""
+        return False
+
+    def forward_surface(self, sampling: Sampling, want=None) -> Dict[str, Tensor]:
+        """forward()'s inference outputs plus `distance_grad` and `normal` [B,S,3]: the position gradient of the distance (NeuS:
+        sdf) and the value the colour trunk receives -- NeDDF: distance_grad / (|distance_grad| + 1e-7) (neddf.py:241), NeuS: the
+        sdf gradient as it is (neus.py:144-145).  Both come out of the hand-off record of the distance kernel; the other outputs
+        are forward()'s bit for bit.  Inference only: call it under torch.no_grad().  NeRF fields raise."""
+        if not self._has_surface():
+            raise NotImplementedError("%s fields have no distance or sdf, hence no surface normal" % type(self).__name__)
+        if torch.is_grad_enabled():
+            raise RuntimeError("forward_surface runs the inference kernels and carries no autograd graph: call it under torch.no_grad()")
+        out_mode, names = self._surface_outputs()
+        if want is not None:
+            names = tuple(want)
+        pos = sampling.sample_pos
+        ctx = Context.get(pos.device)
+        self.upload(ctx, self._slot)
+        B, S = pos.shape[0], pos.shape[1]
+        o = ctx.field_forward_surface(self._slot, pos, sampling.sample_dir, sampling.diag_variance, out_mode, names)
+        wide = ("color", "distance_grad", "normal")
+        return {k: (v.view(B, S, 3) if k in wide else v.view(B, S)) for k, v in o.items()}
+
+    def _surface_outputs(self):
+        """(out mode, output names) of forward_surface."""
+        raise NotImplementedError()
 
     # ---- training at hidden widths other than 256 ---------------------------------------------------------------------
     # The training kernels are built for hidden width 256 (every field kind) and, on their per-layer route in 256 x 256 blocks,
@@ -347,6 +417,14 @@ class NeDDF(BaseNeuralField):
         if self.output_mode == "full":
             return self._run(sampling, OUT_FULL, ("distance", "density", "color", "fields_penalty", "aux_grad"))
         return self._run(sampling, OUT_MINIMAL, ("distance", "density", "color", "aux_grad"))
+
+    def _has_surface(self) -> bool:
+        return True
+
+    def _surface_outputs(self):
+        if self.output_mode == "full":
+            return OUT_FULL, ("distance", "density", "color", "fields_penalty", "aux_grad", "distance_grad", "normal")
+        return OUT_MINIMAL, ("distance", "density", "color", "aux_grad", "distance_grad", "normal")
 
     def set_iter(self, iter: int) -> None:
         """Warm-up schedule (neddf.py:311-326); -1 = evaluation."""
@@ -552,6 +630,18 @@ class NeuS(BaseNeuralField):
 
     def set_iter(self, iter: int) -> None:      # base_neuralfield.py:14-22: no warm-up state
         pass
+
+    def _has_surface(self) -> bool:
+        return True
+
+    def _surface_outputs(self):
+        return OUT_MINIMAL, ("distance", "density", "color", "distance_grad", "normal")
+
+    def forward_surface(self, sampling: Sampling, want=None) -> Dict[str, Tensor]:
+        o = super().forward_surface(sampling, want)
+        if "distance" in o:
+            o["sdf"] = o.pop("distance")
+        return o
 
     def _grid_fields(self):
         return {"sdf": "distance", "density": "density"}

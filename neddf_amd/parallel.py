@@ -187,6 +187,9 @@ def render_image_sharded(render, width: int, height: int, camera, target_types: 
     draws only its own uniforms, which makes the image independent of the world
     size and the host cost proportional to the slab."""
     keys = list(target_types)
+    if "normal" in keys:
+        raise NotImplementedError("render_image_sharded gathers five floats per ray (colour, depth, transmittance): the normal target "
+                                  "is not wired through the pixel gather; render it on one device with NeRFRender.render_image")
     w, h = width // downsampling, height // downsampling
     n = w * h
     rank, world = dist.get_rank(group), dist.get_world_size(group)

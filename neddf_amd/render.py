@@ -19,7 +19,7 @@ from .config import instantiate
 from .network import BaseNeuralField, NeDDF
 from .rng import skip_uniforms
 
-RenderTarget = str          # Literal["color", "depth", "transmittance"]
+RenderTarget = str          # Literal["color", "depth", "transmittance", "normal"]
 SamplingType = str          # Literal["point", "cone"]
 
 
@@ -62,9 +62,17 @@ class NeRFRender(BaseNeuralRender):
                    generation and the samplers join the graph as in the reference (camera.py:155-171, ray.py:88-194 are
                    differentiable torch there), so loss.backward() fills camera.params.grad.  NeDDF and NeRF fields with fp32
                    operands and world-space rays; NeuS, NDC rays and split-fp16 operands raise.  The intrinsics get no gradient.
+    normal_output  (attribute) False (default): render_rays returns the reference's keys.  True: its inference path appends `normal`
+                   and `normal_coarse` [B,3] = sum_j weight[b,j] * normal[b,j], the field's per-sample normal (the value its colour trunk
+                   receives: BaseNeuralField.forward_surface) integrated over the intervals and with the weights of `color`
+                   (base_neural_render.py:154-160).  Not normalised: the length is at most 1 - transmittance for NeDDF's unit
+                   normals, the background is the zero vector.  NeDDF and NeuS fields; NeRF fields raise.  The autograd path
+                   (training) ignores it.  render_image takes the same quantity as the target type "normal",
+                   render_image_single_pass as normals=True.
     """
 
     pose_gradients = False
+    normal_output = False
 
     def __init__(self, network_config: Any, sample_coarse: int = 128, sample_fine: int = 128, dist_near: float = 2.0,
                  dist_far: float = 6.0, max_dist: float = 6.0, use_coarse_network: bool = True,
@@ -160,8 +168,14 @@ class NeRFRender(BaseNeuralRender):
         return out
 
     # -------------------------------------------------------------- render_rays
+    def _check_normal_fields(self, coarse: bool) -> None:
+        for net in ([self.network_coarse] if coarse else []) + [self.network_fine]:
+            if not net._has_surface():
+                raise NotImplementedError("the normal target needs a field with a distance or sdf trunk (NeDDF, NeuS); %s has none"
+                                          % type(net).__name__)
+
     def _render(self, ctx: Context, uv: Tensor, camera: Camera, U_c: Tensor, U_f: Tensor, full: bool, cam_desc=None,
-                nan_group: int = 0, nan_group_offset: int = 0) -> Dict[str, Tensor]:
+                nan_group: int = 0, nan_group_offset: int = 0, normal: bool = False) -> Dict[str, Tensor]:
         B = uv.shape[0]
         dev = uv.device
         S2 = self.sample_coarse + self.sample_fine + 2
@@ -175,13 +189,20 @@ class NeRFRender(BaseNeuralRender):
                      weight_coarse=buf(B, self.sample_coarse))
             if self._has_penalty():
                 o.update(fields_penalty=buf(B), fields_penalty_coarse=buf(B))
+        if normal:
+            self._check_normal_fields(coarse=full)
+            o.update(normal=buf(B, 3))
+            if full:
+                o.update(normal_coarse=buf(B, 3))
         flag = torch.zeros(1, device=dev, dtype=torch.int32)
         ctx.render_rays(uv, camera.descriptor() if cam_desc is None else cam_desc, self._params(nan_group, nan_group_offset), U_c, U_f, dict(o, nan_flag=flag))
         o["_nan"] = flag
         return o
 
     def render_rays(self, uv: Tensor, camera: Camera) -> Dict[str, Tensor]:
-        """nerf_render.py:109-188.  Keys: weight, depth, color, transmittance[, fields_penalty] + *_coarse."""
+        """nerf_render.py:109-188.  Keys: weight, depth, color, transmittance[, fields_penalty] + *_coarse.
+        With the attribute normal_output set, the inference path appends normal and normal_coarse [B,3] (see the class
+        docstring); the autograd path below ignores the attribute."""
         uv = uv.to(camera.device)
         B = uv.shape[0]
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
@@ -189,10 +210,10 @@ class NeRFRender(BaseNeuralRender):
         ctx = self._ctx(uv.device)
         U_c = self._rand(B, self.sample_coarse + 1, uv.device)       # draw order is part of the contract
         U_f = self._rand(B, self.sample_fine + 1, uv.device)
-        o = self._render(ctx, uv, camera, U_c, U_f, full=True)
+        o = self._render(ctx, uv, camera, U_c, U_f, full=True, normal=bool(self.normal_output))
         assert int(o.pop("_nan").item()) == 0, "NaN weight in integrate_volume_render"
         order = ["weight", "depth", "color", "transmittance", "fields_penalty", "weight_coarse", "depth_coarse",
-                 "color_coarse", "transmittance_coarse", "fields_penalty_coarse"]
+                 "color_coarse", "transmittance_coarse", "fields_penalty_coarse", "normal", "normal_coarse"]
         return {k: o[k] for k in order if k in o}
 
     def _render_rays_with_grad(self, uv: Tensor, camera: Camera) -> Dict[str, Tensor]:
@@ -286,8 +307,13 @@ class NeRFRender(BaseNeuralRender):
         row-major pixel index and returns flat [hi-lo, C] tensors -- the unit of
         multi-GPU ray sharding (neddf_amd/parallel.py); the slab's uniforms are the
         ones the whole-frame draw would have given it (generator jump-ahead, rng.py),
-        so the image does not depend on the sharding."""
+        so the image does not depend on the sharding.
+        target_types may hold "normal" (not a reference target): [h, w, 3], the normal_output quantity of the class docstring;
+        the other targets are the same bits with or without it."""
         target_types = list(target_types)
+        want_normal = "normal" in target_types
+        if want_normal:
+            self._check_normal_fields(coarse=False)
         with torch.no_grad():
             dev = camera.device
             w, h = width // downsampling, height // downsampling
@@ -308,7 +334,7 @@ class NeRFRender(BaseNeuralRender):
                 # sample_pdf's NaN fallback keeps the reference's per-chunk granularity: batches start on chunk boundaries,
                 # except a slab's first batch, which may start inside a chunk another rank shares
                 o = self._render(ctx, uv[below:above], camera, U_c, U_f, full=False, cam_desc=cam_desc, nan_group=chunk,
-                                 nan_group_offset=below % chunk)
+                                 nan_group_offset=below % chunk, normal=want_normal)
                 flags.append(o["_nan"])
                 for k in target_types:
                     parts[k].append(o[k])
@@ -347,7 +373,7 @@ class NeRFRender(BaseNeuralRender):
             if pixel_range is None:
                 images = {k: torch.cat(parts[k], 0).reshape(h, w, -1) for k in target_types}
             elif hi <= lo:          # an empty slab (more ranks than chunks)
-                images = {k: torch.empty(0, 3 if k == "color" else 1, device=dev) for k in target_types}
+                images = {k: torch.empty(0, 3 if k in ("color", "normal") else 1, device=dev) for k in target_types}
             else:
                 images = {k: torch.cat(parts[k], 0).reshape(hi - lo, -1) for k in target_types}
             self.network_coarse.train(True)
@@ -355,12 +381,15 @@ class NeRFRender(BaseNeuralRender):
         return images
 
     def render_image_single_pass(self, width: int, height: int, camera: Camera, samples: int,
-                                 U: Optional[Tensor] = None, pixel_range=None) -> Dict[str, Tensor]:
+                                 U: Optional[Tensor] = None, pixel_range=None, normals: bool = False) -> Dict[str, Tensor]:
         """One stratified pass of `samples` points per ray through network_fine
         (BASELINE.json configs[1]).  Not a reference method: it is render_rays'
         coarse half (nerf_render.py:128-152) at image scale.  pixel_range=(lo,hi)
         restricts to a slab of the row-major pixel index (multi-GPU sharding).
-        Returns flat per-ray tensors color [n,3], depth [n], transmittance [n]."""
+        Returns flat per-ray tensors color [n,3], depth [n], transmittance [n]; with normals=True also normal [n,3]
+        (the normal_output quantity of the class docstring), the others unchanged."""
+        if normals:
+            self._check_normal_fields(coarse=False)
         with torch.no_grad():
             dev = camera.device
             lo, hi = (0, width * height) if pixel_range is None else pixel_range
@@ -370,6 +399,8 @@ class NeRFRender(BaseNeuralRender):
             ctx = self._ctx(dev)
             out = dict(color=torch.empty(n, 3, device=dev), depth=torch.empty(n, device=dev),
                        transmittance=torch.empty(n, device=dev))
+            if normals:
+                out["normal"] = torch.empty(n, 3, device=dev)
             flag = torch.zeros(1, device=dev, dtype=torch.int32)
             cam_desc = camera.descriptor()
             for below in range(0, n, self.rays_per_call):

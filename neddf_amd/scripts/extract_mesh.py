@@ -1,10 +1,12 @@
 """`python neddf/scripts/extract_mesh.py <run_dir> [--epoch 2000] [--resolution 64] [--threshold 0.0275] [--field distance]
-[--cube-range 1.1]` -- the reference's mesh export (neddf/scripts/fields_visualizer.py:528-566, generate_mesh: voxelize
+[--cube-range 1.1] [--normals [field|geometric]] [--colors]` -- the reference's mesh export (neddf/scripts/fields_visualizer.py:528-566, generate_mesh: voxelize
 "distance" on a 64^3 cube of half-width 1.1, marching cubes at 0.0275, export) without its Open3D viewer.  The run is
 loaded as run_eval loads it (`<run_dir>/.hydra/config.yaml`, `models/model_{epoch:05}.pth`); the mesh of
 `trainer.neural_render.get_network()` is written to `<run_dir>/mesh/mesh_{resolution}_threshold{threshold}.ply` (the
 reference's file name, PLY in place of collada), in world coordinates.  Prints the vertex and triangle counts and the wall
-time of the grid evaluation and of marching cubes."""
+time of the grid evaluation and of marching cubes.  --normals adds per-vertex normals (`property float nx, ny, nz`): the field's
+own (NeDDF, NeuS; the default where the field has one) or geometric ones; --colors adds the colour trunk's value at every vertex
+seen straight on (`property uchar red, green, blue`).  Without them the file is the plain positions-and-triangles PLY."""
 from argparse import ArgumentParser
 from pathlib import Path
 
@@ -12,7 +14,7 @@ from neddf_amd.mesh import write_ply
 from neddf_amd.scripts.run_eval import load_config, load_trainer
 
 
-def main(argv=None) -> Path:
+def build_parser() -> ArgumentParser:
     parser = ArgumentParser()
     parser.add_argument("output_dir", type=Path, help="directory path where models are located")
     parser.add_argument("--epoch", type=int, default=2000, help="epoch number of model")
@@ -20,17 +22,36 @@ def main(argv=None) -> Path:
     parser.add_argument("--threshold", type=float, default=0.0275, help="iso-level of the field")
     parser.add_argument("--field", default="distance", help="distance (NeDDF), sdf (NeuS) or density")
     parser.add_argument("--cube-range", type=float, default=1.1, help="half-width of the meshed cube")
-    args = parser.parse_args(argv)
+    parser.add_argument("--normals", nargs="?", const="auto", default=None, choices=["auto", "field", "geometric"],
+                        help="write vertex normals: the field's own (default for NeDDF / NeuS) or geometric ones (NeRF)")
+    parser.add_argument("--colors", action="store_true", help="write vertex colours (the colour trunk seen against the normal)")
+    return parser
+
+
+def main(argv=None) -> Path:
+    args = build_parser().parse_args(argv)
     output_dir = args.output_dir.resolve()
     trainer = load_trainer(load_config(output_dir), output_dir, args.epoch)
     trainer.neural_render.set_iter(-1)                  # the evaluation state, as render_all sets it
     network = trainer.neural_render.get_network()
     times = {}
-    verts, tris = network.extract_mesh(args.field, args.threshold, args.cube_range, args.resolution, timings=times)
+    normals, colors = None, None
+    if args.normals or args.colors:
+        want_n = True if args.normals == "auto" else (args.normals or False)
+        res = list(network.extract_mesh(args.field, args.threshold, args.cube_range, args.resolution, timings=times,
+                                        normals=want_n, colors=args.colors))
+        verts, tris = res[0], res[1]
+        normals = res[2] if want_n else None
+        colors = res[-1] if args.colors else None
+    else:
+        verts, tris = network.extract_mesh(args.field, args.threshold, args.cube_range, args.resolution, timings=times)
     save_dir = output_dir / "mesh"
     save_dir.mkdir(exist_ok=True)
     path = save_dir / "mesh_{}_threshold{}.ply".format(args.resolution, args.threshold)
-    write_ply(path, verts, tris)
+    if normals is None and colors is None:
+        write_ply(path, verts, tris)
+    else:
+        write_ply(path, verts, tris, normals=normals, colors=colors)
     print("vertices: %d, triangles: %d" % (verts.shape[0], tris.shape[0]))
     print("grid evaluation: %.3f s, marching cubes: %.3f s" % (times["grid"], times["mcubes"]))
     print("wrote %s" % path)

@@ -34,14 +34,21 @@ def load_trainer(cfg: dict, output_dir: Path, epoch: int):
     return trainer
 
 
-def main(argv=None) -> None:
+def build_parser() -> ArgumentParser:
     parser = ArgumentParser()
     parser.add_argument("output_dir", type=Path, help="directory path where models and render are located")
     parser.add_argument("--epoch", type=int, default=2000, help="epoch number of model")
     parser.add_argument("--seed", type=int, default=None,
                         help="torch seed for the sample uniforms (not a reference option: the reference's run_eval never seeds, and "
                              "torch seeds its default generator randomly per process)")
-    args = parser.parse_args(argv)
+    parser.add_argument("--normals", action="store_true",
+                        help="also write {id:03}_normal.png, the normal render target as clamp((n * 0.5 + 0.5) * 255) with world "
+                             "x, y, z as R, G, B (not a reference option; NeDDF and NeuS fields, one device)")
+    return parser
+
+
+def main(argv=None) -> None:
+    args = build_parser().parse_args(argv)
     output_dir = args.output_dir.resolve()
     cfg = load_config(output_dir)
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
@@ -70,7 +77,10 @@ def main(argv=None) -> None:
         seed = int(box[0]) % (1 << 63)
     if seed is not None:
         torch.manual_seed(seed)
-    trainer.render_all(save_dir)
+    if args.normals:
+        trainer.render_all(save_dir, normals=True)
+    else:
+        trainer.render_all(save_dir)
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

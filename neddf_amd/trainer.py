@@ -53,13 +53,16 @@ class BaseTrainer:
         """base_trainer.py:115-121"""
         self.neural_render.load_state_dict(torch.load(str(model_path), map_location="cpu"))
 
-    def render_test(self, output_dir: Path, camera_id: int, downsampling: int = 1, sharded: Any = None) -> None:
+    def render_test(self, output_dir: Path, camera_id: int, downsampling: int = 1, sharded: Any = None, normals: bool = False) -> None:
         """base_trainer.py:123-174: colour -> clamp(c*255) uint8, depth -> clamp((d-2)/4*50000/256) uint8,
         PNGs {id:03}_rgb / _rgb_gt / _depth, PSNR + SSIM vs the ground truth at full resolution.
         sharded (not a reference keyword): None = ray-shard the frame over the ranks whenever a process group is up (a
         COLLECTIVE: every rank must call, with the same torch seed -- run_eval.py / render_all); False = render on this rank
-        alone (the periodic test render of a data-parallel training run, which only rank 0 makes)."""
+        alone (the periodic test render of a data-parallel training run, which only rank 0 makes).
+        normals (not a reference keyword): also render the "normal" target and write {id:03}_normal.png =
+        clamp((n * 0.5 + 0.5) * 255), world x, y, z as R, G, B; single-device renders only."""
         rgb_gt = self.dataset[camera_id]["rgb_images"].astype(np.uint8)
+        targets = ["color", "depth"] + (["normal"] if normals else [])
         camera = self.cameras[camera_id]
         camera.update_transform()
         h, w = rgb_gt.shape[0], rgb_gt.shape[1]
@@ -68,30 +71,33 @@ class BaseTrainer:
         if sharded:
             # under a launcher (scripts/run_eval.py, BASELINE.json configs[3]): every rank renders a slab of the frame's pixel
             # index, one all-gather of the pixels, rank 0 writes the files.  Same seed on every rank => the single-GPU image
-            images = render_image_sharded(self.neural_render, w, h, camera, ["color", "depth"], downsampling, self.chunk)
+            images = render_image_sharded(self.neural_render, w, h, camera, targets, downsampling, self.chunk)
             if not self.writes_outputs:
                 return
         else:
-            images = self.neural_render.render_image(w, h, camera, ["color", "depth"], downsampling, self.chunk)
+            images = self.neural_render.render_image(w, h, camera, targets, downsampling, self.chunk)
         rgb_np = torch.clamp(images["color"] * 255, 0, 255).detach().cpu().numpy().astype(np.uint8)
         depth_np = torch.clamp((images["depth"] - 2.0) / 4.0 * 50000 / 256, 0, 255).detach().cpu().numpy().astype(np.uint8)
         output_dir = Path(output_dir)
         imwrite_bgr(output_dir / "{:03}_rgb.png".format(camera_id), rgb_np)
         imwrite_bgr(output_dir / "{:03}_rgb_gt.png".format(camera_id), rgb_gt)
         imwrite_bgr(output_dir / "{:03}_depth.png".format(camera_id), depth_np)
+        if normals:         # imwrite_bgr takes B, G, R: x, y, z -> R, G, B
+            normal_np = torch.clamp((images["normal"] * 0.5 + 0.5) * 255, 0, 255).detach().cpu().numpy().astype(np.uint8)
+            imwrite_bgr(output_dir / "{:03}_normal.png".format(camera_id), np.ascontiguousarray(normal_np[:, :, ::-1]))
         if downsampling == 1:
             psnr = peak_signal_noise_ratio(rgb_np, rgb_gt)
             ssim = structural_similarity(rgb_np, rgb_gt, channel_axis=2)
             print("psnr: {}, ssim: {}".format(psnr, ssim))
             self.last_metrics = (psnr, ssim)
 
-    def render_all(self, output_dir: Path) -> None:
-        """base_trainer.py:176-188"""
+    def render_all(self, output_dir: Path, normals: bool = False) -> None:
+        """base_trainer.py:176-188; normals: as render_test"""
         self.neural_render.set_iter(-1)
         for camera_id in range(len(self.dataset)):
             if self.writes_outputs:
                 print("rendering from camera {}".format(camera_id))
-            self.render_test(output_dir, camera_id, 1)
+            self.render_test(output_dir, camera_id, 1, normals=normals)
         if self.writes_outputs and len(self.dataset):
             # (one line after the reference's own printout, not inside it: the "psnr: .., ssim: .." lines keep the reference's format)
             print("note: PSNR is pinned on the reference's eval harness (tests/golden/eval_harness.npz); SSIM is restated from the published "
