@@ -426,6 +426,37 @@ int neddf_marching_cubes(neddf_ctx *ctx, const float *d_volume, int nx, int ny, 
 int neddf_mesh_vertex_normals(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles,
                               int64_t n_triangles, float *d_normals, void *stream);
 
+/* ---- mesh clean-up (additive to ABI v7; no reference counterpart) --------------------------------------------------
+ * Connected components of an indexed mesh (d_triangles [T][3] int32 over n_vertices vertices): two vertices belong to one
+ * component when a chain of triangles sharing vertices joins them.
+ *   - components are numbered 0 .. C-1 in the order of their lowest vertex index
+ *   - d_vertex_label [V] int32: the component of every vertex; -1 for a vertex no valid triangle references (not a component)
+ *   - a triangle with an index outside [0, n_vertices) is ignored and gets label -1 (neddf_mesh_vertex_normals' rule);
+ *     degenerate triangles (a, a, b) are valid and counted.  d_triangle_label [T] int32 may be NULL
+ *   - d_component_triangles: int64, capacity n_vertices; entry c < C = the number of valid triangles of component c, the rest untouched
+ *   - *h_n_components (HOST) = C.  T == 0 and V == 0 are legal and give C = 0
+ *   - the output does not depend on timing: union-find on the device whose root is the lowest vertex of the set (atomicMin hooks,
+ *     pointer jumping, repeated until a round changes nothing -- a unique fixed point whatever order the atomics land in), dense
+ *     labels by flag / scan / gather, counts by integer atomic adds (exact)
+ * Synchronises `stream` once per batch of 4 rounds and once at the end.  The iteration ends for every input; should it exceed
+ * 256 rounds the call returns NEDDF_EUNSUPPORTED instead of going on (a marching-cubes tube 14 380 triangles long takes 7).
+ * NEDDF_EUNSUPPORTED also for V >= 2^31. */
+int neddf_mesh_components(neddf_ctx *ctx, const int32_t *d_triangles, int64_t n_triangles, int64_t n_vertices, int32_t *d_vertex_label,
+                          int32_t *d_triangle_label, int64_t *d_component_triangles, int64_t *h_n_components, void *stream);
+/* Rounds the last neddf_mesh_components call on this context ran (0 for an empty mesh); NEDDF_EINVAL for a NULL context. */
+int neddf_mesh_components_rounds(neddf_ctx *ctx);
+/* Order-preserving compaction: keeps the triangles whose d_keep_triangle [T] byte is non-zero and whose indices all lie in
+ * [0, n_vertices), and exactly the vertices a kept triangle references.
+ *   - both keep their relative order; d_out_triangles holds the kept triangles in the new vertex numbering
+ *   - vertex coordinates are copied bit for bit (NaN payloads included); d_out_vertices must not overlap d_vertices
+ *   - d_vertex_map [V] int32 (may be NULL): the new index of every vertex, -1 for a dropped one
+ *   - the output does not depend on timing (count / scan / write launches; no atomics decide a position)
+ * Two calls, as neddf_marching_cubes: with d_out_vertices or d_out_triangles NULL, or a cap below its count, only *h_n_vertices /
+ * *h_n_triangles (HOST) are written; otherwise the mesh and d_vertex_map are too.  Synchronises `stream` once (to read the counts). */
+int neddf_mesh_compact(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                       const unsigned char *d_keep_triangle, float *d_out_vertices, int64_t vertex_cap, int32_t *d_out_triangles,
+                       int64_t triangle_cap, int32_t *d_vertex_map, int64_t *h_n_vertices, int64_t *h_n_triangles, void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

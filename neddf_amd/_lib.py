@@ -121,6 +121,9 @@ SYMBOLS = [
     ("neddf_render_rays_single_surface", C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, C.POINTER(CameraDesc),
                                                    C.POINTER(RenderParams), C.c_int, _vp, C.POINTER(RenderOutputs), _vp, _vp]),
     ("neddf_mesh_vertex_normals", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    ("neddf_mesh_components", C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    ("neddf_mesh_components_rounds", C.c_int, [_vp]),
+    ("neddf_mesh_compact", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
 ]
 
 _lib = None
@@ -368,6 +371,58 @@ class Context:
         if nv.value and nt.value:
             call(verts, tris)
         return verts, tris
+
+    @staticmethod
+    def _triangles(triangles, what):
+        require_device(triangles, "triangles")
+        t = triangles.contiguous() if triangles.dtype == torch.int32 else triangles.to(torch.int32).contiguous()
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise NeddfError("%s: triangles [T, 3] expected (got %s)" % (what, tuple(t.shape)))
+        return t
+
+    def mesh_components(self, triangles, n_vertices):
+        """Connected components of an indexed device mesh (neddf_mesh_components): (vertex_label int32 [V], triangle_label int32 [T],
+        component_triangles int64 [C]), components numbered by their lowest vertex index, -1 for what belongs to none."""
+        t = self._triangles(triangles, "mesh_components")
+        V = int(n_vertices)
+        if V < 0:
+            raise NeddfError("mesh_components: n_vertices must not be negative (got %d)" % V)
+        vl = torch.empty(V, device=t.device, dtype=torch.int32)
+        tl = torch.empty(t.shape[0], device=t.device, dtype=torch.int32)
+        sizes = torch.empty(V, device=t.device, dtype=torch.int64)          # capacity V; the first C entries are written
+        nc = _i64(0)
+        self.check(self.lib.neddf_mesh_components(self.h, _ptr(t), t.shape[0], V, _ptr(vl), _ptr(tl), _ptr(sizes), C.byref(nc),
+                                                  self.stream()))
+        return vl, tl, sizes[:nc.value].clone()
+
+    def mesh_components_rounds(self):
+        """Union-find rounds of this context's last mesh_components call."""
+        return int(self.lib.neddf_mesh_components_rounds(self.h))
+
+    def mesh_compact(self, vertices, triangles, keep_triangle):
+        """The kept triangles and the vertices they reference, both in their old order (neddf_mesh_compact), by a counting call and a
+        writing call of exactly that size: (vertices float32 [V', 3], triangles int32 [T', 3], vertex_map int32 [V])."""
+        require_device(vertices, "vertices")
+        t = self._triangles(triangles, "mesh_compact")
+        v = f32c(vertices)
+        require_device(keep_triangle, "keep_triangle")
+        k = keep_triangle.contiguous() if keep_triangle.dtype == torch.uint8 else (keep_triangle != 0).to(torch.uint8).contiguous()
+        if v.dim() != 2 or v.shape[1] != 3 or k.dim() != 1 or k.shape[0] != t.shape[0]:
+            raise NeddfError("mesh_compact: vertices [V, 3] and keep_triangle [T] expected (got %s, %s)" % (tuple(v.shape), tuple(k.shape)))
+        nv, nt = _i64(0), _i64(0)
+
+        def call(ov, ot, vmap):
+            self.check(self.lib.neddf_mesh_compact(self.h, _ptr(v), v.shape[0], _ptr(t), t.shape[0], _ptr(k), _ptr(ov),
+                                                   0 if ov is None else ov.shape[0], _ptr(ot), 0 if ot is None else ot.shape[0],
+                                                   _ptr(vmap), C.byref(nv), C.byref(nt), self.stream()))
+        call(None, None, None)
+        ov = torch.empty(nv.value, 3, device=v.device, dtype=torch.float32)
+        ot = torch.empty(nt.value, 3, device=v.device, dtype=torch.int32)
+        if nt.value == 0:           # nothing kept, hence no vertex either
+            return ov, ot, torch.full((v.shape[0],), -1, device=v.device, dtype=torch.int32)
+        vmap = torch.empty(v.shape[0], device=v.device, dtype=torch.int32)
+        call(ov, ot, vmap)
+        return ov, ot, vmap
 
     def composite(self, dists, dens, col, max_dist):
         require_device(dists, "dists")

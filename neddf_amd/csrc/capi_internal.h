@@ -98,6 +98,9 @@ struct neddf_ctx {
     DevBuf grid_pts;             // neddf_field_grid: pos / dir / var of one chunk of the lattice
     DevBuf mc_mask, mc_vbase, mc_blk;         // neddf_marching_cubes: crossed-edge byte and first vertex id per lattice point, block bases
     DevBuf mc_nacc;              // neddf_mesh_vertex_normals: 64-bit fixed-point sums [3 V] + the scale word
+    DevBuf cc_parent, cc_used, cc_blk;        // neddf_mesh_components / neddf_mesh_compact: parent (or new index) and used byte per vertex,
+                                              // block totals followed by the "changed" words of one batch of rounds
+    int cc_rounds = 0;           // union-find rounds of the last neddf_mesh_components call
     std::vector<GuardBand> carve_guards;      // NEDDF_GUARD=1: the bands behind the carves of the last render call
     bool timing = false;
     std::vector<EventPair> events;

@@ -214,6 +214,28 @@ void launch_mc_triangles(const McGrid &g, const unsigned char *mask, const int64
 // geometric vertex normals of an indexed mesh; acc: workspace of (3 V + 1) 64-bit words
 void launch_mesh_normals(const float *vertices, int64_t V, const int32_t *tris, int64_t T, unsigned long long *acc, float *normals, hipStream_t s);
 
+// Mesh clean-up (mesh_kernels.hip): connected components by union-find on the device, order-preserving compaction.
+// Every launcher takes V >= 0 and T >= 0 and launches nothing over an empty range.
+constexpr int kCcBatch = 4;              // union-find rounds between two reads of the "changed" words (one stream synchronise each)
+constexpr int kCcMaxRounds = 256;        // neddf_mesh_components gives up (NEDDF_EUNSUPPORTED) after this many rounds
+// parent[v] = v, used[v] = 0; then used[v] = 1 for the vertices of the valid triangles
+void launch_cc_init(int32_t *parent, unsigned char *used, int64_t V, const int32_t *tris, int64_t T, hipStream_t s);
+// one round: hook (per triangle, atomicMin) and one pointer jump (per vertex); *changed is set when either did anything
+void launch_cc_round(int32_t *parent, int64_t V, const int32_t *tris, int64_t T, int *changed, hipStream_t s);
+// single array, one workgroup: a[0..n) -> exclusive prefix sums in place, a[n] = the total
+void launch_scan_totals(int64_t *a, int64_t n, hipStream_t s);
+// roots (parent[v] == v, used) -> dense labels in vertex order; vertex / triangle labels and the triangle count of every component.
+// blk: [mc_blocks(V) + 1], blk[mc_blocks(V)] = the number of components afterwards
+void launch_cc_labels(const int32_t *parent, const unsigned char *used, int64_t V, const int32_t *tris, int64_t T, int64_t *blk,
+                      int32_t *vertex_label, int32_t *triangle_label, int64_t *component_triangles, hipStream_t s);
+// kept = keep flag set and every index in [0, V): used[] of their vertices, per-block totals of both, scanned
+// (vblk [mc_blocks(V) + 1], tblk [mc_blocks(T) + 1], the totals behind the bases)
+void launch_compact_count(const int32_t *tris, int64_t T, int64_t V, const unsigned char *keep, unsigned char *used, int64_t *vblk,
+                          int64_t *tblk, hipStream_t s);
+void launch_compact_write(const float *vertices, int64_t V, const int32_t *tris, int64_t T, const unsigned char *keep,
+                          const unsigned char *used, const int64_t *vblk, const int64_t *tblk, int32_t *vmap, float *out_vertices,
+                          int32_t *out_tris, hipStream_t s);
+
 void launch_linear_grad(const float *x, const float *J, int64_t n, int cin, int ldx, int cout_block, int ksteps, const float *wp,
                         const float *bias, float *y, float *G, int ldo, int nvalid, int accumulate, int grid, hipStream_t s);
 void launch_op_activation(int kind, const float *x, const float *J, int64_t N, int C, float *y, float *G, hipStream_t s);

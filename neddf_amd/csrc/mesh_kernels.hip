@@ -9,6 +9,8 @@
 //   mc_triangle_kernel   per cell: its first triangle id (block scan + block base), the triangles of its case
 //   mesh_normal_*        geometric vertex normals of an indexed mesh: area-weighted sums of the incident triangles' cross products,
 //                        accumulated in 64-bit fixed point with INTEGER atomics (exact, hence order-independent), then normalised
+//   cc_*                 connected components of an indexed mesh: union-find with atomicMin hooks and pointer jumps, dense labels
+//   compact_*            order-preserving removal of triangles and of the vertices nothing references any more
 //
 // Placement is decided by count -> scan -> write launches only: no atomics, no exchange between workgroups inside a launch,
 // so the output is the same on every run (tests/mesh_check.py restates it in numpy bit for bit).  A corner is inside when
@@ -267,6 +269,248 @@ void launch_mesh_normals(const float *vertices, int64_t V, const int32_t *tris, 
         hipLaunchKernelGGL(mesh_normal_accum_kernel, dim3(tb), dim3(kMcThreads), 0, s, vertices, V, tris, T, maxbits, acc);
     }
     hipLaunchKernelGGL(mesh_normal_finish_kernel, dim3((unsigned)((V + kMcThreads - 1) / kMcThreads)), dim3(kMcThreads), 0, s, V, maxbits, acc, normals);
+}
+
+// ---- mesh clean-up: connected components and compaction ---------------------------------------------------------------------
+// Components: union-find over the vertices with parent[v] <= v throughout, so that a set's root is its LOWEST vertex index.
+//   cc_hook_kernel   per valid triangle: m = the lowest of its three vertices' parents; the other parents (the heads of the higher
+//                    trees) and the vertices themselves are put under m with atomicMin -- whatever order the atomics land in, a
+//                    parent only ever DEcreases and always names a vertex of the same component
+//   cc_jump_kernel   per vertex: parent[v] = parent[parent[parent[v]]] (two pointer jumps)
+// Both are loop-free; the host repeats the pair until a round changes nothing (neddf_capi.hip).  A round that changes nothing leaves
+// parent[a] == parent[b] == parent[c] on every valid triangle and parent[parent[v]] == parent[v] everywhere: all vertices of a component
+// then share ONE parent r with parent[r] == r, r <= each of them and r inside the component -- r is the component's lowest vertex.  That
+// fixed point is unique, so the labels do not depend on timing (only the number of rounds may).  While it is not reached a round
+// strictly lowers some parent (if no jump can, every parent is a root, and a triangle with two parents hooks the higher root), so the
+// iteration ends for every input.  parent[] only ever holds indices in [0, V): no load leaves the array.
+// Dense labels: flag the roots (used and parent[v] == v), count / scan / write as marching cubes does, gather through parent[].
+// Triangle counts per component: integer atomic adds (exact, so order-independent), one per workgroup for the label its first
+// triangle has -- neighbouring triangles of a marching-cubes mesh share their component.
+// Compaction: keep flags -> used vertices -> per-block totals -> scans -> writes: no atomics decide a position.
+__device__ __forceinline__ bool tri_ids(const int32_t *tris, int64_t t, int64_t V, int32_t id[3])
+{
+    id[0] = tris[3 * t]; id[1] = tris[3 * t + 1]; id[2] = tris[3 * t + 2];
+    return id[0] >= 0 && id[0] < V && id[1] >= 0 && id[1] < V && id[2] >= 0 && id[2] < V;
+}
+
+// parent[] is read while other lanes lower it: a relaxed agent-scope load, never a value the compiler kept in a register
+__device__ __forceinline__ int32_t cc_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ void __launch_bounds__(kMcThreads) cc_init_kernel(int32_t *parent, unsigned char *used, int64_t V)
+{
+    const int64_t v = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    if (v >= V) return;
+    parent[v] = (int32_t)v;
+    used[v] = 0;
+}
+
+__global__ void __launch_bounds__(kMcThreads) cc_mark_kernel(const int32_t *tris, int64_t T, int64_t V, unsigned char *used)
+{
+    const int64_t t = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    int32_t id[3];
+    if (t >= T || !tri_ids(tris, t, V, id)) return;
+    used[id[0]] = 1; used[id[1]] = 1; used[id[2]] = 1;        // every writer stores the same byte
+}
+
+__global__ void __launch_bounds__(kMcThreads) cc_hook_kernel(int32_t *parent, const int32_t *tris, int64_t T, int64_t V, int *changed)
+{
+    const int64_t t = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    int32_t id[3];
+    if (t >= T || !tri_ids(tris, t, V, id)) return;
+    const int32_t p0 = cc_load(parent + id[0]), p1 = cc_load(parent + id[1]), p2 = cc_load(parent + id[2]);
+    const int32_t p[3] = { p0, p1, p2 };
+    const int32_t m = min(p0, min(p1, p2));
+    if (p0 == m && p1 == m && p2 == m) return;
+    *changed = 1;
+    for (int k = 0; k < 3; ++k)
+        if (p[k] > m) {
+            atomicMin(parent + p[k], m);           // the head of the higher tree
+            atomicMin(parent + id[k], m);          // and the vertex itself (a shortcut: the jump would get there too)
+        }
+}
+
+__global__ void __launch_bounds__(kMcThreads) cc_jump_kernel(int32_t *parent, int64_t V, int *changed)
+{
+    const int64_t v = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    if (v >= V) return;
+    const int32_t p = cc_load(parent + v);
+    const int32_t g = cc_load(parent + cc_load(parent + p));     // this launch's only writer of parent[v] is this thread
+    if (g == p) return;
+    __hip_atomic_store(parent + v, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *changed = 1;
+}
+
+__global__ void __launch_bounds__(kMcScanThreads) scan_totals_kernel(int64_t *a, int64_t n)
+{
+    __shared__ int64_t lds[kMcScanThreads];
+    int64_t carry = 0;
+    for (int64_t base = 0; base < n; base += kMcScanThreads) {
+        const int64_t q = base + threadIdx.x;
+        const int64_t v = q < n ? a[q] : 0;
+        int64_t total;
+        const int64_t e = block_exclusive_scan(v, lds, &total);
+        if (q < n) a[q] = carry + e;
+        carry += total;
+    }
+    if (threadIdx.x == 0) a[n] = carry;
+}
+
+__global__ void __launch_bounds__(kMcThreads) cc_root_count_kernel(const int32_t *parent, const unsigned char *used, int64_t V, int64_t *blk)
+{
+    const int64_t v = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    const int n = __syncthreads_count(v < V && used[v] && parent[v] == (int32_t)v);
+    if (threadIdx.x == 0) blk[blockIdx.x] = n;
+}
+
+// roots get their dense label, unused vertices -1; the other vertices are filled in by cc_gather_kernel
+__global__ void __launch_bounds__(kMcThreads) cc_root_label_kernel(const int32_t *parent, const unsigned char *used, int64_t V, const int64_t *blk,
+                                                                   int32_t *vertex_label)
+{
+    __shared__ int lds[kMcThreads];
+    const int64_t v = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    const bool use = v < V && used[v];
+    const int root = use && parent[v] == (int32_t)v;
+    int total;
+    const int off = block_exclusive_scan(root, lds, &total);
+    if (v >= V) return;
+    if (!use) vertex_label[v] = -1;
+    else if (root) vertex_label[v] = (int32_t)(blk[blockIdx.x] + off);
+}
+
+// a non-root reads its root's entry, which the launch before wrote and this one leaves alone; the first C counts are zeroed here
+__global__ void __launch_bounds__(kMcThreads) cc_gather_kernel(const int32_t *parent, const unsigned char *used, int64_t V, const int64_t *n_components,
+                                                               int32_t *vertex_label, int64_t *component_triangles)
+{
+    const int64_t v = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    if (v >= V) return;
+    if (v < *n_components) component_triangles[v] = 0;
+    const int32_t p = parent[v];
+    if (used[v] && p != (int32_t)v) vertex_label[v] = vertex_label[p];
+}
+
+__global__ void __launch_bounds__(kMcThreads) cc_triangle_kernel(const int32_t *tris, int64_t T, int64_t V, const int32_t *vertex_label,
+                                                                 int32_t *triangle_label, unsigned long long *component_triangles)
+{
+    __shared__ int head;
+    const int64_t t = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    int32_t id[3], label = -1;
+    if (t < T && tri_ids(tris, t, V, id)) label = vertex_label[id[0]];
+    if (t < T && triangle_label) triangle_label[t] = label;
+    if (threadIdx.x == 0) head = label;
+    __syncthreads();
+    const bool same = label >= 0 && label == head;
+    const int n = __syncthreads_count(same);
+    if (threadIdx.x == 0 && n) atomicAdd(component_triangles + head, (unsigned long long)n);
+    if (label >= 0 && !same) atomicAdd(component_triangles + label, 1ULL);
+}
+
+__device__ __forceinline__ bool compact_kept(const int32_t *tris, int64_t t, int64_t T, int64_t V, const unsigned char *keep, int32_t id[3])
+{
+    return t < T && keep[t] && tri_ids(tris, t, V, id);
+}
+
+__global__ void __launch_bounds__(kMcThreads) compact_mark_kernel(const int32_t *tris, int64_t T, int64_t V, const unsigned char *keep,
+                                                                  unsigned char *used, int64_t *tblk)
+{
+    const int64_t t = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    int32_t id[3];
+    const bool kept = compact_kept(tris, t, T, V, keep, id);
+    if (kept) { used[id[0]] = 1; used[id[1]] = 1; used[id[2]] = 1; }
+    const int n = __syncthreads_count(kept);
+    if (threadIdx.x == 0) tblk[blockIdx.x] = n;
+}
+
+__global__ void __launch_bounds__(kMcThreads) compact_vertex_count_kernel(const unsigned char *used, int64_t V, int64_t *vblk)
+{
+    const int64_t v = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    const int n = __syncthreads_count(v < V && used[v]);
+    if (threadIdx.x == 0) vblk[blockIdx.x] = n;
+}
+
+__global__ void __launch_bounds__(kMcThreads) compact_vertex_kernel(const unsigned *vertices, int64_t V, const unsigned char *used, const int64_t *vblk,
+                                                                    int32_t *vmap, unsigned *out_vertices)
+{
+    __shared__ int lds[kMcThreads];
+    const int64_t v = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    const int use = v < V && used[v];
+    int total;
+    const int off = block_exclusive_scan(use, lds, &total);
+    if (v >= V) return;
+    if (!use) { vmap[v] = -1; return; }
+    const int64_t o = vblk[blockIdx.x] + off;
+    vmap[v] = (int32_t)o;
+    out_vertices[3 * o] = vertices[3 * v];                // as 32-bit words: every bit pattern survives, NaN payloads included
+    out_vertices[3 * o + 1] = vertices[3 * v + 1];
+    out_vertices[3 * o + 2] = vertices[3 * v + 2];
+}
+
+__global__ void __launch_bounds__(kMcThreads) compact_triangle_kernel(const int32_t *tris, int64_t T, int64_t V, const unsigned char *keep,
+                                                                      const int64_t *tblk, const int32_t *vmap, int32_t *out_tris)
+{
+    __shared__ int lds[kMcThreads];
+    const int64_t t = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    int32_t id[3];
+    const int kept = compact_kept(tris, t, T, V, keep, id);
+    int total;
+    const int off = block_exclusive_scan(kept, lds, &total);
+    if (!kept) return;
+    const int64_t o = tblk[blockIdx.x] + off;
+    out_tris[3 * o] = vmap[id[0]];
+    out_tris[3 * o + 1] = vmap[id[1]];
+    out_tris[3 * o + 2] = vmap[id[2]];
+}
+
+void launch_cc_init(int32_t *parent, unsigned char *used, int64_t V, const int32_t *tris, int64_t T, hipStream_t s)
+{
+    if (V > 0) hipLaunchKernelGGL(cc_init_kernel, dim3((unsigned)mc_blocks(V)), dim3(kMcThreads), 0, s, parent, used, V);
+    if (V > 0 && T > 0) hipLaunchKernelGGL(cc_mark_kernel, dim3((unsigned)mc_blocks(T)), dim3(kMcThreads), 0, s, tris, T, V, used);
+}
+
+void launch_cc_round(int32_t *parent, int64_t V, const int32_t *tris, int64_t T, int *changed, hipStream_t s)
+{
+    if (V <= 0 || T <= 0) return;
+    hipLaunchKernelGGL(cc_hook_kernel, dim3((unsigned)mc_blocks(T)), dim3(kMcThreads), 0, s, parent, tris, T, V, changed);
+    hipLaunchKernelGGL(cc_jump_kernel, dim3((unsigned)mc_blocks(V)), dim3(kMcThreads), 0, s, parent, V, changed);
+}
+
+void launch_scan_totals(int64_t *a, int64_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(kMcScanThreads), 0, s, a, n);
+}
+
+void launch_cc_labels(const int32_t *parent, const unsigned char *used, int64_t V, const int32_t *tris, int64_t T, int64_t *blk,
+                      int32_t *vertex_label, int32_t *triangle_label, int64_t *component_triangles, hipStream_t s)
+{
+    const int64_t nb = mc_blocks(V);
+    if (V > 0) hipLaunchKernelGGL(cc_root_count_kernel, dim3((unsigned)nb), dim3(kMcThreads), 0, s, parent, used, V, blk);
+    launch_scan_totals(blk, nb, s);
+    if (V > 0) {
+        hipLaunchKernelGGL(cc_root_label_kernel, dim3((unsigned)nb), dim3(kMcThreads), 0, s, parent, used, V, blk, vertex_label);
+        hipLaunchKernelGGL(cc_gather_kernel, dim3((unsigned)nb), dim3(kMcThreads), 0, s, parent, used, V, blk + nb, vertex_label, component_triangles);
+    }
+    if (T > 0)          // with V == 0 every triangle is invalid: label -1, nothing counted
+        hipLaunchKernelGGL(cc_triangle_kernel, dim3((unsigned)mc_blocks(T)), dim3(kMcThreads), 0, s, tris, T, V, vertex_label, triangle_label,
+                           (unsigned long long *)component_triangles);
+}
+
+void launch_compact_count(const int32_t *tris, int64_t T, int64_t V, const unsigned char *keep, unsigned char *used, int64_t *vblk,
+                          int64_t *tblk, hipStream_t s)
+{
+    const int64_t nbv = mc_blocks(V), nbt = mc_blocks(T);
+    if (V > 0) (void)hipMemsetAsync(used, 0, (size_t)V, s);
+    if (T > 0) hipLaunchKernelGGL(compact_mark_kernel, dim3((unsigned)nbt), dim3(kMcThreads), 0, s, tris, T, V, keep, used, tblk);
+    if (V > 0) hipLaunchKernelGGL(compact_vertex_count_kernel, dim3((unsigned)nbv), dim3(kMcThreads), 0, s, used, V, vblk);
+    launch_scan_totals(vblk, nbv, s);
+    launch_scan_totals(tblk, nbt, s);
+}
+
+void launch_compact_write(const float *vertices, int64_t V, const int32_t *tris, int64_t T, const unsigned char *keep,
+                          const unsigned char *used, const int64_t *vblk, const int64_t *tblk, int32_t *vmap, float *out_vertices,
+                          int32_t *out_tris, hipStream_t s)
+{
+    if (V > 0) hipLaunchKernelGGL(compact_vertex_kernel, dim3((unsigned)mc_blocks(V)), dim3(kMcThreads), 0, s, (const unsigned *)vertices, V, used, vblk,
+                                  vmap, (unsigned *)out_vertices);
+    if (T > 0) hipLaunchKernelGGL(compact_triangle_kernel, dim3((unsigned)mc_blocks(T)), dim3(kMcThreads), 0, s, tris, T, V, keep, tblk, vmap, out_tris);
 }
 
 void launch_grid_points(const McGrid &g, int64_t first, int64_t n, float *pos, float *dir, float *var, hipStream_t s)

@@ -758,7 +758,8 @@ void neddf_destroy(neddf_ctx *ctx)
         if (f.last_use) (void)hipEventDestroy(f.last_use);
     }
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack, &ctx->ttmp, &ctx->tamax,
-                      &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc })
+                      &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc,
+                      &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk })
         if (b->p) (void)hipFree(b->base ? b->base : b->p);
     for (auto &e : ctx->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : ctx->pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -777,7 +778,8 @@ int neddf_debug_check_guards(neddf_ctx *ctx, int64_t *n_bands, int64_t *n_bad_by
     HIPCHK(hipDeviceSynchronize());
     std::vector<GuardBand> bands = ctx->carve_guards;
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack,
-                       &ctx->ttmp, &ctx->tamax, &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc })
+                       &ctx->ttmp, &ctx->tamax, &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc,
+                      &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk })
         if (b->base) {
             bands.push_back(GuardBand{ b->base, kGuardBytes });
             bands.push_back(GuardBand{ (char *)b->p + b->cap, kGuardBytes });
@@ -1348,6 +1350,91 @@ int neddf_mesh_vertex_normals(neddf_ctx *ctx, const float *d_vertices, int64_t n
     DeviceGuard guard_(ctx->device);
     if (int rc = ensure(ctx, ctx->mc_nacc, (size_t)(3 * n_vertices + 1) * sizeof(unsigned long long))) return rc;
     launch_mesh_normals(d_vertices, n_vertices, d_triangles, n_triangles, (unsigned long long *)ctx->mc_nacc.p, d_normals, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// block totals of nbv vertex blocks and nbt triangle blocks (each with its grand total behind it), then kCcBatch "changed" words
+static int mesh_workspace(neddf_ctx *ctx, int64_t V, int64_t nbv, int64_t nbt)
+{
+    if (int rc = ensure(ctx, ctx->cc_parent, (size_t)(V > 0 ? V : 1) * sizeof(int32_t))) return rc;
+    if (int rc = ensure(ctx, ctx->cc_used, (size_t)(V > 0 ? V : 1))) return rc;
+    return ensure(ctx, ctx->cc_blk, (size_t)(nbv + nbt + 2) * sizeof(int64_t) + kCcBatch * sizeof(int));
+}
+
+int neddf_mesh_components(neddf_ctx *ctx, const int32_t *d_triangles, int64_t n_triangles, int64_t n_vertices, int32_t *d_vertex_label,
+                          int32_t *d_triangle_label, int64_t *d_component_triangles, int64_t *h_n_components, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    const int64_t V = n_vertices, T = n_triangles;
+    if (V < 0 || T < 0) return fail(ctx, NEDDF_EINVAL, "mesh_components: negative count");
+    if (!h_n_components || (T > 0 && !d_triangles) || (V > 0 && (!d_vertex_label || !d_component_triangles)))
+        return fail(ctx, NEDDF_EINVAL, "mesh_components: NULL triangles, vertex labels, component counts or count");
+    const int64_t nbv = mc_blocks(V), nbt = mc_blocks(T);
+    if (V >= ((int64_t)1 << 31) || nbt > 0x7fffffff) return fail(ctx, NEDDF_EUNSUPPORTED, "mesh_components: 2^31 vertices or more, or too many triangles");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = mesh_workspace(ctx, V, nbv, 0)) return rc;
+    int32_t *parent = (int32_t *)ctx->cc_parent.p;
+    unsigned char *used = (unsigned char *)ctx->cc_used.p;
+    int64_t *blk = (int64_t *)ctx->cc_blk.p;
+    int *changed = (int *)(blk + nbv + 2);
+    launch_cc_init(parent, used, V, d_triangles, T, s);
+    HIPCHK(hipGetLastError());
+    // rounds of (hook, jump) until one changes nothing; the "changed" words are read once per batch of kCcBatch rounds
+    ctx->cc_rounds = 0;
+    for (bool done = V == 0 || T == 0; !done;) {
+        if (ctx->cc_rounds >= kCcMaxRounds) return fail(ctx, NEDDF_EUNSUPPORTED, "mesh_components: no fixed point within the round limit");
+        int h_changed[kCcBatch];
+        HIPCHK(hipMemsetAsync(changed, 0, sizeof(h_changed), s));
+        for (int r = 0; r < kCcBatch; ++r) launch_cc_round(parent, V, d_triangles, T, changed + r, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_changed, changed, sizeof(h_changed), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int r = 0; r < kCcBatch && !done; ++r) {
+            ++ctx->cc_rounds;
+            done = h_changed[r] == 0;
+        }
+    }
+    launch_cc_labels(parent, used, V, d_triangles, T, blk, d_vertex_label, d_triangle_label, d_component_triangles, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_n_components, blk + nbv, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int neddf_mesh_components_rounds(neddf_ctx *ctx)
+{
+    return ctx ? ctx->cc_rounds : NEDDF_EINVAL;
+}
+
+int neddf_mesh_compact(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                       const unsigned char *d_keep_triangle, float *d_out_vertices, int64_t vertex_cap, int32_t *d_out_triangles,
+                       int64_t triangle_cap, int32_t *d_vertex_map, int64_t *h_n_vertices, int64_t *h_n_triangles, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    const int64_t V = n_vertices, T = n_triangles;
+    if (V < 0 || T < 0) return fail(ctx, NEDDF_EINVAL, "mesh_compact: negative count");
+    if (!h_n_vertices || !h_n_triangles || (V > 0 && !d_vertices) || (T > 0 && (!d_triangles || !d_keep_triangle)))
+        return fail(ctx, NEDDF_EINVAL, "mesh_compact: NULL vertices, triangles, keep flags or count");
+    const int64_t nbv = mc_blocks(V), nbt = mc_blocks(T);
+    if (V >= ((int64_t)1 << 31) || nbt > 0x7fffffff) return fail(ctx, NEDDF_EUNSUPPORTED, "mesh_compact: 2^31 vertices or more, or too many triangles");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = mesh_workspace(ctx, V, nbv, nbt)) return rc;
+    unsigned char *used = (unsigned char *)ctx->cc_used.p;
+    int64_t *vblk = (int64_t *)ctx->cc_blk.p, *tblk = vblk + nbv + 1;
+    launch_compact_count(d_triangles, T, V, d_keep_triangle, used, vblk, tblk, s);
+    HIPCHK(hipGetLastError());
+    int64_t counts[2];
+    HIPCHK(hipMemcpyAsync(&counts[0], vblk + nbv, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&counts[1], tblk + nbt, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *h_n_vertices = counts[0];
+    *h_n_triangles = counts[1];
+    if (!d_out_vertices || !d_out_triangles || vertex_cap < counts[0] || triangle_cap < counts[1]) return 0;     // the counting call
+    launch_compact_write(d_vertices, V, d_triangles, T, d_keep_triangle, used, vblk, tblk, d_vertex_map ? d_vertex_map : (int32_t *)ctx->cc_parent.p,
+                         d_out_vertices, d_out_triangles, s);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -1,8 +1,10 @@
-"""Surface extraction: marching cubes on the GPU and a PLY writer.
+"""Surface extraction: marching cubes on the GPU, mesh clean-up (connected components, floater removal) and a PLY writer.
 
 The reference meshes a trained field inside its Open3D viewer (neddf/scripts/fields_visualizer.py:528-566: voxelize ->
 PyMCubes -> .dae).  Here the grid evaluation and marching cubes are HIP kernels (include/neddf_hip.h neddf_field_grid,
-neddf_marching_cubes); BaseNeuralField.extract_mesh and neddf/scripts/extract_mesh.py are built on this module.
+neddf_marching_cubes); BaseNeuralField.extract_mesh and neddf/scripts/extract_mesh.py are built on this module.  A level set of a
+trained field comes with small closed blobs in empty space and open shreds at the cube's faces: connected_components,
+compact_mesh and remove_small_components drop them on the device (neddf_mesh_components, neddf_mesh_compact).
 """
 import numpy as np
 import torch
@@ -36,6 +38,74 @@ def vertex_normals(vertices, triangles):
     if not isinstance(vertices, torch.Tensor) or not vertices.is_cuda:
         raise NeddfError("vertex_normals: the mesh must live on a HIP device")
     return Context.get(vertices.device).mesh_vertex_normals(vertices, triangles)
+
+
+def _device_mesh(what, **tensors):
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise NeddfError("%s: %s must be a tensor on a HIP device (got %s)"
+                             % (what, name, t.device if isinstance(t, torch.Tensor) else type(t).__name__))
+
+
+def connected_components(triangles, n_vertices):
+    """Connected components of an indexed device mesh (triangles int32 [T, 3] over n_vertices vertices): two vertices belong to
+    one component when a chain of triangles sharing vertices joins them.
+
+    Returns (vertex_label int32 [V], triangle_label int32 [T], component_triangles int64 [C]).  Components are numbered in the
+    order of their lowest vertex index; a vertex no valid triangle references and a triangle with an index outside [0, V) get
+    -1; component_triangles[c] counts the valid triangles of component c.  Independent of timing (include/neddf_hip.h
+    neddf_mesh_components)."""
+    _device_mesh("connected_components", triangles=triangles)
+    return Context.get(triangles.device).mesh_components(triangles, n_vertices)
+
+
+def compact_mesh(vertices, triangles, keep_triangle):
+    """Drops the triangles whose keep_triangle [T] entry is zero (and those with an index outside [0, V)), then the vertices
+    nothing references any more, and reindexes; both keep their relative order and the coordinates are copied bit for bit.
+
+    Returns (vertices float32 [V', 3], triangles int32 [T', 3], vertex_map int32 [V]: the new index of every old vertex or -1)
+    (include/neddf_hip.h neddf_mesh_compact)."""
+    _device_mesh("compact_mesh", vertices=vertices, triangles=triangles, keep_triangle=keep_triangle)
+    return Context.get(vertices.device).mesh_compact(vertices, triangles, keep_triangle)
+
+
+def select_components(component_triangles, min_triangles=0, keep_largest=0):
+    """bool [C]: the components with at least min_triangles triangles that, if keep_largest > 0, are also among the keep_largest
+    largest by triangle count (ties go to the lower label)."""
+    sizes = component_triangles
+    keep = sizes >= int(min_triangles)
+    if int(keep_largest) > 0 and sizes.numel() > int(keep_largest):
+        order = torch.sort(sizes, descending=True, stable=True).indices        # stable: equal counts stay in label order
+        top = torch.zeros_like(keep)
+        top[order[:int(keep_largest)]] = True
+        keep = keep & top
+    return keep
+
+
+def _clean(vertices, triangles, min_triangles, keep_largest):
+    """remove_small_components plus what it did: {"components", "components_kept", "triangles_removed"}."""
+    _device_mesh("remove_small_components", vertices=vertices, triangles=triangles)
+    if int(min_triangles) < 0 or int(keep_largest) < 0:
+        raise ValueError("remove_small_components: min_triangles and keep_largest must not be negative")
+    _, tri_label, sizes = connected_components(triangles, vertices.shape[0])
+    keep = select_components(sizes, min_triangles, keep_largest)
+    if sizes.numel():
+        keep_tri = ((tri_label >= 0) & keep[tri_label.clamp_min(0).long()]).to(torch.uint8)
+    else:
+        keep_tri = torch.zeros(triangles.shape[0], device=triangles.device, dtype=torch.uint8)
+    out = compact_mesh(vertices, triangles, keep_tri)
+    stats = {"components": int(sizes.numel()), "components_kept": int(keep.sum().item()),
+             "triangles_removed": int(triangles.shape[0] - out[1].shape[0])}
+    return out, stats
+
+
+def remove_small_components(vertices, triangles, min_triangles=0, keep_largest=0):
+    """Floater removal: keeps the connected components with at least min_triangles triangles and, if keep_largest > 0, only the
+    keep_largest largest of them by triangle count (ties go to the lower label, i.e. the lower first vertex).  Triangles with an
+    index outside [0, V) go too.  Labelling and compaction run in the library; the choice over the [C] counts is torch.
+
+    Returns (vertices, triangles, vertex_map) as compact_mesh does."""
+    return _clean(vertices, triangles, min_triangles, keep_largest)[0]
 
 
 def _host(a, dtype):
@@ -85,4 +155,4 @@ def write_ply(path, vertices, triangles, normals=None, colors=None):
     return path
 
 
-__all__ = ["marching_cubes", "vertex_normals", "write_ply"]
+__all__ = ["marching_cubes", "vertex_normals", "connected_components", "compact_mesh", "remove_small_components", "write_ply"]

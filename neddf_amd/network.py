@@ -142,7 +142,8 @@ class BaseNeuralField(ABC, nn.Module):
         return {"distance": "distance", "density": "density"}
 
     def extract_mesh(self, field_name: str = "distance", threshold: float = 0.0275, cube_range: float = 1.1,
-                     resolution: int = 64, timings: Optional[Dict[str, float]] = None, normals=False, colors: bool = False):
+                     resolution: int = 64, timings: Optional[Dict[str, float]] = None, normals=False, colors: bool = False,
+                     min_component_triangles: int = 0, keep_largest: int = 0):
         """Triangle mesh of the `threshold` level set of `field_name` in the cube [-cube_range, cube_range]^3 sampled at
         resolution^3 points -- the reference's generate_mesh (fields_visualizer.py:528-566: voxelize("distance", 1.1, 64),
         mcubes.marching_cubes(voxel, 0.0275)) with the grid evaluation and marching cubes on the GPU.
@@ -160,9 +161,15 @@ class BaseNeuralField(ABC, nn.Module):
         incident triangles' normals (mesh.vertex_normals).  True takes "field" where the field has one and "geometric" for NeRF.
         colors: the colour trunk at every vertex seen straight on, dir = -normal (for NeRF fields the geometric normal), float32
         [V, 3] in the field's channel order (the dataset's B, G, R).  With either option the result is a tuple
-        (vertices, triangles[, normals][, colors]); "normals" / "colors" in `timings` receive their wall time."""
+        (vertices, triangles[, normals][, colors]); "normals" / "colors" in `timings` receive their wall time.
+
+        min_component_triangles / keep_largest (not in the reference): floater removal, mesh.remove_small_components -- connected
+        components with fewer triangles are dropped, and with keep_largest > 0 only that many of the largest stay.  It runs right
+        after marching cubes, before normals and colours, so the field is never evaluated at a vertex that is thrown away.
+        `timings` receives the stage's wall time ("clean") and what it did ("components", "components_kept",
+        "triangles_removed").  With both 0 nothing runs and the mesh is marching cubes' as it is."""
         import time
-        from .mesh import marching_cubes, vertex_normals
+        from .mesh import _clean, marching_cubes, vertex_normals
         if normals is True:
             normals = "field" if self._has_surface() else "geometric"
         if normals not in (False, None, "field", "geometric"):
@@ -185,6 +192,12 @@ class BaseNeuralField(ABC, nn.Module):
                 tris = tris[:, [0, 2, 1]].contiguous()
             torch.cuda.synchronize(self.device)
             t2 = time.perf_counter()
+            t_mc = t2
+            cleaned = None
+            if min_component_triangles or keep_largest:
+                (verts, tris, _), cleaned = _clean(verts, tris, min_component_triangles, keep_largest)
+                torch.cuda.synchronize(self.device)
+                t2 = time.perf_counter()
             out = [verts, tris]
             nrm = None
             if normals or colors:
@@ -210,7 +223,10 @@ class BaseNeuralField(ABC, nn.Module):
             torch.cuda.synchronize(self.device)
             t4 = time.perf_counter()
         if timings is not None:
-            timings["grid"], timings["mcubes"] = t1 - t0, t2 - t1
+            timings["grid"], timings["mcubes"] = t1 - t0, t_mc - t1
+            if cleaned is not None:
+                timings["clean"] = t2 - t_mc
+                timings.update(cleaned)
             if normals:
                 timings["normals"] = t3 - t2
             if colors:

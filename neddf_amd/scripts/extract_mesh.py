@@ -1,12 +1,15 @@
 """`python neddf/scripts/extract_mesh.py <run_dir> [--epoch 2000] [--resolution 64] [--threshold 0.0275] [--field distance]
-[--cube-range 1.1] [--normals [field|geometric]] [--colors]` -- the reference's mesh export (neddf/scripts/fields_visualizer.py:528-566, generate_mesh: voxelize
+[--cube-range 1.1] [--normals [field|geometric]] [--colors] [--min-component N] [--keep-largest [K]]` -- the reference's mesh export (neddf/scripts/fields_visualizer.py:528-566, generate_mesh: voxelize
 "distance" on a 64^3 cube of half-width 1.1, marching cubes at 0.0275, export) without its Open3D viewer.  The run is
 loaded as run_eval loads it (`<run_dir>/.hydra/config.yaml`, `models/model_{epoch:05}.pth`); the mesh of
 `trainer.neural_render.get_network()` is written to `<run_dir>/mesh/mesh_{resolution}_threshold{threshold}.ply` (the
 reference's file name, PLY in place of collada), in world coordinates.  Prints the vertex and triangle counts and the wall
 time of the grid evaluation and of marching cubes.  --normals adds per-vertex normals (`property float nx, ny, nz`): the field's
 own (NeDDF, NeuS; the default where the field has one) or geometric ones; --colors adds the colour trunk's value at every vertex
-seen straight on (`property uchar red, green, blue`).  Without them the file is the plain positions-and-triangles PLY."""
+seen straight on (`property uchar red, green, blue`).  Without them the file is the plain positions-and-triangles PLY.
+--min-component N drops the connected components with fewer than N triangles and --keep-largest [K] all but the K (default 1)
+largest, on the device and before normals and colours; one more line then reports the components found and kept, the triangles
+removed and the clean-up time."""
 from argparse import ArgumentParser
 from pathlib import Path
 
@@ -25,6 +28,9 @@ def build_parser() -> ArgumentParser:
     parser.add_argument("--normals", nargs="?", const="auto", default=None, choices=["auto", "field", "geometric"],
                         help="write vertex normals: the field's own (default for NeDDF / NeuS) or geometric ones (NeRF)")
     parser.add_argument("--colors", action="store_true", help="write vertex colours (the colour trunk seen against the normal)")
+    parser.add_argument("--min-component", type=int, default=0, metavar="N", help="drop connected components with fewer than N triangles")
+    parser.add_argument("--keep-largest", type=int, nargs="?", const=1, default=0, metavar="K",
+                        help="keep only the K largest connected components (K = 1 when omitted)")
     return parser
 
 
@@ -36,15 +42,18 @@ def main(argv=None) -> Path:
     network = trainer.neural_render.get_network()
     times = {}
     normals, colors = None, None
+    clean = {}
+    if args.min_component or args.keep_largest:
+        clean = dict(min_component_triangles=args.min_component, keep_largest=args.keep_largest)
     if args.normals or args.colors:
         want_n = True if args.normals == "auto" else (args.normals or False)
         res = list(network.extract_mesh(args.field, args.threshold, args.cube_range, args.resolution, timings=times,
-                                        normals=want_n, colors=args.colors))
+                                        normals=want_n, colors=args.colors, **clean))
         verts, tris = res[0], res[1]
         normals = res[2] if want_n else None
         colors = res[-1] if args.colors else None
     else:
-        verts, tris = network.extract_mesh(args.field, args.threshold, args.cube_range, args.resolution, timings=times)
+        verts, tris = network.extract_mesh(args.field, args.threshold, args.cube_range, args.resolution, timings=times, **clean)
     save_dir = output_dir / "mesh"
     save_dir.mkdir(exist_ok=True)
     path = save_dir / "mesh_{}_threshold{}.ply".format(args.resolution, args.threshold)
@@ -54,6 +63,9 @@ def main(argv=None) -> Path:
         write_ply(path, verts, tris, normals=normals, colors=colors)
     print("vertices: %d, triangles: %d" % (verts.shape[0], tris.shape[0]))
     print("grid evaluation: %.3f s, marching cubes: %.3f s" % (times["grid"], times["mcubes"]))
+    if clean:
+        print("components: %d found, %d kept, triangles removed: %d, clean-up: %.3f s"
+              % (times["components"], times["components_kept"], times["triangles_removed"], times["clean"]))
     print("wrote %s" % path)
     return path
 
