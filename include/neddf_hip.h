@@ -457,6 +457,57 @@ int neddf_mesh_compact(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertic
                        const unsigned char *d_keep_triangle, float *d_out_vertices, int64_t vertex_cap, int32_t *d_out_triangles,
                        int64_t triangle_cap, int32_t *d_vertex_map, int64_t *h_n_vertices, int64_t *h_n_triangles, void *stream);
 
+/* ---- empty-space skipping (additive to ABI v7; no reference counterpart: the reference evaluates every sample) ------
+ * An occupancy grid of R^3 cells (R in [1, 1024]) over the box h_lo[3] .. h_hi[3] (HOST doubles), one bit per cell: cell
+ * (x, y, z) has bit index (z R + y) R + x, bit i lives in word i >> 5 at position i & 31 of d_bits ((R^3 + 31) / 32 uint32 words),
+ * the unused high bits of the last word are 0.  The caller fills the struct: lo = (float)h_lo, inv_cell = (float)(R / (h_hi -
+ * h_lo)) per axis, the quotient taken in double. */
+typedef struct {
+    const uint32_t *d_bits;
+    int res;                  /* R */
+    float lo[3];
+    float inv_cell[3];
+} neddf_occupancy;
+/* Builds the bitfield from d_volume, the [R+1]^3 lattice of cell-CORNER densities -- what neddf_field_grid(..., NEDDF_GRID_DENSITY,
+ * R+1, R+1, R+1, lo, hi, ...) writes.  A cell is occupied when any of its 8 corners satisfies !(v <= threshold): a NaN corner
+ * occupies its cells (the grid only ever removes work it is sure about).  The occupied set is then grown by `dilate` cells (0..4)
+ * in the Chebyshev (26-neighbour) sense, clipped at the box.  Whole words are written, one lane per word and no atomics: the
+ * result does not depend on timing.  *h_n_occupied (HOST) = the population count; synchronises `stream` once to read it. */
+int neddf_occupancy_build(neddf_ctx *ctx, const float *d_volume, int R, float threshold, int dilate, uint32_t *d_bits,
+                          int64_t *h_n_occupied, void *stream);
+/* d_keep[i] (one byte, 0 / 1) for each of the N points d_pos [N,3]: per axis c = (int)floorf((p - lo) * inv_cell) in fp32, in
+ * exactly that operation order; a point with a c outside [0, R) or a non-finite coordinate is KEPT (the grid claims nothing about
+ * space it never looked at), any other point exactly when its cell's bit is set. */
+int neddf_occupancy_classify(neddf_ctx *ctx, const neddf_occupancy *occ, const float *d_pos, int64_t n_points, unsigned char *d_keep,
+                             void *stream);
+/* Order-preserving compaction of the points whose d_keep byte is non-zero: their d_pos / d_dir / d_var rows ([N,3] each) are
+ * copied bit for bit (NaN payloads included) to d_out_pos / d_out_dir / d_out_var and their old index to d_index (int32, strictly
+ * increasing); all four need room for N rows.  *h_n_kept (HOST) = M; synchronises `stream` once to read it.  Count / scan / write
+ * launches, no atomics.  NEDDF_EUNSUPPORTED for N >= 2^31. */
+int neddf_occupancy_gather(neddf_ctx *ctx, const unsigned char *d_keep, const float *d_pos, const float *d_dir, const float *d_var,
+                           int64_t n_points, float *d_out_pos, float *d_out_dir, float *d_out_var, int32_t *d_index,
+                           int64_t *h_n_kept, void *stream);
+/* The inverse: zero-fills d_density [N], d_color [N,3] and d_normal [N,3] (each may be NULL together with its source) and writes
+ * row d_index[k] of each from row k < n_kept of the compact d_c_density [M], d_c_color [M,3], d_c_normal [M,3]. */
+int neddf_occupancy_scatter(neddf_ctx *ctx, const int32_t *d_index, int64_t n_kept, int64_t n_points, const float *d_c_density,
+                            const float *d_c_color, const float *d_c_normal, float *d_density, float *d_color, float *d_normal,
+                            void *stream);
+/* neddf_render_rays_surface / neddf_render_rays_single_surface with a trailing occupancy grid.  occ == NULL: the plain call.  With
+ * a grid every pass writes its sampling tensors (neddf_sampling's kernel), classifies the sample positions, evaluates the field on
+ * the kept points only and scatters the results; a culled sample has density 0, colour 0 and normal 0, and a pass in which nothing
+ * is kept does not run the field.  Compositing is the plain call's.  One synchronise of `stream` per pass (the host learns the
+ * number of kept points).  NEDDF_EUNSUPPORTED when a fields_penalty output is requested together with a grid. */
+int neddf_render_rays_culled(neddf_ctx *ctx, const void *d_uv, int uv_type, int64_t n_rays, const neddf_camera *h_cam,
+                             const neddf_render_params *params, const float *d_U_coarse, const float *d_U_fine,
+                             const neddf_render_outputs *out, float *d_normal, float *d_normal_coarse, void *stream,
+                             const neddf_occupancy *occ);
+int neddf_render_rays_single_culled(neddf_ctx *ctx, int slot, const void *d_uv, int uv_type, int64_t n_rays,
+                                    const neddf_camera *h_cam, const neddf_render_params *params, int S1, const float *d_U,
+                                    const neddf_render_outputs *out, float *d_normal, void *stream, const neddf_occupancy *occ);
+/* Running totals over the culled passes of this context: samples classified and samples kept (either pointer may be NULL);
+ * reset != 0 zeroes them after reading. */
+int neddf_cull_stats(neddf_ctx *ctx, int64_t *h_samples, int64_t *h_kept, int reset);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -61,6 +61,11 @@ class RenderOutputs(C.Structure):
                                    "dists_coarse", "dists_fine", "nan_flag")]
 
 
+class Occupancy(C.Structure):
+    """neddf_occupancy: an R^3 bitfield over the box lo .. hi (neddf_amd/occupancy.py fills it)."""
+    _fields_ = [("d_bits", _vp), ("res", C.c_int), ("lo", C.c_float * 3), ("inv_cell", C.c_float * 3)]
+
+
 # every symbol include/neddf_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("neddf_abi_version", C.c_int, []),
@@ -124,6 +129,16 @@ SYMBOLS = [
     ("neddf_mesh_components", C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
     ("neddf_mesh_components_rounds", C.c_int, [_vp]),
     ("neddf_mesh_compact", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    ("neddf_occupancy_build", C.c_int, [_vp, _vp, C.c_int, C.c_float, C.c_int, _vp, C.POINTER(_i64), _vp]),
+    ("neddf_occupancy_classify", C.c_int, [_vp, C.POINTER(Occupancy), _vp, _i64, _vp, _vp]),
+    ("neddf_occupancy_gather", C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    ("neddf_occupancy_scatter", C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_render_rays_culled", C.c_int, [_vp, _vp, C.c_int, _i64, C.POINTER(CameraDesc), C.POINTER(RenderParams), _vp, _vp,
+                                           C.POINTER(RenderOutputs), _vp, _vp, _vp, C.POINTER(Occupancy)]),
+    ("neddf_render_rays_single_culled", C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, C.POINTER(CameraDesc),
+                                                  C.POINTER(RenderParams), C.c_int, _vp, C.POINTER(RenderOutputs), _vp, _vp,
+                                                  C.POINTER(Occupancy)]),
+    ("neddf_cull_stats", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.c_int]),
 ]
 
 _lib = None
@@ -458,9 +473,10 @@ class Context:
                                                       _ptr(out), _ptr(ids), self.stream()))
         return (out, ids) if want_ids else out
 
-    def render_rays(self, uv, cam, params, U_coarse, U_fine, outputs, single_slot=None):
+    def render_rays(self, uv, cam, params, U_coarse, U_fine, outputs, single_slot=None, occupancy=None):
         """outputs: dict name -> preallocated device tensor (subset of RenderOutputs fields, plus "normal" / "normal_coarse"
-        [B, 3]: with either present the call goes through the *_surface entry points)."""
+        [B, 3]: with either present the call goes through the *_surface entry points).  occupancy: an Occupancy struct whose
+        bits live on this device -- the call goes through the *_culled entry points (empty-space skipping)."""
         require_device(uv, "uv")
         if uv.dtype not in UV_TYPES:
             uv = uv.to(torch.float32)
@@ -470,7 +486,16 @@ class Context:
         normal, normal_coarse = outputs.pop("normal", None), outputs.pop("normal_coarse", None)
         for k, t in outputs.items():
             setattr(ro, k, t.data_ptr())
-        if normal is not None or normal_coarse is not None:
+        if occupancy is not None:
+            if single_slot is None:
+                self.check(self.lib.neddf_render_rays_culled(self.h, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0], C.byref(cam),
+                                                             C.byref(params), _ptr(U_coarse), _ptr(U_fine), C.byref(ro),
+                                                             _ptr(normal), _ptr(normal_coarse), self.stream(), C.byref(occupancy)))
+            else:
+                self.check(self.lib.neddf_render_rays_single_culled(self.h, single_slot, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0],
+                                                                    C.byref(cam), C.byref(params), U_coarse.shape[1], _ptr(U_coarse),
+                                                                    C.byref(ro), _ptr(normal), self.stream(), C.byref(occupancy)))
+        elif normal is not None or normal_coarse is not None:
             if single_slot is None:
                 self.check(self.lib.neddf_render_rays_surface(self.h, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0], C.byref(cam),
                                                               C.byref(params), _ptr(U_coarse), _ptr(U_fine), C.byref(ro),
@@ -486,6 +511,65 @@ class Context:
             self.check(self.lib.neddf_render_rays_single(self.h, single_slot, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0],
                                                          C.byref(cam), C.byref(params), U_coarse.shape[1], _ptr(U_coarse),
                                                          C.byref(ro), self.stream()))
+
+    # ------------------------------------------------------------------ empty-space skipping
+    def occupancy_build(self, volume, threshold, dilate):
+        """Bitfield of the R^3 cells of a contiguous float32 [R+1, R+1, R+1] device volume of corner densities
+        (neddf_occupancy_build): (bits int32 [(R^3 + 31) // 32], number of occupied cells)."""
+        require_device(volume, "volume")
+        if volume.dtype != torch.float32 or not volume.is_contiguous() or volume.dim() != 3 or len(set(volume.shape)) != 1:
+            raise NeddfError("occupancy_build: a contiguous float32 [R+1, R+1, R+1] volume expected (got %s)" % (tuple(volume.shape),))
+        R = volume.shape[0] - 1
+        bits = torch.empty(max((R ** 3 + 31) // 32, 0), device=volume.device, dtype=torch.int32)
+        n = _i64(0)
+        self.check(self.lib.neddf_occupancy_build(self.h, _ptr(volume), R, float(threshold), int(dilate), _ptr(bits), C.byref(n),
+                                                  self.stream()))
+        return bits, int(n.value)
+
+    def occupancy_classify(self, occ, points):
+        """uint8 [N]: 1 for the points [N, 3] the grid keeps (neddf_occupancy_classify)."""
+        require_device(points, "points")
+        p = f32c(points).reshape(-1, 3)
+        keep = torch.empty(p.shape[0], device=p.device, dtype=torch.uint8)
+        self.check(self.lib.neddf_occupancy_classify(self.h, C.byref(occ), _ptr(p), p.shape[0], _ptr(keep), self.stream()))
+        return keep
+
+    def occupancy_gather(self, keep, pos, dir, var):
+        """Kept rows of pos / dir / var [N, 3] in their old order and their old indices (neddf_occupancy_gather):
+        (pos [M, 3], dir [M, 3], var [M, 3], index int32 [M])."""
+        require_device(keep, "keep")
+        pos, dir, var = f32c(pos).reshape(-1, 3), f32c(dir).reshape(-1, 3), f32c(var).reshape(-1, 3)
+        N = pos.shape[0]
+        if keep.dtype != torch.uint8 or not keep.is_contiguous() or keep.numel() != N or dir.shape[0] != N or var.shape[0] != N:
+            raise NeddfError("occupancy_gather: keep uint8 [N] and pos / dir / var [N, 3] expected")
+        out = [torch.empty(N, 3, device=pos.device, dtype=torch.float32) for _ in range(3)]
+        index = torch.empty(N, device=pos.device, dtype=torch.int32)
+        m = _i64(0)
+        self.check(self.lib.neddf_occupancy_gather(self.h, _ptr(keep), _ptr(pos), _ptr(dir), _ptr(var), N, _ptr(out[0]), _ptr(out[1]),
+                                                   _ptr(out[2]), _ptr(index), C.byref(m), self.stream()))
+        M = int(m.value)
+        return out[0][:M], out[1][:M], out[2][:M], index[:M]
+
+    def occupancy_scatter(self, index, n_points, density=None, color=None, normal=None):
+        """Compact density [M] / color [M, 3] / normal [M, 3] -> zero-filled [N] / [N, 3] / [N, 3] with row index[k] = row k
+        (neddf_occupancy_scatter); None stays None."""
+        require_device(index, "index")
+        index = index.contiguous()
+        M, N = index.shape[0], int(n_points)
+        if M == 0:          # nothing kept: all zero (empty tensors have no pointer to hand over)
+            z = [None if t is None else torch.zeros(N * w, device=index.device, dtype=torch.float32) for t, w in zip((density, color, normal), (1, 3, 3))]
+            return z[0], None if z[1] is None else z[1].view(N, 3), None if z[2] is None else z[2].view(N, 3)
+        src = [None if t is None else f32c(t) for t in (density, color, normal)]
+        dst = [None if t is None else torch.empty(N * w, device=index.device, dtype=torch.float32) for t, w in zip(src, (1, 3, 3))]
+        self.check(self.lib.neddf_occupancy_scatter(self.h, _ptr(index), M, N, _ptr(src[0]), _ptr(src[1]), _ptr(src[2]), _ptr(dst[0]),
+                                                    _ptr(dst[1]), _ptr(dst[2]), self.stream()))
+        return dst[0], None if dst[1] is None else dst[1].view(N, 3), None if dst[2] is None else dst[2].view(N, 3)
+
+    def cull_stats(self, reset=False):
+        """(samples classified, samples kept) over the culled render passes of this context (neddf_cull_stats)."""
+        a, b = _i64(0), _i64(0)
+        self.check(self.lib.neddf_cull_stats(self.h, C.byref(a), C.byref(b), int(bool(reset))))
+        return int(a.value), int(b.value)
 
     # ----------------------------------------------------------- stand-alone ops
     def op_activation(self, op, x, J=None):

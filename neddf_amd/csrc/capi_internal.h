@@ -101,6 +101,8 @@ struct neddf_ctx {
     DevBuf cc_parent, cc_used, cc_blk;        // neddf_mesh_components / neddf_mesh_compact: parent (or new index) and used byte per vertex,
                                               // block totals followed by the "changed" words of one batch of rounds
     int cc_rounds = 0;           // union-find rounds of the last neddf_mesh_components call
+    DevBuf occ_cells, occ_blk;   // neddf_occupancy_build: two byte planes of R^3 cells; block totals of build / gather
+    int64_t cull_samples = 0, cull_kept = 0;  // neddf_cull_stats: samples classified / kept by the culled render passes
     std::vector<GuardBand> carve_guards;      // NEDDF_GUARD=1: the bands behind the carves of the last render call
     bool timing = false;
     std::vector<EventPair> events;

@@ -236,6 +236,30 @@ void launch_compact_write(const float *vertices, int64_t V, const int32_t *tris,
                           const unsigned char *used, const int64_t *vblk, const int64_t *tblk, int32_t *vmap, float *out_vertices,
                           int32_t *out_tris, hipStream_t s);
 
+// Empty-space skipping (occupancy_kernels.hip): an R^3 bitfield over the box lo .. hi, bit (z R + y) R + x of cell (x, y, z) in
+// 32-bit words; classification of sample points against it and order-preserving compaction of the kept ones.
+constexpr int kOccThreads = 1024;        // points per workgroup of the count / gather kernels (16 waves: ballot + popcount offsets)
+constexpr int kOccMaxRes = 1024, kOccMaxDilate = 4;
+struct OccGrid {
+    const uint32_t *bits;
+    int res;
+    float lo[3], inv_cell[3];
+};
+static inline int64_t occ_words(int R) { return ((int64_t)R * R * R + 31) >> 5; }
+static inline int64_t occ_blocks(int64_t n) { return (n + kOccThreads - 1) / kOccThreads; }
+// vol: [R+1]^3 corner densities; cell_a / cell_b: R^3 bytes each (workspace); bits: occ_words(R) words;
+// blk: [mc_blocks(occ_words(R)) + 1], the population count behind the block bases afterwards
+void launch_occ_build(const float *vol, int R, float threshold, int dilate, unsigned char *cell_a, unsigned char *cell_b, uint32_t *bits,
+                      int64_t *blk, hipStream_t s);
+void launch_occ_classify(const OccGrid &g, const float *pos, int64_t n, unsigned char *keep, hipStream_t s);
+// kept points per block, scanned (launch_scan_totals): blk [occ_blocks(n) + 1], blk[occ_blocks(n)] = the number of kept points
+void launch_occ_count(const unsigned char *keep, int64_t n, int64_t *blk, hipStream_t s);
+// gather: rows of the kept points, order preserved, and their old index; scatter: compact results back to rows index[k] < n (any may be NULL)
+void launch_occ_gather(const unsigned char *keep, const float *pos, const float *dir, const float *var, int64_t n, const int64_t *blk,
+                       float *cpos, float *cdir, float *cvar, int32_t *index, hipStream_t s);
+void launch_occ_scatter(const int32_t *index, int64_t m, int64_t n, const float *cdens, const float *ccol, const float *cnrm, float *dens,
+                        float *col, float *nrm, hipStream_t s);
+
 void launch_linear_grad(const float *x, const float *J, int64_t n, int cin, int ldx, int cout_block, int ksteps, const float *wp,
                         const float *bias, float *y, float *G, int ldo, int nvalid, int accumulate, int grid, hipStream_t s);
 void launch_op_activation(int kind, const float *x, const float *J, int64_t N, int C, float *y, float *G, hipStream_t s);

@@ -759,7 +759,7 @@ void neddf_destroy(neddf_ctx *ctx)
     }
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack, &ctx->ttmp, &ctx->tamax,
                       &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc,
-                      &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk })
+                      &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk, &ctx->occ_cells, &ctx->occ_blk })
         if (b->p) (void)hipFree(b->base ? b->base : b->p);
     for (auto &e : ctx->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : ctx->pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -779,7 +779,7 @@ int neddf_debug_check_guards(neddf_ctx *ctx, int64_t *n_bands, int64_t *n_bad_by
     std::vector<GuardBand> bands = ctx->carve_guards;
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack,
                        &ctx->ttmp, &ctx->tamax, &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc,
-                      &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk })
+                      &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk, &ctx->occ_cells, &ctx->occ_blk })
         if (b->base) {
             bands.push_back(GuardBand{ b->base, kGuardBytes });
             bands.push_back(GuardBand{ (char *)b->p + b->cap, kGuardBytes });
@@ -1000,10 +1000,78 @@ static size_t carve_bytes(size_t n_floats)
     return (n_floats * sizeof(float) + 255) & ~(size_t)255;
 }
 
+// ---- empty-space skipping: the workspace of one culled render call (carved from the arena, sized for its longest pass) ----
+struct OccWork {
+    OccGrid grid;
+    unsigned char *keep;            // [N]
+    int32_t *index;                 // [N]
+    int64_t *blk;                   // [occ_blocks(N) + 1]
+    float *cpos, *cdir, *cvar;      // [N, 3] each: the kept points
+    float *cdens, *ccol, *cnrm;     // [N], [N, 3], [N, 3] (cnrm only with a normal target): their results
+};
+
+static size_t occ_work_bytes(int64_t N, bool normals)
+{
+    return carve_bytes((size_t)(N + 3) / 4) + carve_bytes((size_t)N) + carve_bytes((size_t)(occ_blocks(N) + 1) * 2) + 4 * carve_bytes((size_t)N * 3) +
+           carve_bytes((size_t)N) + (normals ? carve_bytes((size_t)N * 3) : 0);
+}
+
+static OccWork occ_work(Carver &cv, const neddf_occupancy *occ, int64_t N, bool normals)
+{
+    OccWork w{};
+    w.grid.bits = occ->d_bits; w.grid.res = occ->res;
+    for (int a = 0; a < 3; ++a) { w.grid.lo[a] = occ->lo[a]; w.grid.inv_cell[a] = occ->inv_cell[a]; }
+    w.keep = (unsigned char *)cv.take((size_t)(N + 3) / 4);
+    w.index = (int32_t *)cv.take((size_t)N);
+    w.blk = (int64_t *)cv.take((size_t)(occ_blocks(N) + 1) * 2);
+    w.cpos = cv.take((size_t)N * 3); w.cdir = cv.take((size_t)N * 3); w.cvar = cv.take((size_t)N * 3);
+    w.cdens = cv.take((size_t)N); w.ccol = cv.take((size_t)N * 3);
+    w.cnrm = normals ? cv.take((size_t)N * 3) : nullptr;
+    return w;
+}
+
+static bool occ_ok(const neddf_occupancy *occ) { return occ->d_bits && occ->res >= 1 && occ->res <= kOccMaxRes; }
+
+// kept points of keep[0..n) -> compact rows + index; *m = their number (one stream synchronise)
+static int occ_compact(neddf_ctx *ctx, const unsigned char *keep, const float *pos, const float *dir, const float *var, int64_t n, int64_t *blk,
+                       float *cpos, float *cdir, float *cvar, int32_t *index, int64_t *m, hipStream_t s)
+{
+    launch_occ_count(keep, n, blk, s);
+    launch_occ_gather(keep, pos, dir, var, n, blk, cpos, cdir, cvar, index, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(m, blk + occ_blocks(n), sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+// The field of one culled pass: sampling tensors -> classify -> gather -> field on the kept points -> scatter into zero-filled outputs.
+// dens [B, S]; col / nrm [B, S, 3] or NULL.  A culled sample has density 0, colour 0 and normal 0.
+static int culled_field(neddf_ctx *ctx, int slot, const RaySrc &rays, int64_t B, int S, float *pos, float *dir, float *var, float *dens, float *col,
+                        float *nrm, const OccWork &w, hipStream_t s)
+{
+    const int64_t N = B * S;
+    STAGE(ctx, s, NEDDF_STAGE_SAMPLING, launch_sampling(rays.rd, rays.ro, rays.view, rays.dists, B, S, rays.radius, pos, dir, var, s));
+    launch_occ_classify(w.grid, pos, N, w.keep, s);
+    int64_t M = 0;
+    if (int rc = occ_compact(ctx, w.keep, pos, dir, var, N, w.blk, w.cpos, w.cdir, w.cvar, w.index, &M, s)) return rc;
+    ctx->cull_samples += N;
+    ctx->cull_kept += M;
+    HIPCHK(hipMemsetAsync(dens, 0, (size_t)N * sizeof(float), s));
+    if (col) HIPCHK(hipMemsetAsync(col, 0, (size_t)N * 3 * sizeof(float), s));
+    if (nrm) HIPCHK(hipMemsetAsync(nrm, 0, (size_t)N * 3 * sizeof(float), s));
+    if (M == 0) return 0;           // nothing kept: the field does not run
+    if (int rc = field_forward(ctx, slot, w.cpos, w.cdir, w.cvar, M, NEDDF_OUT_MINIMAL, nullptr, w.cdens, col ? w.ccol : nullptr, nullptr, nullptr, s,
+                               nullptr, nullptr, nrm ? w.cnrm : nullptr)) return rc;
+    launch_occ_scatter(w.index, M, N, w.cdens, col ? w.ccol : nullptr, nrm ? w.cnrm : nullptr, dens, col, nrm, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 static int render_pass(neddf_ctx *ctx, int slot, const float *rd, const float *ro, const float *view, const float *dists, int64_t B, int S,
                        const neddf_render_params *rp, float *pos, float *dir, float *var, float *dens, float *col, float *pen,
                        float *w_out, float *depth, float *color, float *trans, float *pen_out, int *nan_flag, hipStream_t s,
-                       float *nrm = nullptr, float *normal_out = nullptr)      // nrm [B, S, 3] workspace, normal_out [B, 3] (the normal target)
+                       float *nrm = nullptr, float *normal_out = nullptr,      // nrm [B, S, 3] workspace, normal_out [B, 3] (the normal target)
+                       const OccWork *ow = nullptr)                            // an occupancy grid and its workspace: the culled pass
 {
     RaySrc rays;
     rays.rd = rd; rays.ro = ro; rays.view = view; rays.dists = dists; rays.S = S;
@@ -1014,6 +1082,12 @@ static int render_pass(neddf_ctx *ctx, int slot, const float *rd, const float *r
     // a pass whose pixels nobody asked for (the coarse pass of render_image: only its resampling weights are consumed) needs the
     // densities only -- the colour trunk is skipped (the reference evaluates and discards it)
     const bool want_col = depth || color || trans || want_pen;
+    if (ow) {
+        if (int rc = culled_field(ctx, slot, rays, B, S, pos, dir, var, dens, want_col ? col : nullptr, normal_out ? nrm : nullptr, *ow, s)) return rc;
+        STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite(dists, dens, want_col ? col : nullptr, B, S, rp->max_dist, w_out, depth, color, trans, nan_flag, s));
+        if (normal_out) STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite_normal(dists, dens, nrm, B, S, normal_out, s));
+        return 0;
+    }
     int rc = field_forward(ctx, slot, pos, dir, var, B * S, want_pen ? NEDDF_OUT_FULL : NEDDF_OUT_MINIMAL, nullptr, dens, want_col ? col : nullptr,
                            want_pen ? pen : nullptr, nullptr, s, &rays, nullptr, normal_out ? nrm : nullptr);
     if (rc) return rc;
@@ -1024,11 +1098,15 @@ static int render_pass(neddf_ctx *ctx, int slot, const float *rd, const float *r
 }
 
 static int render_rays_impl(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, const neddf_camera *cam, const neddf_render_params *rp,
-                            const float *Uc, const float *Uf, const neddf_render_outputs *out, float *normal, float *normal_coarse, void *stream)
+                            const float *Uc, const float *Uf, const neddf_render_outputs *out, float *normal, float *normal_coarse, void *stream,
+                            const neddf_occupancy *occ = nullptr)
 {
     if (!ctx) return NEDDF_EINVAL;
     if (B <= 0) return 0;           // empty batch: nothing to do (pointers of empty tensors may be NULL)
     if (!uv || !cam || !rp || !Uc || !Uf || !out) return NEDDF_EINVAL;
+    if (occ && !occ_ok(occ)) return fail(ctx, NEDDF_EINVAL, "render_rays_culled: the grid needs its bits and a resolution in [1, 1024]");
+    if (occ && (out->fields_penalty || out->fields_penalty_coarse))
+        return fail(ctx, NEDDF_EUNSUPPORTED, "render_rays_culled: no fields_penalty output with an occupancy grid (a culled sample has no penalty)");
     DeviceGuard guard_(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     const int Sc1 = rp->sample_coarse + 1, Sf1 = rp->sample_fine + 1, S2 = Sc1 + Sf1;
@@ -1037,6 +1115,8 @@ static int render_rays_impl(neddf_ctx *ctx, const void *uv, int uv_type, int64_t
                   2 * carve_bytes(B * S2) + carve_bytes(B * S2 * 3) + carve_bytes(B * (Sc1 - 1)) + carve_bytes(B * (S2 - 1)) +
                   8 * carve_bytes(B * 3);
     if (normal || normal_coarse) need += carve_bytes(B * S2 * 3);       // the per-sample normals of one pass
+    if (occ && B * S2 >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "render_rays_culled: 2^31 samples or more in one pass (compaction indices are int32)");
+    if (occ) need += occ_work_bytes(B * S2, normal || normal_coarse);
     // the arena is also used by field_forward as a colour sink only when colour is not requested; never the case here
     if (int rc = ensure(ctx, ctx->arena, need)) return rc;
     ctx->carve_guards.clear();
@@ -1056,6 +1136,9 @@ static int render_rays_impl(neddf_ctx *ctx, const void *uv, int uv_type, int64_t
     float *color = out->color ? out->color : cv.take(B * 3);
     float *trans = out->transmittance ? out->transmittance : cv.take(B);
     float *nrm = (normal || normal_coarse) ? cv.take(B * S2 * 3) : nullptr;
+    OccWork work{};
+    if (occ) work = occ_work(cv, occ, B * S2, normal || normal_coarse);
+    const OccWork *ow = occ ? &work : nullptr;
     int *flags = (int *)ctx->flags.p;
     int *nan_flag = out->nan_flag ? out->nan_flag : flags;
 
@@ -1068,7 +1151,7 @@ static int render_rays_impl(neddf_ctx *ctx, const void *uv, int uv_type, int64_t
     }
     STAGE(ctx, s, NEDDF_STAGE_SAMPLE_COARSE, launch_sample_coarse(Uc, B, Sc1, rp->dist_near, rp->dist_far, dc, s));
     int rc = render_pass(ctx, NEDDF_SLOT_COARSE, rd, ro, view, dc, B, Sc1, rp, pos, dir, var, dens, col, pen, wc, depth_c, color_c,
-                         trans_c, out->fields_penalty_coarse, nan_flag, s, nrm, normal_coarse);
+                         trans_c, out->fields_penalty_coarse, nan_flag, s, nrm, normal_coarse, ow);
     if (rc) return rc;
     // the reference takes the NaN-fallback decision of sample_pdf per render_rays call, i.e. per `chunk` rays of render_image
     const int64_t group = rp->nan_group > 0 ? rp->nan_group : B;
@@ -1076,7 +1159,7 @@ static int render_rays_impl(neddf_ctx *ctx, const void *uv, int uv_type, int64_t
     if (int rc = ensure(ctx, ctx->rflags, (size_t)((B + goff + group - 1) / group) * sizeof(int))) return rc;
     STAGE(ctx, s, NEDDF_STAGE_RESAMPLE, launch_resample(dc, wc, Uf, B, Sc1, Sf1, 1, df, nullptr, (int *)ctx->rflags.p, group, goff, s));
     rc = render_pass(ctx, NEDDF_SLOT_FINE, rd, ro, view, df, B, S2, rp, pos, dir, var, dens, col, pen, out->weight, depth, color, trans,
-                     out->fields_penalty, nan_flag, s, nrm, normal);
+                     out->fields_penalty, nan_flag, s, nrm, normal, ow);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     return 0;
@@ -1097,17 +1180,22 @@ int neddf_render_rays_surface(neddf_ctx *ctx, const void *uv, int uv_type, int64
 
 static int render_rays_single_impl(neddf_ctx *ctx, int slot, const void *uv, int uv_type, int64_t B, const neddf_camera *cam,
                                    const neddf_render_params *rp, int S1, const float *U, const neddf_render_outputs *out, float *normal,
-                                   void *stream)
+                                   void *stream, const neddf_occupancy *occ = nullptr)
 {
     if (!ctx) return NEDDF_EINVAL;
     if (B <= 0) return 0;
     if (!uv || !cam || !rp || !U || !out || S1 < 2) return NEDDF_EINVAL;
+    if (occ && !occ_ok(occ)) return fail(ctx, NEDDF_EINVAL, "render_rays_single_culled: the grid needs its bits and a resolution in [1, 1024]");
+    if (occ && out->fields_penalty)
+        return fail(ctx, NEDDF_EUNSUPPORTED, "render_rays_single_culled: no fields_penalty output with an occupancy grid (a culled sample has no penalty)");
     DeviceGuard guard_(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     if (slot < 0 || slot >= NEDDF_NUM_SLOTS || !ctx->field[slot].valid) return fail(ctx, NEDDF_ENOFIELD, "no field in slot");
     size_t need = 2 * carve_bytes(B * 3) + carve_bytes(B * S1) + 3 * carve_bytes(B * S1 * 3) + 2 * carve_bytes(B * S1) +
                   carve_bytes(B * S1 * 3) + 5 * carve_bytes(B * 3);
     if (normal) need += carve_bytes(B * S1 * 3);
+    if (occ && B * S1 >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "render_rays_single_culled: 2^31 samples or more (compaction indices are int32)");
+    if (occ) need += occ_work_bytes(B * S1, normal != nullptr);
     if (int rc = ensure(ctx, ctx->arena, need)) return rc;
     ctx->carve_guards.clear();
     Carver cv{ (char *)ctx->arena.p, ctx, s };
@@ -1119,6 +1207,8 @@ static int render_rays_single_impl(neddf_ctx *ctx, int slot, const void *uv, int
     float *color = out->color ? out->color : cv.take(B * 3);
     float *trans = out->transmittance ? out->transmittance : cv.take(B);
     float *nrm = normal ? cv.take(B * S1 * 3) : nullptr;
+    OccWork work{};
+    if (occ) work = occ_work(cv, occ, B * S1, normal != nullptr);
     int *nan_flag = out->nan_flag ? out->nan_flag : (int *)ctx->flags.p;
     STAGE(ctx, s, NEDDF_STAGE_RAYGEN, launch_raygen(uv, uv_type, B, cam_arg(cam), rd, ro, s));
     const float *view = nullptr;
@@ -1129,7 +1219,7 @@ static int render_rays_single_impl(neddf_ctx *ctx, int slot, const void *uv, int
     }
     STAGE(ctx, s, NEDDF_STAGE_SAMPLE_COARSE, launch_sample_coarse(U, B, S1, rp->dist_near, rp->dist_far, dc, s));
     int rc = render_pass(ctx, slot, rd, ro, view, dc, B, S1, rp, pos, dir, var, dens, col, pen, out->weight, depth, color, trans,
-                         out->fields_penalty, nan_flag, s, nrm, normal);
+                         out->fields_penalty, nan_flag, s, nrm, normal, occ ? &work : nullptr);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     return 0;
@@ -1435,6 +1525,104 @@ int neddf_mesh_compact(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertic
     if (!d_out_vertices || !d_out_triangles || vertex_cap < counts[0] || triangle_cap < counts[1]) return 0;     // the counting call
     launch_compact_write(d_vertices, V, d_triangles, T, d_keep_triangle, used, vblk, tblk, d_vertex_map ? d_vertex_map : (int32_t *)ctx->cc_parent.p,
                          d_out_vertices, d_out_triangles, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- empty-space skipping (occupancy_kernels.hip) ----
+int neddf_render_rays_culled(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, const neddf_camera *cam, const neddf_render_params *rp,
+                             const float *Uc, const float *Uf, const neddf_render_outputs *out, float *normal, float *normal_coarse,
+                             void *stream, const neddf_occupancy *occ)
+{
+    return render_rays_impl(ctx, uv, uv_type, B, cam, rp, Uc, Uf, out, normal, normal_coarse, stream, occ);
+}
+
+int neddf_render_rays_single_culled(neddf_ctx *ctx, int slot, const void *uv, int uv_type, int64_t B, const neddf_camera *cam,
+                                    const neddf_render_params *rp, int S1, const float *U, const neddf_render_outputs *out, float *normal,
+                                    void *stream, const neddf_occupancy *occ)
+{
+    return render_rays_single_impl(ctx, slot, uv, uv_type, B, cam, rp, S1, U, out, normal, stream, occ);
+}
+
+int neddf_cull_stats(neddf_ctx *ctx, int64_t *h_samples, int64_t *h_kept, int reset)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (h_samples) *h_samples = ctx->cull_samples;
+    if (h_kept) *h_kept = ctx->cull_kept;
+    if (reset) ctx->cull_samples = ctx->cull_kept = 0;
+    return 0;
+}
+
+int neddf_occupancy_build(neddf_ctx *ctx, const float *d_volume, int R, float threshold, int dilate, uint32_t *d_bits, int64_t *h_n_occupied,
+                          void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!d_volume || !d_bits || !h_n_occupied) return fail(ctx, NEDDF_EINVAL, "occupancy_build: NULL volume, bits or count");
+    if (R < 1 || R > kOccMaxRes) return fail(ctx, NEDDF_EINVAL, "occupancy_build: the resolution must be in [1, 1024]");
+    if (dilate < 0 || dilate > kOccMaxDilate) return fail(ctx, NEDDF_EINVAL, "occupancy_build: dilate must be in [0, 4]");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_cells = (int64_t)R * R * R, nb = mc_blocks(occ_words(R));
+    if (int rc = ensure(ctx, ctx->occ_cells, (size_t)2 * n_cells)) return rc;
+    if (int rc = ensure(ctx, ctx->occ_blk, (size_t)(nb + 1) * sizeof(int64_t))) return rc;
+    unsigned char *cells = (unsigned char *)ctx->occ_cells.p;
+    int64_t *blk = (int64_t *)ctx->occ_blk.p;
+    launch_occ_build(d_volume, R, threshold, dilate, cells, cells + n_cells, d_bits, blk, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_n_occupied, blk + nb, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int neddf_occupancy_classify(neddf_ctx *ctx, const neddf_occupancy *occ, const float *d_pos, int64_t n_points, unsigned char *d_keep,
+                             void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!occ || !occ_ok(occ)) return fail(ctx, NEDDF_EINVAL, "occupancy_classify: the grid needs its bits and a resolution in [1, 1024]");
+    if (n_points < 0) return fail(ctx, NEDDF_EINVAL, "occupancy_classify: negative count");
+    if (n_points == 0) return 0;
+    if (!d_pos || !d_keep) return fail(ctx, NEDDF_EINVAL, "occupancy_classify: NULL points or keep bytes");
+    if (mc_blocks(n_points) > 0x7fffffff) return fail(ctx, NEDDF_EUNSUPPORTED, "occupancy_classify: too many points for one launch");
+    DeviceGuard guard_(ctx->device);
+    OccGrid g{};
+    g.bits = occ->d_bits; g.res = occ->res;
+    for (int a = 0; a < 3; ++a) { g.lo[a] = occ->lo[a]; g.inv_cell[a] = occ->inv_cell[a]; }
+    launch_occ_classify(g, d_pos, n_points, d_keep, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_occupancy_gather(neddf_ctx *ctx, const unsigned char *d_keep, const float *d_pos, const float *d_dir, const float *d_var,
+                           int64_t n_points, float *d_out_pos, float *d_out_dir, float *d_out_var, int32_t *d_index, int64_t *h_n_kept,
+                           void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!h_n_kept || n_points < 0) return fail(ctx, NEDDF_EINVAL, "occupancy_gather: NULL count or negative size");
+    *h_n_kept = 0;
+    if (n_points == 0) return 0;
+    if (!d_keep || !d_pos || !d_dir || !d_var || !d_out_pos || !d_out_dir || !d_out_var || !d_index)
+        return fail(ctx, NEDDF_EINVAL, "occupancy_gather: NULL keep bytes, rows, outputs or index");
+    if (n_points >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "occupancy_gather: 2^31 points or more (indices are int32)");
+    DeviceGuard guard_(ctx->device);
+    if (int rc = ensure(ctx, ctx->occ_blk, (size_t)(occ_blocks(n_points) + 1) * sizeof(int64_t))) return rc;
+    return occ_compact(ctx, d_keep, d_pos, d_dir, d_var, n_points, (int64_t *)ctx->occ_blk.p, d_out_pos, d_out_dir, d_out_var, d_index, h_n_kept,
+                       (hipStream_t)stream);
+}
+
+int neddf_occupancy_scatter(neddf_ctx *ctx, const int32_t *d_index, int64_t n_kept, int64_t n_points, const float *d_c_density,
+                            const float *d_c_color, const float *d_c_normal, float *d_density, float *d_color, float *d_normal, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (n_kept < 0 || n_points < n_kept) return fail(ctx, NEDDF_EINVAL, "occupancy_scatter: 0 <= n_kept <= n_points expected");
+    if ((n_kept > 0 && !d_index) || (!d_c_density != !d_density) || (!d_c_color != !d_color) || (!d_c_normal != !d_normal))
+        return fail(ctx, NEDDF_EINVAL, "occupancy_scatter: NULL index, or an output without its source");
+    if (n_points >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "occupancy_scatter: 2^31 points or more (indices are int32)");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (d_density && n_points) HIPCHK(hipMemsetAsync(d_density, 0, (size_t)n_points * sizeof(float), s));
+    if (d_color && n_points) HIPCHK(hipMemsetAsync(d_color, 0, (size_t)n_points * 3 * sizeof(float), s));
+    if (d_normal && n_points) HIPCHK(hipMemsetAsync(d_normal, 0, (size_t)n_points * 3 * sizeof(float), s));
+    launch_occ_scatter(d_index, n_kept, n_points, d_c_density, d_c_color, d_c_normal, d_density, d_color, d_normal, s);
     HIPCHK(hipGetLastError());
     return 0;
 }

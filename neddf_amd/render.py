@@ -69,10 +69,17 @@ class NeRFRender(BaseNeuralRender):
                    normals, the background is the zero vector.  NeDDF and NeuS fields; NeRF fields raise.  The autograd path
                    (training) ignores it.  render_image takes the same quantity as the target type "normal",
                    render_image_single_pass as normals=True.
+    occupancy      (attribute) None (default): every sample of every ray goes through the field.  An OccupancyGrid
+                   (occupancy.py; build_occupancy makes one from the networks): render_image and render_image_single_pass skip
+                   empty space -- every pass classifies its sample positions against the grid, evaluates the field on the kept ones
+                   only and gives the others density 0, colour 0 and normal 0; samples outside the grid's box are evaluated as
+                   before.  One stream synchronise per pass.  render_rays, the autograd paths and render_field_slice never use it.
+                   World-space rays only (ray_space="ndc" raises); the grid must live on the camera's device.
     """
 
     pose_gradients = False
     normal_output = False
+    occupancy = None
 
     def __init__(self, network_config: Any, sample_coarse: int = 128, sample_fine: int = 128, dist_near: float = 2.0,
                  dist_far: float = 6.0, max_dist: float = 6.0, use_coarse_network: bool = True,
@@ -174,8 +181,33 @@ class NeRFRender(BaseNeuralRender):
                 raise NotImplementedError("the normal target needs a field with a distance or sdf trunk (NeDDF, NeuS); %s has none"
                                           % type(net).__name__)
 
+    def build_occupancy(self, **kw: Any):
+        """Builds the occupancy grid of network_fine (OccupancyGrid.from_field's keywords: resolution, cube_range, threshold,
+        dilate, lo, hi), ORs in the grid of network_coarse when use_coarse_network is set -- a coarse pass never loses what only
+        the coarse network sees -- stores it in `occupancy` and returns it."""
+        from .occupancy import OccupancyGrid
+        if self.ray_space == "ndc":
+            raise NotImplementedError("occupancy grids live in world space: ray_space='ndc' is not supported")
+        grid = OccupancyGrid.from_field(self.network_fine, **kw)
+        if self.use_coarse_network:
+            grid.union_(OccupancyGrid.from_field(self.network_coarse, **kw))
+        self.occupancy = grid
+        return grid
+
+    def _occupancy_desc(self, device):
+        """The library descriptor of `occupancy` for a culled image render on `device`, or None without a grid."""
+        grid = self.occupancy
+        if grid is None:
+            return None
+        if self.ray_space == "ndc":
+            raise NotImplementedError("occupancy grids live in world space: ray_space='ndc' is not supported")
+        dev = torch.device(device)
+        if grid.device.type != dev.type or (dev.index is not None and grid.device.index != dev.index):
+            raise ValueError("the occupancy grid lives on %s, the camera on %s" % (grid.device, dev))
+        return grid.descriptor()
+
     def _render(self, ctx: Context, uv: Tensor, camera: Camera, U_c: Tensor, U_f: Tensor, full: bool, cam_desc=None,
-                nan_group: int = 0, nan_group_offset: int = 0, normal: bool = False) -> Dict[str, Tensor]:
+                nan_group: int = 0, nan_group_offset: int = 0, normal: bool = False, occupancy=None) -> Dict[str, Tensor]:
         B = uv.shape[0]
         dev = uv.device
         S2 = self.sample_coarse + self.sample_fine + 2
@@ -195,7 +227,8 @@ class NeRFRender(BaseNeuralRender):
             if full:
                 o.update(normal_coarse=buf(B, 3))
         flag = torch.zeros(1, device=dev, dtype=torch.int32)
-        ctx.render_rays(uv, camera.descriptor() if cam_desc is None else cam_desc, self._params(nan_group, nan_group_offset), U_c, U_f, dict(o, nan_flag=flag))
+        ctx.render_rays(uv, camera.descriptor() if cam_desc is None else cam_desc, self._params(nan_group, nan_group_offset), U_c, U_f, dict(o, nan_flag=flag),
+                        occupancy=occupancy)
         o["_nan"] = flag
         return o
 
@@ -329,12 +362,13 @@ class NeRFRender(BaseNeuralRender):
             lo, hi = (0, n) if pixel_range is None else pixel_range
 
             cam_desc = camera.descriptor()          # three device -> host reads: once per image, not per batch
+            occ = self._occupancy_desc(dev)
 
             def launch(below, above, U_c, U_f):
                 # sample_pdf's NaN fallback keeps the reference's per-chunk granularity: batches start on chunk boundaries,
                 # except a slab's first batch, which may start inside a chunk another rank shares
                 o = self._render(ctx, uv[below:above], camera, U_c, U_f, full=False, cam_desc=cam_desc, nan_group=chunk,
-                                 nan_group_offset=below % chunk, normal=want_normal)
+                                 nan_group_offset=below % chunk, normal=want_normal, occupancy=occ)
                 flags.append(o["_nan"])
                 for k in target_types:
                     parts[k].append(o[k])
@@ -403,13 +437,14 @@ class NeRFRender(BaseNeuralRender):
                 out["normal"] = torch.empty(n, 3, device=dev)
             flag = torch.zeros(1, device=dev, dtype=torch.int32)
             cam_desc = camera.descriptor()
+            occ = self._occupancy_desc(dev)
             for below in range(0, n, self.rays_per_call):
                 above = min(n, below + self.rays_per_call)
                 o = {k: v[below:above] for k, v in out.items()}
                 # without U the uniforms are drawn per batch: in "torch_cpu" mode the host draws batch k+1 while batch k renders
                 Ub = U[below:above] if U is not None else self._rand(above - below, samples, dev)
                 ctx.render_rays(uv[below:above], cam_desc, self._params(), Ub, None,
-                                dict(o, nan_flag=flag), single_slot=SLOT_FINE)
+                                dict(o, nan_flag=flag), single_slot=SLOT_FINE, occupancy=occ)
             out["_nan"] = flag
         return out
 

@@ -44,6 +44,10 @@ def build_parser() -> ArgumentParser:
     parser.add_argument("--normals", action="store_true",
                         help="also write {id:03}_normal.png, the normal render target as clamp((n * 0.5 + 0.5) * 255) with world "
                              "x, y, z as R, G, B (not a reference option; NeDDF and NeuS fields, one device)")
+    parser.add_argument("--skip-empty", type=int, nargs="?", const=128, default=None, metavar="R",
+                        help="skip empty space: build an R^3 occupancy grid (default 128) from the loaded networks and render through "
+                             "the culled entry points (not a reference option; world-space rays; prints the occupied fraction and "
+                             "kept / total samples)")
     return parser
 
 
@@ -77,10 +81,21 @@ def main(argv=None) -> None:
         seed = int(box[0]) % (1 << 63)
     if seed is not None:
         torch.manual_seed(seed)
+    if args.skip_empty is not None:
+        # after the checkpoint is loaded, in the state render_all evaluates in; the grid is integer-valued: every rank builds the same one
+        trainer.neural_render.set_iter(-1)
+        grid = trainer.neural_render.build_occupancy(resolution=args.skip_empty)
+        if rank == 0:
+            print("skip-empty: %d^3 grid, %.2f %% of the cells occupied" % (grid.resolution, 100.0 * grid.occupied_fraction))
+        from neddf_amd import Context
+        Context.get(grid.device).cull_stats(reset=True)
     if args.normals:
         trainer.render_all(save_dir, normals=True)
     else:
         trainer.render_all(save_dir)
+    if args.skip_empty is not None:
+        samples, kept = Context.get(grid.device).cull_stats()
+        print("skip-empty: rank %d evaluated %d of %d samples (%.2f %%)" % (rank, kept, samples, 100.0 * kept / max(samples, 1)))
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
