@@ -418,6 +418,51 @@ int neddf_marching_cubes(neddf_ctx *ctx, const float *d_volume, int nx, int ny, 
                          float *d_vertices, int64_t vertex_cap, int32_t *d_triangles, int64_t triangle_cap, int64_t *h_n_vertices,
                          int64_t *h_n_triangles, void *stream);
 
+/* ---- brick-wise surface extraction (additive to ABI v7; no reference counterpart) ------------------------------------
+ * The lattice above cut into bricks of B^3 cells, B = `brick` in [2, 16]: nb_a = ceil((n_a - 1) / B) bricks per axis, brick
+ * (bx, by, bz) at linear index (bz nby + by) nbx + bx; the last brick of an axis may be partial.  A brick's lattice is (B+1)^3
+ * points at local index (lz (B+1) + ly)(B+1) + lx, lattice point b B + l per axis; points past the fine lattice are padding and
+ * hold a quiet NaN, and the cells that touch them do not exist.  The coarse lattice is the (nbx+1)(nby+1)(nbz+1) fine lattice
+ * points at index min(b B, n - 1) per axis.  Every entry point: NEDDF_EINVAL for a brick size outside [2, 16], a dimension
+ * below 2 or lo >= hi on an axis.
+ *
+ * neddf_field_grid_coarse: neddf_field_grid's values at the coarse lattice points, d_coarse [nbz+1][nby+1][nbx+1]. */
+int neddf_field_grid_coarse(neddf_ctx *ctx, int slot, int field, int nx, int ny, int nz, int brick, const double *h_lo, const double *h_hi,
+                            float *d_coarse, void *stream);
+/* Brick selection from d_coarse [nbz+1][nby+1][nbx+1]: a brick is active when, among its 8 coarse corners, one is NaN, (v < iso)
+ * differs between two, or fabsf(v - iso) <= band for one (band >= 0); the active set is then grown by `dilate` bricks (0..4) in the
+ * Chebyshev sense, clipped at the grid.  For an L-Lipschitz field band = L * (half the brick's diagonal) misses no brick that holds
+ * a piece of the level set.
+ *   - d_slot_map int32 [nbz][nby][nbx]: the rank of the brick among the active ones in ascending brick index, or -1
+ *   - d_brick_ids int32, capacity nbx nby nbz: the first M entries = the active brick indices, ascending
+ *   - *h_n_active (HOST) = M (0 is legal); synchronises `stream` once to read it
+ * Count / scan / write launches, no atomics: the result does not depend on timing. */
+int neddf_brick_select(neddf_ctx *ctx, const float *d_coarse, int nbx, int nby, int nbz, float iso, float band, int dilate,
+                       int32_t *d_slot_map, int32_t *d_brick_ids, int64_t *h_n_active, void *stream);
+/* The field on the lattices of the n_bricks bricks listed in d_brick_ids: d_values float [n_bricks][(B+1)^3].  Every value carries
+ * the bits neddf_field_grid gives that lattice point (a point shared by several bricks is evaluated once per brick); padding -- and
+ * every point of a brick index outside the grid -- gets a quiet NaN.  Points are generated on the device and evaluated in chunks of
+ * at most 2^23 (the padding of a partial brick rides along at a clamped lattice point and is overwritten). */
+int neddf_field_bricks(neddf_ctx *ctx, int slot, int field, int nx, int ny, int nz, int brick, const double *h_lo, const double *h_hi,
+                       const int32_t *d_brick_ids, int64_t n_bricks, float *d_values, void *stream);
+/* Marching cubes over the listed bricks: d_values [M][(B+1)^3] as neddf_field_bricks writes them, d_brick_ids [M] strictly ascending,
+ * d_slot_map [nbz][nby][nbx] its inverse (-1 for an unlisted brick) -- what neddf_brick_select returns, or any subset built the same way.
+ *   - the triangles are exactly neddf_marching_cubes' triangles of the cells that lie in listed bricks, the vertices exactly those
+ *     these triangles reference, each once, with neddf_marching_cubes' coordinates bit for bit
+ *   - a lattice edge belongs to the listed brick of lowest index whose lattice contains it: an edge on a face or edge shared by
+ *     listed bricks gives one vertex, an edge shared with an unlisted brick is still produced
+ *   - order: bricks ascending, then lattice points / cells by local index, then x, y, z edge / table order
+ *   - d_vertex_key int64 [V] = (the edge's lower lattice point's fine linear index) * 3 + axis; d_triangle_key int64 [T] = (the cell's
+ *     corner-0 fine linear index) * 5 + position in the case's table order: sorting by them gives neddf_marching_cubes' order
+ *   - the output does not depend on timing (count / scan / write launches, no atomics)
+ * Two calls, as neddf_marching_cubes: with an output pointer NULL or a cap below its count only the HOST counts are written.
+ * Synchronises `stream` once.  NEDDF_EINVAL also for n_bricks outside [0, nbx nby nbz], a brick index outside the grid, a list that
+ * is not strictly ascending or a slot map that is not its inverse (checked on the device); NEDDF_EUNSUPPORTED when V >= 2^31. */
+int neddf_marching_cubes_bricks(neddf_ctx *ctx, const float *d_values, const int32_t *d_brick_ids, int64_t n_bricks, const int32_t *d_slot_map,
+                                int nx, int ny, int nz, int brick, const double *h_lo, const double *h_hi, float iso, float *d_vertices,
+                                int64_t vertex_cap, int32_t *d_triangles, int64_t triangle_cap, int64_t *d_vertex_key, int64_t *d_triangle_key,
+                                int64_t *h_n_vertices, int64_t *h_n_triangles, void *stream);
+
 /* Geometric vertex normals of an indexed mesh (no reference counterpart: its .dae export carries none): d_normals[v] = the
  * normalised sum, over the triangles that hold v, of (p1 - p0) x (p2 - p0) -- weighted by area, pointing where the triangles'
  * orientation points (out of the object for neddf_marching_cubes' meshes).  Cross products in fp32, sums in 64-bit fixed point with

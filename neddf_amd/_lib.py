@@ -119,6 +119,11 @@ SYMBOLS = [
     ("neddf_field_grid", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _vp, _vp]),
     ("neddf_marching_cubes", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_float, _vp, _i64, _vp, _i64,
                                        C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    ("neddf_field_grid_coarse", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _vp, _vp]),
+    ("neddf_brick_select", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _vp, _vp, C.POINTER(_i64), _vp]),
+    ("neddf_field_bricks", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _vp, _i64, _vp, _vp]),
+    ("neddf_marching_cubes_bricks", C.c_int, [_vp, _vp, _vp, _i64, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_float, _vp, _i64,
+                                              _vp, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp]),
     ("neddf_field_forward_surface", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("neddf_composite_normal", C.c_int, [_vp, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),
     ("neddf_render_rays_surface", C.c_int, [_vp, _vp, C.c_int, _i64, C.POINTER(CameraDesc), C.POINTER(RenderParams), _vp, _vp,
@@ -386,6 +391,70 @@ class Context:
         if nv.value and nt.value:
             call(verts, tris)
         return verts, tris
+
+    # ------------------------------------------------------------------ brick-wise surface extraction
+    @staticmethod
+    def brick_counts(shape, brick):
+        """(nbx, nby, nbz): ceil((n - 1) / brick) bricks per axis of the lattice shape = (nx, ny, nz)."""
+        return tuple((int(n) - 2 + int(brick)) // int(brick) for n in shape)
+
+    def field_grid_coarse(self, slot, field, shape, brick, lo, hi):
+        """field_grid's values at the brick corners, the lattice points min(b * brick, n - 1) per axis: float32 [nbz+1, nby+1, nbx+1]
+        (neddf_field_grid_coarse)."""
+        if field not in GRID_FIELDS:
+            raise NeddfError("field_grid_coarse: field must be one of %s (got %r)" % (sorted(GRID_FIELDS), field))
+        nx, ny, nz = (int(n) for n in shape)
+        blo, bhi = self._bounds(lo, hi)
+        nbx, nby, nbz = (max(n, 0) for n in self.brick_counts((nx, ny, nz), max(int(brick), 1)))
+        vol = torch.empty(nbz + 1, nby + 1, nbx + 1, device=self.device, dtype=torch.float32)
+        self.check(self.lib.neddf_field_grid_coarse(self.h, slot, GRID_FIELDS[field], nx, ny, nz, int(brick), blo, bhi, _ptr(vol), self.stream()))
+        return vol
+
+    def brick_select(self, coarse, iso, band, dilate=0):
+        """Active bricks of a contiguous float32 [nbz+1, nby+1, nbx+1] device volume of brick-corner values (neddf_brick_select):
+        (slot_map int32 [nbz, nby, nbx], brick_ids int32 [M] ascending)."""
+        nbz, nby, nbx = (int(n) - 1 for n in coarse.shape)
+        slot_map = torch.empty(max(nbz, 0), max(nby, 0), max(nbx, 0), device=coarse.device, dtype=torch.int32)
+        ids = torch.empty(slot_map.numel(), device=coarse.device, dtype=torch.int32)
+        m = _i64(0)
+        self.check(self.lib.neddf_brick_select(self.h, _ptr(coarse), nbx, nby, nbz, float(iso), float(band), int(dilate), _ptr(slot_map),
+                                               _ptr(ids), C.byref(m), self.stream()))
+        return slot_map, ids[:m.value].clone()
+
+    def field_bricks(self, slot, field, shape, brick, lo, hi, brick_ids):
+        """`field` on the lattices of the listed bricks: float32 [M, (brick + 1)^3], NaN past the fine lattice (neddf_field_bricks)."""
+        if field not in GRID_FIELDS:
+            raise NeddfError("field_bricks: field must be one of %s (got %r)" % (sorted(GRID_FIELDS), field))
+        nx, ny, nz = (int(n) for n in shape)
+        blo, bhi = self._bounds(lo, hi)
+        require_device(brick_ids, "brick_ids")
+        ids = brick_ids.contiguous() if brick_ids.dtype == torch.int32 else brick_ids.to(torch.int32).contiguous()
+        vals = torch.empty(ids.shape[0], (int(brick) + 1) ** 3, device=ids.device, dtype=torch.float32)
+        self.check(self.lib.neddf_field_bricks(self.h, slot, GRID_FIELDS[field], nx, ny, nz, int(brick), blo, bhi, _ptr(ids), ids.shape[0],
+                                               _ptr(vals), self.stream()))
+        return vals
+
+    def marching_cubes_bricks(self, values, brick_ids, slot_map, shape, brick, iso, lo, hi):
+        """Marching cubes over the listed bricks (neddf_marching_cubes_bricks), by a counting call and a writing call of exactly that
+        size: (vertices float32 [V, 3], triangles int32 [T, 3], vertex_key int64 [V], triangle_key int64 [T]) in the library's order."""
+        nx, ny, nz = (int(n) for n in shape)
+        blo, bhi = self._bounds(lo, hi)
+        nv, nt = _i64(0), _i64(0)
+        dev = slot_map.device
+
+        def call(v, t, vk, tk):
+            self.check(self.lib.neddf_marching_cubes_bricks(self.h, _ptr(values), _ptr(brick_ids), brick_ids.shape[0], _ptr(slot_map), nx, ny, nz,
+                                                            int(brick), blo, bhi, float(iso), _ptr(v), 0 if v is None else v.shape[0], _ptr(t),
+                                                            0 if t is None else t.shape[0], _ptr(vk), _ptr(tk), C.byref(nv), C.byref(nt),
+                                                            self.stream()))
+        call(None, None, None, None)
+        verts = torch.empty(nv.value, 3, device=dev, dtype=torch.float32)
+        tris = torch.empty(nt.value, 3, device=dev, dtype=torch.int32)
+        vkey = torch.empty(nv.value, device=dev, dtype=torch.int64)
+        tkey = torch.empty(nt.value, device=dev, dtype=torch.int64)
+        if nv.value and nt.value:
+            call(verts, tris, vkey, tkey)
+        return verts, tris, vkey, tkey
 
     @staticmethod
     def _triangles(triangles, what):

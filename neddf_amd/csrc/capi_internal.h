@@ -102,6 +102,8 @@ struct neddf_ctx {
                                               // block totals followed by the "changed" words of one batch of rounds
     int cc_rounds = 0;           // union-find rounds of the last neddf_mesh_components call
     DevBuf occ_cells, occ_blk;   // neddf_occupancy_build: two byte planes of R^3 cells; block totals of build / gather
+    DevBuf brick_flags, brick_blk;            // neddf_brick_select: two byte planes of one flag per brick, block totals
+    DevBuf brick_mask, brick_vbase;           // neddf_marching_cubes_bricks: owned crossed edges and first vertex id per brick lattice point
     int64_t cull_samples = 0, cull_kept = 0;  // neddf_cull_stats: samples classified / kept by the culled render passes
     std::vector<GuardBand> carve_guards;      // NEDDF_GUARD=1: the bands behind the carves of the last render call
     bool timing = false;

@@ -236,6 +236,42 @@ void launch_compact_write(const float *vertices, int64_t V, const int32_t *tris,
                           const unsigned char *used, const int64_t *vblk, const int64_t *tblk, int32_t *vmap, float *out_vertices,
                           int32_t *out_tris, hipStream_t s);
 
+// Brick-wise surface extraction (mesh_kernels.hip): the fine lattice of McGrid cut into bricks of B^3 cells, brick (bx, by, bz) at linear
+// index (bz nby + by) nbx + bx, its lattice (B+1)^3 points at local index (lz (B+1) + ly)(B+1) + lx; the last brick of an axis may be
+// partial (its points past the fine lattice are padding).
+constexpr int kBrickMin = 2, kBrickMax = 16, kBrickMaxDilate = 4;
+constexpr int kBrickMaxPoints = (kBrickMax + 1) * (kBrickMax + 1) * (kBrickMax + 1);
+struct BrickGrid {
+    McGrid g;                            // the fine lattice; vol unused
+    int B, P;                            // cells per brick and axis; (B + 1)^3
+    int nbx, nby, nbz;                   // ceil((n - 1) / B) per axis
+    int64_t nb;                          // nbx * nby * nbz
+};
+struct BrickMesh {
+    BrickGrid bg;
+    const float *values;                 // [M][P]
+    const int32_t *ids;                  // [M], strictly ascending brick indices
+    const int32_t *slot_map;             // [nb]: the rank of a brick in ids, or -1
+    int64_t M;
+};
+// the (nbx+1)(nby+1)(nbz+1) fine lattice points at index min(b B, n - 1) per axis, x fastest
+void launch_coarse_points(const BrickGrid &bg, int64_t first, int64_t n, float *pos, float *dir, float *var, hipStream_t s);
+// points first .. first + n of the [M][P] brick lattices (padding: the clamped lattice point); brick_pad writes NaN over the padding's results
+void launch_brick_points(const BrickGrid &bg, const int32_t *ids, int64_t first, int64_t n, float *pos, float *dir, float *var, hipStream_t s);
+void launch_brick_pad(const BrickGrid &bg, const int32_t *ids, int64_t first, int64_t n, float *out, hipStream_t s);
+// coarse: [nbz+1][nby+1][nbx+1]; flag_a / flag_b: nb bytes each (workspace); blk: [mc_blocks(nb) + 1], the number of active bricks behind
+// the block bases afterwards; slot_map [nb], ids [capacity nb]
+void launch_brick_select(const float *coarse, int nbx, int nby, int nbz, float iso, float band, int dilate, unsigned char *flag_a,
+                         unsigned char *flag_b, int64_t *blk, int32_t *slot_map, int32_t *ids, hipStream_t s);
+// *bad = 1 unless ids is strictly ascending inside [0, nb) and slot_map is exactly its inverse (-1 elsewhere)
+void launch_brick_check(const BrickMesh &k, int *bad, hipStream_t s);
+// mask [M][P]: the crossed edges each brick lattice point OWNS; vblk / tblk [M + 1]: per-brick vertex / triangle totals (launch_mc_scan next)
+void launch_brick_mc_count(const BrickMesh &k, unsigned char *mask, int64_t *vblk, int64_t *tblk, hipStream_t s);
+void launch_brick_mc_vertices(const BrickMesh &k, const unsigned char *mask, const int64_t *vblk, int32_t *vbase, float *vertices,
+                              int64_t *vertex_key, hipStream_t s);
+void launch_brick_mc_triangles(const BrickMesh &k, const unsigned char *mask, const int64_t *tblk, const int32_t *vbase, int32_t *tris,
+                               int64_t *triangle_key, hipStream_t s);
+
 // Empty-space skipping (occupancy_kernels.hip): an R^3 bitfield over the box lo .. hi, bit (z R + y) R + x of cell (x, y, z) in
 // 32-bit words; classification of sample points against it and order-preserving compaction of the kept ones.
 constexpr int kOccThreads = 1024;        // points per workgroup of the count / gather kernels (16 waves: ballot + popcount offsets)

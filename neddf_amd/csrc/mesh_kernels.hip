@@ -539,4 +539,376 @@ void launch_mc_triangles(const McGrid &g, const unsigned char *mask, const int64
     hipLaunchKernelGGL(mc_triangle_kernel, dim3((unsigned)mc_blocks(g.n)), dim3(kMcThreads), 0, s, g, mask, tblk, vbase, tris);
 }
 
+// ---- brick-wise marching cubes -------------------------------------------------------------------------------------------------
+// The fine lattice is cut into bricks of B^3 cells (kernels.h BrickGrid); only the listed ("active") bricks carry values, [M][P] floats.
+//   coarse_points_kernel    the brick corners: fine lattice points min(b B, n - 1) per axis
+//   brick_flag_kernel       a brick is active when one of its 8 corners is NaN, two of them lie on different sides of iso, or one
+//                           is within `band` of it; brick_dilate_kernel grows the set along one axis (three launches: a Chebyshev ball)
+//   brick_count / _list     active bricks per workgroup (scan_totals_kernel in between), then slot map and ascending list by wave
+//                           ballots: the rank of a brick among the active ones is its position in both
+//   brick_points / _pad     the lattice points of the listed bricks for the field kernels; NaN over what lies past the fine lattice
+//   brick_mc_*              one workgroup per brick, the brick's values in LDS: count (the owned crossed edges of every point, the
+//                           brick's totals), vertices, triangles -- dense marching cubes' arithmetic on the same lattice points
+// Ownership: a lattice edge with lower point p along axis a lies in the lattice of brick p[a] / B on that axis and, on each other axis
+// c, of brick p[c] / B and -- when p[c] is a multiple of B -- of the brick below it.  The edge belongs to the ACTIVE brick of lowest
+// index among these (up to four); every brick finds the same owner from the slot map alone, so that an edge on a face or edge shared
+// by active bricks gives one vertex, and one next to an inactive brick is still produced.  A triangle corner is the owner's first
+// vertex id of the edge's lower point (vbase [M][P]) plus the owned crossed edges of lower axis there (mask [M][P]).
+// Order: bricks ascending, points / cells by local index, then x / y / z edge / table order; the keys (fine linear index of the lower
+// point * 3 + axis, of the cell's corner 0 * 5 + position) sort it into the dense kernel's order.
+__device__ __forceinline__ void brick_coords(const BrickGrid &bg, int32_t id, int b[3])
+{
+    b[0] = id % bg.nbx; b[1] = (id / bg.nbx) % bg.nby; b[2] = id / (bg.nbx * bg.nby);
+}
+
+// last valid local index per axis: B, less in the last brick of an axis the bricks do not divide
+__device__ __forceinline__ void brick_extent(const BrickGrid &bg, const int b[3], int e[3])
+{
+    const int dim[3] = { bg.g.nx, bg.g.ny, bg.g.nz };
+    for (int a = 0; a < 3; ++a) e[a] = min(bg.B, dim[a] - 1 - b[a] * bg.B);
+}
+
+__global__ void __launch_bounds__(kMcThreads) coarse_points_kernel(BrickGrid bg, int64_t first, int64_t n, float *pos, float *dir, float *var)
+{
+    const int64_t q = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    if (q >= n) return;
+    const int64_t p = first + q;
+    const int cx = (int)(p % (bg.nbx + 1)), cy = (int)((p / (bg.nbx + 1)) % (bg.nby + 1)), cz = (int)(p / ((int64_t)(bg.nbx + 1) * (bg.nby + 1)));
+    pos[3 * q + 0] = lattice_coord(bg.g.lo[0], bg.g.hi[0], bg.g.nx, min(cx * bg.B, bg.g.nx - 1));
+    pos[3 * q + 1] = lattice_coord(bg.g.lo[1], bg.g.hi[1], bg.g.ny, min(cy * bg.B, bg.g.ny - 1));
+    pos[3 * q + 2] = lattice_coord(bg.g.lo[2], bg.g.hi[2], bg.g.nz, min(cz * bg.B, bg.g.nz - 1));
+    dir[3 * q + 0] = 1.f; dir[3 * q + 1] = 0.f; dir[3 * q + 2] = 0.f;
+    var[3 * q + 0] = 0.f; var[3 * q + 1] = 0.f; var[3 * q + 2] = 0.f;
+}
+
+// fine indices of point p of the [M][P] brick lattices; false for padding (and for a brick index outside the grid), then clamped
+__device__ __forceinline__ bool brick_point(const BrickGrid &bg, const int32_t *ids, int64_t p, int idx[3])
+{
+    const int32_t id = ids[p / bg.P];
+    const int l = (int)(p % bg.P), L = bg.B + 1;
+    const int loc[3] = { l % L, (l / L) % L, l / (L * L) };
+    const int dim[3] = { bg.g.nx, bg.g.ny, bg.g.nz };
+    if (id < 0 || id >= bg.nb) { idx[0] = idx[1] = idx[2] = 0; return false; }
+    int b[3];
+    brick_coords(bg, id, b);
+    bool valid = true;
+    for (int a = 0; a < 3; ++a) {
+        idx[a] = b[a] * bg.B + loc[a];
+        if (idx[a] > dim[a] - 1) { idx[a] = dim[a] - 1; valid = false; }
+    }
+    return valid;
+}
+
+__global__ void __launch_bounds__(kMcThreads) brick_points_kernel(BrickGrid bg, const int32_t *ids, int64_t first, int64_t n, float *pos, float *dir,
+                                                                   float *var)
+{
+    const int64_t q = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    if (q >= n) return;
+    int idx[3];
+    (void)brick_point(bg, ids, first + q, idx);
+    pos[3 * q + 0] = lattice_coord(bg.g.lo[0], bg.g.hi[0], bg.g.nx, idx[0]);
+    pos[3 * q + 1] = lattice_coord(bg.g.lo[1], bg.g.hi[1], bg.g.ny, idx[1]);
+    pos[3 * q + 2] = lattice_coord(bg.g.lo[2], bg.g.hi[2], bg.g.nz, idx[2]);
+    dir[3 * q + 0] = 1.f; dir[3 * q + 1] = 0.f; dir[3 * q + 2] = 0.f;
+    var[3 * q + 0] = 0.f; var[3 * q + 1] = 0.f; var[3 * q + 2] = 0.f;
+}
+
+__global__ void __launch_bounds__(kMcThreads) brick_pad_kernel(BrickGrid bg, const int32_t *ids, int64_t first, int64_t n, float *out)
+{
+    const int64_t q = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    if (q >= n) return;
+    int idx[3];
+    if (!brick_point(bg, ids, first + q, idx)) out[q] = __uint_as_float(0x7fc00000u);
+}
+
+__global__ void __launch_bounds__(kMcThreads) brick_flag_kernel(const float *coarse, int nbx, int nby, int nbz, int64_t nb, float iso, float band,
+                                                                 unsigned char *flag)
+{
+    const int64_t c = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    if (c >= nb) return;
+    const int x = (int)(c % nbx), y = (int)((c / nbx) % nby), z = (int)(c / ((int64_t)nbx * nby));
+    const int64_t sy = nbx + 1, sz = (int64_t)(nbx + 1) * (nby + 1);
+    const int64_t p = z * sz + y * sy + x;
+    bool any = false;
+    int in = 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const float v = coarse[p + (b & 1) + ((b >> 1) & 1) * sy + (b >> 2) * sz];
+        any |= v != v || fabsf(v - iso) <= band;
+        in += inside(v, iso);
+    }
+    flag[c] = any || (in != 0 && in != 8) ? 1 : 0;
+}
+
+// dst = maximum of src over [i - d, i + d] along one axis, clipped to the brick grid
+__global__ void __launch_bounds__(kMcThreads) brick_dilate_kernel(const unsigned char *src, unsigned char *dst, int nbx, int nby, int nbz, int64_t nb,
+                                                                   int d, int axis)
+{
+    const int64_t c = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    if (c >= nb) return;
+    const int64_t stride = axis == 0 ? 1 : (axis == 1 ? (int64_t)nbx : (int64_t)nbx * nby);
+    const int n = axis == 0 ? nbx : (axis == 1 ? nby : nbz);
+    const int i = (int)((c / stride) % n);
+    const int a = i - d < 0 ? 0 : i - d, b = i + d > n - 1 ? n - 1 : i + d;
+    unsigned char m = 0;
+    for (int j = a; j <= b; ++j) m |= src[c + (int64_t)(j - i) * stride];
+    dst[c] = m;
+}
+
+__global__ void __launch_bounds__(kMcThreads) brick_count_kernel(const unsigned char *flag, int64_t nb, int64_t *blk)
+{
+    const int64_t c = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    const int n = __syncthreads_count(c < nb && flag[c]);
+    if (threadIdx.x == 0) blk[blockIdx.x] = n;
+}
+
+__global__ void __launch_bounds__(kMcThreads) brick_list_kernel(const unsigned char *flag, int64_t nb, const int64_t *blk, int32_t *slot_map,
+                                                                 int32_t *ids)
+{
+    __shared__ int lds[kMcThreads / 64];
+    const int64_t c = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    const bool k = c < nb && flag[c];
+    const unsigned long long ballot = __ballot(k);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int in_wave = (int)__popcll(ballot & ((1ull << lane) - 1ull));
+    if (lane == 0) lds[wave] = (int)__popcll(ballot);
+    __syncthreads();
+    int before = 0;
+    for (int w = 0; w < wave; ++w) before += lds[w];
+    if (c >= nb) return;
+    const int64_t o = blk[blockIdx.x] + before + in_wave;
+    slot_map[c] = k ? (int32_t)o : -1;
+    if (k) ids[o] = (int32_t)c;
+}
+
+__global__ void __launch_bounds__(kMcThreads) brick_check_kernel(BrickMesh k, int *bad)
+{
+    const int64_t t = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
+    bool wrong = false;
+    if (t < k.M) {
+        const int32_t id = k.ids[t];
+        if (id < 0 || id >= k.bg.nb) wrong = true;
+        else wrong = k.slot_map[id] != (int32_t)t || (t > 0 && k.ids[t - 1] >= id);
+    }
+    if (t < k.bg.nb) {
+        const int32_t s = k.slot_map[t];
+        if (s != -1 && (s < 0 || s >= k.M || k.ids[s] != (int32_t)t)) wrong = true;
+    }
+    if (wrong) *bad = 1;            // every writer stores the same word
+}
+
+// the brick that owns the edge from local point l of brick b (slot `self`) along `axis`, and the edge's lower point in that brick's lattice
+__device__ __forceinline__ int64_t edge_owner(const BrickMesh &k, const int b[3], const int l[3], int axis, int64_t self, int ol[3])
+{
+    const BrickGrid &bg = k.bg;
+    const int c1 = axis == 0 ? 1 : 0, c2 = axis == 2 ? 1 : 2;          // the other two axes, c2 the slower one
+    const int nbs[3] = { bg.nbx, bg.nby, bg.nbz };
+    // on a face of the brick the edge also lies in the neighbour's lattice (l == B only occurs in a full brick)
+    const int lo1 = b[c1] - (l[c1] == 0 && b[c1] > 0), hi1 = b[c1] + (l[c1] == bg.B && b[c1] + 1 < nbs[c1]);
+    const int lo2 = b[c2] - (l[c2] == 0 && b[c2] > 0), hi2 = b[c2] + (l[c2] == bg.B && b[c2] + 1 < nbs[c2]);
+    ol[0] = l[0]; ol[1] = l[1]; ol[2] = l[2];
+    for (int o2 = lo2; o2 <= hi2; ++o2)
+        for (int o1 = lo1; o1 <= hi1; ++o1) {         // ascending brick index
+            if (o1 == b[c1] && o2 == b[c2]) return self;
+            int o[3] = { b[0], b[1], b[2] };
+            o[c1] = o1; o[c2] = o2;
+            const int32_t s = k.slot_map[((int64_t)o[2] * bg.nby + o[1]) * bg.nbx + o[0]];
+            if (s >= 0 && s < k.M) {
+                ol[c1] = l[c1] + (b[c1] - o1) * bg.B;
+                ol[c2] = l[c2] + (b[c2] - o2) * bg.B;
+                return s;
+            }
+        }
+    return self;            // (bricks above this one never own: it is active and lower)
+}
+
+// what every brick kernel starts with: the brick's coordinates and extent (false: an index outside the grid, nothing to do), its values in LDS
+__device__ __forceinline__ bool brick_stage(const BrickMesh &k, int64_t m, int b[3], int e[3], float *val)
+{
+    const int32_t id = k.ids[m];
+    if (id < 0 || id >= k.bg.nb) return false;
+    brick_coords(k.bg, id, b);
+    brick_extent(k.bg, b, e);
+    for (int l = threadIdx.x; l < k.bg.P; l += kMcThreads) val[l] = k.values[m * k.bg.P + l];
+    __syncthreads();
+    return true;
+}
+
+__device__ __forceinline__ int brick_cell_case(const float *val, int l, int L, float iso)
+{
+    const int sx = 1, sy = L, sz = L * L;
+    const int off[8] = { 0, sx, sx + sy, sy, sz, sx + sz, sx + sy + sz, sy + sz };
+    int c = 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) c |= inside(val[l + off[b]], iso) << b;
+    return c;
+}
+
+__global__ void __launch_bounds__(kMcThreads) brick_mc_count_kernel(BrickMesh k, unsigned char *mask, int64_t *vblk, int64_t *tblk)
+{
+    __shared__ float val[kBrickMaxPoints];
+    __shared__ int lds[kMcThreads];
+    const int64_t m = blockIdx.x;
+    const int L = k.bg.B + 1, P = k.bg.P;
+    const float iso = k.bg.g.iso;
+    int b[3], e[3], nv = 0, nt = 0;
+    const bool ok = brick_stage(k, m, b, e, val);           // uniform over the workgroup
+    for (int l = threadIdx.x; l < P; l += kMcThreads) {
+        const int loc[3] = { l % L, (l / L) % L, l / (L * L) };
+        const int stride[3] = { 1, L, L * L };
+        int msk = 0;
+        if (ok && loc[0] <= e[0] && loc[1] <= e[1] && loc[2] <= e[2]) {
+            const bool in0 = inside(val[l], iso);
+            for (int a = 0; a < 3; ++a) {
+                int ol[3];
+                if (loc[a] < e[a] && inside(val[l + stride[a]], iso) != in0 && edge_owner(k, b, loc, a, m, ol) == m) msk |= 1 << a;
+            }
+            if (loc[0] < e[0] && loc[1] < e[1] && loc[2] < e[2]) nt += case_triangles(brick_cell_case(val, l, L, iso));
+        }
+        mask[m * P + l] = (unsigned char)msk;
+        nv += (int)__popc(msk);
+    }
+    int tv, tt;
+    (void)block_exclusive_scan(nv, lds, &tv);
+    (void)block_exclusive_scan(nt, lds, &tt);
+    if (threadIdx.x == 0) { vblk[m] = tv; tblk[m] = tt; }
+}
+
+__global__ void __launch_bounds__(kMcThreads) brick_mc_vertex_kernel(BrickMesh k, const unsigned char *mask, const int64_t *vblk, int32_t *vbase,
+                                                                      float *vertices, int64_t *vertex_key)
+{
+    __shared__ float val[kBrickMaxPoints];
+    __shared__ int lds[kMcThreads];
+    const int64_t m = blockIdx.x;
+    const int L = k.bg.B + 1, P = k.bg.P;
+    const McGrid &g = k.bg.g;
+    int b[3], e[3];
+    if (!brick_stage(k, m, b, e, val)) return;
+    int64_t carry = vblk[m];
+    for (int base = 0; base < P; base += kMcThreads) {
+        const int l = base + threadIdx.x;
+        const int msk = l < P ? mask[m * P + l] : 0;
+        int total;
+        const int off = block_exclusive_scan((int)__popc(msk), lds, &total);
+        int64_t id = carry + off;
+        carry += total;
+        if (l >= P) continue;
+        vbase[m * P + l] = (int32_t)id;
+        if (!msk) continue;
+        const int loc[3] = { l % L, (l / L) % L, l / (L * L) };
+        const int idx[3] = { b[0] * k.bg.B + loc[0], b[1] * k.bg.B + loc[1], b[2] * k.bg.B + loc[2] };
+        const int dim[3] = { g.nx, g.ny, g.nz }, stride[3] = { 1, L, L * L };
+        const float c[3] = { lattice_coord(g.lo[0], g.hi[0], g.nx, idx[0]), lattice_coord(g.lo[1], g.hi[1], g.ny, idx[1]),
+                             lattice_coord(g.lo[2], g.hi[2], g.nz, idx[2]) };
+        const int64_t p = ((int64_t)idx[2] * g.ny + idx[1]) * g.nx + idx[0];
+        const float v0 = val[l];
+        for (int a = 0; a < 3; ++a) {
+            if (!(msk >> a & 1)) continue;
+            const float v1 = val[l + stride[a]];
+            float t = (g.iso - v0) / (v1 - v0);
+            if (t != t) t = 0.5f;
+            const float g0 = c[a], g1 = lattice_coord(g.lo[a], g.hi[a], dim[a], idx[a] + 1);
+            float out[3] = { c[0], c[1], c[2] };
+            out[a] = g0 + t * (g1 - g0);
+            vertices[3 * id + 0] = out[0];
+            vertices[3 * id + 1] = out[1];
+            vertices[3 * id + 2] = out[2];
+            vertex_key[id] = 3 * p + a;
+            ++id;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kMcThreads) brick_mc_triangle_kernel(BrickMesh k, const unsigned char *mask, const int64_t *tblk,
+                                                                        const int32_t *vbase, int32_t *tris, int64_t *triangle_key)
+{
+    __shared__ float val[kBrickMaxPoints];
+    __shared__ int lds[kMcThreads];
+    const int64_t m = blockIdx.x;
+    const int L = k.bg.B + 1, P = k.bg.P;
+    const McGrid &g = k.bg.g;
+    int b[3], e[3];
+    if (!brick_stage(k, m, b, e, val)) return;
+    int64_t carry = tblk[m];
+    for (int base = 0; base < P; base += kMcThreads) {
+        const int l = base + threadIdx.x;
+        const int loc[3] = { l % L, (l / L) % L, l / (L * L) };
+        int c = 0, nt = 0;
+        if (l < P && loc[0] < e[0] && loc[1] < e[1] && loc[2] < e[2]) {
+            c = brick_cell_case(val, l, L, g.iso);
+            nt = case_triangles(c);
+        }
+        int total;
+        const int off = block_exclusive_scan(nt, lds, &total);
+        const int64_t first = carry + off;
+        carry += total;
+        if (!nt) continue;
+        const int64_t p = ((int64_t)(b[2] * k.bg.B + loc[2]) * g.ny + (b[1] * k.bg.B + loc[1])) * g.nx + (b[0] * k.bg.B + loc[0]);
+        for (int i = 0; i < 3 * nt; ++i) {
+            const int own = kMcEdgeOwner[kMcTriTable[c][i]];
+            const int ql[3] = { loc[0] + (own & 1), loc[1] + ((own >> 1) & 1), loc[2] + ((own >> 2) & 1) };
+            const int axis = own >> 3;
+            int ol[3];
+            const int64_t s = edge_owner(k, b, ql, axis, m, ol);
+            const int64_t q = s * P + (ol[2] * L + ol[1]) * L + ol[0];
+            tris[3 * first + i] = vbase[q] + (int32_t)__popc(mask[q] & ((1 << axis) - 1));
+        }
+        for (int i = 0; i < nt; ++i) triangle_key[first + i] = 5 * p + i;
+    }
+}
+
+void launch_coarse_points(const BrickGrid &bg, int64_t first, int64_t n, float *pos, float *dir, float *var, hipStream_t s)
+{
+    hipLaunchKernelGGL(coarse_points_kernel, dim3((unsigned)mc_blocks(n)), dim3(kMcThreads), 0, s, bg, first, n, pos, dir, var);
+}
+
+void launch_brick_points(const BrickGrid &bg, const int32_t *ids, int64_t first, int64_t n, float *pos, float *dir, float *var, hipStream_t s)
+{
+    hipLaunchKernelGGL(brick_points_kernel, dim3((unsigned)mc_blocks(n)), dim3(kMcThreads), 0, s, bg, ids, first, n, pos, dir, var);
+}
+
+void launch_brick_pad(const BrickGrid &bg, const int32_t *ids, int64_t first, int64_t n, float *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(brick_pad_kernel, dim3((unsigned)mc_blocks(n)), dim3(kMcThreads), 0, s, bg, ids, first, n, out);
+}
+
+void launch_brick_select(const float *coarse, int nbx, int nby, int nbz, float iso, float band, int dilate, unsigned char *flag_a,
+                         unsigned char *flag_b, int64_t *blk, int32_t *slot_map, int32_t *ids, hipStream_t s)
+{
+    const int64_t nb = (int64_t)nbx * nby * nbz, blocks = mc_blocks(nb);
+    hipLaunchKernelGGL(brick_flag_kernel, dim3((unsigned)blocks), dim3(kMcThreads), 0, s, coarse, nbx, nby, nbz, nb, iso, band, flag_a);
+    unsigned char *src = flag_a, *dst = flag_b;
+    if (dilate > 0)
+        for (int axis = 0; axis < 3; ++axis) {
+            hipLaunchKernelGGL(brick_dilate_kernel, dim3((unsigned)blocks), dim3(kMcThreads), 0, s, src, dst, nbx, nby, nbz, nb, dilate, axis);
+            unsigned char *t = src; src = dst; dst = t;
+        }
+    hipLaunchKernelGGL(brick_count_kernel, dim3((unsigned)blocks), dim3(kMcThreads), 0, s, src, nb, blk);
+    launch_scan_totals(blk, blocks, s);
+    hipLaunchKernelGGL(brick_list_kernel, dim3((unsigned)blocks), dim3(kMcThreads), 0, s, src, nb, blk, slot_map, ids);
+}
+
+void launch_brick_check(const BrickMesh &k, int *bad, hipStream_t s)
+{
+    const int64_t n = k.M > k.bg.nb ? k.M : k.bg.nb;
+    hipLaunchKernelGGL(brick_check_kernel, dim3((unsigned)mc_blocks(n)), dim3(kMcThreads), 0, s, k, bad);
+}
+
+void launch_brick_mc_count(const BrickMesh &k, unsigned char *mask, int64_t *vblk, int64_t *tblk, hipStream_t s)
+{
+    hipLaunchKernelGGL(brick_mc_count_kernel, dim3((unsigned)k.M), dim3(kMcThreads), 0, s, k, mask, vblk, tblk);
+}
+
+void launch_brick_mc_vertices(const BrickMesh &k, const unsigned char *mask, const int64_t *vblk, int32_t *vbase, float *vertices,
+                              int64_t *vertex_key, hipStream_t s)
+{
+    hipLaunchKernelGGL(brick_mc_vertex_kernel, dim3((unsigned)k.M), dim3(kMcThreads), 0, s, k, mask, vblk, vbase, vertices, vertex_key);
+}
+
+void launch_brick_mc_triangles(const BrickMesh &k, const unsigned char *mask, const int64_t *tblk, const int32_t *vbase, int32_t *tris,
+                               int64_t *triangle_key, hipStream_t s)
+{
+    hipLaunchKernelGGL(brick_mc_triangle_kernel, dim3((unsigned)k.M), dim3(kMcThreads), 0, s, k, mask, tblk, vbase, tris, triangle_key);
+}
+
 }  // namespace neddf

@@ -759,7 +759,8 @@ void neddf_destroy(neddf_ctx *ctx)
     }
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack, &ctx->ttmp, &ctx->tamax,
                       &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc,
-                      &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk, &ctx->occ_cells, &ctx->occ_blk })
+                      &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk, &ctx->occ_cells, &ctx->occ_blk,
+                      &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase })
         if (b->p) (void)hipFree(b->base ? b->base : b->p);
     for (auto &e : ctx->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : ctx->pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -779,7 +780,8 @@ int neddf_debug_check_guards(neddf_ctx *ctx, int64_t *n_bands, int64_t *n_bad_by
     std::vector<GuardBand> bands = ctx->carve_guards;
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack,
                        &ctx->ttmp, &ctx->tamax, &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc,
-                      &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk, &ctx->occ_cells, &ctx->occ_blk })
+                      &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk, &ctx->occ_cells, &ctx->occ_blk,
+                      &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase })
         if (b->base) {
             bands.push_back(GuardBand{ b->base, kGuardBytes });
             bands.push_back(GuardBand{ (char *)b->p + b->cap, kGuardBytes });
@@ -1425,6 +1427,161 @@ int neddf_marching_cubes(neddf_ctx *ctx, const float *d_volume, int nx, int ny, 
     int32_t *vbase = (int32_t *)ctx->mc_vbase.p;
     launch_mc_vertices(g, mask, vblk, vbase, d_vertices, s);
     launch_mc_triangles(g, mask, tblk, vbase, d_triangles, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- brick-wise surface extraction ----
+static bool brick_ok(int brick) { return brick >= kBrickMin && brick <= kBrickMax; }
+
+static BrickGrid brick_grid(int nx, int ny, int nz, int brick, const double *lo, const double *hi, float iso)
+{
+    BrickGrid bg{};
+    bg.g = mc_grid(nullptr, nx, ny, nz, lo, hi, iso);
+    bg.B = brick;
+    bg.P = (brick + 1) * (brick + 1) * (brick + 1);
+    bg.nbx = (nx - 2 + brick) / brick; bg.nby = (ny - 2 + brick) / brick; bg.nbz = (nz - 2 + brick) / brick;
+    bg.nb = (int64_t)bg.nbx * bg.nby * bg.nbz;
+    return bg;
+}
+
+static int grid_field_ok(neddf_ctx *ctx, int slot, int field, const char *what)
+{
+    if (field != NEDDF_GRID_DISTANCE && field != NEDDF_GRID_DENSITY)
+        return fail(ctx, NEDDF_EINVAL, std::string(what) + ": field must be NEDDF_GRID_DISTANCE or NEDDF_GRID_DENSITY");
+    if (slot < 0 || slot >= NEDDF_NUM_SLOTS || !ctx->field[slot].valid) return fail(ctx, NEDDF_ENOFIELD, "no field in slot");
+    if (field == NEDDF_GRID_DISTANCE && ctx->field[slot].d.kind == NEDDF_FIELD_NERF)
+        return fail(ctx, NEDDF_EINVAL, std::string(what) + ": a NeRF field has no distance output");
+    return 0;
+}
+
+// `total` generated points through the field in chunks of at most 2^23, as neddf_field_grid does: points(first, n, pos, dir, var) fills a
+// chunk, after(first, n, out) runs behind its evaluation
+static int eval_generated(neddf_ctx *ctx, int slot, int field, int64_t total, float *d_out, hipStream_t s,
+                          const std::function<void(int64_t, int64_t, float *, float *, float *)> &points,
+                          const std::function<void(int64_t, int64_t, float *)> &after)
+{
+    const int64_t chunk = total < ((int64_t)1 << 23) ? total : ((int64_t)1 << 23);
+    if (int rc = ensure(ctx, ctx->grid_pts, (size_t)chunk * 9 * sizeof(float))) return rc;
+    float *pos = (float *)ctx->grid_pts.p, *dir = pos + chunk * 3, *var = dir + chunk * 3;
+    for (int64_t off = 0; off < total; off += chunk) {
+        const int64_t n = total - off < chunk ? total - off : chunk;
+        points(off, n, pos, dir, var);
+        HIPCHK(hipGetLastError());
+        float *out = d_out + off;
+        if (int rc = field_forward(ctx, slot, pos, dir, var, n, NEDDF_OUT_MINIMAL, field == NEDDF_GRID_DISTANCE ? out : nullptr,
+                                   field == NEDDF_GRID_DENSITY ? out : nullptr, nullptr, nullptr, nullptr, s)) return rc;
+        after(off, n, out);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+int neddf_field_grid_coarse(neddf_ctx *ctx, int slot, int field, int nx, int ny, int nz, int brick, const double *h_lo, const double *h_hi,
+                            float *d_coarse, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!h_lo || !h_hi || !d_coarse) return fail(ctx, NEDDF_EINVAL, "field_grid_coarse: NULL bounds or volume");
+    if (!lattice_ok(nx, ny, nz, h_lo, h_hi)) return fail(ctx, NEDDF_EINVAL, "field_grid_coarse: every dimension must be >= 2 and lo < hi on every axis");
+    if (!brick_ok(brick)) return fail(ctx, NEDDF_EINVAL, "field_grid_coarse: the brick size must lie in [2, 16]");
+    if (int rc = grid_field_ok(ctx, slot, field, "field_grid_coarse")) return rc;
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const BrickGrid bg = brick_grid(nx, ny, nz, brick, h_lo, h_hi, 0.f);
+    const int64_t total = (int64_t)(bg.nbx + 1) * (bg.nby + 1) * (bg.nbz + 1);
+    return eval_generated(ctx, slot, field, total, d_coarse, s,
+                          [&](int64_t first, int64_t n, float *pos, float *dir, float *var) { launch_coarse_points(bg, first, n, pos, dir, var, s); },
+                          [](int64_t, int64_t, float *) {});
+}
+
+int neddf_brick_select(neddf_ctx *ctx, const float *d_coarse, int nbx, int nby, int nbz, float iso, float band, int dilate, int32_t *d_slot_map,
+                       int32_t *d_brick_ids, int64_t *h_n_active, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!d_coarse || !d_slot_map || !d_brick_ids || !h_n_active) return fail(ctx, NEDDF_EINVAL, "brick_select: NULL volume, slot map, list or count");
+    if (nbx < 1 || nby < 1 || nbz < 1) return fail(ctx, NEDDF_EINVAL, "brick_select: every axis needs at least one brick");
+    if (!(band >= 0.f)) return fail(ctx, NEDDF_EINVAL, "brick_select: the band must not be negative");
+    if (dilate < 0 || dilate > kBrickMaxDilate) return fail(ctx, NEDDF_EINVAL, "brick_select: dilate must lie in [0, 4]");
+    const int64_t nb = (int64_t)nbx * nby * nbz, blocks = mc_blocks(nb);
+    if (nb >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "brick_select: 2^31 bricks or more (brick indices are int32)");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ensure(ctx, ctx->brick_flags, (size_t)2 * nb)) return rc;
+    if (int rc = ensure(ctx, ctx->brick_blk, (size_t)(blocks + 1) * sizeof(int64_t))) return rc;
+    unsigned char *flags = (unsigned char *)ctx->brick_flags.p;
+    int64_t *blk = (int64_t *)ctx->brick_blk.p;
+    launch_brick_select(d_coarse, nbx, nby, nbz, iso, band, dilate, flags, flags + nb, blk, d_slot_map, d_brick_ids, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_n_active, blk + blocks, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int neddf_field_bricks(neddf_ctx *ctx, int slot, int field, int nx, int ny, int nz, int brick, const double *h_lo, const double *h_hi,
+                       const int32_t *d_brick_ids, int64_t n_bricks, float *d_values, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!h_lo || !h_hi) return fail(ctx, NEDDF_EINVAL, "field_bricks: NULL bounds");
+    if (!lattice_ok(nx, ny, nz, h_lo, h_hi)) return fail(ctx, NEDDF_EINVAL, "field_bricks: every dimension must be >= 2 and lo < hi on every axis");
+    if (!brick_ok(brick)) return fail(ctx, NEDDF_EINVAL, "field_bricks: the brick size must lie in [2, 16]");
+    const BrickGrid bg = brick_grid(nx, ny, nz, brick, h_lo, h_hi, 0.f);
+    if (n_bricks < 0 || n_bricks > bg.nb) return fail(ctx, NEDDF_EINVAL, "field_bricks: the number of bricks must lie in [0, the bricks of the grid]");
+    if (bg.nb >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "field_bricks: 2^31 bricks or more (brick indices are int32)");
+    if (n_bricks > 0 && (!d_brick_ids || !d_values)) return fail(ctx, NEDDF_EINVAL, "field_bricks: NULL brick list or values");
+    if (int rc = grid_field_ok(ctx, slot, field, "field_bricks")) return rc;
+    if (n_bricks == 0) return 0;
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    return eval_generated(ctx, slot, field, n_bricks * bg.P, d_values, s,
+                          [&](int64_t first, int64_t n, float *pos, float *dir, float *var) { launch_brick_points(bg, d_brick_ids, first, n, pos, dir, var, s); },
+                          [&](int64_t first, int64_t n, float *out) { launch_brick_pad(bg, d_brick_ids, first, n, out, s); });
+}
+
+int neddf_marching_cubes_bricks(neddf_ctx *ctx, const float *d_values, const int32_t *d_brick_ids, int64_t n_bricks, const int32_t *d_slot_map,
+                                int nx, int ny, int nz, int brick, const double *h_lo, const double *h_hi, float iso, float *d_vertices,
+                                int64_t vertex_cap, int32_t *d_triangles, int64_t triangle_cap, int64_t *d_vertex_key, int64_t *d_triangle_key,
+                                int64_t *h_n_vertices, int64_t *h_n_triangles, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!d_slot_map || !h_lo || !h_hi || !h_n_vertices || !h_n_triangles) return fail(ctx, NEDDF_EINVAL, "marching_cubes_bricks: NULL slot map, bounds or count");
+    if (!lattice_ok(nx, ny, nz, h_lo, h_hi)) return fail(ctx, NEDDF_EINVAL, "marching_cubes_bricks: every dimension must be >= 2 and lo < hi on every axis");
+    if (!brick_ok(brick)) return fail(ctx, NEDDF_EINVAL, "marching_cubes_bricks: the brick size must lie in [2, 16]");
+    BrickMesh k{};
+    k.bg = brick_grid(nx, ny, nz, brick, h_lo, h_hi, iso);
+    k.values = d_values; k.ids = d_brick_ids; k.slot_map = d_slot_map; k.M = n_bricks;
+    const int64_t M = n_bricks;
+    if (M < 0 || M > k.bg.nb) return fail(ctx, NEDDF_EINVAL, "marching_cubes_bricks: the number of bricks must lie in [0, the bricks of the grid]");
+    if (k.bg.nb >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "marching_cubes_bricks: 2^31 bricks or more (brick indices are int32)");
+    if (M > 0 && (!d_values || !d_brick_ids)) return fail(ctx, NEDDF_EINVAL, "marching_cubes_bricks: NULL values or brick list");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    // block totals of both kinds (each with its grand total behind it), then the word the list / slot-map check raises
+    if (int rc = ensure(ctx, ctx->brick_blk, (size_t)2 * (M + 1) * sizeof(int64_t) + sizeof(int))) return rc;
+    if (int rc = ensure(ctx, ctx->brick_mask, (size_t)(M > 0 ? M * k.bg.P : 1))) return rc;
+    unsigned char *mask = (unsigned char *)ctx->brick_mask.p;
+    int64_t *vblk = (int64_t *)ctx->brick_blk.p, *tblk = vblk + M + 1;
+    int *bad = (int *)(tblk + M + 1);
+    HIPCHK(hipMemsetAsync(bad, 0, sizeof(int), s));
+    launch_brick_check(k, bad, s);
+    if (M > 0) launch_brick_mc_count(k, mask, vblk, tblk, s);
+    launch_mc_scan(vblk, tblk, M, s);
+    HIPCHK(hipGetLastError());
+    int64_t counts[2];
+    int h_bad = 0;
+    HIPCHK(hipMemcpyAsync(&counts[0], vblk + M, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&counts[1], tblk + M, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h_bad) return fail(ctx, NEDDF_EINVAL, "marching_cubes_bricks: the brick list must be strictly ascending inside the grid and the slot map its inverse");
+    *h_n_vertices = counts[0];
+    *h_n_triangles = counts[1];
+    if (counts[0] >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "marching_cubes_bricks: 2^31 vertices or more (triangle indices are int32)");
+    if (!d_vertices || !d_triangles || !d_vertex_key || !d_triangle_key || vertex_cap < counts[0] || triangle_cap < counts[1]) return 0;     // the counting call
+    if (M == 0) return 0;
+    if (int rc = ensure(ctx, ctx->brick_vbase, (size_t)M * k.bg.P * sizeof(int32_t))) return rc;
+    int32_t *vbase = (int32_t *)ctx->brick_vbase.p;
+    launch_brick_mc_vertices(k, mask, vblk, vbase, d_vertices, d_vertex_key, s);
+    launch_brick_mc_triangles(k, mask, tblk, vbase, d_triangles, d_triangle_key, s);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -31,6 +31,66 @@ def marching_cubes(volume, iso, lo=(-1.0, -1.0, -1.0), hi=(1.0, 1.0, 1.0)):
     return Context.get(volume.device).marching_cubes(volume.contiguous(), iso, lo, hi)
 
 
+def select_bricks(coarse, iso, band, dilate=0):
+    """Bricks that can hold the `iso` level set, from the field's values at the brick corners: coarse float32 [nbz+1, nby+1, nbx+1]
+    on a HIP device (Context.field_grid_coarse, or every brick-th sample of a dense volume and its last one per axis).
+
+    A brick is active when one of its 8 corners is NaN, two of them lie on different sides of iso, or one is within `band` of it;
+    the set is then grown by `dilate` bricks (0..4) in the Chebyshev sense.  For an L-Lipschitz field, band = L * half the brick's
+    diagonal leaves out no brick the surface passes through.  Returns (slot_map int32 [nbz, nby, nbx]: the rank of each brick among
+    the active ones or -1, brick_ids int32 [M]: the active brick indices (bz * nby + by) * nbx + bx, ascending), independent of
+    timing (include/neddf_hip.h neddf_brick_select)."""
+    _device_mesh("select_bricks", coarse=coarse)
+    if coarse.dtype != torch.float32 or coarse.dim() != 3 or min(coarse.shape) < 2:
+        raise NeddfError("select_bricks: a float32 [nbz+1, nby+1, nbx+1] volume of at least 2 points per axis expected (got %s %s)"
+                         % (coarse.dtype, tuple(coarse.shape)))
+    if not float(band) >= 0.0:
+        raise NeddfError("select_bricks: the band must not be negative (got %r)" % (band,))
+    if int(dilate) < 0 or int(dilate) > 4:
+        raise NeddfError("select_bricks: dilate must lie in [0, 4] (got %r)" % (dilate,))
+    return Context.get(coarse.device).brick_select(coarse.contiguous(), iso, band, dilate)
+
+
+def marching_cubes_bricks(values, brick_ids, slot_map, shape, brick, iso, lo=(-1.0, -1.0, -1.0), hi=(1.0, 1.0, 1.0), dense_order=True):
+    """marching_cubes restricted to the listed bricks of `brick`^3 cells of the lattice shape = (nx, ny, nz) between lo and hi.
+
+    values float32 [M, (brick + 1)^3]: the samples on each listed brick's lattice (x fastest, NaN past the fine lattice:
+    Context.field_bricks); brick_ids int32 [M] strictly ascending; slot_map int32 [nbz, nby, nbx] its inverse (select_bricks).  The
+    triangles are marching_cubes' triangles of the cells inside listed bricks and the vertices those they reference, bit for bit.
+    dense_order=True: reordered on the device by the library's keys into marching_cubes' order -- whenever the listed bricks cover
+    every cell the surface crosses, the result IS marching_cubes' mesh.  Returns (vertices, triangles).
+    dense_order=False: the library's order (bricks ascending, then local index) and the keys:
+    (vertices, triangles, vertex_key int64 [V], triangle_key int64 [T]) (include/neddf_hip.h neddf_marching_cubes_bricks)."""
+    _device_mesh("marching_cubes_bricks", values=values, brick_ids=brick_ids, slot_map=slot_map)
+    brick = int(brick)
+    if len(tuple(shape)) != 3:
+        raise NeddfError("marching_cubes_bricks: shape must be (nx, ny, nz) (got %r)" % (shape,))
+    if values.dtype != torch.float32 or values.dim() != 2 or values.shape != (brick_ids.shape[0], (brick + 1) ** 3):
+        raise NeddfError("marching_cubes_bricks: values must be float32 [M, (brick + 1)^3] (got %s %s for %d bricks of %d)"
+                         % (values.dtype, tuple(values.shape), brick_ids.shape[0], brick))
+    if brick_ids.dtype != torch.int32 or slot_map.dtype != torch.int32 or brick_ids.dim() != 1:
+        raise NeddfError("marching_cubes_bricks: brick_ids [M] and slot_map must be int32")
+    ctx = Context.get(values.device)
+    if 2 <= brick <= 16 and min(int(n) for n in shape) >= 2:        # (otherwise the library reports what is wrong)
+        nb = ctx.brick_counts(shape, brick)
+        if tuple(slot_map.shape) != nb[::-1]:
+            raise NeddfError("marching_cubes_bricks: slot_map must be [nbz, nby, nbx] = %s (got %s)" % (nb[::-1], tuple(slot_map.shape)))
+    verts, tris, vkey, tkey = ctx.marching_cubes_bricks(values.contiguous(), brick_ids.contiguous(), slot_map.contiguous(), shape, brick,
+                                                        iso, lo, hi)
+    if not dense_order:
+        return verts, tris, vkey, tkey
+    return _dense_order(verts, tris, vkey, tkey)
+
+
+def _dense_order(verts, tris, vkey, tkey):
+    """Vertices sorted by their key, triangle corners renumbered, triangles sorted by theirs (the keys are unique)."""
+    order = torch.sort(vkey).indices
+    new_id = torch.empty(order.shape[0], device=order.device, dtype=torch.int32)
+    new_id[order] = torch.arange(order.shape[0], device=order.device, dtype=torch.int32)
+    tris = new_id[tris.long()] if tris.numel() else tris
+    return verts[order].contiguous(), tris[torch.sort(tkey).indices].contiguous()
+
+
 def vertex_normals(vertices, triangles):
     """Geometric vertex normals float32 [V, 3] of an indexed device mesh: the normalised, area-weighted sum of the incident
     triangles' cross products (p1 - p0) x (p2 - p0); a vertex whose sum vanishes gets (0, 0, 0).  Independent of timing
@@ -155,4 +215,4 @@ def write_ply(path, vertices, triangles, normals=None, colors=None):
     return path
 
 
-__all__ = ["marching_cubes", "vertex_normals", "connected_components", "compact_mesh", "remove_small_components", "write_ply"]
+__all__ = ["marching_cubes", "select_bricks", "marching_cubes_bricks", "vertex_normals", "connected_components", "compact_mesh", "remove_small_components", "write_ply"]

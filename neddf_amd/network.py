@@ -143,7 +143,8 @@ class BaseNeuralField(ABC, nn.Module):
 
     def extract_mesh(self, field_name: str = "distance", threshold: float = 0.0275, cube_range: float = 1.1,
                      resolution: int = 64, timings: Optional[Dict[str, float]] = None, normals=False, colors: bool = False,
-                     min_component_triangles: int = 0, keep_largest: int = 0):
+                     min_component_triangles: int = 0, keep_largest: int = 0, brick: int = 0, band: Optional[float] = None,
+                     lipschitz: float = 1.0, brick_dilate: int = 0):
         """Triangle mesh of the `threshold` level set of `field_name` in the cube [-cube_range, cube_range]^3 sampled at
         resolution^3 points -- the reference's generate_mesh (fields_visualizer.py:528-566: voxelize("distance", 1.1, 64),
         mcubes.marching_cubes(voxel, 0.0275)) with the grid evaluation and marching cubes on the GPU.
@@ -167,9 +168,28 @@ class BaseNeuralField(ABC, nn.Module):
         components with fewer triangles are dropped, and with keep_largest > 0 only that many of the largest stay.  It runs right
         after marching cubes, before normals and colours, so the field is never evaluated at a vertex that is thrown away.
         `timings` receives the stage's wall time ("clean") and what it did ("components", "components_kept",
-        "triangles_removed").  With both 0 nothing runs and the mesh is marching cubes' as it is."""
+        "triangles_removed").  With both 0 nothing runs and the mesh is marching cubes' as it is.
+
+        brick (not in the reference; 0 = off): sparse extraction in bricks of brick^3 cells, 2..16.  The field is first evaluated at
+        the brick corners only; a brick is kept when a corner is NaN, two corners lie on different sides of the threshold or one is
+        within `band` of it (mesh.select_bricks), grown by brick_dilate bricks; the field then runs on the kept bricks' lattice
+        points only and marching cubes over those bricks (mesh.marching_cubes_bricks).  Whenever the kept bricks hold every cell
+        the surface crosses, the mesh is the dense call's bit for bit, order included, and everything after it is unchanged.
+        band=None: lipschitz * half the brick's diagonal, which misses nothing of a field whose value changes by at most
+        `lipschitz` per unit length -- a distance or sdf is 1-Lipschitz where it is exact, a trained one only roughly (raise
+        `lipschitz` to be safer at the price of more bricks).  A density has no such bound: there `band` must be given.
+        `timings` receives "coarse" (corner evaluation and selection), "grid" and "mcubes" (the brick stages), and the counts
+        "bricks" (all bricks of the lattice) and "bricks_active"."""
         import time
-        from .mesh import _clean, marching_cubes, vertex_normals
+        from .mesh import _clean, marching_cubes, marching_cubes_bricks, select_bricks, vertex_normals
+        brick = int(brick)
+        if brick and not 2 <= brick <= 16:
+            raise ValueError("extract_mesh: brick must be 0 (dense) or lie in [2, 16] (got %r)" % (brick,))
+        if brick and band is None:
+            if field_name == "density":
+                raise ValueError("extract_mesh: a density has no Lipschitz bound, so sparse extraction of one needs an explicit band")
+            if not float(lipschitz) > 0.0:
+                raise ValueError("extract_mesh: lipschitz must be positive (got %r)" % (lipschitz,))
         if normals is True:
             normals = "field" if self._has_surface() else "geometric"
         if normals not in (False, None, "field", "geometric"):
@@ -184,10 +204,27 @@ class BaseNeuralField(ABC, nn.Module):
             ctx = Context.get(self.device)
             self.upload(ctx, self._slot)
             t0 = time.perf_counter()
-            vol = ctx.field_grid(self._slot, names[field_name], (resolution,) * 3, lo, hi)
+            t_coarse, n_bricks = 0.0, None
+            if brick:
+                shape = (int(resolution),) * 3
+                if band is None:
+                    h = 2.0 * float(cube_range) / (int(resolution) - 1) if int(resolution) > 1 else 0.0
+                    band = float(lipschitz) * 0.5 * brick * (3.0 * h * h) ** 0.5
+                coarse = ctx.field_grid_coarse(self._slot, names[field_name], shape, brick, lo, hi)
+                slot_map, brick_ids = select_bricks(coarse, float(threshold), float(band), brick_dilate)
+                n_bricks = (slot_map.numel(), brick_ids.shape[0])
+                torch.cuda.synchronize(self.device)
+                t_coarse = time.perf_counter() - t0
+                t0 += t_coarse
+                vol = ctx.field_bricks(self._slot, names[field_name], shape, brick, lo, hi, brick_ids)
+            else:
+                vol = ctx.field_grid(self._slot, names[field_name], (resolution,) * 3, lo, hi)
             torch.cuda.synchronize(self.device)
             t1 = time.perf_counter()
-            verts, tris = marching_cubes(vol, float(threshold), lo, hi)
+            if brick:
+                verts, tris = marching_cubes_bricks(vol, brick_ids, slot_map, shape, brick, float(threshold), lo, hi)
+            else:
+                verts, tris = marching_cubes(vol, float(threshold), lo, hi)
             if field_name == "density":                 # the object is above the threshold: turn the normals outward
                 tris = tris[:, [0, 2, 1]].contiguous()
             torch.cuda.synchronize(self.device)
@@ -224,6 +261,8 @@ class BaseNeuralField(ABC, nn.Module):
             t4 = time.perf_counter()
         if timings is not None:
             timings["grid"], timings["mcubes"] = t1 - t0, t_mc - t1
+            if n_bricks is not None:
+                timings["coarse"], timings["bricks"], timings["bricks_active"] = t_coarse, n_bricks[0], n_bricks[1]
             if cleaned is not None:
                 timings["clean"] = t2 - t_mc
                 timings.update(cleaned)

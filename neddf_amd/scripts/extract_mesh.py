@@ -1,5 +1,6 @@
 """`python neddf/scripts/extract_mesh.py <run_dir> [--epoch 2000] [--resolution 64] [--threshold 0.0275] [--field distance]
-[--cube-range 1.1] [--normals [field|geometric]] [--colors] [--min-component N] [--keep-largest [K]]` -- the reference's mesh export (neddf/scripts/fields_visualizer.py:528-566, generate_mesh: voxelize
+[--cube-range 1.1] [--normals [field|geometric]] [--colors] [--min-component N] [--keep-largest [K]] [--sparse [B]] [--band W]
+[--lipschitz L] [--brick-dilate D]` -- the reference's mesh export (neddf/scripts/fields_visualizer.py:528-566, generate_mesh: voxelize
 "distance" on a 64^3 cube of half-width 1.1, marching cubes at 0.0275, export) without its Open3D viewer.  The run is
 loaded as run_eval loads it (`<run_dir>/.hydra/config.yaml`, `models/model_{epoch:05}.pth`); the mesh of
 `trainer.neural_render.get_network()` is written to `<run_dir>/mesh/mesh_{resolution}_threshold{threshold}.ply` (the
@@ -9,7 +10,11 @@ own (NeDDF, NeuS; the default where the field has one) or geometric ones; --colo
 seen straight on (`property uchar red, green, blue`).  Without them the file is the plain positions-and-triangles PLY.
 --min-component N drops the connected components with fewer than N triangles and --keep-largest [K] all but the K (default 1)
 largest, on the device and before normals and colours; one more line then reports the components found and kept, the triangles
-removed and the clean-up time."""
+removed and the clean-up time.
+--sparse [B] (B = 8 when omitted) evaluates the field only on the bricks of B^3 cells that can hold the level set, picked from the
+field's values at the brick corners: a corner within --band of the threshold keeps a brick (default: --lipschitz, 1 when omitted,
+times half the brick's diagonal; a density needs an explicit --band), --brick-dilate grows the set.  The mesh and the file are the
+dense run's whenever no brick the surface crosses was left out; one more line reports the active and the total number of bricks."""
 from argparse import ArgumentParser
 from pathlib import Path
 
@@ -31,6 +36,11 @@ def build_parser() -> ArgumentParser:
     parser.add_argument("--min-component", type=int, default=0, metavar="N", help="drop connected components with fewer than N triangles")
     parser.add_argument("--keep-largest", type=int, nargs="?", const=1, default=0, metavar="K",
                         help="keep only the K largest connected components (K = 1 when omitted)")
+    parser.add_argument("--sparse", type=int, nargs="?", const=8, default=0, metavar="B",
+                        help="sparse extraction in bricks of B^3 cells, 2..16 (B = 8 when omitted)")
+    parser.add_argument("--band", type=float, default=None, help="a brick corner this close to the threshold keeps its brick")
+    parser.add_argument("--lipschitz", type=float, default=1.0, help="the default band is this times half the brick's diagonal")
+    parser.add_argument("--brick-dilate", type=int, default=0, metavar="D", help="grow the set of kept bricks by D bricks (0..4)")
     return parser
 
 
@@ -45,6 +55,8 @@ def main(argv=None) -> Path:
     clean = {}
     if args.min_component or args.keep_largest:
         clean = dict(min_component_triangles=args.min_component, keep_largest=args.keep_largest)
+    if args.sparse:
+        clean = dict(clean, brick=args.sparse, band=args.band, lipschitz=args.lipschitz, brick_dilate=args.brick_dilate)
     if args.normals or args.colors:
         want_n = True if args.normals == "auto" else (args.normals or False)
         res = list(network.extract_mesh(args.field, args.threshold, args.cube_range, args.resolution, timings=times,
@@ -63,7 +75,9 @@ def main(argv=None) -> Path:
         write_ply(path, verts, tris, normals=normals, colors=colors)
     print("vertices: %d, triangles: %d" % (verts.shape[0], tris.shape[0]))
     print("grid evaluation: %.3f s, marching cubes: %.3f s" % (times["grid"], times["mcubes"]))
-    if clean:
+    if args.sparse:
+        print("bricks: %d active of %d, corner evaluation and selection: %.3f s" % (times["bricks_active"], times["bricks"], times["coarse"]))
+    if "clean" in times:
         print("components: %d found, %d kept, triangles removed: %d, clean-up: %.3f s"
               % (times["components"], times["components_kept"], times["triangles_removed"], times["clean"]))
     print("wrote %s" % path)
