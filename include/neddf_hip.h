@@ -553,6 +553,68 @@ int neddf_render_rays_single_culled(neddf_ctx *ctx, int slot, const void *d_uv, 
  * reset != 0 zeroes them after reading. */
 int neddf_cull_stats(neddf_ctx *ctx, int64_t *h_samples, int64_t *h_kept, int reset);
 
+/* ---- sphere tracing (additive to ABI v7; no reference counterpart: the reference renders by volume integration only) ------
+ * Rays o + t d march through a distance field D towards the level set D = threshold: where the distance is d the ray may advance
+ * by step_scale * (d - threshold) without crossing it (exactly so for a 1-Lipschitz D and step_scale <= 1).  Per-ray state lives in
+ * flat DEVICE arrays of n_rays entries, owned by the caller:
+ *   d_t       float   current depth along the ray
+ *   d_t_lo    float   last depth at which the distance was still above the threshold
+ *   d_status  uint8   NEDDF_TRACE_*
+ *   d_steps   int32   advances taken
+ *   d_dist    float   last distance read
+ * Every floating-point step below is one rounded fp32 operation in the order written (no fused multiply-add):
+ * tests/trace_check.py restates all of it in numpy, bit for bit.  Compaction is count / scan / write launches with wave ballots, no
+ * atomics: no output depends on timing.  Every entry point: NEDDF_EINVAL for a negative count or a NULL array it needs,
+ * NEDDF_EUNSUPPORTED for n_rays >= 2^31 (indices are int32). */
+enum { NEDDF_TRACE_ACTIVE = 0,      /* still marching */
+       NEDDF_TRACE_HIT = 1,         /* reached the level set: D(t) <= threshold */
+       NEDDF_TRACE_MISS = 2,        /* t passed t_far */
+       NEDDF_TRACE_EXHAUSTED = 3,   /* still active after max_steps iterations */
+       NEDDF_TRACE_INVALID = 4 };   /* non-finite origin or direction, or a NaN distance */
+typedef struct {
+    float threshold;          /* the level set */
+    float t_near, t_far;      /* t_near < t_far */
+    float step_scale;         /* in (0, 1]; below 1 for a field that is not 1-Lipschitz */
+    float min_step;           /* > 0: the least advance */
+    int max_steps;            /* 1..4096 marching iterations */
+    int refine;               /* 0..32 bisection rounds on the HIT rays */
+} neddf_trace_params;
+/* t = t_lo = t_near, steps = 0, dist = NaN; status ACTIVE, or INVALID when a component of the ray's origin or direction is not finite. */
+int neddf_trace_begin(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, float t_near, float *d_t,
+                      float *d_t_lo, unsigned char *d_status, int32_t *d_steps, float *d_dist, void *stream);
+/* The ACTIVE rays in ascending order: their indices to d_index (int32) and their points pos = o + t * d to d_pos ([.,3]: the rounded
+ * product, then the rounded sum); both need room for n_rays rows.  *h_n_active (HOST) = M; synchronises `stream` once to read it. */
+int neddf_trace_compact(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_t,
+                        const unsigned char *d_status, int32_t *d_index, float *d_pos, int64_t *h_n_active, void *stream);
+/* One step of the rays r = d_index[k], k < n_active, from the distances d = d_distance[k] at their points, in this order:
+ *   dist[r] = d;  d NaN: INVALID;  d <= threshold: HIT (t and t_lo stay);  otherwise t_lo = t,
+ *   t = t + max(step_scale * (d - threshold), min_step), steps += 1, and MISS when !(t <= t_far).
+ * An index outside [0, n_rays) is ignored; the indices must be distinct (neddf_trace_compact's are). */
+int neddf_trace_advance(neddf_ctx *ctx, const int32_t *d_index, const float *d_distance, int64_t n_active, int64_t n_rays, float threshold,
+                        float step_scale, float min_step, float t_far, float *d_t, float *d_t_lo, unsigned char *d_status, int32_t *d_steps,
+                        float *d_dist, void *stream);
+/* ACTIVE -> EXHAUSTED: the relabelling after the last marching iteration. */
+int neddf_trace_finish(neddf_ctx *ctx, unsigned char *d_status, int64_t n_rays, void *stream);
+/* Refinement of the HIT rays with t_lo < t by bisection of [t_lo, t].  _points: their indices (ascending) and the points at
+ * mid = 0.5 * (t_lo + t), as neddf_trace_compact does for the ACTIVE rays (*h_n_points = M, one synchronise).  _update, with the
+ * distances at those points: d <= threshold or d NaN: t = mid, dist = d; otherwise t_lo = mid.  D(t) <= threshold < D(t_lo) holds
+ * after every round for a NaN-free field. */
+int neddf_trace_bisect_points(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_t,
+                              const float *d_t_lo, const unsigned char *d_status, int32_t *d_index, float *d_pos, int64_t *h_n_points,
+                              void *stream);
+int neddf_trace_bisect_update(neddf_ctx *ctx, const int32_t *d_index, const float *d_distance, int64_t n_points, int64_t n_rays,
+                              float threshold, float *d_t, float *d_t_lo, float *d_dist, void *stream);
+/* The whole loop on the distance (NeuS: sdf) of field slot `slot`: begin; at most max_steps iterations of compact -> field -> advance,
+ * ended early once no ray is ACTIVE; finish; at most `refine` rounds of bisect_points -> field -> bisect_update, ended early once no
+ * ray is left to refine.  The field is evaluated on the compacted points only, distance output alone (no colour kernel), dir = (1, 0, 0)
+ * and var = 0 as neddf_field_grid passes them, under the slot's operand policy, in chunks of at most 2^23 points.  *h_evaluations
+ * (HOST, may be NULL) = the number of points evaluated.  One synchronise of `stream` per iteration and per round (the host learns the
+ * number of rays left).  NEDDF_EINVAL unless t_near < t_far, 0 < step_scale <= 1, min_step > 0, 1 <= max_steps <= 4096 and
+ * 0 <= refine <= 32; NEDDF_EUNSUPPORTED for a NeRF field (no distance). */
+int neddf_trace_field(neddf_ctx *ctx, int slot, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays,
+                      const neddf_trace_params *params, float *d_t, float *d_t_lo, unsigned char *d_status, int32_t *d_steps, float *d_dist,
+                      int64_t *h_evaluations, void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -66,6 +66,12 @@ class Occupancy(C.Structure):
     _fields_ = [("d_bits", _vp), ("res", C.c_int), ("lo", C.c_float * 3), ("inv_cell", C.c_float * 3)]
 
 
+class TraceParams(C.Structure):
+    """neddf_trace_params: the constants of one sphere-tracing run (neddf_amd/trace.py validates and fills them)."""
+    _fields_ = [("threshold", C.c_float), ("t_near", C.c_float), ("t_far", C.c_float), ("step_scale", C.c_float),
+                ("min_step", C.c_float), ("max_steps", C.c_int), ("refine", C.c_int)]
+
+
 # every symbol include/neddf_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("neddf_abi_version", C.c_int, []),
@@ -144,6 +150,13 @@ SYMBOLS = [
                                                   C.POINTER(RenderParams), C.c_int, _vp, C.POINTER(RenderOutputs), _vp, _vp,
                                                   C.POINTER(Occupancy)]),
     ("neddf_cull_stats", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.c_int]),
+    ("neddf_trace_begin", C.c_int, [_vp, _vp, _vp, _i64, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_trace_compact", C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    ("neddf_trace_advance", C.c_int, [_vp, _vp, _vp, _i64, _i64, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_trace_finish", C.c_int, [_vp, _vp, _i64, _vp]),
+    ("neddf_trace_bisect_points", C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    ("neddf_trace_bisect_update", C.c_int, [_vp, _vp, _vp, _i64, _i64, C.c_float, _vp, _vp, _vp, _vp]),
+    ("neddf_trace_field", C.c_int, [_vp, C.c_int, _vp, _vp, _i64, C.POINTER(TraceParams), _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
 ]
 
 _lib = None
@@ -639,6 +652,85 @@ class Context:
         a, b = _i64(0), _i64(0)
         self.check(self.lib.neddf_cull_stats(self.h, C.byref(a), C.byref(b), int(bool(reset))))
         return int(a.value), int(b.value)
+
+    # ------------------------------------------------------------------ sphere tracing
+    def trace_state(self, n):
+        """Fresh per-ray state arrays on this device: dict t, t_lo, distance float32 [n], status uint8 [n], steps int32 [n]."""
+        f = dict(device=self.device, dtype=torch.float32)
+        return dict(t=torch.empty(n, **f), t_lo=torch.empty(n, **f), status=torch.empty(n, device=self.device, dtype=torch.uint8),
+                    steps=torch.empty(n, device=self.device, dtype=torch.int32), distance=torch.empty(n, **f))
+
+    @staticmethod
+    def _rays(origins, dirs, what):
+        require_device(origins, "ray origins")
+        require_device(dirs, "ray directions")
+        o, d = f32c(origins), f32c(dirs)
+        if o.dim() != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise NeddfError("%s: origins and directions [n, 3] expected (got %s, %s)" % (what, tuple(o.shape), tuple(d.shape)))
+        return o, d
+
+    def trace_begin(self, origins, dirs, t_near):
+        """The state of neddf_trace_begin for the rays origins / dirs [n, 3]."""
+        o, d = self._rays(origins, dirs, "trace_begin")
+        st = self.trace_state(o.shape[0])
+        self.check(self.lib.neddf_trace_begin(self.h, _ptr(o), _ptr(d), o.shape[0], float(t_near), _ptr(st["t"]), _ptr(st["t_lo"]),
+                                              _ptr(st["status"]), _ptr(st["steps"]), _ptr(st["distance"]), self.stream()))
+        return st
+
+    def trace_compact(self, origins, dirs, st):
+        """(index int32 [M], pos [M, 3]) of the ACTIVE rays, ascending (neddf_trace_compact; one stream synchronise)."""
+        o, d = self._rays(origins, dirs, "trace_compact")
+        n = o.shape[0]
+        index, pos = torch.empty(n, device=o.device, dtype=torch.int32), torch.empty(n, 3, device=o.device, dtype=torch.float32)
+        m = _i64(0)
+        self.check(self.lib.neddf_trace_compact(self.h, _ptr(o), _ptr(d), n, _ptr(st["t"]), _ptr(st["status"]), _ptr(index), _ptr(pos),
+                                                C.byref(m), self.stream()))
+        return index[:m.value], pos[:m.value]
+
+    @staticmethod
+    def _rows(index, distance, what):
+        require_device(index, "index")
+        require_device(distance, "distances")
+        D = f32c(distance).reshape(-1)
+        if index.dtype != torch.int32 or not index.is_contiguous() or index.dim() != 1 or D.shape[0] != index.shape[0]:
+            raise NeddfError("%s: index int32 [M] and distances [M] expected (got %s, %s)" % (what, tuple(index.shape), tuple(D.shape)))
+        return D
+
+    def trace_advance(self, index, distance, st, threshold, step_scale, min_step, t_far):
+        """One step of the rays index[k] from the distances distance[k] at their points (neddf_trace_advance); st changes in place."""
+        D = self._rows(index, distance, "trace_advance")
+        self.check(self.lib.neddf_trace_advance(self.h, _ptr(index), _ptr(D), index.shape[0], st["t"].shape[0], float(threshold), float(step_scale),
+                                                float(min_step), float(t_far), _ptr(st["t"]), _ptr(st["t_lo"]), _ptr(st["status"]),
+                                                _ptr(st["steps"]), _ptr(st["distance"]), self.stream()))
+
+    def trace_finish(self, st):
+        """ACTIVE -> EXHAUSTED (neddf_trace_finish)."""
+        self.check(self.lib.neddf_trace_finish(self.h, _ptr(st["status"]), st["status"].shape[0], self.stream()))
+
+    def trace_bisect_points(self, origins, dirs, st):
+        """(index int32 [M], pos [M, 3]) of the HIT rays with t_lo < t at 0.5 (t_lo + t) (neddf_trace_bisect_points; one synchronise)."""
+        o, d = self._rays(origins, dirs, "trace_bisect_points")
+        n = o.shape[0]
+        index, pos = torch.empty(n, device=o.device, dtype=torch.int32), torch.empty(n, 3, device=o.device, dtype=torch.float32)
+        m = _i64(0)
+        self.check(self.lib.neddf_trace_bisect_points(self.h, _ptr(o), _ptr(d), n, _ptr(st["t"]), _ptr(st["t_lo"]), _ptr(st["status"]),
+                                                      _ptr(index), _ptr(pos), C.byref(m), self.stream()))
+        return index[:m.value], pos[:m.value]
+
+    def trace_bisect_update(self, index, distance, st, threshold):
+        """One bisection round from the distances at trace_bisect_points' points (neddf_trace_bisect_update); st changes in place."""
+        D = self._rows(index, distance, "trace_bisect_update")
+        self.check(self.lib.neddf_trace_bisect_update(self.h, _ptr(index), _ptr(D), index.shape[0], st["t"].shape[0], float(threshold),
+                                                      _ptr(st["t"]), _ptr(st["t_lo"]), _ptr(st["distance"]), self.stream()))
+
+    def trace_field(self, slot, origins, dirs, params):
+        """The whole loop in the library on the distance of the field in `slot` (neddf_trace_field): (state dict, evaluations)."""
+        o, d = self._rays(origins, dirs, "trace_field")
+        st = self.trace_state(o.shape[0])
+        ev = _i64(0)
+        self.check(self.lib.neddf_trace_field(self.h, slot, _ptr(o), _ptr(d), o.shape[0], C.byref(params), _ptr(st["t"]), _ptr(st["t_lo"]),
+                                              _ptr(st["status"]), _ptr(st["steps"]), _ptr(st["distance"]), C.byref(ev), self.stream()))
+        return st, int(ev.value)
 
     # ----------------------------------------------------------- stand-alone ops
     def op_activation(self, op, x, J=None):

@@ -296,6 +296,30 @@ void launch_occ_gather(const unsigned char *keep, const float *pos, const float 
 void launch_occ_scatter(const int32_t *index, int64_t m, int64_t n, const float *cdens, const float *ccol, const float *cnrm, float *dens,
                         float *col, float *nrm, hipStream_t s);
 
+// Sphere tracing (trace_kernels.hip): per-ray state in flat arrays -- t, t_lo, dist float [n], status uint8 [n], steps int32 [n].
+enum { kTraceActive = 0, kTraceHit = 1, kTraceMiss = 2, kTraceExhausted = 3, kTraceInvalid = 4 };
+struct TraceState {
+    float *t, *t_lo, *dist;
+    unsigned char *status;
+    int32_t *steps;
+};
+// t = t_lo = t_near, steps = 0, dist = NaN, status ACTIVE (INVALID for a non-finite origin or direction component)
+void launch_trace_begin(const float *ro, const float *rd, int64_t n, float t_near, const TraceState &st, hipStream_t s);
+// Order-preserving compaction of the selected rays: bisect == 0 the ACTIVE ones at depth t, bisect != 0 the HIT ones with t_lo < t at
+// depth 0.5 (t_lo + t).  index [n] int32, pos [n, 3] = o + depth * d (a rounded product, then a rounded sum);
+// blk [occ_blocks(n) + 1], blk[occ_blocks(n)] = the number of selected rays afterwards
+void launch_trace_compact(const float *ro, const float *rd, int64_t n, const TraceState &st, int bisect, int64_t *blk, int32_t *index,
+                          float *pos, hipStream_t s);
+// one sphere-tracing step of rays index[k] < n with the distances D[k], k < m
+void launch_trace_advance(const int32_t *index, const float *D, int64_t m, int64_t n, float threshold, float step_scale, float min_step,
+                          float t_far, const TraceState &st, hipStream_t s);
+// one bisection round of rays index[k] < n with the distances D[k] at their midpoints, k < m
+void launch_trace_bisect_update(const int32_t *index, const float *D, int64_t m, int64_t n, float threshold, const TraceState &st, hipStream_t s);
+// ACTIVE -> EXHAUSTED
+void launch_trace_finish(unsigned char *status, int64_t n, hipStream_t s);
+// dir = (1, 0, 0), var = 0 for n rows: the constant field inputs of a distance-only evaluation
+void launch_trace_unit_inputs(float *dir, float *var, int64_t n, hipStream_t s);
+
 void launch_linear_grad(const float *x, const float *J, int64_t n, int cin, int ldx, int cout_block, int ksteps, const float *wp,
                         const float *bias, float *y, float *G, int ldo, int nvalid, int accumulate, int grid, hipStream_t s);
 void launch_op_activation(int kind, const float *x, const float *J, int64_t N, int C, float *y, float *G, hipStream_t s);

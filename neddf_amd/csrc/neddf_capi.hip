@@ -760,7 +760,7 @@ void neddf_destroy(neddf_ctx *ctx)
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack, &ctx->ttmp, &ctx->tamax,
                       &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc,
                       &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk, &ctx->occ_cells, &ctx->occ_blk,
-                      &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase })
+                      &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase, &ctx->trace_blk, &ctx->trace_ws })
         if (b->p) (void)hipFree(b->base ? b->base : b->p);
     for (auto &e : ctx->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : ctx->pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -781,7 +781,7 @@ int neddf_debug_check_guards(neddf_ctx *ctx, int64_t *n_bands, int64_t *n_bad_by
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack,
                        &ctx->ttmp, &ctx->tamax, &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc,
                       &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk, &ctx->occ_cells, &ctx->occ_blk,
-                      &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase })
+                      &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase, &ctx->trace_blk, &ctx->trace_ws })
         if (b->base) {
             bands.push_back(GuardBand{ b->base, kGuardBytes });
             bands.push_back(GuardBand{ (char *)b->p + b->cap, kGuardBytes });
@@ -1781,6 +1781,176 @@ int neddf_occupancy_scatter(neddf_ctx *ctx, const int32_t *d_index, int64_t n_ke
     if (d_normal && n_points) HIPCHK(hipMemsetAsync(d_normal, 0, (size_t)n_points * 3 * sizeof(float), s));
     launch_occ_scatter(d_index, n_kept, n_points, d_c_density, d_c_color, d_c_normal, d_density, d_color, d_normal, s);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- sphere tracing (trace_kernels.hip) ----
+static TraceState trace_state(const float *t, const float *t_lo, const unsigned char *status, const int32_t *steps, const float *dist)
+{
+    return TraceState{ (float *)t, (float *)t_lo, (float *)dist, (unsigned char *)status, (int32_t *)steps };
+}
+
+static int trace_count_ok(neddf_ctx *ctx, int64_t n, const char *what)
+{
+    if (n < 0) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": negative count");
+    if (n >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, std::string(what) + ": 2^31 rays or more (indices are int32)");
+    return 0;
+}
+
+// selected rays -> index + points; *m = their number (one stream synchronise)
+static int trace_compact(neddf_ctx *ctx, const float *ro, const float *rd, int64_t n, const TraceState &st, int bisect, int32_t *index, float *pos,
+                         int64_t *m, hipStream_t s)
+{
+    *m = 0;
+    if (n == 0) return 0;
+    if (int rc = ensure(ctx, ctx->trace_blk, (size_t)(occ_blocks(n) + 1) * sizeof(int64_t))) return rc;
+    int64_t *blk = (int64_t *)ctx->trace_blk.p;
+    launch_trace_compact(ro, rd, n, st, bisect, blk, index, pos, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(m, blk + occ_blocks(n), sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int neddf_trace_begin(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, float t_near, float *d_t, float *d_t_lo,
+                      unsigned char *d_status, int32_t *d_steps, float *d_dist, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = trace_count_ok(ctx, n_rays, "trace_begin")) return rc;
+    if (n_rays == 0) return 0;
+    if (!d_ray_orig || !d_ray_dir || !d_t || !d_t_lo || !d_status || !d_steps || !d_dist) return fail(ctx, NEDDF_EINVAL, "trace_begin: NULL rays or state");
+    DeviceGuard guard_(ctx->device);
+    launch_trace_begin(d_ray_orig, d_ray_dir, n_rays, t_near, trace_state(d_t, d_t_lo, d_status, d_steps, d_dist), (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_trace_compact(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_t,
+                        const unsigned char *d_status, int32_t *d_index, float *d_pos, int64_t *h_n_active, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!h_n_active) return fail(ctx, NEDDF_EINVAL, "trace_compact: NULL count");
+    if (int rc = trace_count_ok(ctx, n_rays, "trace_compact")) return rc;
+    *h_n_active = 0;
+    if (n_rays == 0) return 0;
+    if (!d_ray_orig || !d_ray_dir || !d_t || !d_status || !d_index || !d_pos) return fail(ctx, NEDDF_EINVAL, "trace_compact: NULL rays, state or outputs");
+    DeviceGuard guard_(ctx->device);
+    return trace_compact(ctx, d_ray_orig, d_ray_dir, n_rays, trace_state(d_t, nullptr, d_status, nullptr, nullptr), 0, d_index, d_pos, h_n_active,
+                         (hipStream_t)stream);
+}
+
+int neddf_trace_advance(neddf_ctx *ctx, const int32_t *d_index, const float *d_distance, int64_t n_active, int64_t n_rays, float threshold,
+                        float step_scale, float min_step, float t_far, float *d_t, float *d_t_lo, unsigned char *d_status, int32_t *d_steps,
+                        float *d_dist, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = trace_count_ok(ctx, n_rays, "trace_advance")) return rc;
+    if (n_active < 0 || n_active > n_rays) return fail(ctx, NEDDF_EINVAL, "trace_advance: 0 <= n_active <= n_rays expected");
+    if (n_active == 0) return 0;
+    if (!d_index || !d_distance || !d_t || !d_t_lo || !d_status || !d_steps || !d_dist) return fail(ctx, NEDDF_EINVAL, "trace_advance: NULL index, distances or state");
+    DeviceGuard guard_(ctx->device);
+    launch_trace_advance(d_index, d_distance, n_active, n_rays, threshold, step_scale, min_step, t_far,
+                         trace_state(d_t, d_t_lo, d_status, d_steps, d_dist), (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_trace_finish(neddf_ctx *ctx, unsigned char *d_status, int64_t n_rays, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = trace_count_ok(ctx, n_rays, "trace_finish")) return rc;
+    if (n_rays == 0) return 0;
+    if (!d_status) return fail(ctx, NEDDF_EINVAL, "trace_finish: NULL status");
+    DeviceGuard guard_(ctx->device);
+    launch_trace_finish(d_status, n_rays, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_trace_bisect_points(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_t, const float *d_t_lo,
+                              const unsigned char *d_status, int32_t *d_index, float *d_pos, int64_t *h_n_points, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!h_n_points) return fail(ctx, NEDDF_EINVAL, "trace_bisect_points: NULL count");
+    if (int rc = trace_count_ok(ctx, n_rays, "trace_bisect_points")) return rc;
+    *h_n_points = 0;
+    if (n_rays == 0) return 0;
+    if (!d_ray_orig || !d_ray_dir || !d_t || !d_t_lo || !d_status || !d_index || !d_pos)
+        return fail(ctx, NEDDF_EINVAL, "trace_bisect_points: NULL rays, state or outputs");
+    DeviceGuard guard_(ctx->device);
+    return trace_compact(ctx, d_ray_orig, d_ray_dir, n_rays, trace_state(d_t, d_t_lo, d_status, nullptr, nullptr), 1, d_index, d_pos, h_n_points,
+                         (hipStream_t)stream);
+}
+
+int neddf_trace_bisect_update(neddf_ctx *ctx, const int32_t *d_index, const float *d_distance, int64_t n_points, int64_t n_rays, float threshold,
+                              float *d_t, float *d_t_lo, float *d_dist, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = trace_count_ok(ctx, n_rays, "trace_bisect_update")) return rc;
+    if (n_points < 0 || n_points > n_rays) return fail(ctx, NEDDF_EINVAL, "trace_bisect_update: 0 <= n_points <= n_rays expected");
+    if (n_points == 0) return 0;
+    if (!d_index || !d_distance || !d_t || !d_t_lo || !d_dist) return fail(ctx, NEDDF_EINVAL, "trace_bisect_update: NULL index, distances or state");
+    DeviceGuard guard_(ctx->device);
+    launch_trace_bisect_update(d_index, d_distance, n_points, n_rays, threshold, trace_state(d_t, d_t_lo, nullptr, nullptr, d_dist), (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_trace_field(neddf_ctx *ctx, int slot, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const neddf_trace_params *p,
+                      float *d_t, float *d_t_lo, unsigned char *d_status, int32_t *d_steps, float *d_dist, int64_t *h_evaluations, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (!p) return fail(ctx, NEDDF_EINVAL, "trace_field: NULL parameters");
+    if (int rc = trace_count_ok(ctx, n_rays, "trace_field")) return rc;
+    if (!(p->t_near < p->t_far)) return fail(ctx, NEDDF_EINVAL, "trace_field: t_near < t_far expected");
+    if (!(p->step_scale > 0.f && p->step_scale <= 1.f)) return fail(ctx, NEDDF_EINVAL, "trace_field: step_scale must lie in (0, 1]");
+    if (!(p->min_step > 0.f)) return fail(ctx, NEDDF_EINVAL, "trace_field: min_step must be positive");
+    if (p->max_steps < 1 || p->max_steps > 4096) return fail(ctx, NEDDF_EINVAL, "trace_field: max_steps must lie in [1, 4096]");
+    if (p->refine < 0 || p->refine > 32) return fail(ctx, NEDDF_EINVAL, "trace_field: refine must lie in [0, 32]");
+    if (slot < 0 || slot >= NEDDF_NUM_SLOTS || !ctx->field[slot].valid) return fail(ctx, NEDDF_ENOFIELD, "no field in slot");
+    if (ctx->field[slot].d.kind == NEDDF_FIELD_NERF) return fail(ctx, NEDDF_EUNSUPPORTED, "trace_field: a NeRF field has no distance to trace");
+    if (h_evaluations) *h_evaluations = 0;
+    if (n_rays == 0) return 0;
+    if (!d_ray_orig || !d_ray_dir || !d_t || !d_t_lo || !d_status || !d_steps || !d_dist) return fail(ctx, NEDDF_EINVAL, "trace_field: NULL rays or state");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    // workspace: index [n], points [n, 3], distances [n], and dir / var of one field chunk (at most 2^23 points, the field kernels' launch size)
+    const int64_t chunk = n_rays < ((int64_t)1 << 23) ? n_rays : ((int64_t)1 << 23);
+    const size_t bytes = carve_bytes((size_t)n_rays) * 2 + carve_bytes((size_t)n_rays * 3) + 2 * carve_bytes((size_t)chunk * 3);
+    if (int rc = ensure(ctx, ctx->trace_ws, bytes)) return rc;
+    Carver cv{ (char *)ctx->trace_ws.p };          // (no bands between the carves: the block's own two stand at its ends)
+    int32_t *index = (int32_t *)cv.take((size_t)n_rays);
+    float *D = cv.take((size_t)n_rays), *pos = cv.take((size_t)n_rays * 3), *dir = cv.take((size_t)chunk * 3), *var = cv.take((size_t)chunk * 3);
+    launch_trace_unit_inputs(dir, var, chunk, s);
+    const TraceState st = trace_state(d_t, d_t_lo, d_status, d_steps, d_dist);
+    launch_trace_begin(d_ray_orig, d_ray_dir, n_rays, p->t_near, st, s);
+    HIPCHK(hipGetLastError());
+    int64_t evaluations = 0;
+    auto distances = [&](int64_t M) -> int {        // the field on the M compacted points, distance output only: no colour kernel runs
+        for (int64_t off = 0; off < M; off += chunk) {
+            const int64_t n = M - off < chunk ? M - off : chunk;
+            if (int rc = field_forward(ctx, slot, pos + off * 3, dir, var, n, NEDDF_OUT_MINIMAL, D + off, nullptr, nullptr, nullptr, nullptr, s)) return rc;
+        }
+        evaluations += M;
+        return 0;
+    };
+    for (int it = 0; it < p->max_steps; ++it) {
+        int64_t M = 0;
+        if (int rc = trace_compact(ctx, d_ray_orig, d_ray_dir, n_rays, st, 0, index, pos, &M, s)) return rc;
+        if (M == 0) break;
+        if (int rc = distances(M)) return rc;
+        launch_trace_advance(index, D, M, n_rays, p->threshold, p->step_scale, p->min_step, p->t_far, st, s);
+    }
+    launch_trace_finish(d_status, n_rays, s);
+    for (int round = 0; round < p->refine; ++round) {
+        int64_t M = 0;
+        if (int rc = trace_compact(ctx, d_ray_orig, d_ray_dir, n_rays, st, 1, index, pos, &M, s)) return rc;
+        if (M == 0) break;
+        if (int rc = distances(M)) return rc;
+        launch_trace_bisect_update(index, D, M, n_rays, p->threshold, st, s);
+    }
+    HIPCHK(hipGetLastError());
+    if (h_evaluations) *h_evaluations = evaluations;
     return 0;
 }
 

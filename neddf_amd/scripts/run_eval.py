@@ -48,7 +48,42 @@ def build_parser() -> ArgumentParser:
                         help="skip empty space: build an R^3 occupancy grid (default 128) from the loaded networks and render through "
                              "the culled entry points (not a reference option; world-space rays; prints the occupied fraction and "
                              "kept / total samples)")
+    parser.add_argument("--trace", type=float, default=None, metavar="THRESHOLD",
+                        help="also render every view by sphere tracing the distance field to this level set (extract_mesh's threshold; "
+                             "0.0275 for the shipped bunny) and write {id:03}_rgb_traced.png / _depth_traced.png (and _normal_traced.png "
+                             "with --normals) next to the usual images; prints hit share, mean advances per ray and milliseconds per "
+                             "view (not a reference option; NeDDF and NeuS fields, world-space rays, rank 0's device)")
+    parser.add_argument("--trace-steps", type=int, default=64, metavar="N", help="marching iterations of --trace (default 64)")
     return parser
+
+
+def render_traced(trainer, save_dir: Path, threshold: float, max_steps: int, normals: bool) -> None:
+    """Every test view through NeRFRender.render_image_traced: the images with a _traced suffix and one line per view."""
+    import time
+
+    import numpy as np
+
+    from neddf_amd.trainer import imwrite_bgr
+    trainer.neural_render.set_iter(-1)
+    targets = ["color", "depth", "transmittance", "steps"] + (["normal"] if normals else [])
+    for camera_id in range(len(trainer.dataset)):
+        camera = trainer.cameras[camera_id]
+        camera.update_transform()
+        h, w = trainer.dataset[camera_id]["rgb_images"].shape[:2]
+        torch.cuda.synchronize(trainer.device)
+        t0 = time.perf_counter()
+        images = trainer.neural_render.render_image_traced(w, h, camera, targets, threshold, max_steps=max_steps)
+        torch.cuda.synchronize(trainer.device)
+        ms = 1e3 * (time.perf_counter() - t0)
+        rgb = torch.clamp(images["color"] * 255, 0, 255).cpu().numpy().astype(np.uint8)
+        depth = torch.clamp((images["depth"] - 2.0) / 4.0 * 50000 / 256, 0, 255).cpu().numpy().astype(np.uint8)
+        imwrite_bgr(save_dir / "{:03}_rgb_traced.png".format(camera_id), rgb)
+        imwrite_bgr(save_dir / "{:03}_depth_traced.png".format(camera_id), depth)
+        if normals:
+            nrm = torch.clamp((images["normal"] * 0.5 + 0.5) * 255, 0, 255).cpu().numpy().astype(np.uint8)
+            imwrite_bgr(save_dir / "{:03}_normal_traced.png".format(camera_id), np.ascontiguousarray(nrm[:, :, ::-1]))
+        print("traced camera {}: hit share {:.4f}, mean advances per ray {:.2f}, {:.1f} ms".format(
+            camera_id, 1.0 - float(images["transmittance"].mean()), float(images["steps"].float().mean()), ms))
 
 
 def main(argv=None) -> None:
@@ -93,6 +128,8 @@ def main(argv=None) -> None:
         trainer.render_all(save_dir, normals=True)
     else:
         trainer.render_all(save_dir)
+    if args.trace is not None and rank == 0:
+        render_traced(trainer, save_dir, args.trace, args.trace_steps, args.normals)
     if args.skip_empty is not None:
         samples, kept = Context.get(grid.device).cull_stats()
         print("skip-empty: rank %d evaluated %d of %d samples (%.2f %%)" % (rank, kept, samples, 100.0 * kept / max(samples, 1)))
