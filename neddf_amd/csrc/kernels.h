@@ -204,10 +204,9 @@ struct McGrid {
 };
 static inline int64_t mc_blocks(int64_t n) { return (n + kMcThreads - 1) / kMcThreads; }
 void launch_grid_points(const McGrid &g, int64_t first, int64_t n, float *pos, float *dir, float *var, hipStream_t s);
-// per-block vertex / triangle totals (vblk / tblk [mc_blocks(n) + 1]) and the crossed-edge byte of every lattice point
+// per-block vertex / triangle totals (vblk / tblk [mc_blocks(n) + 1]) and the crossed-edge byte of every lattice point;
+// launch_scan_totals on each turns them into block bases, [mc_blocks(n)] = the vertex / triangle count of the mesh
 void launch_mc_count(const McGrid &g, unsigned char *mask, int64_t *vblk, int64_t *tblk, hipStream_t s);
-// block totals -> exclusive block bases in place; [nblocks] = the vertex / triangle count of the mesh
-void launch_mc_scan(int64_t *vblk, int64_t *tblk, int64_t nblocks, hipStream_t s);
 void launch_mc_vertices(const McGrid &g, const unsigned char *mask, const int64_t *vblk, int32_t *vbase, float *vertices, hipStream_t s);
 void launch_mc_triangles(const McGrid &g, const unsigned char *mask, const int64_t *tblk, const int32_t *vbase, int32_t *tris,
                          hipStream_t s);
@@ -222,8 +221,12 @@ constexpr int kCcMaxRounds = 256;        // neddf_mesh_components gives up (NEDD
 void launch_cc_init(int32_t *parent, unsigned char *used, int64_t V, const int32_t *tris, int64_t T, hipStream_t s);
 // one round: hook (per triangle, atomicMin) and one pointer jump (per vertex); *changed is set when either did anything
 void launch_cc_round(int32_t *parent, int64_t V, const int32_t *tris, int64_t T, int *changed, hipStream_t s);
-// single array, one workgroup: a[0..n) -> exclusive prefix sums in place, a[n] = the total
+// one workgroup: a[0..n) -> exclusive prefix sums in place, a[n] = the total: the block totals of every count kernel (block_scan.h)
+// -> block bases, the grand total behind them
 void launch_scan_totals(int64_t *a, int64_t n, hipStream_t s);
+// Chebyshev dilation by d cells of an [nz][ny][nx] byte grid held in a (b: as large, scratch): one launch per axis, each clipped to
+// the grid.  Returns the buffer that holds the result (a itself for d <= 0).
+const unsigned char *launch_dilate(unsigned char *a, unsigned char *b, int nx, int ny, int nz, int d, hipStream_t s);
 // roots (parent[v] == v, used) -> dense labels in vertex order; vertex / triangle labels and the triangle count of every component.
 // blk: [mc_blocks(V) + 1], blk[mc_blocks(V)] = the number of components afterwards
 void launch_cc_labels(const int32_t *parent, const unsigned char *used, int64_t V, const int32_t *tris, int64_t T, int64_t *blk,
@@ -265,7 +268,7 @@ void launch_brick_select(const float *coarse, int nbx, int nby, int nbz, float i
                          unsigned char *flag_b, int64_t *blk, int32_t *slot_map, int32_t *ids, hipStream_t s);
 // *bad = 1 unless ids is strictly ascending inside [0, nb) and slot_map is exactly its inverse (-1 elsewhere)
 void launch_brick_check(const BrickMesh &k, int *bad, hipStream_t s);
-// mask [M][P]: the crossed edges each brick lattice point OWNS; vblk / tblk [M + 1]: per-brick vertex / triangle totals (launch_mc_scan next)
+// mask [M][P]: the crossed edges each brick lattice point OWNS; vblk / tblk [M + 1]: per-brick vertex / triangle totals (launch_scan_totals next)
 void launch_brick_mc_count(const BrickMesh &k, unsigned char *mask, int64_t *vblk, int64_t *tblk, hipStream_t s);
 void launch_brick_mc_vertices(const BrickMesh &k, const unsigned char *mask, const int64_t *vblk, int32_t *vbase, float *vertices,
                               int64_t *vertex_key, hipStream_t s);
@@ -274,7 +277,7 @@ void launch_brick_mc_triangles(const BrickMesh &k, const unsigned char *mask, co
 
 // Empty-space skipping (occupancy_kernels.hip): an R^3 bitfield over the box lo .. hi, bit (z R + y) R + x of cell (x, y, z) in
 // 32-bit words; classification of sample points against it and order-preserving compaction of the kept ones.
-constexpr int kOccThreads = 1024;        // points per workgroup of the count / gather kernels (16 waves: ballot + popcount offsets)
+constexpr int kOccThreads = 1024;        // points per workgroup of the count / gather kernels (16 waves: block_rank offsets)
 constexpr int kOccMaxRes = 1024, kOccMaxDilate = 4;
 struct OccGrid {
     const uint32_t *bits;

@@ -4,7 +4,7 @@
 //   grid_points_kernel   the lattice of neddf_field_grid: np.linspace coordinates per axis, x fastest
 //   mc_count_kernel      per lattice point: which of the three edges it owns are crossed (one byte); per block: vertex and
 //                        triangle totals
-//   mc_scan_kernel       one workgroup: exclusive scans of the block totals (in place, the grand totals behind them)
+//   scan_totals_kernel   one workgroup: exclusive scan of an array of block totals (in place, the grand total behind them)
 //   mc_vertex_kernel     per point: its first vertex id (block scan + block base), the vertices of its crossed edges
 //   mc_triangle_kernel   per cell: its first triangle id (block scan + block base), the triangles of its case
 //   mesh_normal_*        geometric vertex normals of an indexed mesh: area-weighted sums of the incident triangles' cross products,
@@ -12,10 +12,11 @@
 //   cc_*                 connected components of an indexed mesh: union-find with atomicMin hooks and pointer jumps, dense labels
 //   compact_*            order-preserving removal of triangles and of the vertices nothing references any more
 //
-// Placement is decided by count -> scan -> write launches only: no atomics, no exchange between workgroups inside a launch,
-// so the output is the same on every run (tests/mesh_check.py restates it in numpy bit for bit).  A corner is inside when
+// Placement is decided by count -> scan -> write launches only (block_scan.h): no atomics, no exchange between workgroups inside
+// a launch, so the output is the same on every run (tests/mesh_check.py restates it in numpy bit for bit).  A corner is inside when
 // value < iso; NaN compares false and is outside.  A vertex on an edge with a NaN end (t = NaN) sits at the edge's middle.
 #include "kernels.h"
+#include "block_scan.h"
 #include "mc_tables.h"
 
 namespace neddf {
@@ -28,6 +29,13 @@ __device__ __forceinline__ float lattice_coord(double lo, double hi, int n, int 
     return (float)(lo + (double)i * step);
 }
 
+// the constant inputs of a point that is evaluated for its position alone (base_neuralfield.py:49-79): dir (1, 0, 0), var 0
+__device__ __forceinline__ void unit_inputs(int64_t q, float *dir, float *var)
+{
+    dir[3 * q + 0] = 1.f; dir[3 * q + 1] = 0.f; dir[3 * q + 2] = 0.f;
+    var[3 * q + 0] = 0.f; var[3 * q + 1] = 0.f; var[3 * q + 2] = 0.f;
+}
+
 __global__ void __launch_bounds__(kMcThreads) grid_points_kernel(McGrid g, int64_t first, int64_t n, float *pos, float *dir, float *var)
 {
     const int64_t q = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
@@ -37,27 +45,7 @@ __global__ void __launch_bounds__(kMcThreads) grid_points_kernel(McGrid g, int64
     pos[3 * q + 0] = lattice_coord(g.lo[0], g.hi[0], g.nx, i);
     pos[3 * q + 1] = lattice_coord(g.lo[1], g.hi[1], g.ny, j);
     pos[3 * q + 2] = lattice_coord(g.lo[2], g.hi[2], g.nz, k);
-    dir[3 * q + 0] = 1.f; dir[3 * q + 1] = 0.f; dir[3 * q + 2] = 0.f;          // base_neuralfield.py:49-79: dir (1, 0, 0), var 0
-    var[3 * q + 0] = 0.f; var[3 * q + 1] = 0.f; var[3 * q + 2] = 0.f;
-}
-
-// exclusive scan of one value per thread over the workgroup; *total = the sum of all
-template <typename T>
-__device__ T block_exclusive_scan(T v, T *lds, T *total)
-{
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (int d = 1; d < (int)blockDim.x; d <<= 1) {
-        const T add = t >= d ? lds[t - d] : (T)0;
-        __syncthreads();
-        lds[t] += add;
-        __syncthreads();
-    }
-    const T incl = lds[t];
-    *total = lds[blockDim.x - 1];
-    __syncthreads();                // lds may be reused by the caller's next scan
-    return incl - v;
+    unit_inputs(q, dir, var);
 }
 
 __device__ __forceinline__ bool inside(float v, float iso) { return v < iso; }
@@ -72,16 +60,18 @@ __device__ __forceinline__ int point_mask(const McGrid &g, int64_t p, int i, int
     return m;
 }
 
-// case index of the cell whose corner 0 is lattice point p (Bourke's corner numbering, mc_tables.h)
-__device__ __forceinline__ int cell_case(const McGrid &g, int64_t p)
+// case index of the cell whose corner 0 is v[0], in values with strides 1 / sy / sz (Bourke's corner numbering, mc_tables.h)
+template <typename I> __device__ __forceinline__ int cell_case(const float *v, I sy, I sz, float iso)
 {
-    const int64_t sx = 1, sy = g.nx, sz = (int64_t)g.nx * g.ny;
-    const int64_t off[8] = { 0, sx, sx + sy, sy, sz, sx + sz, sx + sy + sz, sy + sz };
+    const I sx = 1;
+    const I off[8] = { 0, sx, sx + sy, sy, sz, sx + sz, sx + sy + sz, sy + sz };
     int c = 0;
 #pragma unroll
-    for (int b = 0; b < 8; ++b) c |= inside(g.vol[p + off[b]], g.iso) << b;
+    for (int b = 0; b < 8; ++b) c |= inside(v[off[b]], iso) << b;
     return c;
 }
+
+__device__ __forceinline__ int dense_cell_case(const McGrid &g, int64_t p) { return cell_case(g.vol + p, (int64_t)g.nx, (int64_t)g.nx * g.ny, g.iso); }
 
 __device__ __forceinline__ int case_triangles(int c)
 {
@@ -90,9 +80,46 @@ __device__ __forceinline__ int case_triangles(int c)
     return n;
 }
 
+// The vertices of the crossed edges `m` (bit a: the edge along axis a) of the fine lattice point idx[], written at ids id, id + 1, ...
+// in axis order.  v0 = the point's value, next(a) = the value one step along axis a; vertex_key (or NULL) receives 3 p + a.
+template <typename Next>
+__device__ __forceinline__ void edge_vertices(const McGrid &g, const int idx[3], int m, float v0, Next next, int64_t id, float *vertices,
+                                              int64_t *vertex_key)
+{
+    const int dim[3] = { g.nx, g.ny, g.nz };
+    const float c[3] = { lattice_coord(g.lo[0], g.hi[0], g.nx, idx[0]), lattice_coord(g.lo[1], g.hi[1], g.ny, idx[1]),
+                         lattice_coord(g.lo[2], g.hi[2], g.nz, idx[2]) };
+    const int64_t p = ((int64_t)idx[2] * g.ny + idx[1]) * g.nx + idx[0];
+    for (int a = 0; a < 3; ++a) {
+        if (!(m >> a & 1)) continue;
+        const float v1 = next(a);
+        float t = (g.iso - v0) / (v1 - v0);
+        if (t != t) t = 0.5f;
+        const float g0 = c[a], g1 = lattice_coord(g.lo[a], g.hi[a], dim[a], idx[a] + 1);
+        float out[3] = { c[0], c[1], c[2] };
+        out[a] = g0 + t * (g1 - g0);
+        vertices[3 * id + 0] = out[0];
+        vertices[3 * id + 1] = out[1];
+        vertices[3 * id + 2] = out[2];
+        if (vertex_key) vertex_key[id] = 3 * p + a;
+        ++id;
+    }
+}
+
+// The vertex id of one triangle corner.  own (kMcEdgeOwner): the corner's edge runs along axis own >> 3 from the cell's point at offset
+// (own & 1, own >> 1 & 1, own >> 2 & 1); point(dx, dy, dz, axis) = where that point's entries of vbase / mask are.  The id is the point's
+// first vertex plus its crossed edges of lower axis.
+template <typename Point>
+__device__ __forceinline__ int32_t corner_vertex(int own, const int32_t *vbase, const unsigned char *mask, Point point)
+{
+    const int axis = own >> 3;
+    const int64_t q = point(own & 1, (own >> 1) & 1, (own >> 2) & 1, axis);
+    return vbase[q] + (int32_t)__popc(mask[q] & ((1 << axis) - 1));
+}
+
 __global__ void __launch_bounds__(kMcThreads) mc_count_kernel(McGrid g, unsigned char *mask, int64_t *vblk, int64_t *tblk)
 {
-    __shared__ int lds[kMcThreads];
+    __shared__ int lds[kMcThreads / 64];
     const int64_t p = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
     int nv = 0, nt = 0;
     if (p < g.n) {
@@ -100,29 +127,10 @@ __global__ void __launch_bounds__(kMcThreads) mc_count_kernel(McGrid g, unsigned
         const int m = point_mask(g, p, i, j, k);
         mask[p] = (unsigned char)m;
         nv = (int)__popc(m);
-        if (i + 1 < g.nx && j + 1 < g.ny && k + 1 < g.nz) nt = case_triangles(cell_case(g, p));
+        if (i + 1 < g.nx && j + 1 < g.ny && k + 1 < g.nz) nt = case_triangles(dense_cell_case(g, p));
     }
-    int tv, tt;
-    (void)block_exclusive_scan(nv, lds, &tv);
-    (void)block_exclusive_scan(nt, lds, &tt);
+    const int tv = block_sum(nv, lds), tt = block_sum(nt, lds);
     if (threadIdx.x == 0) { vblk[blockIdx.x] = tv; tblk[blockIdx.x] = tt; }
-}
-
-// a single workgroup: a[0..n) -> exclusive prefix sums in place, a[n] = the total (for both arrays)
-__global__ void __launch_bounds__(kMcScanThreads) mc_scan_kernel(int64_t *va, int64_t *ta, int64_t n)
-{
-    __shared__ int64_t lds[kMcScanThreads];
-    int64_t vcarry = 0, tcarry = 0;
-    for (int64_t base = 0; base < n; base += kMcScanThreads) {
-        const int64_t q = base + threadIdx.x;
-        const int64_t v = q < n ? va[q] : 0, t = q < n ? ta[q] : 0;
-        int64_t vt, tt;
-        const int64_t ve = block_exclusive_scan(v, lds, &vt);
-        const int64_t te = block_exclusive_scan(t, lds, &tt);
-        if (q < n) { va[q] = vcarry + ve; ta[q] = tcarry + te; }
-        vcarry += vt; tcarry += tt;
-    }
-    if (threadIdx.x == 0) { va[n] = vcarry; ta[n] = tcarry; }
 }
 
 __global__ void __launch_bounds__(kMcThreads) mc_vertex_kernel(McGrid g, const unsigned char *mask, const int64_t *vblk, int32_t *vbase,
@@ -134,28 +142,12 @@ __global__ void __launch_bounds__(kMcThreads) mc_vertex_kernel(McGrid g, const u
     int total;
     const int off = block_exclusive_scan((int)__popc(m), lds, &total);
     if (p >= g.n) return;
-    int64_t id = vblk[blockIdx.x] + off;
+    const int64_t id = vblk[blockIdx.x] + off;
     vbase[p] = (int32_t)id;
     if (!m) return;
-    const int i = (int)(p % g.nx), j = (int)((p / g.nx) % g.ny), k = (int)(p / ((int64_t)g.nx * g.ny));
-    const float c[3] = { lattice_coord(g.lo[0], g.hi[0], g.nx, i), lattice_coord(g.lo[1], g.hi[1], g.ny, j),
-                         lattice_coord(g.lo[2], g.hi[2], g.nz, k) };
-    const int idx[3] = { i, j, k }, dim[3] = { g.nx, g.ny, g.nz };
+    const int idx[3] = { (int)(p % g.nx), (int)((p / g.nx) % g.ny), (int)(p / ((int64_t)g.nx * g.ny)) };
     const int64_t stride[3] = { 1, g.nx, (int64_t)g.nx * g.ny };
-    const float v0 = g.vol[p];
-    for (int a = 0; a < 3; ++a) {
-        if (!(m >> a & 1)) continue;
-        const float v1 = g.vol[p + stride[a]];
-        float t = (g.iso - v0) / (v1 - v0);
-        if (t != t) t = 0.5f;
-        const float g0 = c[a], g1 = lattice_coord(g.lo[a], g.hi[a], dim[a], idx[a] + 1);
-        float out[3] = { c[0], c[1], c[2] };
-        out[a] = g0 + t * (g1 - g0);
-        vertices[3 * id + 0] = out[0];
-        vertices[3 * id + 1] = out[1];
-        vertices[3 * id + 2] = out[2];
-        ++id;
-    }
+    edge_vertices(g, idx, m, g.vol[p], [&](int a) { return g.vol[p + stride[a]]; }, id, vertices, nullptr);
 }
 
 __global__ void __launch_bounds__(kMcThreads) mc_triangle_kernel(McGrid g, const unsigned char *mask, const int64_t *tblk,
@@ -167,7 +159,7 @@ __global__ void __launch_bounds__(kMcThreads) mc_triangle_kernel(McGrid g, const
     if (p < g.n) {
         const int i = (int)(p % g.nx), j = (int)((p / g.nx) % g.ny), k = (int)(p / ((int64_t)g.nx * g.ny));
         if (i + 1 < g.nx && j + 1 < g.ny && k + 1 < g.nz) {
-            c = cell_case(g, p);
+            c = dense_cell_case(g, p);
             nt = case_triangles(c);
         }
     }
@@ -176,12 +168,9 @@ __global__ void __launch_bounds__(kMcThreads) mc_triangle_kernel(McGrid g, const
     if (!nt) return;
     const int64_t first = tblk[blockIdx.x] + off;
     const int64_t sy = g.nx, sz = (int64_t)g.nx * g.ny;
-    for (int e = 0; e < 3 * nt; ++e) {
-        const int own = kMcEdgeOwner[kMcTriTable[c][e]];
-        const int64_t q = p + (own & 1) + ((own >> 1) & 1) * sy + ((own >> 2) & 1) * sz;
-        const int axis = own >> 3;
-        tris[3 * first + e] = vbase[q] + (int32_t)__popc(mask[q] & ((1 << axis) - 1));
-    }
+    for (int e = 0; e < 3 * nt; ++e)
+        tris[3 * first + e] = corner_vertex(kMcEdgeOwner[kMcTriTable[c][e]], vbase, mask,
+                                            [&](int dx, int dy, int dz, int) { return p + dx + dy * sy + dz * sz; });
 }
 
 // ---- geometric vertex normals ------------------------------------------------------------------------------------------------
@@ -340,6 +329,7 @@ __global__ void __launch_bounds__(kMcThreads) cc_jump_kernel(int32_t *parent, in
     *changed = 1;
 }
 
+// a single workgroup: a[0..n) -> exclusive prefix sums in place, a[n] = the total
 __global__ void __launch_bounds__(kMcScanThreads) scan_totals_kernel(int64_t *a, int64_t n)
 {
     __shared__ int64_t lds[kMcScanThreads];
@@ -366,12 +356,11 @@ __global__ void __launch_bounds__(kMcThreads) cc_root_count_kernel(const int32_t
 __global__ void __launch_bounds__(kMcThreads) cc_root_label_kernel(const int32_t *parent, const unsigned char *used, int64_t V, const int64_t *blk,
                                                                    int32_t *vertex_label)
 {
-    __shared__ int lds[kMcThreads];
+    __shared__ int lds[kMcThreads / 64];
     const int64_t v = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
     const bool use = v < V && used[v];
-    const int root = use && parent[v] == (int32_t)v;
-    int total;
-    const int off = block_exclusive_scan(root, lds, &total);
+    const bool root = use && parent[v] == (int32_t)v;
+    const int off = block_rank(root, lds);
     if (v >= V) return;
     if (!use) vertex_label[v] = -1;
     else if (root) vertex_label[v] = (int32_t)(blk[blockIdx.x] + off);
@@ -430,11 +419,10 @@ __global__ void __launch_bounds__(kMcThreads) compact_vertex_count_kernel(const 
 __global__ void __launch_bounds__(kMcThreads) compact_vertex_kernel(const unsigned *vertices, int64_t V, const unsigned char *used, const int64_t *vblk,
                                                                     int32_t *vmap, unsigned *out_vertices)
 {
-    __shared__ int lds[kMcThreads];
+    __shared__ int lds[kMcThreads / 64];
     const int64_t v = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
-    const int use = v < V && used[v];
-    int total;
-    const int off = block_exclusive_scan(use, lds, &total);
+    const bool use = v < V && used[v];
+    const int off = block_rank(use, lds);
     if (v >= V) return;
     if (!use) { vmap[v] = -1; return; }
     const int64_t o = vblk[blockIdx.x] + off;
@@ -447,12 +435,11 @@ __global__ void __launch_bounds__(kMcThreads) compact_vertex_kernel(const unsign
 __global__ void __launch_bounds__(kMcThreads) compact_triangle_kernel(const int32_t *tris, int64_t T, int64_t V, const unsigned char *keep,
                                                                       const int64_t *tblk, const int32_t *vmap, int32_t *out_tris)
 {
-    __shared__ int lds[kMcThreads];
+    __shared__ int lds[kMcThreads / 64];
     const int64_t t = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
     int32_t id[3];
-    const int kept = compact_kept(tris, t, T, V, keep, id);
-    int total;
-    const int off = block_exclusive_scan(kept, lds, &total);
+    const bool kept = compact_kept(tris, t, T, V, keep, id);
+    const int off = block_rank(kept, lds);
     if (!kept) return;
     const int64_t o = tblk[blockIdx.x] + off;
     out_tris[3 * o] = vmap[id[0]];
@@ -524,11 +511,6 @@ void launch_mc_count(const McGrid &g, unsigned char *mask, int64_t *vblk, int64_
     hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)mc_blocks(g.n)), dim3(kMcThreads), 0, s, g, mask, vblk, tblk);
 }
 
-void launch_mc_scan(int64_t *vblk, int64_t *tblk, int64_t nblocks, hipStream_t s)
-{
-    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(kMcScanThreads), 0, s, vblk, tblk, nblocks);
-}
-
 void launch_mc_vertices(const McGrid &g, const unsigned char *mask, const int64_t *vblk, int32_t *vbase, float *vertices, hipStream_t s)
 {
     hipLaunchKernelGGL(mc_vertex_kernel, dim3((unsigned)mc_blocks(g.n)), dim3(kMcThreads), 0, s, g, mask, vblk, vbase, vertices);
@@ -543,9 +525,9 @@ void launch_mc_triangles(const McGrid &g, const unsigned char *mask, const int64
 // The fine lattice is cut into bricks of B^3 cells (kernels.h BrickGrid); only the listed ("active") bricks carry values, [M][P] floats.
 //   coarse_points_kernel    the brick corners: fine lattice points min(b B, n - 1) per axis
 //   brick_flag_kernel       a brick is active when one of its 8 corners is NaN, two of them lie on different sides of iso, or one
-//                           is within `band` of it; brick_dilate_kernel grows the set along one axis (three launches: a Chebyshev ball)
-//   brick_count / _list     active bricks per workgroup (scan_totals_kernel in between), then slot map and ascending list by wave
-//                           ballots: the rank of a brick among the active ones is its position in both
+//                           is within `band` of it; dilate_axis_kernel grows the set along one axis (three launches: a Chebyshev ball)
+//   brick_count / _list     active bricks per workgroup (scan_totals_kernel in between), then slot map and ascending list by
+//                           block_rank: the rank of a brick among the active ones is its position in both
 //   brick_points / _pad     the lattice points of the listed bricks for the field kernels; NaN over what lies past the fine lattice
 //   brick_mc_*              one workgroup per brick, the brick's values in LDS: count (the owned crossed edges of every point, the
 //                           brick's totals), vertices, triangles -- dense marching cubes' arithmetic on the same lattice points
@@ -577,8 +559,7 @@ __global__ void __launch_bounds__(kMcThreads) coarse_points_kernel(BrickGrid bg,
     pos[3 * q + 0] = lattice_coord(bg.g.lo[0], bg.g.hi[0], bg.g.nx, min(cx * bg.B, bg.g.nx - 1));
     pos[3 * q + 1] = lattice_coord(bg.g.lo[1], bg.g.hi[1], bg.g.ny, min(cy * bg.B, bg.g.ny - 1));
     pos[3 * q + 2] = lattice_coord(bg.g.lo[2], bg.g.hi[2], bg.g.nz, min(cz * bg.B, bg.g.nz - 1));
-    dir[3 * q + 0] = 1.f; dir[3 * q + 1] = 0.f; dir[3 * q + 2] = 0.f;
-    var[3 * q + 0] = 0.f; var[3 * q + 1] = 0.f; var[3 * q + 2] = 0.f;
+    unit_inputs(q, dir, var);
 }
 
 // fine indices of point p of the [M][P] brick lattices; false for padding (and for a brick index outside the grid), then clamped
@@ -609,8 +590,7 @@ __global__ void __launch_bounds__(kMcThreads) brick_points_kernel(BrickGrid bg, 
     pos[3 * q + 0] = lattice_coord(bg.g.lo[0], bg.g.hi[0], bg.g.nx, idx[0]);
     pos[3 * q + 1] = lattice_coord(bg.g.lo[1], bg.g.hi[1], bg.g.ny, idx[1]);
     pos[3 * q + 2] = lattice_coord(bg.g.lo[2], bg.g.hi[2], bg.g.nz, idx[2]);
-    dir[3 * q + 0] = 1.f; dir[3 * q + 1] = 0.f; dir[3 * q + 2] = 0.f;
-    var[3 * q + 0] = 0.f; var[3 * q + 1] = 0.f; var[3 * q + 2] = 0.f;
+    unit_inputs(q, dir, var);
 }
 
 __global__ void __launch_bounds__(kMcThreads) brick_pad_kernel(BrickGrid bg, const int32_t *ids, int64_t first, int64_t n, float *out)
@@ -640,14 +620,15 @@ __global__ void __launch_bounds__(kMcThreads) brick_flag_kernel(const float *coa
     flag[c] = any || (in != 0 && in != 8) ? 1 : 0;
 }
 
-// dst = maximum of src over [i - d, i + d] along one axis, clipped to the brick grid
-__global__ void __launch_bounds__(kMcThreads) brick_dilate_kernel(const unsigned char *src, unsigned char *dst, int nbx, int nby, int nbz, int64_t nb,
-                                                                   int d, int axis)
+// dst = maximum of src over [i - d, i + d] along one axis of an [nz][ny][nx] byte grid of n cells, clipped to the grid (the bricks
+// of launch_brick_select, the cells of launch_occ_build)
+__global__ void __launch_bounds__(kMcThreads) dilate_axis_kernel(const unsigned char *src, unsigned char *dst, int nx, int ny, int nz, int64_t n_cells,
+                                                                  int d, int axis)
 {
     const int64_t c = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
-    if (c >= nb) return;
-    const int64_t stride = axis == 0 ? 1 : (axis == 1 ? (int64_t)nbx : (int64_t)nbx * nby);
-    const int n = axis == 0 ? nbx : (axis == 1 ? nby : nbz);
+    if (c >= n_cells) return;
+    const int64_t stride = axis == 0 ? 1 : (axis == 1 ? (int64_t)nx : (int64_t)nx * ny);
+    const int n = axis == 0 ? nx : (axis == 1 ? ny : nz);
     const int i = (int)((c / stride) % n);
     const int a = i - d < 0 ? 0 : i - d, b = i + d > n - 1 ? n - 1 : i + d;
     unsigned char m = 0;
@@ -668,15 +649,9 @@ __global__ void __launch_bounds__(kMcThreads) brick_list_kernel(const unsigned c
     __shared__ int lds[kMcThreads / 64];
     const int64_t c = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
     const bool k = c < nb && flag[c];
-    const unsigned long long ballot = __ballot(k);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int in_wave = (int)__popcll(ballot & ((1ull << lane) - 1ull));
-    if (lane == 0) lds[wave] = (int)__popcll(ballot);
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wave; ++w) before += lds[w];
+    const int rank = block_rank(k, lds);
     if (c >= nb) return;
-    const int64_t o = blk[blockIdx.x] + before + in_wave;
+    const int64_t o = blk[blockIdx.x] + rank;
     slot_map[c] = k ? (int32_t)o : -1;
     if (k) ids[o] = (int32_t)c;
 }
@@ -734,20 +709,10 @@ __device__ __forceinline__ bool brick_stage(const BrickMesh &k, int64_t m, int b
     return true;
 }
 
-__device__ __forceinline__ int brick_cell_case(const float *val, int l, int L, float iso)
-{
-    const int sx = 1, sy = L, sz = L * L;
-    const int off[8] = { 0, sx, sx + sy, sy, sz, sx + sz, sx + sy + sz, sy + sz };
-    int c = 0;
-#pragma unroll
-    for (int b = 0; b < 8; ++b) c |= inside(val[l + off[b]], iso) << b;
-    return c;
-}
-
 __global__ void __launch_bounds__(kMcThreads) brick_mc_count_kernel(BrickMesh k, unsigned char *mask, int64_t *vblk, int64_t *tblk)
 {
     __shared__ float val[kBrickMaxPoints];
-    __shared__ int lds[kMcThreads];
+    __shared__ int lds[kMcThreads / 64];
     const int64_t m = blockIdx.x;
     const int L = k.bg.B + 1, P = k.bg.P;
     const float iso = k.bg.g.iso;
@@ -763,14 +728,12 @@ __global__ void __launch_bounds__(kMcThreads) brick_mc_count_kernel(BrickMesh k,
                 int ol[3];
                 if (loc[a] < e[a] && inside(val[l + stride[a]], iso) != in0 && edge_owner(k, b, loc, a, m, ol) == m) msk |= 1 << a;
             }
-            if (loc[0] < e[0] && loc[1] < e[1] && loc[2] < e[2]) nt += case_triangles(brick_cell_case(val, l, L, iso));
+            if (loc[0] < e[0] && loc[1] < e[1] && loc[2] < e[2]) nt += case_triangles(cell_case(val + l, L, L * L, iso));
         }
         mask[m * P + l] = (unsigned char)msk;
         nv += (int)__popc(msk);
     }
-    int tv, tt;
-    (void)block_exclusive_scan(nv, lds, &tv);
-    (void)block_exclusive_scan(nt, lds, &tt);
+    const int tv = block_sum(nv, lds), tt = block_sum(nt, lds);
     if (threadIdx.x == 0) { vblk[m] = tv; tblk[m] = tt; }
 }
 
@@ -790,32 +753,15 @@ __global__ void __launch_bounds__(kMcThreads) brick_mc_vertex_kernel(BrickMesh k
         const int msk = l < P ? mask[m * P + l] : 0;
         int total;
         const int off = block_exclusive_scan((int)__popc(msk), lds, &total);
-        int64_t id = carry + off;
+        const int64_t id = carry + off;
         carry += total;
         if (l >= P) continue;
         vbase[m * P + l] = (int32_t)id;
         if (!msk) continue;
         const int loc[3] = { l % L, (l / L) % L, l / (L * L) };
         const int idx[3] = { b[0] * k.bg.B + loc[0], b[1] * k.bg.B + loc[1], b[2] * k.bg.B + loc[2] };
-        const int dim[3] = { g.nx, g.ny, g.nz }, stride[3] = { 1, L, L * L };
-        const float c[3] = { lattice_coord(g.lo[0], g.hi[0], g.nx, idx[0]), lattice_coord(g.lo[1], g.hi[1], g.ny, idx[1]),
-                             lattice_coord(g.lo[2], g.hi[2], g.nz, idx[2]) };
-        const int64_t p = ((int64_t)idx[2] * g.ny + idx[1]) * g.nx + idx[0];
-        const float v0 = val[l];
-        for (int a = 0; a < 3; ++a) {
-            if (!(msk >> a & 1)) continue;
-            const float v1 = val[l + stride[a]];
-            float t = (g.iso - v0) / (v1 - v0);
-            if (t != t) t = 0.5f;
-            const float g0 = c[a], g1 = lattice_coord(g.lo[a], g.hi[a], dim[a], idx[a] + 1);
-            float out[3] = { c[0], c[1], c[2] };
-            out[a] = g0 + t * (g1 - g0);
-            vertices[3 * id + 0] = out[0];
-            vertices[3 * id + 1] = out[1];
-            vertices[3 * id + 2] = out[2];
-            vertex_key[id] = 3 * p + a;
-            ++id;
-        }
+        const int stride[3] = { 1, L, L * L };
+        edge_vertices(g, idx, msk, val[l], [&](int a) { return val[l + stride[a]]; }, id, vertices, vertex_key);
     }
 }
 
@@ -835,7 +781,7 @@ __global__ void __launch_bounds__(kMcThreads) brick_mc_triangle_kernel(BrickMesh
         const int loc[3] = { l % L, (l / L) % L, l / (L * L) };
         int c = 0, nt = 0;
         if (l < P && loc[0] < e[0] && loc[1] < e[1] && loc[2] < e[2]) {
-            c = brick_cell_case(val, l, L, g.iso);
+            c = cell_case(val + l, L, L * L, g.iso);
             nt = case_triangles(c);
         }
         int total;
@@ -844,15 +790,13 @@ __global__ void __launch_bounds__(kMcThreads) brick_mc_triangle_kernel(BrickMesh
         carry += total;
         if (!nt) continue;
         const int64_t p = ((int64_t)(b[2] * k.bg.B + loc[2]) * g.ny + (b[1] * k.bg.B + loc[1])) * g.nx + (b[0] * k.bg.B + loc[0]);
-        for (int i = 0; i < 3 * nt; ++i) {
-            const int own = kMcEdgeOwner[kMcTriTable[c][i]];
-            const int ql[3] = { loc[0] + (own & 1), loc[1] + ((own >> 1) & 1), loc[2] + ((own >> 2) & 1) };
-            const int axis = own >> 3;
-            int ol[3];
-            const int64_t s = edge_owner(k, b, ql, axis, m, ol);
-            const int64_t q = s * P + (ol[2] * L + ol[1]) * L + ol[0];
-            tris[3 * first + i] = vbase[q] + (int32_t)__popc(mask[q] & ((1 << axis) - 1));
-        }
+        for (int i = 0; i < 3 * nt; ++i)
+            tris[3 * first + i] = corner_vertex(kMcEdgeOwner[kMcTriTable[c][i]], vbase, mask, [&](int dx, int dy, int dz, int axis) {
+                const int ql[3] = { loc[0] + dx, loc[1] + dy, loc[2] + dz };
+                int ol[3];
+                const int64_t s = edge_owner(k, b, ql, axis, m, ol);         // the brick whose lattice holds the vertex
+                return s * P + (ol[2] * L + ol[1]) * L + ol[0];
+            });
         for (int i = 0; i < nt; ++i) triangle_key[first + i] = 5 * p + i;
     }
 }
@@ -872,17 +816,22 @@ void launch_brick_pad(const BrickGrid &bg, const int32_t *ids, int64_t first, in
     hipLaunchKernelGGL(brick_pad_kernel, dim3((unsigned)mc_blocks(n)), dim3(kMcThreads), 0, s, bg, ids, first, n, out);
 }
 
+const unsigned char *launch_dilate(unsigned char *a, unsigned char *b, int nx, int ny, int nz, int d, hipStream_t s)
+{
+    const int64_t n = (int64_t)nx * ny * nz;
+    for (int axis = 0; axis < 3 && d > 0; ++axis) {
+        hipLaunchKernelGGL(dilate_axis_kernel, dim3((unsigned)mc_blocks(n)), dim3(kMcThreads), 0, s, (const unsigned char *)a, b, nx, ny, nz, n, d, axis);
+        unsigned char *t = a; a = b; b = t;
+    }
+    return a;
+}
+
 void launch_brick_select(const float *coarse, int nbx, int nby, int nbz, float iso, float band, int dilate, unsigned char *flag_a,
                          unsigned char *flag_b, int64_t *blk, int32_t *slot_map, int32_t *ids, hipStream_t s)
 {
     const int64_t nb = (int64_t)nbx * nby * nbz, blocks = mc_blocks(nb);
     hipLaunchKernelGGL(brick_flag_kernel, dim3((unsigned)blocks), dim3(kMcThreads), 0, s, coarse, nbx, nby, nbz, nb, iso, band, flag_a);
-    unsigned char *src = flag_a, *dst = flag_b;
-    if (dilate > 0)
-        for (int axis = 0; axis < 3; ++axis) {
-            hipLaunchKernelGGL(brick_dilate_kernel, dim3((unsigned)blocks), dim3(kMcThreads), 0, s, src, dst, nbx, nby, nbz, nb, dilate, axis);
-            unsigned char *t = src; src = dst; dst = t;
-        }
+    const unsigned char *src = launch_dilate(flag_a, flag_b, nbx, nby, nbz, dilate, s);
     hipLaunchKernelGGL(brick_count_kernel, dim3((unsigned)blocks), dim3(kMcThreads), 0, s, src, nb, blk);
     launch_scan_totals(blk, blocks, s);
     hipLaunchKernelGGL(brick_list_kernel, dim3((unsigned)blocks), dim3(kMcThreads), 0, s, src, nb, blk, slot_map, ids);

@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <functional>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -1002,6 +1003,18 @@ static size_t carve_bytes(size_t n_floats)
     return (n_floats * sizeof(float) + 255) & ~(size_t)255;
 }
 
+// The end of every count -> scan pass: the launches before are checked, the grand totals (8 bytes each, behind their block bases; at
+// most three) and an optional flag word come back on the stream, then ONE synchronise.
+struct TotalRead { int64_t *host; const int64_t *dev; };
+static int read_totals(neddf_ctx *ctx, hipStream_t s, std::initializer_list<TotalRead> totals, int *h_flag = nullptr, const int *d_flag = nullptr)
+{
+    HIPCHK(hipGetLastError());
+    for (const TotalRead &t : totals) HIPCHK(hipMemcpyAsync(t.host, t.dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (h_flag) HIPCHK(hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
 // ---- empty-space skipping: the workspace of one culled render call (carved from the arena, sized for its longest pass) ----
 struct OccWork {
     OccGrid grid;
@@ -1040,10 +1053,7 @@ static int occ_compact(neddf_ctx *ctx, const unsigned char *keep, const float *p
 {
     launch_occ_count(keep, n, blk, s);
     launch_occ_gather(keep, pos, dir, var, n, blk, cpos, cdir, cvar, index, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(m, blk + occ_blocks(n), sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
+    return read_totals(ctx, s, { { m, blk + occ_blocks(n) } });
 }
 
 // The field of one culled pass: sampling tensors -> classify -> gather -> field on the kept points -> scatter into zero-filled outputs.
@@ -1367,33 +1377,52 @@ static McGrid mc_grid(const float *vol, int nx, int ny, int nz, const double *lo
     return g;
 }
 
+static int grid_field_ok(neddf_ctx *ctx, int slot, int field, const char *what)
+{
+    if (field != NEDDF_GRID_DISTANCE && field != NEDDF_GRID_DENSITY)
+        return fail(ctx, NEDDF_EINVAL, std::string(what) + ": field must be NEDDF_GRID_DISTANCE or NEDDF_GRID_DENSITY");
+    if (slot < 0 || slot >= NEDDF_NUM_SLOTS || !ctx->field[slot].valid) return fail(ctx, NEDDF_ENOFIELD, "no field in slot");
+    if (field == NEDDF_GRID_DISTANCE && ctx->field[slot].d.kind == NEDDF_FIELD_NERF)
+        return fail(ctx, NEDDF_EINVAL, std::string(what) + ": a NeRF field has no distance output");
+    return 0;
+}
+
+// `total` generated points through the field in chunks: points(first, n, pos, dir, var) fills a chunk, after(first, n, out) runs behind
+// its evaluation.  One chunk = one launch of field_forward at its own launch size (2^23 points): 302 MB of pos / dir / var
+static int eval_generated(neddf_ctx *ctx, int slot, int field, int64_t total, float *d_out, hipStream_t s,
+                          const std::function<void(int64_t, int64_t, float *, float *, float *)> &points,
+                          const std::function<void(int64_t, int64_t, float *)> &after)
+{
+    const int64_t chunk = total < ((int64_t)1 << 23) ? total : ((int64_t)1 << 23);
+    if (int rc = ensure(ctx, ctx->grid_pts, (size_t)chunk * 9 * sizeof(float))) return rc;
+    float *pos = (float *)ctx->grid_pts.p, *dir = pos + chunk * 3, *var = dir + chunk * 3;
+    for (int64_t off = 0; off < total; off += chunk) {
+        const int64_t n = total - off < chunk ? total - off : chunk;
+        points(off, n, pos, dir, var);
+        HIPCHK(hipGetLastError());
+        float *out = d_out + off;
+        // no colour: the colour kernel and its hand-off are skipped (field_forward, a.features)
+        if (int rc = field_forward(ctx, slot, pos, dir, var, n, NEDDF_OUT_MINIMAL, field == NEDDF_GRID_DISTANCE ? out : nullptr,
+                                   field == NEDDF_GRID_DENSITY ? out : nullptr, nullptr, nullptr, nullptr, s)) return rc;
+        after(off, n, out);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
 int neddf_field_grid(neddf_ctx *ctx, int slot, int field, int nx, int ny, int nz, const double *h_lo, const double *h_hi, float *d_volume,
                      void *stream)
 {
     if (!ctx) return NEDDF_EINVAL;
     if (!h_lo || !h_hi || !d_volume) return fail(ctx, NEDDF_EINVAL, "field_grid: NULL bounds or volume");
     if (!lattice_ok(nx, ny, nz, h_lo, h_hi)) return fail(ctx, NEDDF_EINVAL, "field_grid: every dimension must be >= 2 and lo < hi on every axis");
-    if (field != NEDDF_GRID_DISTANCE && field != NEDDF_GRID_DENSITY) return fail(ctx, NEDDF_EINVAL, "field_grid: field must be NEDDF_GRID_DISTANCE or NEDDF_GRID_DENSITY");
-    if (slot < 0 || slot >= NEDDF_NUM_SLOTS || !ctx->field[slot].valid) return fail(ctx, NEDDF_ENOFIELD, "no field in slot");
-    if (field == NEDDF_GRID_DISTANCE && ctx->field[slot].d.kind == NEDDF_FIELD_NERF)
-        return fail(ctx, NEDDF_EINVAL, "field_grid: a NeRF field has no distance output");
+    if (int rc = grid_field_ok(ctx, slot, field, "field_grid")) return rc;
     DeviceGuard guard_(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     const McGrid g = mc_grid(nullptr, nx, ny, nz, h_lo, h_hi, 0.f);
-    // one chunk = one launch of field_forward at its own launch size (2^23 points): 302 MB of pos / dir / var
-    const int64_t chunk = g.n < ((int64_t)1 << 23) ? g.n : ((int64_t)1 << 23);
-    if (int rc = ensure(ctx, ctx->grid_pts, (size_t)chunk * 9 * sizeof(float))) return rc;
-    float *pos = (float *)ctx->grid_pts.p, *dir = pos + chunk * 3, *var = dir + chunk * 3;
-    for (int64_t off = 0; off < g.n; off += chunk) {
-        const int64_t n = g.n - off < chunk ? g.n - off : chunk;
-        launch_grid_points(g, off, n, pos, dir, var, s);
-        HIPCHK(hipGetLastError());
-        float *out = d_volume + off;
-        // no colour: the colour kernel and its hand-off are skipped (field_forward, a.features)
-        if (int rc = field_forward(ctx, slot, pos, dir, var, n, NEDDF_OUT_MINIMAL, field == NEDDF_GRID_DISTANCE ? out : nullptr,
-                                   field == NEDDF_GRID_DENSITY ? out : nullptr, nullptr, nullptr, nullptr, s)) return rc;
-    }
-    return 0;
+    return eval_generated(ctx, slot, field, g.n, d_volume, s,
+                          [&](int64_t first, int64_t n, float *pos, float *dir, float *var) { launch_grid_points(g, first, n, pos, dir, var, s); },
+                          [](int64_t, int64_t, float *) {});
 }
 
 int neddf_marching_cubes(neddf_ctx *ctx, const float *d_volume, int nx, int ny, int nz, const double *h_lo, const double *h_hi, float iso,
@@ -1413,12 +1442,10 @@ int neddf_marching_cubes(neddf_ctx *ctx, const float *d_volume, int nx, int ny, 
     unsigned char *mask = (unsigned char *)ctx->mc_mask.p;
     int64_t *vblk = (int64_t *)ctx->mc_blk.p, *tblk = vblk + nb + 1;
     launch_mc_count(g, mask, vblk, tblk, s);
-    launch_mc_scan(vblk, tblk, nb, s);
-    HIPCHK(hipGetLastError());
+    launch_scan_totals(vblk, nb, s);
+    launch_scan_totals(tblk, nb, s);
     int64_t counts[2];
-    HIPCHK(hipMemcpyAsync(&counts[0], vblk + nb, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&counts[1], tblk + nb, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    if (int rc = read_totals(ctx, s, { { &counts[0], vblk + nb }, { &counts[1], tblk + nb } })) return rc;
     *h_n_vertices = counts[0];
     *h_n_triangles = counts[1];
     if (counts[0] >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "marching_cubes: 2^31 vertices or more (triangle indices are int32)");
@@ -1443,38 +1470,6 @@ static BrickGrid brick_grid(int nx, int ny, int nz, int brick, const double *lo,
     bg.nbx = (nx - 2 + brick) / brick; bg.nby = (ny - 2 + brick) / brick; bg.nbz = (nz - 2 + brick) / brick;
     bg.nb = (int64_t)bg.nbx * bg.nby * bg.nbz;
     return bg;
-}
-
-static int grid_field_ok(neddf_ctx *ctx, int slot, int field, const char *what)
-{
-    if (field != NEDDF_GRID_DISTANCE && field != NEDDF_GRID_DENSITY)
-        return fail(ctx, NEDDF_EINVAL, std::string(what) + ": field must be NEDDF_GRID_DISTANCE or NEDDF_GRID_DENSITY");
-    if (slot < 0 || slot >= NEDDF_NUM_SLOTS || !ctx->field[slot].valid) return fail(ctx, NEDDF_ENOFIELD, "no field in slot");
-    if (field == NEDDF_GRID_DISTANCE && ctx->field[slot].d.kind == NEDDF_FIELD_NERF)
-        return fail(ctx, NEDDF_EINVAL, std::string(what) + ": a NeRF field has no distance output");
-    return 0;
-}
-
-// `total` generated points through the field in chunks of at most 2^23, as neddf_field_grid does: points(first, n, pos, dir, var) fills a
-// chunk, after(first, n, out) runs behind its evaluation
-static int eval_generated(neddf_ctx *ctx, int slot, int field, int64_t total, float *d_out, hipStream_t s,
-                          const std::function<void(int64_t, int64_t, float *, float *, float *)> &points,
-                          const std::function<void(int64_t, int64_t, float *)> &after)
-{
-    const int64_t chunk = total < ((int64_t)1 << 23) ? total : ((int64_t)1 << 23);
-    if (int rc = ensure(ctx, ctx->grid_pts, (size_t)chunk * 9 * sizeof(float))) return rc;
-    float *pos = (float *)ctx->grid_pts.p, *dir = pos + chunk * 3, *var = dir + chunk * 3;
-    for (int64_t off = 0; off < total; off += chunk) {
-        const int64_t n = total - off < chunk ? total - off : chunk;
-        points(off, n, pos, dir, var);
-        HIPCHK(hipGetLastError());
-        float *out = d_out + off;
-        if (int rc = field_forward(ctx, slot, pos, dir, var, n, NEDDF_OUT_MINIMAL, field == NEDDF_GRID_DISTANCE ? out : nullptr,
-                                   field == NEDDF_GRID_DENSITY ? out : nullptr, nullptr, nullptr, nullptr, s)) return rc;
-        after(off, n, out);
-        HIPCHK(hipGetLastError());
-    }
-    return 0;
 }
 
 int neddf_field_grid_coarse(neddf_ctx *ctx, int slot, int field, int nx, int ny, int nz, int brick, const double *h_lo, const double *h_hi,
@@ -1511,10 +1506,7 @@ int neddf_brick_select(neddf_ctx *ctx, const float *d_coarse, int nbx, int nby, 
     unsigned char *flags = (unsigned char *)ctx->brick_flags.p;
     int64_t *blk = (int64_t *)ctx->brick_blk.p;
     launch_brick_select(d_coarse, nbx, nby, nbz, iso, band, dilate, flags, flags + nb, blk, d_slot_map, d_brick_ids, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_n_active, blk + blocks, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
+    return read_totals(ctx, s, { { h_n_active, blk + blocks } });
 }
 
 int neddf_field_bricks(neddf_ctx *ctx, int slot, int field, int nx, int ny, int nz, int brick, const double *h_lo, const double *h_hi,
@@ -1564,14 +1556,11 @@ int neddf_marching_cubes_bricks(neddf_ctx *ctx, const float *d_values, const int
     HIPCHK(hipMemsetAsync(bad, 0, sizeof(int), s));
     launch_brick_check(k, bad, s);
     if (M > 0) launch_brick_mc_count(k, mask, vblk, tblk, s);
-    launch_mc_scan(vblk, tblk, M, s);
-    HIPCHK(hipGetLastError());
+    launch_scan_totals(vblk, M, s);
+    launch_scan_totals(tblk, M, s);
     int64_t counts[2];
     int h_bad = 0;
-    HIPCHK(hipMemcpyAsync(&counts[0], vblk + M, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&counts[1], tblk + M, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    if (int rc = read_totals(ctx, s, { { &counts[0], vblk + M }, { &counts[1], tblk + M } }, &h_bad, bad)) return rc;
     if (h_bad) return fail(ctx, NEDDF_EINVAL, "marching_cubes_bricks: the brick list must be strictly ascending inside the grid and the slot map its inverse");
     *h_n_vertices = counts[0];
     *h_n_triangles = counts[1];
@@ -1644,10 +1633,7 @@ int neddf_mesh_components(neddf_ctx *ctx, const int32_t *d_triangles, int64_t n_
         }
     }
     launch_cc_labels(parent, used, V, d_triangles, T, blk, d_vertex_label, d_triangle_label, d_component_triangles, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_n_components, blk + nbv, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
+    return read_totals(ctx, s, { { h_n_components, blk + nbv } });
 }
 
 int neddf_mesh_components_rounds(neddf_ctx *ctx)
@@ -1672,11 +1658,8 @@ int neddf_mesh_compact(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertic
     unsigned char *used = (unsigned char *)ctx->cc_used.p;
     int64_t *vblk = (int64_t *)ctx->cc_blk.p, *tblk = vblk + nbv + 1;
     launch_compact_count(d_triangles, T, V, d_keep_triangle, used, vblk, tblk, s);
-    HIPCHK(hipGetLastError());
     int64_t counts[2];
-    HIPCHK(hipMemcpyAsync(&counts[0], vblk + nbv, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&counts[1], tblk + nbt, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    if (int rc = read_totals(ctx, s, { { &counts[0], vblk + nbv }, { &counts[1], tblk + nbt } })) return rc;
     *h_n_vertices = counts[0];
     *h_n_triangles = counts[1];
     if (!d_out_vertices || !d_out_triangles || vertex_cap < counts[0] || triangle_cap < counts[1]) return 0;     // the counting call
@@ -1725,10 +1708,7 @@ int neddf_occupancy_build(neddf_ctx *ctx, const float *d_volume, int R, float th
     unsigned char *cells = (unsigned char *)ctx->occ_cells.p;
     int64_t *blk = (int64_t *)ctx->occ_blk.p;
     launch_occ_build(d_volume, R, threshold, dilate, cells, cells + n_cells, d_bits, blk, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_n_occupied, blk + nb, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
+    return read_totals(ctx, s, { { h_n_occupied, blk + nb } });
 }
 
 int neddf_occupancy_classify(neddf_ctx *ctx, const neddf_occupancy *occ, const float *d_pos, int64_t n_points, unsigned char *d_keep,
@@ -1806,10 +1786,7 @@ static int trace_compact(neddf_ctx *ctx, const float *ro, const float *rd, int64
     if (int rc = ensure(ctx, ctx->trace_blk, (size_t)(occ_blocks(n) + 1) * sizeof(int64_t))) return rc;
     int64_t *blk = (int64_t *)ctx->trace_blk.p;
     launch_trace_compact(ro, rd, n, st, bisect, blk, index, pos, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(m, blk + occ_blocks(n), sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
+    return read_totals(ctx, s, { { m, blk + occ_blocks(n) } });
 }
 
 int neddf_trace_begin(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, float t_near, float *d_t, float *d_t_lo,

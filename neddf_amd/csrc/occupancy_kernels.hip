@@ -2,7 +2,7 @@
 //
 //   occ_cell_kernel      per cell of the R^3 grid: one byte, set when any of its 8 corner densities satisfies !(v <= threshold)
 //                        (a NaN corner sets it: the grid only removes work it is sure about)
-//   occ_dilate_kernel    one axis of the Chebyshev dilation (a box maximum is separable: x, then y, then z), clipped at the box
+//   launch_dilate        the Chebyshev dilation (a box maximum is separable: x, then y, then z; dilate_axis_kernel of mesh_kernels.hip)
 //   occ_pack_kernel      one lane per 32-bit word: bit i of the grid lives in word i >> 5 at position i & 31, whole words stored,
 //                        unused high bits of the last word 0; per-block population counts
 //   occ_classify_kernel  per point: keep byte (outside the box or non-finite: keep; inside: the cell's bit)
@@ -10,10 +10,10 @@
 //   occ_gather_kernel    kept rows of pos / dir / var -> compact arrays in their old order, and the old index of each
 //   occ_scatter_kernel   compact density / colour / normal rows -> their old places
 //
-// Placement is decided by count -> scan -> write launches (launch_scan_totals of mesh_kernels.hip scans the block totals; inside a
-// block the offsets come from wave64 ballots and population counts): no atomics, so every output is the same on every run
-// (tests/occupancy_check.py restates all of it in numpy, bit for bit).
+// Placement is decided by count -> scan -> write launches (block_scan.h; launch_scan_totals of mesh_kernels.hip scans the block
+// totals): no atomics, so every output is the same on every run (tests/occupancy_check.py restates all of it in numpy, bit for bit).
 #include "kernels.h"
+#include "block_scan.h"
 
 namespace neddf {
 
@@ -30,33 +30,6 @@ __global__ void __launch_bounds__(kMcThreads) occ_cell_kernel(const float *vol, 
 #pragma unroll
     for (int b = 0; b < 8; ++b) occ |= corner_occupied(vol[p + (b & 1) + ((b >> 1) & 1) * L + (b >> 2) * L * L], threshold);
     cell[c] = occ ? 1 : 0;
-}
-
-// dst = maximum of src over [i - d, i + d] along one axis (stride in cells), clipped to [0, R)
-__global__ void __launch_bounds__(kMcThreads) occ_dilate_kernel(const unsigned char *src, unsigned char *dst, int R, int64_t n_cells, int d,
-                                                                 int axis)
-{
-    const int64_t c = (int64_t)blockIdx.x * kMcThreads + threadIdx.x;
-    if (c >= n_cells) return;
-    const int64_t stride = axis == 0 ? 1 : (axis == 1 ? (int64_t)R : (int64_t)R * R);
-    const int i = (int)((c / stride) % R);
-    const int a = i - d < 0 ? 0 : i - d, b = i + d > R - 1 ? R - 1 : i + d;
-    unsigned char m = 0;
-    for (int j = a; j <= b; ++j) m |= src[c + (int64_t)(j - i) * stride];
-    dst[c] = m;
-}
-
-// sum of one int per thread over the workgroup (every thread receives it)
-__device__ __forceinline__ int block_sum(int v, int *lds)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    if ((threadIdx.x & 63) == 0) lds[wave] = v;
-    __syncthreads();
-    int t = 0;
-    for (int w = 0; w < n_waves; ++w) t += lds[w];
-    __syncthreads();
-    return t;
 }
 
 __global__ void __launch_bounds__(kMcThreads) occ_pack_kernel(const unsigned char *cell, int64_t n_cells, int64_t n_words, uint32_t *bits,
@@ -100,9 +73,8 @@ __global__ void __launch_bounds__(kMcThreads) occ_classify_kernel(OccGrid g, con
 
 __global__ void __launch_bounds__(kOccThreads) occ_count_kernel(const unsigned char *keep, int64_t n, int64_t *blk)
 {
-    __shared__ int lds[kOccThreads / 64];
     const int64_t i = (int64_t)blockIdx.x * kOccThreads + threadIdx.x;
-    const int total = block_sum(i < n && keep[i] ? 1 : 0, lds);
+    const int total = __syncthreads_count(i < n && keep[i]);
     if (threadIdx.x == 0) blk[blockIdx.x] = total;
 }
 
@@ -113,15 +85,9 @@ __global__ void __launch_bounds__(kOccThreads) occ_gather_kernel(const unsigned 
     __shared__ int lds[kOccThreads / 64];
     const int64_t i = (int64_t)blockIdx.x * kOccThreads + threadIdx.x;
     const bool k = i < n && keep[i];
-    const unsigned long long ballot = __ballot(k);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int in_wave = (int)__popcll(ballot & ((1ull << lane) - 1ull));
-    if (lane == 0) lds[wave] = (int)__popcll(ballot);
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wave; ++w) before += lds[w];
+    const int rank = block_rank(k, lds);
     if (!k) return;
-    const int64_t o = blk[blockIdx.x] + before + in_wave;       // bit copies: NaN payloads survive
+    const int64_t o = blk[blockIdx.x] + rank;       // bit copies: NaN payloads survive
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         cpos[3 * o + a] = pos[3 * i + a];
@@ -153,13 +119,9 @@ void launch_occ_build(const float *vol, int R, float threshold, int dilate, unsi
     const int64_t n_cells = (int64_t)R * R * R, n_words = occ_words(R);
     const unsigned grid = (unsigned)mc_blocks(n_cells);
     hipLaunchKernelGGL(occ_cell_kernel, dim3(grid), dim3(kMcThreads), 0, s, vol, R, n_cells, threshold, cell_a);
-    unsigned char *src = cell_a, *dst = cell_b;
-    for (int axis = 0; axis < 3 && dilate > 0; ++axis) {
-        hipLaunchKernelGGL(occ_dilate_kernel, dim3(grid), dim3(kMcThreads), 0, s, (const unsigned char *)src, dst, R, n_cells, dilate, axis);
-        unsigned char *t = src; src = dst; dst = t;
-    }
+    const unsigned char *cell = launch_dilate(cell_a, cell_b, R, R, R, dilate, s);
     const int64_t nb = mc_blocks(n_words);
-    hipLaunchKernelGGL(occ_pack_kernel, dim3((unsigned)nb), dim3(kMcThreads), 0, s, (const unsigned char *)src, n_cells, n_words, bits, blk);
+    hipLaunchKernelGGL(occ_pack_kernel, dim3((unsigned)nb), dim3(kMcThreads), 0, s, cell, n_cells, n_words, bits, blk);
     launch_scan_totals(blk, nb, s);
 }
 

@@ -11,8 +11,8 @@
 //   trace_finish_kernel         ACTIVE -> EXHAUSTED
 //
 // "Selected" is ACTIVE at depth t (the marching loop) or HIT with t_lo < t at depth 0.5 (t_lo + t) (the refinement).  Placement is decided
-// by count -> scan -> write launches as in occupancy_kernels.hip (launch_scan_totals scans the block totals, wave64 ballots and
-// population counts place a ray inside its block): no atomics, the same output on every run.  Every floating-point step is one
+// by count -> scan -> write launches as in occupancy_kernels.hip (block_scan.h; launch_scan_totals scans the block totals): no
+// atomics, the same output on every run.  Every floating-point step is one
 // explicitly rounded operation (__fmul_rn / __fadd_rn / __fsub_rn, never a fused multiply-add), so that tests/trace_check.py restates
 // all of it in numpy float32, bit for bit.
 //
@@ -21,6 +21,7 @@
 // origins, directions and points are 12 bytes apart: consecutive lanes cover them without gaps.  The compacted kernels reach the state
 // through an ascending index, i.e. nearly coalesced.  The cost of tracing lies in the field evaluations between these kernels.
 #include "kernels.h"
+#include "block_scan.h"
 
 namespace neddf {
 
@@ -79,18 +80,10 @@ template <bool kBisect> __device__ __forceinline__ bool trace_selected(const Tra
 
 template <bool kBisect> __global__ void __launch_bounds__(kOccThreads) trace_count_kernel(TraceState st, int64_t n, int64_t *blk)
 {
-    __shared__ int lds[kOccThreads / 64];
     const int64_t i = (int64_t)blockIdx.x * kOccThreads + threadIdx.x;
     float depth;
-    const bool k = i < n && trace_selected<kBisect>(st, i, &depth);
-    const unsigned long long ballot = __ballot(k);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = (int)__popcll(ballot);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-        for (int w = 0; w < kOccThreads / 64; ++w) total += lds[w];
-        blk[blockIdx.x] = total;
-    }
+    const int total = __syncthreads_count(i < n && trace_selected<kBisect>(st, i, &depth));
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
 }
 
 template <bool kBisect> __global__ void __launch_bounds__(kOccThreads) trace_write_kernel(const float *ro, const float *rd, TraceState st, int64_t n,
@@ -100,15 +93,9 @@ template <bool kBisect> __global__ void __launch_bounds__(kOccThreads) trace_wri
     const int64_t i = (int64_t)blockIdx.x * kOccThreads + threadIdx.x;
     float depth = 0.f;
     const bool k = i < n && trace_selected<kBisect>(st, i, &depth);
-    const unsigned long long ballot = __ballot(k);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int in_wave = (int)__popcll(ballot & ((1ull << lane) - 1ull));
-    if (lane == 0) lds[wave] = (int)__popcll(ballot);
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wave; ++w) before += lds[w];
+    const int rank = block_rank(k, lds);
     if (!k) return;
-    const int64_t o = blk[blockIdx.x] + before + in_wave;
+    const int64_t o = blk[blockIdx.x] + rank;
 #pragma unroll
     for (int a = 0; a < 3; ++a) pos[3 * o + a] = __fadd_rn(ro[3 * i + a], __fmul_rn(depth, rd[3 * i + a]));
     index[o] = (int32_t)i;

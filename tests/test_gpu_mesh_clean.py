@@ -1,7 +1,7 @@
 """Mesh clean-up on the GPU: neddf_mesh_components and neddf_mesh_compact against the host restatement
 (tests/mesh_clean_check.py) exactly -- every result is an integer or a copied bit pattern -- on marching-cubes meshes with
-floaters, shreds, a tie, a long tube and no triangles at all, a hand-made irregular mesh, the two-call protocol, the guard
-bands, extract_mesh's clean-up options on the shipped bunny and neddf/scripts/extract_mesh.py end to end."""
+floaters, shreds, a tie, a long tube and no triangles at all, a hand-made irregular mesh, triangle strips that end at the edges of a
+wave and of a workgroup, the two-call protocol, the guard bands, extract_mesh's clean-up options on the shipped bunny and neddf/scripts/extract_mesh.py end to end."""
 import ctypes as C
 import os
 
@@ -135,6 +135,45 @@ def test_hand_made_mesh(dev):
     keep = rng.random(700) < 0.5
     _same_compaction(compact_mesh(v, t, torch.from_numpy(keep).to(dev)), cc.compact_mesh(vn, tn, keep), "isolated triangles")
     _same_compaction(remove_small_components(v, t, 2, 0), cc.remove_small_components(vn, tn, 2, 0), "isolated triangles")
+
+
+def _strip(V):
+    """A triangle strip over V vertices built on the host: triangle i = (i, i + 1, i + 2), T = V - 2; vertex 0 carries a NaN payload."""
+    v = np.random.default_rng(V).standard_normal((V, 3)).astype(np.float32)
+    v.view(np.int32)[0, 1] = 0x7fc01234
+    t = (np.arange(V - 2, dtype=np.int32)[:, None] + np.arange(3, dtype=np.int32)[None, :]).astype(np.int32)
+    return v, t
+
+
+def _strip_masks(T):
+    every_other = np.zeros(T, np.uint8)
+    every_other[::2] = 1
+    last = np.zeros(T, np.uint8)
+    last[-1] = 1
+    every_fourth = np.zeros(T, np.uint8)            # leaves every fourth vertex unused: a vertex's rank differs from its index
+    every_fourth[::4] = 1
+    return {"all": np.ones(T, np.uint8), "none": np.zeros(T, np.uint8), "every other": every_other, "only the last": last,
+            "every fourth": every_fourth}
+
+
+@pytest.mark.parametrize("V", [63, 64, 65, 255, 256, 257, 1025])
+def test_strip_ranks_across_waves_and_workgroups(dev, V):
+    """The kernels that place by rank inside the workgroup (cc_root_label, compact_vertex, compact_triangle) at the edges of a wave
+    (64 lanes) and of a workgroup (256 threads): kept elements that end or begin exactly there, none, all, and a single one in the
+    last workgroup.  Every result against tests/mesh_clean_check.py bit for bit.  A strip is one component (one root); every
+    fourth and every third triangle alone give separate components with roots in every wave."""
+    from neddf_amd.mesh import compact_mesh, connected_components
+    vn, tn = _strip(V)
+    v, t = torch.from_numpy(vn).to(dev), torch.from_numpy(tn).to(dev)
+    for name, keep in _strip_masks(len(tn)).items():
+        what = ("strip", V, name)
+        _same_compaction(compact_mesh(v, t, torch.from_numpy(keep).to(dev)), cc.compact_mesh(vn, tn, keep), what)
+        sub = np.ascontiguousarray(tn[keep != 0])
+        _same_components(connected_components(torch.from_numpy(sub).to(dev), V), cc.connected_components(sub, V), what)
+    sub = np.ascontiguousarray(tn[::3])
+    want = cc.connected_components(sub, V)
+    assert len(want[2]) == len(sub) == (V - 2 + 2) // 3
+    _same_components(connected_components(torch.from_numpy(sub).to(dev), V), want, ("strip", V, "every third"))
 
 
 def test_compact_two_call_protocol_and_errors(dev, meshes):
