@@ -615,6 +615,55 @@ int neddf_trace_field(neddf_ctx *ctx, int slot, const float *d_ray_orig, const f
                       const neddf_trace_params *params, float *d_t, float *d_t_lo, unsigned char *d_status, int32_t *d_steps, float *d_dist,
                       int64_t *h_evaluations, void *stream);
 
+/* ---- distances between surfaces (additive to ABI v7; no reference counterpart: its evaluation compares images only) ------
+ * Random numbers: hash(seed, t, k, w) = mix(mix(mix(mix(seed + 0x9e3779b9) ^ t) ^ k) + w * 0x85ebca6b) in uint32 arithmetic with
+ * mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16; a uniform is (hash >> 8) * 2^-24.
+ *
+ * Surface samples of an indexed mesh (d_vertices [V][3] float, d_triangles [T][3] int32), `density` samples per unit area:
+ *   - triangle t receives floor(A_t * density + u_t) samples, in fp64: A_t = 0.5 sqrt(|e1 x e2|^2) from the fp32 edges e1 = p1 - p0,
+ *     e2 = p2 - p0 widened to double, u_t = uniform(seed, t, 0xffffffff, 2): floor(A density) or one more, A density on average
+ *   - 0 for a triangle with an index outside [0, V), a non-finite vertex, a zero or non-finite area
+ *   - sample k of triangle t: (a, b) = uniform(seed, t, k, 0 / 1), folded (a + b > 1: a = 1 - a, b = 1 - b), p = (p0 + a * e1) + b * e2
+ *     per axis, every operation one rounded fp32 operation (no fused multiply-add, no square root)
+ *   - order: triangle-major; d_points [N][3] float, d_triangle_id [N] int32.  Count / scan / write launches, no atomics: the output
+ *     does not depend on timing or on the launch shape (tests/geometry_check.py restates it in numpy bit for bit)
+ * _count writes *h_n_samples (HOST) = N; _write counts again and, with N > 0, needs both outputs and sample_cap >= N (NEDDF_EINVAL
+ * otherwise).  Each synchronises `stream` once.  NEDDF_EINVAL also for a density that is negative or not finite and for N >= 2^31
+ * (never a wrapped count); NEDDF_EUNSUPPORTED for V >= 2^31. */
+int neddf_mesh_sample_count(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                            double density, uint32_t seed, int64_t *h_n_samples, void *stream);
+int neddf_mesh_sample_write(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                            double density, uint32_t seed, float *d_points, int32_t *d_triangle_id, int64_t sample_cap,
+                            int64_t *h_n_samples, void *stream);
+/* Exact nearest neighbour of every query (d_queries [Q][3]) among the targets (d_targets [N][3]): d_d2 [Q] float, d_index [Q] int32.
+ *   - d2 = (dx dx + dy dy) + dz dz with dx = qx - px, every operation one rounded fp32 operation
+ *   - the result is the LOWEST target index that attains the minimal d2 (best starts at (+inf, -1); candidate j replaces it when
+ *     d2 < best, or d2 == best and j is below the current index, -1 counting as highest): it does not depend on the visiting order
+ *   - a target with a non-finite coordinate is never a candidate; a query with one gets (NaN, -1); no valid target: (+inf, -1)
+ * neddf_nn_brute: one lane per query visits every target (tiles staged through LDS) -- the yardstick of the grid and the method for
+ * small sets.  Q == 0 and N == 0 are legal.  NEDDF_EUNSUPPORTED for 2^31 points or more. */
+int neddf_nn_brute(neddf_ctx *ctx, const float *d_queries, int64_t n_queries, const float *d_targets, int64_t n_targets, float *d_d2,
+                   int32_t *d_index, void *stream);
+/* A uniform grid of h_cells = (gx, gy, gz) cells, each in [1, 1024] and at most 2^24 in all (NEDDF_EINVAL above), over the box h_lo ..
+ * h_hi (HOST doubles, finite, hi >= lo).  Per axis lo = (float)h_lo, inv_cell = (float)(g / (h_hi - h_lo)) with the quotient in double,
+ * 0 for a zero-extent axis; cell = f >= g ? g - 1 : f > 0 ? (int)f : 0 with f = (p - lo) * inv_cell in fp32 (two rounded operations):
+ * points outside the box land in border cells.  Cell (x, y, z) has index (z gy + y) gx + x.
+ *   - d_cell_start int32 [G + 1]: the number of finite targets in the cells before each cell, [G] = all of them = *h_n_valid (HOST)
+ *   - d_order int32 [capacity N]: the indices of the finite targets grouped by cell.  Histogram and placement use integer atomicAdd:
+ *     d_cell_start does not depend on timing, the order INSIDE a cell may -- the query's result does not (the tie rule above)
+ * Synchronises `stream` once. */
+int neddf_nn_grid_build(neddf_ctx *ctx, const float *d_targets, int64_t n_targets, const double *h_lo, const double *h_hi, const int *h_cells,
+                        int32_t *d_cell_start, int32_t *d_order, int64_t *h_n_valid, void *stream);
+/* neddf_nn_brute's result, bit for bit, through the grid neddf_nn_grid_build made of the same targets, box and cells (any box, also one
+ * that covers only part of the points): one lane per query visits the Chebyshev shells r = 0, 1, 2, ... of cells around the query's
+ * (clamped) cell and stops after shell r once (r * safe_cell)^2 > best d2 and >= 1e-30, safe_cell = 0.99 * the smallest cell edge --
+ * every target of a later shell is at least r smallest cell edges away, the 1 % covers every fp32 rounding involved -- or when the
+ * shell has left the grid on all sides.  d_order may be NULL when the build listed no target (*h_n_valid == 0): every query then gets
+ * (+inf, -1). */
+int neddf_nn_grid_query(neddf_ctx *ctx, const float *d_queries, int64_t n_queries, const float *d_targets, int64_t n_targets,
+                        const double *h_lo, const double *h_hi, const int *h_cells, const int32_t *d_cell_start, const int32_t *d_order,
+                        float *d_d2, int32_t *d_index, void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

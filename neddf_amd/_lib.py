@@ -157,6 +157,12 @@ SYMBOLS = [
     ("neddf_trace_bisect_points", C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
     ("neddf_trace_bisect_update", C.c_int, [_vp, _vp, _vp, _i64, _i64, C.c_float, _vp, _vp, _vp, _vp]),
     ("neddf_trace_field", C.c_int, [_vp, C.c_int, _vp, _vp, _i64, C.POINTER(TraceParams), _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    # (the uint32 seed travels as a C int: the same 32 bits in the same register; _seed() below folds it into that range)
+    ("neddf_mesh_sample_count", C.c_int, [_vp, _vp, _i64, _vp, _i64, C.c_double, C.c_int, C.POINTER(_i64), _vp]),
+    ("neddf_mesh_sample_write", C.c_int, [_vp, _vp, _i64, _vp, _i64, C.c_double, C.c_int, _vp, _vp, _i64, C.POINTER(_i64), _vp]),
+    ("neddf_nn_brute", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    ("neddf_nn_grid_build", C.c_int, [_vp, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), _vp, _vp, C.POINTER(_i64), _vp]),
+    ("neddf_nn_grid_query", C.c_int, [_vp, _vp, _i64, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _lib = None
@@ -182,6 +188,14 @@ def load():
 
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _seed(seed):
+    """A seed in [0, 2^32) as the signed 32-bit integer with the same bits."""
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 32:
+        raise NeddfError("the seed must fit 32 bits (got %r)" % (seed,))
+    return seed - 2 ** 32 if seed >= 2 ** 31 else seed
 
 
 def require_device(t, what):
@@ -520,6 +534,65 @@ class Context:
         vmap = torch.empty(v.shape[0], device=v.device, dtype=torch.int32)
         call(ov, ot, vmap)
         return ov, ot, vmap
+
+    # ------------------------------------------------------------------ distances between surfaces
+    def mesh_sample_count(self, vertices, triangles, density, seed):
+        """How many surface samples `density` (per unit area) and `seed` give the mesh (neddf_mesh_sample_count)."""
+        require_device(vertices, "vertices")
+        t = self._triangles(triangles, "mesh_sample_count")
+        v = f32c(vertices)
+        n = _i64(0)
+        self.check(self.lib.neddf_mesh_sample_count(self.h, _ptr(v), v.shape[0], _ptr(t), t.shape[0], float(density), _seed(seed), C.byref(n),
+                                                    self.stream()))
+        return int(n.value)
+
+    def mesh_sample_write(self, vertices, triangles, density, seed, n):
+        """The n = mesh_sample_count(...) samples (neddf_mesh_sample_write): (points float32 [n, 3], triangle_id int32 [n])."""
+        require_device(vertices, "vertices")
+        t = self._triangles(triangles, "mesh_sample_write")
+        v = f32c(vertices)
+        pts = torch.empty(int(n), 3, device=v.device, dtype=torch.float32)
+        tid = torch.empty(int(n), device=v.device, dtype=torch.int32)
+        got = _i64(0)
+        self.check(self.lib.neddf_mesh_sample_write(self.h, _ptr(v), v.shape[0], _ptr(t), t.shape[0], float(density), _seed(seed), _ptr(pts),
+                                                    _ptr(tid), int(n), C.byref(got), self.stream()))
+        if got.value != int(n):
+            raise NeddfError("mesh_sample_write: %d samples counted, %d expected" % (got.value, int(n)))
+        return pts, tid
+
+    @staticmethod
+    def _grid_args(lo, hi, cells):
+        if len(tuple(lo)) != 3 or len(tuple(hi)) != 3 or len(tuple(cells)) != 3:
+            raise NeddfError("nearest-neighbour grid: lo, hi and cells must have 3 entries each (got %r, %r, %r)" % (lo, hi, cells))
+        return (C.c_double * 3)(*[float(x) for x in lo]), (C.c_double * 3)(*[float(x) for x in hi]), (C.c_int * 3)(*[int(x) for x in cells])
+
+    def nn_brute(self, queries, targets):
+        """Exact nearest target of every query by brute force (neddf_nn_brute): (d2 float32 [Q], index int32 [Q])."""
+        d2 = torch.empty(queries.shape[0], device=queries.device, dtype=torch.float32)
+        idx = torch.empty(queries.shape[0], device=queries.device, dtype=torch.int32)
+        self.check(self.lib.neddf_nn_brute(self.h, _ptr(queries), queries.shape[0], _ptr(targets), targets.shape[0], _ptr(d2), _ptr(idx),
+                                           self.stream()))
+        return d2, idx
+
+    def nn_grid_build(self, targets, lo, hi, cells):
+        """The uniform grid of the targets (neddf_nn_grid_build): (cell_start int32 [G + 1], order int32 [N_valid])."""
+        blo, bhi, bc = self._grid_args(lo, hi, cells)
+        g = int(cells[0]) * int(cells[1]) * int(cells[2])
+        start = torch.empty(max(g, 0) + 1, device=targets.device, dtype=torch.int32)
+        order = torch.empty(targets.shape[0], device=targets.device, dtype=torch.int32)
+        n = _i64(0)
+        self.check(self.lib.neddf_nn_grid_build(self.h, _ptr(targets), targets.shape[0], blo, bhi, bc, _ptr(start), _ptr(order), C.byref(n),
+                                                self.stream()))
+        return start, order[:n.value]
+
+    def nn_grid_query(self, queries, targets, lo, hi, cells, cell_start, order):
+        """Exact nearest target of every query through the grid (neddf_nn_grid_query): (d2 float32 [Q], index int32 [Q])."""
+        blo, bhi, bc = self._grid_args(lo, hi, cells)
+        d2 = torch.empty(queries.shape[0], device=queries.device, dtype=torch.float32)
+        idx = torch.empty(queries.shape[0], device=queries.device, dtype=torch.int32)
+        self.check(self.lib.neddf_nn_grid_query(self.h, _ptr(queries), queries.shape[0], _ptr(targets), targets.shape[0], blo, bhi, bc,
+                                                _ptr(cell_start), _ptr(order), _ptr(d2), _ptr(idx), self.stream()))
+        return d2, idx
 
     def composite(self, dists, dens, col, max_dist):
         require_device(dists, "dists")

@@ -12,14 +12,16 @@
 
 namespace neddf {
 
-// sum of one int per thread over the workgroup (every thread receives it); lds: blockDim.x / 64 ints, free again on return
-__device__ __forceinline__ int block_sum(int v, int *lds)
+// sum of one integer (int, or int64_t where a total may pass 2^31) per thread over the workgroup (every thread receives it);
+// lds: blockDim.x / 64 values, free again on return
+template <typename T>
+__device__ __forceinline__ T block_sum(T v, T *lds)
 {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     const int wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
     if ((threadIdx.x & 63) == 0) lds[wave] = v;
     __syncthreads();
-    int t = 0;
+    T t = 0;
     for (int w = 0; w < n_waves; ++w) t += lds[w];
     __syncthreads();
     return t;

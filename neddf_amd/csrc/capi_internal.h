@@ -105,6 +105,7 @@ struct neddf_ctx {
     DevBuf brick_flags, brick_blk;            // neddf_brick_select: two byte planes of one flag per brick, block totals
     DevBuf brick_mask, brick_vbase;           // neddf_marching_cubes_bricks: owned crossed edges and first vertex id per brick lattice point
     DevBuf trace_blk, trace_ws;  // sphere tracing: block totals of the compactions; neddf_trace_field's index / points / distances / constant inputs
+    DevBuf geom_blk, geom_ws;    // neddf_mesh_sample_* / neddf_nn_grid_build: block totals; the cell of every target and the count of every cell
     int64_t cull_samples = 0, cull_kept = 0;  // neddf_cull_stats: samples classified / kept by the culled render passes
     std::vector<GuardBand> carve_guards;      // NEDDF_GUARD=1: the bands behind the carves of the last render call
     bool timing = false;

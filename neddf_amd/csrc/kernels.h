@@ -323,6 +323,28 @@ void launch_trace_finish(unsigned char *status, int64_t n, hipStream_t s);
 // dir = (1, 0, 0), var = 0 for n rows: the constant field inputs of a distance-only evaluation
 void launch_trace_unit_inputs(float *dir, float *var, int64_t n, hipStream_t s);
 
+// Distances between surfaces (geom_kernels.hip): area-weighted surface samples of an indexed mesh, exact nearest neighbours by brute
+// force and through a uniform grid.  Every launcher takes counts >= 0 and launches nothing over an empty range.
+constexpr int kNnMaxAxis = 1024;                         // cells per axis of the grid (the stopping rule's error bound assumes it)
+constexpr int64_t kNnMaxCells = (int64_t)1 << 24;        // cells in all: 64 MiB of cell_start
+struct NnGrid {
+    int n[3];                            // cells per axis (x, y, z); cell (x, y, z) at linear index (z n[1] + y) n[0] + x
+    float lo[3], inv_cell[3];            // cell = (p - lo) * inv_cell per axis, clamped to the grid; inv_cell 0 for a zero-extent axis
+    float safe_cell;                     // 0.99 * the smallest cell edge over the axes with an extent (FLT_MAX when there is none)
+};
+// per-block sample totals of the triangles, scanned: blk [mc_blocks(T) + 1], blk[mc_blocks(T)] = the number of samples afterwards
+void launch_sample_count(const float *v, int64_t V, const int32_t *tri, int64_t T, double density, uint32_t seed, int64_t *blk, hipStream_t s);
+// points [N, 3] and triangle_id [N], triangle-major (N < 2^31: the caller has read the total)
+void launch_sample_write(const float *v, int64_t V, const int32_t *tri, int64_t T, double density, uint32_t seed, const int64_t *blk, float *points,
+                         int32_t *triangle_id, hipStream_t s);
+void launch_nn_brute(const float *q, int64_t nq, const float *p, int64_t np, float *d2, int32_t *index, hipStream_t s);
+// cell_of [np], count [cells] (workspace); blk [mc_blocks(cells) + 1], blk[mc_blocks(cells)] = the number of finite targets afterwards;
+// cell_start [cells + 1], order [capacity np]
+void launch_nn_grid_build(const NnGrid &g, const float *p, int64_t np, int32_t *cell_of, int32_t *count, int64_t *blk, int32_t *cell_start,
+                          int32_t *order, hipStream_t s);
+void launch_nn_grid_query(const NnGrid &g, const float *q, int64_t nq, const float *p, int64_t np, const int32_t *cell_start, const int32_t *order,
+                          float *d2, int32_t *index, hipStream_t s);
+
 void launch_linear_grad(const float *x, const float *J, int64_t n, int cin, int ldx, int cout_block, int ksteps, const float *wp,
                         const float *bias, float *y, float *G, int ldo, int nvalid, int accumulate, int grid, hipStream_t s);
 void launch_op_activation(int kind, const float *x, const float *J, int64_t N, int C, float *y, float *G, hipStream_t s);

@@ -761,7 +761,8 @@ void neddf_destroy(neddf_ctx *ctx)
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack, &ctx->ttmp, &ctx->tamax,
                       &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc,
                       &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk, &ctx->occ_cells, &ctx->occ_blk,
-                      &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase, &ctx->trace_blk, &ctx->trace_ws })
+                      &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase, &ctx->trace_blk, &ctx->trace_ws,
+                      &ctx->geom_blk, &ctx->geom_ws })
         if (b->p) (void)hipFree(b->base ? b->base : b->p);
     for (auto &e : ctx->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : ctx->pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -782,7 +783,8 @@ int neddf_debug_check_guards(neddf_ctx *ctx, int64_t *n_bands, int64_t *n_bad_by
     for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack,
                        &ctx->ttmp, &ctx->tamax, &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc,
                       &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk, &ctx->occ_cells, &ctx->occ_blk,
-                      &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase, &ctx->trace_blk, &ctx->trace_ws })
+                      &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase, &ctx->trace_blk, &ctx->trace_ws,
+                      &ctx->geom_blk, &ctx->geom_ws })
         if (b->base) {
             bands.push_back(GuardBand{ b->base, kGuardBytes });
             bands.push_back(GuardBand{ (char *)b->p + b->cap, kGuardBytes });
@@ -1932,3 +1934,127 @@ int neddf_trace_field(neddf_ctx *ctx, int slot, const float *d_ray_orig, const f
 }
 
 }  // extern "C"
+
+// ---- distances between surfaces (geom_kernels.hip) ----
+static int sample_args_ok(neddf_ctx *ctx, const float *v, int64_t V, const int32_t *tri, int64_t T, double density, const int64_t *h_n)
+{
+    if (V < 0 || T < 0) return fail(ctx, NEDDF_EINVAL, "mesh_sample: negative count");
+    if (!h_n || (T > 0 && !tri) || (V > 0 && !v)) return fail(ctx, NEDDF_EINVAL, "mesh_sample: NULL vertices, triangles or count");
+    if (!(density >= 0.0) || !std::isfinite(density)) return fail(ctx, NEDDF_EINVAL, "mesh_sample: the density must be finite and not negative");
+    if (V >= ((int64_t)1 << 31) || mc_blocks(T) > 0x7fffffff) return fail(ctx, NEDDF_EUNSUPPORTED, "mesh_sample: 2^31 vertices or more, or too many triangles");
+    return 0;
+}
+
+// count -> scan -> one synchronise; *n = the number of samples, NEDDF_EINVAL when it does not fit int32
+static int sample_total(neddf_ctx *ctx, const float *v, int64_t V, const int32_t *tri, int64_t T, double density, uint32_t seed, int64_t *n, hipStream_t s)
+{
+    if (int rc = ensure(ctx, ctx->geom_blk, (size_t)(mc_blocks(T) + 1) * sizeof(int64_t))) return rc;
+    int64_t *blk = (int64_t *)ctx->geom_blk.p;
+    launch_sample_count(v, V, tri, T, density, seed, blk, s);
+    if (int rc = read_totals(ctx, s, { { n, blk + mc_blocks(T) } })) return rc;
+    if (*n > 0x7fffffff) return fail(ctx, NEDDF_EINVAL, "mesh_sample: the density gives 2^31 samples or more (indices are int32)");
+    return 0;
+}
+
+int neddf_mesh_sample_count(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles, double density,
+                            uint32_t seed, int64_t *h_n_samples, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = sample_args_ok(ctx, d_vertices, n_vertices, d_triangles, n_triangles, density, h_n_samples)) return rc;
+    DeviceGuard guard_(ctx->device);
+    return sample_total(ctx, d_vertices, n_vertices, d_triangles, n_triangles, density, seed, h_n_samples, (hipStream_t)stream);
+}
+
+int neddf_mesh_sample_write(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles, double density,
+                            uint32_t seed, float *d_points, int32_t *d_triangle_id, int64_t sample_cap, int64_t *h_n_samples, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = sample_args_ok(ctx, d_vertices, n_vertices, d_triangles, n_triangles, density, h_n_samples)) return rc;
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = sample_total(ctx, d_vertices, n_vertices, d_triangles, n_triangles, density, seed, h_n_samples, s)) return rc;
+    if (*h_n_samples == 0) return 0;
+    if (!d_points || !d_triangle_id || sample_cap < *h_n_samples) return fail(ctx, NEDDF_EINVAL, "mesh_sample_write: NULL outputs or a capacity below the count");
+    launch_sample_write(d_vertices, n_vertices, d_triangles, n_triangles, density, seed, (const int64_t *)ctx->geom_blk.p, d_points, d_triangle_id, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int nn_counts_ok(neddf_ctx *ctx, int64_t nq, const float *q, int64_t np, const float *p, const char *what)
+{
+    if (nq < 0 || np < 0) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": negative count");
+    if ((nq > 0 && !q) || (np > 0 && !p)) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": NULL points");
+    if (nq >= ((int64_t)1 << 31) || np >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, std::string(what) + ": 2^31 points or more (indices are int32)");
+    return 0;
+}
+
+int neddf_nn_brute(neddf_ctx *ctx, const float *d_queries, int64_t n_queries, const float *d_targets, int64_t n_targets, float *d_d2, int32_t *d_index,
+                   void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = nn_counts_ok(ctx, n_queries, d_queries, n_targets, d_targets, "nn_brute")) return rc;
+    if (n_queries > 0 && (!d_d2 || !d_index)) return fail(ctx, NEDDF_EINVAL, "nn_brute: NULL outputs");
+    DeviceGuard guard_(ctx->device);
+    launch_nn_brute(d_queries, n_queries, d_targets, n_targets, d_d2, d_index, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the grid of a box and its cell counts: lo = (float)h_lo, inv_cell = (float)(cells / (h_hi - h_lo)) with the quotient in double (0 for a
+// zero-extent axis), safe_cell = 0.99 / max(inv_cell) rounded to float
+static int nn_grid(neddf_ctx *ctx, const double *h_lo, const double *h_hi, const int *h_cells, NnGrid *g, const char *what)
+{
+    if (!h_lo || !h_hi || !h_cells) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": NULL box or cells");
+    int64_t n_cells = 1;
+    float inv_max = 0.f;
+    for (int a = 0; a < 3; ++a) {
+        if (h_cells[a] < 1 || h_cells[a] > kNnMaxAxis) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": 1 to 1024 cells per axis");
+        if (!std::isfinite(h_lo[a]) || !std::isfinite(h_hi[a]) || !(h_hi[a] >= h_lo[a])) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": a finite box with hi >= lo expected");
+        g->n[a] = h_cells[a];
+        g->lo[a] = (float)h_lo[a];
+        const double ext = h_hi[a] - h_lo[a];
+        g->inv_cell[a] = ext > 0.0 ? (float)((double)h_cells[a] / ext) : 0.f;
+        if (!std::isfinite(g->lo[a]) || !std::isfinite(g->inv_cell[a])) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": the box does not fit fp32");
+        inv_max = g->inv_cell[a] > inv_max ? g->inv_cell[a] : inv_max;
+        n_cells *= h_cells[a];
+    }
+    if (n_cells > kNnMaxCells) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": more than 2^24 cells");
+    const double safe = inv_max > 0.f ? 0.99 / (double)inv_max : 3.0e38;
+    g->safe_cell = safe < 3.0e38 ? (float)safe : 3.0e38f;
+    return 0;
+}
+
+int neddf_nn_grid_build(neddf_ctx *ctx, const float *d_targets, int64_t n_targets, const double *h_lo, const double *h_hi, const int *h_cells,
+                        int32_t *d_cell_start, int32_t *d_order, int64_t *h_n_valid, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = nn_counts_ok(ctx, 0, nullptr, n_targets, d_targets, "nn_grid_build")) return rc;
+    NnGrid g;
+    if (int rc = nn_grid(ctx, h_lo, h_hi, h_cells, &g, "nn_grid_build")) return rc;
+    if (!d_cell_start || !h_n_valid || (n_targets > 0 && !d_order)) return fail(ctx, NEDDF_EINVAL, "nn_grid_build: NULL cell_start, order or count");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_cells = (int64_t)g.n[0] * g.n[1] * g.n[2], nb = mc_blocks(n_cells);
+    if (int rc = ensure(ctx, ctx->geom_blk, (size_t)(nb + 1) * sizeof(int64_t))) return rc;
+    if (int rc = ensure(ctx, ctx->geom_ws, (size_t)(n_targets + n_cells) * sizeof(int32_t))) return rc;
+    int32_t *cell_of = (int32_t *)ctx->geom_ws.p, *count = cell_of + n_targets;
+    int64_t *blk = (int64_t *)ctx->geom_blk.p;
+    launch_nn_grid_build(g, d_targets, n_targets, cell_of, count, blk, d_cell_start, d_order, s);
+    return read_totals(ctx, s, { { h_n_valid, blk + nb } });
+}
+
+int neddf_nn_grid_query(neddf_ctx *ctx, const float *d_queries, int64_t n_queries, const float *d_targets, int64_t n_targets, const double *h_lo,
+                        const double *h_hi, const int *h_cells, const int32_t *d_cell_start, const int32_t *d_order, float *d_d2, int32_t *d_index,
+                        void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = nn_counts_ok(ctx, n_queries, d_queries, n_targets, d_targets, "nn_grid_query")) return rc;
+    NnGrid g;
+    if (int rc = nn_grid(ctx, h_lo, h_hi, h_cells, &g, "nn_grid_query")) return rc;
+    if (!d_cell_start || (n_queries > 0 && (!d_d2 || !d_index))) return fail(ctx, NEDDF_EINVAL, "nn_grid_query: NULL cell_start or outputs");
+    DeviceGuard guard_(ctx->device);
+    // a NULL order is the empty list of a build that found no finite target: no range of it is followed
+    launch_nn_grid_query(g, d_queries, n_queries, d_targets, d_order ? n_targets : 0, d_cell_start, d_order, d_d2, d_index, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}

@@ -1,4 +1,5 @@
-"""Surface extraction: marching cubes on the GPU, mesh clean-up (connected components, floater removal) and a PLY writer.
+"""Surface extraction: marching cubes on the GPU, mesh clean-up (connected components, floater removal), area-weighted surface
+sampling and a PLY writer and reader.
 
 The reference meshes a trained field inside its Open3D viewer (neddf/scripts/fields_visualizer.py:528-566: voxelize ->
 PyMCubes -> .dae).  Here the grid evaluation and marching cubes are HIP kernels (include/neddf_hip.h neddf_field_grid,
@@ -215,4 +216,115 @@ def write_ply(path, vertices, triangles, normals=None, colors=None):
     return path
 
 
-__all__ = ["marching_cubes", "select_bricks", "marching_cubes_bricks", "vertex_normals", "connected_components", "compact_mesh", "remove_small_components", "write_ply"]
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply(path):
+    """(vertices float32 [V, 3], triangles int32 [T, 3]) as numpy arrays from a PLY file with the elements write_ply produces: `vertex`
+    with scalar properties among which x, y, z (normals, colours and others are skipped) and `face` with one list property of 3 indices
+    per face -- binary little-endian, as write_ply writes its three variants, or ASCII.  ValueError on anything else."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError("read_ply: %s is not a PLY file (no `ply` magic or no end_header)" % path)
+    lines = [ln.split() for ln in data[:end].decode("ascii", "replace").splitlines()[1:] if ln.strip() and not ln.startswith(("comment", "obj_info"))]
+    body = data[end + len(b"end_header\n"):]
+    if not lines or lines[0][:1] != ["format"] or len(lines[0]) != 3 or lines[0][1] not in ("binary_little_endian", "ascii"):
+        raise ValueError("read_ply: %s: format binary_little_endian or ascii expected (got %r)" % (path, " ".join(lines[0]) if lines else ""))
+    binary = lines[0][1] == "binary_little_endian"
+    elements = []                                       # [name, count, [(property name, scalar type) or (name, count type, item type)]]
+    for ln in lines[1:]:
+        try:
+            if ln[0] == "element" and len(ln) == 3:
+                elements.append([ln[1], int(ln[2]), []])
+            elif ln[0] == "property" and elements and len(ln) == 3:
+                elements[-1][2].append((ln[2], _PLY_TYPES[ln[1]]))
+            elif ln[0] == "property" and elements and len(ln) == 5 and ln[1] == "list":
+                elements[-1][2].append((ln[4], _PLY_TYPES[ln[2]], _PLY_TYPES[ln[3]]))
+            else:
+                raise KeyError(ln[0])
+        except (KeyError, ValueError):
+            raise ValueError("read_ply: %s: header line %r not understood" % (path, " ".join(ln))) from None
+    if [e[0] for e in elements] != ["vertex", "face"] or min(e[1] for e in elements) < 0:
+        raise ValueError("read_ply: %s: the elements `vertex` then `face` expected (got %s)" % (path, [e[0] for e in elements]))
+    (_, nv, vprops), (_, nf, fprops) = elements
+    names = [p[0] for p in vprops]
+    if any(len(p) != 2 for p in vprops) or any(k not in names for k in "xyz") or len(set(names)) != len(names):
+        raise ValueError("read_ply: %s: the vertex element needs scalar properties x, y, z (got %s)" % (path, names))
+    if len(fprops) != 1 or len(fprops[0]) != 3 or fprops[0][1][0] == "f" or fprops[0][2][0] == "f":
+        raise ValueError("read_ply: %s: the face element needs exactly one list property of integer indices" % path)
+    if binary:
+        vdt = np.dtype([(n, "<" + t) for n, t in vprops])
+        fdt = np.dtype([("n", "<" + fprops[0][1]), ("i", "<" + fprops[0][2], (3,))])
+        need = nv * vdt.itemsize + nf * fdt.itemsize
+        if len(body) < need:
+            raise ValueError("read_ply: %s is truncated: %d bytes of data, %d needed for %d vertices and %d triangles" % (path, len(body), need, nv, nf))
+        rec = np.frombuffer(body, dtype=vdt, count=nv)
+        faces = np.frombuffer(body, dtype=fdt, count=nf, offset=nv * vdt.itemsize)
+        if nf and (faces["n"] != 3).any():
+            raise ValueError("read_ply: %s: only triangles are supported (a face with %d vertices found)" % (path, int(faces["n"][faces["n"] != 3][0])))
+        verts = np.stack([rec[k].astype(np.float32) for k in "xyz"], axis=1) if nv else np.zeros((0, 3), np.float32)
+        tris = faces["i"].astype(np.int32)
+    else:
+        rows = body.decode("ascii", "replace").split("\n")
+        rows = [r.split() for r in rows if r.strip()]
+        if len(rows) < nv + nf:
+            raise ValueError("read_ply: %s is truncated: %d data lines, %d needed" % (path, len(rows), nv + nf))
+        try:
+            col = [names.index(k) for k in "xyz"]
+            if any(len(r) != len(names) for r in rows[:nv]):
+                raise ValueError("a vertex line with the wrong number of values")
+            verts = np.array([[float(r[c]) for c in col] for r in rows[:nv]], np.float32).reshape(nv, 3)
+            if any(len(r) != 4 or int(r[0]) != 3 for r in rows[nv:nv + nf]):
+                raise ValueError("only triangles `3 i j k` are supported")
+            tris = np.array([[int(x) for x in r[1:]] for r in rows[nv:nv + nf]], np.int64).reshape(nf, 3).astype(np.int32)
+        except ValueError as e:
+            raise ValueError("read_ply: %s: %s" % (path, e)) from None
+    return np.ascontiguousarray(verts), np.ascontiguousarray(tris.reshape(nf, 3))
+
+
+def surface_area(vertices, triangles):
+    """The total area of a device mesh as a Python float: a torch fp64 sum over the triangles with every index in [0, V) (plumbing: it
+    turns sample_surface's `n` into a density and is not part of the bit-checked path)."""
+    t = triangles.long()
+    ok = ((t >= 0) & (t < vertices.shape[0])).all(dim=1)
+    p = vertices.double()[t[ok]]
+    a = 0.5 * torch.linalg.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]).norm(dim=1)
+    return float(a[torch.isfinite(a)].sum().item())
+
+
+def sample_surface(vertices, triangles, density=None, n=None, seed=0):
+    """Area-weighted random points on a device mesh: (points float32 [N, 3], triangle_id int32 [N]), triangle-major
+    (include/neddf_hip.h neddf_mesh_sample_count / neddf_mesh_sample_write).
+
+    Exactly one of `density` (samples per unit area) and `n` is given.  Triangle t receives floor(A_t * density + u_t) samples, u_t
+    uniform in [0, 1) -- A_t * density on average -- so with `n` (turned into density = n / total area) the number of points returned
+    is CLOSE to n, not equal to it.  The points are a pure function of the mesh, the density and `seed`: the same call gives the same
+    bits on every run; triangles with an index outside [0, V), a non-finite vertex or no area receive none."""
+    _device_mesh("sample_surface", vertices=vertices, triangles=triangles)
+    if (density is None) == (n is None):
+        raise NeddfError("sample_surface: exactly one of density and n must be given")
+    if vertices.device != triangles.device:
+        raise NeddfError("sample_surface: vertices and triangles must live on one device (got %s, %s)" % (vertices.device, triangles.device))
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise NeddfError("sample_surface: vertices must be float32 [V, 3] (got %s %s)" % (vertices.dtype, tuple(vertices.shape)))
+    if not 0 <= int(seed) < 2 ** 32:
+        raise NeddfError("sample_surface: the seed must fit 32 bits (got %r)" % (seed,))
+    if n is not None:
+        if int(n) < 0:
+            raise NeddfError("sample_surface: n must not be negative (got %r)" % (n,))
+        area = surface_area(vertices, triangles)
+        density = int(n) / area if area > 0.0 else 0.0
+    density = float(density)
+    if not (density >= 0.0 and density < float("inf")):
+        raise NeddfError("sample_surface: the density must be finite and not negative (got %r)" % (density,))
+    ctx = Context.get(vertices.device)
+    v = vertices.contiguous()
+    count = ctx.mesh_sample_count(v, triangles, density, seed)
+    return ctx.mesh_sample_write(v, triangles, density, seed, count)
+
+
+__all__ = ["marching_cubes", "select_bricks", "marching_cubes_bricks", "vertex_normals", "connected_components", "compact_mesh", "remove_small_components", "write_ply",
+           "read_ply", "sample_surface", "surface_area"]
