@@ -1097,7 +1097,8 @@ int neddf_raygen_backward(neddf_ctx *ctx, const void *uv, int uv_type, int64_t n
                           const float *g_ro, float *g_RT, void *stream)
 {
     if (!ctx) return NEDDF_EINVAL;
-    if (!uv || !cam || !g_rd || !g_ro || !g_RT || n < 0) return fail(ctx, NEDDF_EINVAL, "raygen_backward: bad argument");
+    // (no rays: the arrays of an empty batch may be null pointers -- the kernel reads none of them and writes zeros)
+    if (!cam || !g_RT || n < 0 || (n > 0 && (!uv || !g_rd || !g_ro))) return fail(ctx, NEDDF_EINVAL, "raygen_backward: bad argument");
     if (uv_type < 0 || uv_type > 3) return fail(ctx, NEDDF_EINVAL, "bad uv_type");
     DeviceGuard guard_(ctx->device);
     CameraArg c;

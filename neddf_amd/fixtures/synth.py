@@ -292,3 +292,33 @@ def input_digest(pos, d, var, ups):
         assert a.dtype == np.float32
         h.update(np.ascontiguousarray(a).tobytes())
     return np.array([np.sum(a, dtype=np.float64) for a in arrs]), h.hexdigest()
+
+
+# ---------------------------------------------------------------- input gradients by backward route (tests/golden/pose_grad_routes.npz)
+# case -> (field kind, rays, samples per ray, seed of the points, seed of the upstream gradients).  The networks are named in the
+# fixture (`<case>_config`, `<case>_state_seed`, `<case>_iteration`); the points are used flattened, [rays * samples, 3].
+POSE_ROUTE_CASES = {
+    "bunny": ("neddf", 7, 14, 9401, 9501),
+    "neddf128": ("neddf", 7, 14, 9402, 9502),
+    "neddf192": ("neddf", 7, 14, 9403, 9503),
+    "neddf384": ("neddf", 7, 14, 9404, 9504),
+    "neddf512": ("neddf", 7, 14, 9405, 9505),
+    "nerf128": ("nerf", 7, 14, 9406, 9506),
+    "nerf384": ("nerf", 7, 14, 9407, 9507),
+    "nerf512": ("nerf", 7, 14, 9408, 9508),
+    "ranks_hi": ("neddf", 7, 14, 9409, 9509),
+    "nerf_ranks_hi": ("nerf", 7, 14, 9410, 9510),
+    "ranks_lo": ("neddf", 7, 14, 9411, 9511),
+    "bunny_many": ("neddf", 8231, 1, 9412, 9512),
+    "neddf512_many": ("neddf", 8231, 1, 9413, 9513),
+}
+
+
+def pose_route_inputs(case):
+    """(pos, dir, var, upstream gradients by key) of one case of pose_grad_routes.npz, from its seeds: `random_sampling` cone samples and
+    standard-normal upstream gradients on every output of the field."""
+    kind, rays, samples, seed_pts, seed_ups = POSE_ROUTE_CASES[case]
+    pos, d, var = random_sampling(rays, samples, seed_pts, cone=True)
+    rng = np.random.default_rng(seed_ups)
+    ups = OrderedDict((k, rng.standard_normal((rays, samples) + ((3,) if k == "color" else ())).astype(np.float32)) for k in FIELD_KEYS[kind])
+    return pos, d, var, ups

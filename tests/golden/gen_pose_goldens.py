@@ -18,6 +18,8 @@ Records
   refinement   rf_*         the reference's Adam trajectory on camera.params for the view of tests/golden/bunny_pose (written here too)
                             from a perturbed pose with the field frozen: settings, initial and final pose error
 `python gen_pose_goldens.py step` / `refine` regenerate those parts alone and merge them into the existing fixture.
+`python gen_pose_goldens.py routes` writes tests/golden/pose_grad_routes.npz alone (gen_routes: the field's input gradients in fp64 on
+every backward route of the training ABI; results only, the inputs are rebuilt from seeds).
 """
 import json
 import os
@@ -323,8 +325,102 @@ def gen_step(arrs):
         print("  step %s: camera.params.grad = %s" % (tag, np.array2string(npy(cam.params.grad), precision=4)))
 
 
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROUTES_MAX_BYTES = 1 << 20          # the size limit of a committed file
+KINK_GATE = 1e-4 / 3                # a third of the tests' base gate, of the largest entry
+KINK_CAP = 32                       # at most one point in 32 of a case may be marked
+ROUTES_OUT_STRIDE = {"bunny_many": 4, "neddf512_many": 4}       # the many-workgroup cases store the outputs of every 4th point (file size)
+
+
+def _route_networks():
+    """case -> (constructor, keywords, state dict (numpy), iteration).  Architectures that already have a parameter-gradient fixture are
+    taken from it (stored `*_config`, the state seed of its generator), so these are the networks test_gpu_train.py already gates."""
+    from neddf.network import NeRF
+    cfg = yaml.safe_load(open(os.path.join(REF, "pretrained/bunny_smoke/.hydra/config.yaml")))
+    bunny_kw = dict(cfg["network"], density_activation_type="ReLU")
+    bunny_kw.pop("_target_")
+    sd = torch.load(os.path.join(REF, "pretrained/bunny_smoke/models/model_02000.pth"), map_location="cpu")
+    bunny_sd = {k[len("network_fine."):]: npy(v) for k, v in sd.items() if k.startswith("network_fine.")}
+    nets = {"bunny": (NeDDF, bunny_kw, bunny_sd, 1500, -1)}
+    for case, fx, seed, it in (("neddf128", "train_widths.npz", 29, 2500), ("neddf192", "train_widths.npz", 29, 2500),
+                               ("neddf384", "train_wide.npz", 37, 2500), ("neddf512", "train_wide.npz", 37, 2500),
+                               ("nerf128", "train_widths.npz", 31, 1500), ("nerf384", "train_wide_nerf.npz", 41, 1500),
+                               ("nerf512", "train_wide_nerf.npz", 41, 1500)):
+        kw = json.loads(str(np.load(os.path.join(HERE, fx))[case + "_config"]))
+        nets[case] = (NeRF if case.startswith("nerf") else NeDDF, kw, None, it, seed)
+    # the encoding limits of the input-gradient kernel: 6 x 10 = 60 of the 64 S-columns, 6 x 20 = 120 of the 128 U-columns; ranks of 1
+    nets["ranks_hi"] = (NeDDF, dict(embed_pos_rank=10, embed_dir_rank=10, ddf_layer_count=5, ddf_layer_width=256, col_layer_count=3,
+                                    col_layer_width=256, d_near=0.01, activation_type="tanhExp", density_activation_type="ReLU", skips=[1],
+                                    lowpass_alpha_offset=10), None, 2500, 43)
+    nets["nerf_ranks_hi"] = (NeRF, dict(embed_pos_rank=10, embed_dir_rank=10, layer_count=5, layer_width=256, activation_type="tanhExp",
+                                        density_activation_type="ReLU", skips=[2], lowpass_alpha_offset=10), None, 1500, 44)
+    nets["ranks_lo"] = (NeDDF, dict(embed_pos_rank=1, embed_dir_rank=1, ddf_layer_count=5, ddf_layer_width=256, col_layer_count=3,
+                                    col_layer_width=256, d_near=0.01, activation_type="LeakyReLU", density_activation_type="ReLU", skips=[1],
+                                    lowpass_alpha_offset=10), None, 2500, 45)
+    nets["bunny_many"], nets["neddf512_many"] = nets["bunny"], nets["neddf512"]
+    return nets
+
+
+def gen_routes():
+    """tests/golden/pose_grad_routes.npz: per case of synth.POSE_ROUTE_CASES the fp64 reference's pos.grad / dir.grad (stored as float32: a
+    rounding of 6e-8, far below the gates), the fp32 reference's outputs and its own deviation from fp64, the kink mask and the digest
+    of the inputs.  Kink points: an fp32 ReLU that flips against fp64 changes one point's gradient by a finite amount, in the reference
+    as much as in any fp32 implementation; the points whose fp32 reference gradient deviates from fp64 by more than KINK_GATE of the
+    largest entry are marked (packed bits), and the recorded deviations are taken over the unmarked points."""
+    arrs = {"cases": np.array(json.dumps(list(synth.POSE_ROUTE_CASES)))}
+    nets = _route_networks()
+    for case, (kind, rays, samples, _, _) in synth.POSE_ROUTE_CASES.items():
+        cls, kw, sd, iteration, state_seed = nets[case]
+        if sd is None:
+            sd = synth.arch_state(kind, kw, state_seed)
+        pos, dd, var, ups = synth.pose_route_inputs(case)
+        grads, outs = {}, None
+        for dt, name in ((torch.float32, "32"), (torch.float64, "64")):
+            torch.set_default_dtype(dt)         # the module's constants (frequencies, scales) are built in the default dtype
+            try:
+                m = cls(**kw)
+                m.load_state_dict({k: torch.from_numpy(np.asarray(v)).to(dt) for k, v in sd.items()})
+                m.set_iter(iteration)
+                leaves = [torch.from_numpy(a).to(dt).requires_grad_(True) for a in (pos, dd, var)]
+                with torch.enable_grad():
+                    o = m(Sampling(*leaves))
+                    sum((o[k] * torch.from_numpy(ups[k]).to(dt)).sum() for k in ups).backward()
+            finally:
+                torch.set_default_dtype(torch.float32)
+            assert leaves[2].grad is None, "the reference differentiates the cone weights after all"
+            grads[name] = [npy(leaves[0].grad).reshape(-1, 3), npy(leaves[1].grad).reshape(-1, 3)]
+            if name == "32":
+                outs = {k: npy(o[k]) for k in ups}
+        n = rays * samples
+        dev_pt = np.zeros(n)
+        for i in range(2):
+            dev_pt = np.maximum(dev_pt, np.abs(grads["32"][i].astype(np.float64) - grads["64"][i]).max(1) / np.abs(grads["64"][i]).max())
+        kink = dev_pt > KINK_GATE
+        assert kink.sum() * KINK_CAP <= n, ("%s: %d of %d points marked as kinks: change the sampling seed" % (case, kink.sum(), n))
+        pre = case + "_"
+        sums, sha = synth.input_digest(pos, dd, var, ups)
+        arrs.update({pre + "config": np.array(json.dumps(kw)), pre + "kind": np.array(kind), pre + "state_seed": np.int32(state_seed),
+                     pre + "iteration": np.int32(iteration), pre + "kink": np.packbits(kink), pre + "digest_sums": sums,
+                     pre + "digest_sha256": np.array(sha)})
+        stride = ROUTES_OUT_STRIDE.get(case, 1)
+        arrs[pre + "out_stride"] = np.int32(stride)
+        for k in ups:
+            arrs[pre + "out_" + k] = outs[k].reshape((n,) + outs[k].shape[2:])[::stride]
+        for i, what in enumerate(("pos", "dir")):
+            arrs[pre + "grad64_" + what] = grads["64"][i].astype(np.float32)
+            dn, de = _deviation(grads["32"][i][~kink], grads["64"][i][~kink])
+            arrs[pre + "ref32_norm_" + what], arrs[pre + "ref32_entry_" + what] = np.float64(dn), np.float64(de)
+            print("  %s d/d%s: reference fp32 vs fp64 norm %.2e entry %.2e (%d of %d points marked)" % (case, what, dn, de, kink.sum(), n), flush=True)
+    save("pose_grad_routes.npz", **arrs)
+    size = os.path.getsize(os.path.join(HERE, "pose_grad_routes.npz"))
+    assert size < ROUTES_MAX_BYTES, "pose_grad_routes.npz is %d bytes: above the size limit of a committed file" % size
+
+
 if __name__ == "__main__":
     arrs = {}
+    if len(sys.argv) > 1 and sys.argv[1] == "routes":       # the route fixture alone
+        gen_routes()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "refine":       # the slow part alone, merged into the existing fixture
         arrs = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "pose_grad.npz")))
         if not os.path.exists(os.path.join(POSE_VIEW_DIR, "test", "r_0.png")):
@@ -344,3 +440,4 @@ if __name__ == "__main__":
     gen_pose_view()
     gen_refine(arrs)
     save("pose_grad.npz", **arrs)
+    gen_routes()

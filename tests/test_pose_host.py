@@ -1,5 +1,7 @@
 """Host half of the pose gradients: ABI 7 and its symbols, configuration plumbing, and the fixture's own consistency
-(tests/golden/pose_grad.npz: params.grad is R.grad / T.grad pushed through Camera.update_transform by torch on the CPU)."""
+(tests/golden/pose_grad.npz: params.grad is R.grad / T.grad pushed through Camera.update_transform by torch on the CPU;
+tests/golden/pose_grad_routes.npz: digests of the regenerated inputs, kink cap, size), and the fp64 restatements of
+test_gpu_pose_routes.py against the reference's recorded sampler and ray-generation gradients."""
 import os
 import re
 
@@ -69,3 +71,52 @@ def test_refine_pose_alias_and_cli():
     assert (a.epoch, a.view, a.steps, a.batch) == (12, 3, 5, 32) and a.perturb == [0.1, 0, 0, 0, -0.2, 0] and str(a.output_dir) == "runs/x"
     d = refine_pose.build_parser().parse_args(["r"])
     assert d.perturb == [0.0] * 6 and d.view == 0
+
+
+def test_route_fixture_is_consistent():
+    """pose_grad_routes.npz loads, stays under the size limit of a committed file, its inputs regenerate from their seeds to the recorded
+    digests, and at most one point in 32 of a case is marked as a kink."""
+    import json
+    import synth
+    from conftest import GOLDEN
+    assert os.path.getsize(os.path.join(GOLDEN, "pose_grad_routes.npz")) < 1 << 20
+    g = golden("pose_grad_routes.npz")
+    assert json.loads(str(g["cases"])) == list(synth.POSE_ROUTE_CASES)
+    for case, (kind, rays, samples, _, _) in synth.POSE_ROUTE_CASES.items():
+        n = rays * samples
+        pos, d, var, ups = synth.pose_route_inputs(case)
+        sums, sha = synth.input_digest(pos, d, var, ups)
+        assert sha == str(g[case + "_digest_sha256"]), case
+        np.testing.assert_array_equal(sums, g[case + "_digest_sums"], err_msg=case)
+        assert str(g[case + "_kind"]) == kind and list(ups) == list(synth.FIELD_KEYS[kind])
+        bits = np.unpackbits(g[case + "_kink"])
+        assert len(bits) >= n and not bits[n:].any()
+        assert int(bits[:n].sum()) * 32 <= n, (case, int(bits[:n].sum()))
+        stride = int(g[case + "_out_stride"])
+        for k in ups:
+            assert g[case + "_out_" + k].shape[0] == (n + stride - 1) // stride
+        for what in ("pos", "dir"):
+            grad = g[case + "_grad64_" + what]
+            assert grad.shape == (n, 3) and grad.dtype == np.float32 and np.isfinite(grad).all() and grad.any()
+            # deviations over the unmarked points: below the marking threshold by construction
+            assert 0 <= float(g[case + "_ref32_entry_" + what]) <= 1e-4 / 3 and 0 <= float(g[case + "_ref32_norm_" + what]) <= 1e-4 / 3
+
+
+def test_restatements_reproduce_the_reference_gradients():
+    """The fp64 restatements of the samplers and of ray generation that test_gpu_pose_routes.py measures the kernels against give the
+    reference's own recorded gradients (pose_grad.npz `s_*`, `r_*`: torch autograd in fp32) within 1e-6 of the largest entry."""
+    from test_gpu_pose_routes import raygen_backward_restatement, sampler_backward_restatement
+    g = golden("pose_grad.npz")
+
+    def same(what, got, want):
+        dev = np.abs(np.asarray(got, np.float64) - want).max() / np.abs(want).max()
+        assert dev <= 1e-6, (what, dev)
+
+    for tag, radius in (("cone", float(g["s_radius"])), ("point", None)):
+        # (the reference's cone variance is differentiable in the ray direction, its point variance is a constant zero)
+        g_rd, g_ro = sampler_backward_restatement(g["s_ro"], g["s_rd"], g["s_dists"], radius, g["s_g_pos"], g["s_g_dir"], g["s_g_var"])
+        same(tag + " d/dray_dir", g_rd, g["s_%s_grad_rd" % tag])
+        same(tag + " d/dray_orig", g_ro, g["s_%s_grad_ro" % tag])
+    gR, gT = raygen_backward_restatement(g["r_uv"], g["r_calib"], g["r_g_rd"], g["r_g_ro"])
+    same("d/dR", gR, g["r_grad_R"])
+    same("d/dT", gT, g["r_grad_T"])
