@@ -664,6 +664,77 @@ int neddf_nn_grid_query(neddf_ctx *ctx, const float *d_queries, int64_t n_querie
                         const double *h_lo, const double *h_hi, const int *h_cells, const int32_t *d_cell_start, const int32_t *d_order,
                         float *d_d2, int32_t *d_index, void *stream);
 
+/* ---- ray casting on meshes (additive to ABI v7; no reference counterpart: the reference looks at meshes through its Open3D viewer) ------
+ * The first intersection of rays (d_ray_orig, d_ray_dir [R][3] float, directions of any length) with an indexed mesh (d_vertices [V][3]
+ * float, d_triangles [T][3] int32), by the watertight test of Woop, Benthin and Wald (JCGT 2013).  Every operation below is ONE
+ * rounded fp32 operation unless stated (no fused multiply-add; `/` is the correctly rounded division); tests/raycast_check.py
+ * restates it in numpy bit for bit.
+ *   per ray (o, d):  kz = the axis of the largest |d| (the lowest axis among equals), kx = (kz + 1) % 3, ky = (kx + 1) % 3, kx and ky
+ *       swapped when d[kz] < 0;  Sz = 1 / d[kz], Sx = d[kx] * Sz, Sy = d[ky] * Sz
+ *   per vertex P:    A = P - o;  Ax = A[kx] - Sx * A[kz], Ay = A[ky] - Sy * A[kz], Az = Sz * A[kz]   (B and C alike)
+ *   edge functions:  U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax; when any of the three is exactly 0 all three
+ *       are computed again with both products and the difference in fp64, then rounded to fp32
+ *   the triangle is a CANDIDATE when U, V, W are all >= 0 or all <= 0 (two-sided: no back-face culling), det = (U + V) + W is not 0,
+ *       t = ((U * Az + V * Bz) + W * Cz) / det satisfies t_min <= t <= t_max (a NaN fails every comparison), and the hit point
+ *       p = o + t * d (per axis a rounded product, then a rounded sum) lies in the triangle's bounding box widened by pad on every
+ *       side (the bounds min3 - pad and max3 + pad are one rounded operation each).  The box clause discards the garbage t of a nearly
+ *       degenerate triangle, and it is what makes the grid equal to brute force (below)
+ *   result per ray:  d_t, d_triangle (int32), d_b1 = V / det, d_b2 = W / det -- the hit point is p0 + b1 (p1 - p0) + b2 (p2 - p0).  The
+ *       smallest t wins, among equal t the LOWEST triangle index (best starts at (+inf, -1, 0, 0); a candidate replaces it when
+ *       t < best, or t == best and its index is below the current one, -1 counting as highest): the result does not depend on the
+ *       visiting order.  No candidate: (+inf, -1, 0, 0).  A ray with a non-finite component or an all-zero direction: (NaN, -1, NaN,
+ *       NaN).  A triangle with an index outside [0, V) or a non-finite vertex is never a candidate.
+ * pad must be finite and >= 0 (NEDDF_EINVAL).  Every entry point: NEDDF_EINVAL for a negative count or a NULL array it needs,
+ * NEDDF_EUNSUPPORTED from 2^31 rays, triangles or vertices on (indices are int32).
+ * neddf_raycast_brute: one lane per ray visits every triangle (tiles staged through LDS) -- the yardstick of the grid and the method
+ * for small meshes.  R == 0 and T == 0 are legal. */
+int neddf_raycast_brute(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_vertices, int64_t n_vertices,
+                        const int32_t *d_triangles, int64_t n_triangles, float t_min, float t_max, float pad, float *d_t, int32_t *d_triangle,
+                        float *d_b1, float *d_b2, void *stream);
+/* The grid: neddf_nn_grid_build's cells (h_lo, h_hi, h_cells: the same parameters, cell function and limits).  With wlo = (float)h_lo -
+ * 2 pad and whi = (float)h_hi + 2 pad per axis (one rounded fp32 operation each; 2 pad is exact):
+ *   - a valid triangle whose box widened by 2 pad, [min3 - 2 pad, max3 + 2 pad] (rounded likewise), lies in [wlo, whi] on every axis is
+ *     listed in the cells cell(min3 - 2 pad) .. cell(max3 + 2 pad) per axis;
+ *   - any other valid triangle is listed once, in the overflow list (index G = gx gy gz), which every ray tests by brute force: the
+ *     result is right for ANY box.  A box that holds every vertex -- the mesh's own bounds -- leaves the list empty.
+ * d_cell_start int32 [G + 2]: the number of (list, triangle) pairs before each list, [G + 1] = all of them = *h_n_items (HOST);
+ * d_items int32 [item_cap]: the triangle indices grouped by list.  Count and placement use integer atomicAdd: d_cell_start does not
+ * depend on timing, the order INSIDE a list may -- no result does (the tie rule).  _count returns the number of pairs; _build needs
+ * item_cap >= that number (d_items may be NULL when it is 0), counts again, and returns NEDDF_EINVAL when the capacity is short or
+ * the number reaches 2^31 (never a wrapped count).  Each of the two synchronises `stream` once.
+ *
+ * neddf_raycast_grid_query: neddf_raycast_brute's bits with the same pad, for any box, any cell counts and any rays, through the
+ * lists _build made of the same mesh, box, cells and pad (n_items = its *h_n_items).  One lane per ray: the overflow list, then the
+ * ray's [t_min, t_max] clipped to [wlo, whi] (fp64 slabs) and a 3D-DDA through the cells from the clipped start.  The parameter at
+ * which the ray leaves cell i of an axis is computed afresh from the integer index in fp64, ((lo + (i + 1) * edge) - o) / d with
+ * edge = 1 / (double)inv_cell, never accumulated; a border cell has no far side (the cell function clamps), so the walk ends at
+ * the clipped end of the ray, or early once best t < t_exit - 1e-6 |t_exit|, t_exit the parameter at which the ray leaves the current cell.
+ *
+ * THE EQUALITY ARGUMENT.  Let a candidate of the brute kernel have parameter t and rounded hit point p.
+ *   (1) p lies within pad of the triangle's box B (the box clause); the exact point p* = o + t d lies within eps_p of p, where eps_p <=
+ *       2^-24 (|o| + 2 |p|) per axis is the rounding of the product and of the sum.
+ *   (2) The triangle is listed in every cell that cell() assigns to a point of B widened by 2 pad (cell() is monotone per axis), or
+ *       it is in the overflow list.  A listed triangle has B inside the box, so p* lies inside [wlo, whi] with pad - eps_p to spare
+ *       and t inside the clipped range.
+ *   (3) The walk's cells tile the clipped range: at parameter t it is in a cell whose ideal interval holds p* per axis up to the fp64
+ *       rounding of the exit parameters, and cell()'s steps lie within 3 * 2^-24 of (extent + 4 pad) of the ideal ones.  Call the sum
+ *       of the two delta.  As long as delta + eps_p + the rounding of the widened bounds (2^-24 of |coordinate|) < pad, a point within
+ *       pad + eps_p of B that the walk places in cell c has c inside the listed range: the triangle is met.
+ *   (4) Ending early is safe: a hit with t below the current cell's exit parameter lies in a cell already visited, by (3).
+ * Hence NEDDF_EINVAL (_count, _build, _query) for a pad below 2^-16 times the largest of |lo|, |hi| and hi - lo over the axes: delta
+ * and the bounds' rounding then stay below 2^-6 pad.  eps_p is the ray's: a ray whose origin has a coordinate beyond
+ * 2^21 pad - 2 (that largest value + 2 pad) -- eps_p could pass pad / 8 -- does not walk the grid but visits every triangle.
+ * Visiting more triangles, or one twice, never changes the result (the tie rule). */
+int neddf_raycast_grid_count(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                             const double *h_lo, const double *h_hi, const int *h_cells, float pad, int64_t *h_n_items, void *stream);
+int neddf_raycast_grid_build(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                             const double *h_lo, const double *h_hi, const int *h_cells, float pad, int32_t *d_cell_start, int32_t *d_items,
+                             int64_t item_cap, int64_t *h_n_items, void *stream);
+int neddf_raycast_grid_query(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_vertices, int64_t n_vertices,
+                             const int32_t *d_triangles, int64_t n_triangles, const double *h_lo, const double *h_hi, const int *h_cells, float pad,
+                             const int32_t *d_cell_start, const int32_t *d_items, int64_t n_items, float t_min, float t_max, float *d_t,
+                             int32_t *d_triangle, float *d_b1, float *d_b2, void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

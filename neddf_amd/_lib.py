@@ -163,6 +163,11 @@ SYMBOLS = [
     ("neddf_nn_brute", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     ("neddf_nn_grid_build", C.c_int, [_vp, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), _vp, _vp, C.POINTER(_i64), _vp]),
     ("neddf_nn_grid_query", C.c_int, [_vp, _vp, _i64, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_raycast_brute", C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_raycast_grid_count", C.c_int, [_vp, _vp, _i64, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), C.c_float, C.POINTER(_i64), _vp]),
+    ("neddf_raycast_grid_build", C.c_int, [_vp, _vp, _i64, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), C.c_float, _vp, _vp, _i64, C.POINTER(_i64), _vp]),
+    ("neddf_raycast_grid_query", C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), C.c_float, _vp, _vp, _i64,
+                                           C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _lib = None
@@ -593,6 +598,50 @@ class Context:
         self.check(self.lib.neddf_nn_grid_query(self.h, _ptr(queries), queries.shape[0], _ptr(targets), targets.shape[0], blo, bhi, bc,
                                                 _ptr(cell_start), _ptr(order), _ptr(d2), _ptr(idx), self.stream()))
         return d2, idx
+
+    # ------------------------------------------------------------------ ray casting on meshes
+    @staticmethod
+    def _hit_buffers(n, device):
+        return (torch.empty(n, device=device, dtype=torch.float32), torch.empty(n, device=device, dtype=torch.int32),
+                torch.empty(n, device=device, dtype=torch.float32), torch.empty(n, device=device, dtype=torch.float32))
+
+    def raycast_brute(self, origins, dirs, vertices, triangles, t_min, t_max, pad):
+        """The first hit of every ray by brute force (neddf_raycast_brute): (t float32 [R], triangle int32 [R], b1, b2 float32 [R])."""
+        t, j, b1, b2 = self._hit_buffers(origins.shape[0], origins.device)
+        self.check(self.lib.neddf_raycast_brute(self.h, _ptr(origins), _ptr(dirs), origins.shape[0], _ptr(vertices), vertices.shape[0],
+                                                _ptr(triangles), triangles.shape[0], float(t_min), float(t_max), float(pad), _ptr(t), _ptr(j),
+                                                _ptr(b1), _ptr(b2), self.stream()))
+        return t, j, b1, b2
+
+    def raycast_grid_count(self, vertices, triangles, lo, hi, cells, pad):
+        """The number of (list, triangle) pairs of the ray-casting grid (neddf_raycast_grid_count)."""
+        blo, bhi, bc = self._grid_args(lo, hi, cells)
+        n = _i64(0)
+        self.check(self.lib.neddf_raycast_grid_count(self.h, _ptr(vertices), vertices.shape[0], _ptr(triangles), triangles.shape[0], blo, bhi, bc,
+                                                     float(pad), C.byref(n), self.stream()))
+        return int(n.value)
+
+    def raycast_grid_build(self, vertices, triangles, lo, hi, cells, pad, item_cap):
+        """The ray-casting grid (neddf_raycast_grid_build): (cell_start int32 [G + 2], items int32 [item_cap])."""
+        blo, bhi, bc = self._grid_args(lo, hi, cells)
+        g = int(cells[0]) * int(cells[1]) * int(cells[2])
+        start = torch.empty(max(g, 0) + 2, device=vertices.device, dtype=torch.int32)
+        items = torch.empty(int(item_cap), device=vertices.device, dtype=torch.int32)
+        n = _i64(0)
+        self.check(self.lib.neddf_raycast_grid_build(self.h, _ptr(vertices), vertices.shape[0], _ptr(triangles), triangles.shape[0], blo, bhi, bc,
+                                                     float(pad), _ptr(start), _ptr(items) if items.numel() else None, int(item_cap), C.byref(n),
+                                                     self.stream()))
+        return start, items[:n.value]
+
+    def raycast_grid_query(self, origins, dirs, vertices, triangles, lo, hi, cells, pad, cell_start, items, t_min, t_max):
+        """The first hit of every ray through the grid (neddf_raycast_grid_query): raycast_brute's result, bit for bit."""
+        blo, bhi, bc = self._grid_args(lo, hi, cells)
+        t, j, b1, b2 = self._hit_buffers(origins.shape[0], origins.device)
+        self.check(self.lib.neddf_raycast_grid_query(self.h, _ptr(origins), _ptr(dirs), origins.shape[0], _ptr(vertices), vertices.shape[0],
+                                                     _ptr(triangles), triangles.shape[0], blo, bhi, bc, float(pad), _ptr(cell_start),
+                                                     _ptr(items) if items.numel() else None, items.shape[0], float(t_min), float(t_max),
+                                                     _ptr(t), _ptr(j), _ptr(b1), _ptr(b2), self.stream()))
+        return t, j, b1, b2
 
     def composite(self, dists, dens, col, max_dist):
         require_device(dists, "dists")

@@ -178,12 +178,7 @@ __global__ void __launch_bounds__(kNnThreads) nn_brute_kernel(const float *q, in
     out_j[i] = best.j;
 }
 
-__device__ __forceinline__ int grid_axis_cell(float p, float lo, float inv_cell, int g)
-{
-    const float f = __fmul_rn(__fsub_rn(p, lo), inv_cell);
-    return f >= (float)g ? g - 1 : (f > 0.f ? (int)f : 0);
-}
-
+// (grid_axis_cell: kernels.h -- raycast_kernels.hip lists triangles by the same cell function)
 __device__ __forceinline__ int grid_cell(const NnGrid &g, float x, float y, float z, int *cx, int *cy, int *cz)
 {
     *cx = grid_axis_cell(x, g.lo[0], g.inv_cell[0], g.n[0]);

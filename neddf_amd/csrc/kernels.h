@@ -332,6 +332,12 @@ struct NnGrid {
     float lo[3], inv_cell[3];            // cell = (p - lo) * inv_cell per axis, clamped to the grid; inv_cell 0 for a zero-extent axis
     float safe_cell;                     // 0.99 * the smallest cell edge over the axes with an extent (FLT_MAX when there is none)
 };
+// the cell of coordinate p along one axis: two rounded fp32 operations, monotone in p, clamped to the grid (NaN: 0)
+__device__ __forceinline__ int grid_axis_cell(float p, float lo, float inv_cell, int g)
+{
+    const float f = __fmul_rn(__fsub_rn(p, lo), inv_cell);
+    return f >= (float)g ? g - 1 : (f > 0.f ? (int)f : 0);
+}
 // per-block sample totals of the triangles, scanned: blk [mc_blocks(T) + 1], blk[mc_blocks(T)] = the number of samples afterwards
 void launch_sample_count(const float *v, int64_t V, const int32_t *tri, int64_t T, double density, uint32_t seed, int64_t *blk, hipStream_t s);
 // points [N, 3] and triangle_id [N], triangle-major (N < 2^31: the caller has read the total)
@@ -344,6 +350,26 @@ void launch_nn_grid_build(const NnGrid &g, const float *p, int64_t np, int32_t *
                           int32_t *order, hipStream_t s);
 void launch_nn_grid_query(const NnGrid &g, const float *q, int64_t nq, const float *p, int64_t np, const int32_t *cell_start, const int32_t *order,
                           float *d2, int32_t *index, hipStream_t s);
+
+// Ray casting on meshes (raycast_kernels.hip): the first watertight hit of every ray by brute force and through the uniform grid of
+// NnGrid's cells, each listing the triangles whose box, widened by 2 pad, overlaps it; list G holds the triangles that leave the box.
+struct RcGrid {
+    NnGrid nn;
+    float pad, pad2;                     // pad and 2 pad
+    float wlo[3], whi[3];                // the box widened by 2 pad: (float)h_lo - pad2 and (float)h_hi + pad2, one rounded operation each
+    float far_origin;                    // a ray whose origin has a larger |coordinate| visits every triangle instead of walking the grid
+    double lo[3], edge[3];               // the walk's cells: (double)nn.lo and 1 / (double)nn.inv_cell (0 for an axis without extent)
+};
+void launch_raycast_brute(const float *ro, const float *rd, int64_t nr, const float *v, int64_t V, const int32_t *tri, int64_t T, float t_min,
+                          float t_max, float pad, float *t, int32_t *triangle, float *b1, float *b2, hipStream_t s);
+// count [G + 1] (workspace): the pairs of every list; blk [mc_blocks(G + 1) + 1], blk[mc_blocks(G + 1)] = the number of pairs afterwards
+void launch_raycast_grid_count(const RcGrid &g, const float *v, int64_t V, const int32_t *tri, int64_t T, int32_t *count, int64_t *blk, hipStream_t s);
+// after launch_raycast_grid_count and once the total is known to fit int32 and items: cell_start [G + 2], items [total]
+void launch_raycast_grid_place(const RcGrid &g, const float *v, int64_t V, const int32_t *tri, int64_t T, int32_t *count, const int64_t *blk,
+                               int32_t *cell_start, int32_t *items, hipStream_t s);
+void launch_raycast_grid_query(const RcGrid &g, const float *ro, const float *rd, int64_t nr, const float *v, int64_t V, const int32_t *tri, int64_t T,
+                               const int32_t *cell_start, const int32_t *items, int64_t n_items, float t_min, float t_max, float *t, int32_t *triangle,
+                               float *b1, float *b2, hipStream_t s);
 
 void launch_linear_grad(const float *x, const float *J, int64_t n, int cin, int ldx, int cout_block, int ksteps, const float *wp,
                         const float *bias, float *y, float *G, int ldo, int nvalid, int accumulate, int grid, hipStream_t s);

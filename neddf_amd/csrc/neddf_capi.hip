@@ -2058,3 +2058,117 @@ int neddf_nn_grid_query(neddf_ctx *ctx, const float *d_queries, int64_t n_querie
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// ---- ray casting on meshes (raycast_kernels.hip) ----
+static int rc_counts_ok(neddf_ctx *ctx, int64_t nr, const float *ro, const float *rd, int64_t V, const float *v, int64_t T, const int32_t *tri, float pad,
+                        const char *what)
+{
+    if (nr < 0 || V < 0 || T < 0) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": negative count");
+    if ((nr > 0 && (!ro || !rd)) || (V > 0 && !v) || (T > 0 && !tri)) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": NULL rays, vertices or triangles");
+    if (!(pad >= 0.f) || !std::isfinite(pad)) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": pad must be finite and not negative");
+    if (nr >= ((int64_t)1 << 31) || V >= ((int64_t)1 << 31) || T >= ((int64_t)1 << 31))
+        return fail(ctx, NEDDF_EUNSUPPORTED, std::string(what) + ": 2^31 rays, triangles or vertices or more (indices are int32)");
+    return 0;
+}
+
+// the grid of a box, its cell counts and pad: neddf_nn_grid_build's cells, the box widened by 2 pad, the walk's fp64 cells and the
+// limits the equality argument of the header needs
+static int rc_grid(neddf_ctx *ctx, const double *h_lo, const double *h_hi, const int *h_cells, float pad, RcGrid *g, const char *what)
+{
+    if (int rc = nn_grid(ctx, h_lo, h_hi, h_cells, &g->nn, what)) return rc;
+    double scale = 0.0;
+    for (int a = 0; a < 3; ++a) scale = std::max(std::max(scale, std::fabs(h_lo[a])), std::max(std::fabs(h_hi[a]), h_hi[a] - h_lo[a]));
+    if (!((double)pad >= scale * 0x1p-16))
+        return fail(ctx, NEDDF_EINVAL, std::string(what) + ": pad below 2^-16 of the largest of |lo|, |hi| and the box extent (the grid would lose hits to rounding)");
+    g->pad = pad;
+    g->pad2 = 2.f * pad;
+    if (!std::isfinite(g->pad2)) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": 2 pad does not fit fp32");
+    for (int a = 0; a < 3; ++a) {
+        const float hi = (float)h_hi[a];
+        g->wlo[a] = g->nn.lo[a] - g->pad2;
+        g->whi[a] = hi + g->pad2;
+        if (!std::isfinite(g->wlo[a]) || !std::isfinite(g->whi[a])) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": the widened box does not fit fp32");
+        g->lo[a] = (double)g->nn.lo[a];
+        g->edge[a] = g->nn.inv_cell[a] > 0.f ? 1.0 / (double)g->nn.inv_cell[a] : 0.0;
+    }
+    // the rounding of o + t d, at most 2^-24 (|o| + 2 |p|) per axis, stays below pad / 8 for an origin inside this limit
+    const double far = (double)pad * 0x1p21 - 2.0 * (scale + 2.0 * (double)pad);
+    g->far_origin = far > 0.0 ? (far < 3.0e38 ? (float)far : 3.0e38f) : 0.f;
+    return 0;
+}
+
+int neddf_raycast_brute(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_vertices, int64_t n_vertices,
+                        const int32_t *d_triangles, int64_t n_triangles, float t_min, float t_max, float pad, float *d_t, int32_t *d_triangle,
+                        float *d_b1, float *d_b2, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = rc_counts_ok(ctx, n_rays, d_ray_orig, d_ray_dir, n_vertices, d_vertices, n_triangles, d_triangles, pad, "raycast_brute")) return rc;
+    if (n_rays > 0 && (!d_t || !d_triangle || !d_b1 || !d_b2)) return fail(ctx, NEDDF_EINVAL, "raycast_brute: NULL outputs");
+    DeviceGuard guard_(ctx->device);
+    launch_raycast_brute(d_ray_orig, d_ray_dir, n_rays, d_vertices, n_vertices, d_triangles, n_triangles, t_min, t_max, pad, d_t, d_triangle, d_b1,
+                         d_b2, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// count -> scan -> one synchronise; *n = the number of (list, triangle) pairs, NEDDF_EINVAL when it does not fit int32
+static int rc_total(neddf_ctx *ctx, const RcGrid &g, const float *v, int64_t V, const int32_t *tri, int64_t T, int64_t *n, hipStream_t s, const char *what)
+{
+    const int64_t n_lists = (int64_t)g.nn.n[0] * g.nn.n[1] * g.nn.n[2] + 1, nb = mc_blocks(n_lists);
+    if (int rc = ensure(ctx, ctx->geom_blk, (size_t)(nb + 1) * sizeof(int64_t))) return rc;
+    if (int rc = ensure(ctx, ctx->geom_ws, (size_t)n_lists * sizeof(int32_t))) return rc;
+    int64_t *blk = (int64_t *)ctx->geom_blk.p;
+    launch_raycast_grid_count(g, v, V, tri, T, (int32_t *)ctx->geom_ws.p, blk, s);
+    if (int rc = read_totals(ctx, s, { { n, blk + nb } })) return rc;
+    if (*n > 0x7fffffff) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": 2^31 (cell, triangle) pairs or more (offsets are int32): fewer cells, or a smaller pad");
+    return 0;
+}
+
+int neddf_raycast_grid_count(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                             const double *h_lo, const double *h_hi, const int *h_cells, float pad, int64_t *h_n_items, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = rc_counts_ok(ctx, 0, nullptr, nullptr, n_vertices, d_vertices, n_triangles, d_triangles, pad, "raycast_grid_count")) return rc;
+    RcGrid g;
+    if (int rc = rc_grid(ctx, h_lo, h_hi, h_cells, pad, &g, "raycast_grid_count")) return rc;
+    if (!h_n_items) return fail(ctx, NEDDF_EINVAL, "raycast_grid_count: NULL count");
+    DeviceGuard guard_(ctx->device);
+    return rc_total(ctx, g, d_vertices, n_vertices, d_triangles, n_triangles, h_n_items, (hipStream_t)stream, "raycast_grid_count");
+}
+
+int neddf_raycast_grid_build(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                             const double *h_lo, const double *h_hi, const int *h_cells, float pad, int32_t *d_cell_start, int32_t *d_items,
+                             int64_t item_cap, int64_t *h_n_items, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = rc_counts_ok(ctx, 0, nullptr, nullptr, n_vertices, d_vertices, n_triangles, d_triangles, pad, "raycast_grid_build")) return rc;
+    RcGrid g;
+    if (int rc = rc_grid(ctx, h_lo, h_hi, h_cells, pad, &g, "raycast_grid_build")) return rc;
+    if (!d_cell_start || !h_n_items) return fail(ctx, NEDDF_EINVAL, "raycast_grid_build: NULL cell_start or count");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = rc_total(ctx, g, d_vertices, n_vertices, d_triangles, n_triangles, h_n_items, s, "raycast_grid_build")) return rc;
+    if (*h_n_items > 0 && (!d_items || item_cap < *h_n_items)) return fail(ctx, NEDDF_EINVAL, "raycast_grid_build: NULL items or a capacity below the count");
+    launch_raycast_grid_place(g, d_vertices, n_vertices, d_triangles, n_triangles, (int32_t *)ctx->geom_ws.p, (const int64_t *)ctx->geom_blk.p,
+                              d_cell_start, *h_n_items > 0 ? d_items : nullptr, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_raycast_grid_query(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_vertices, int64_t n_vertices,
+                             const int32_t *d_triangles, int64_t n_triangles, const double *h_lo, const double *h_hi, const int *h_cells, float pad,
+                             const int32_t *d_cell_start, const int32_t *d_items, int64_t n_items, float t_min, float t_max, float *d_t,
+                             int32_t *d_triangle, float *d_b1, float *d_b2, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = rc_counts_ok(ctx, n_rays, d_ray_orig, d_ray_dir, n_vertices, d_vertices, n_triangles, d_triangles, pad, "raycast_grid_query")) return rc;
+    RcGrid g;
+    if (int rc = rc_grid(ctx, h_lo, h_hi, h_cells, pad, &g, "raycast_grid_query")) return rc;
+    if (!d_cell_start || n_items < 0 || n_items > 0x7fffffff || (n_items > 0 && !d_items) || (n_rays > 0 && (!d_t || !d_triangle || !d_b1 || !d_b2)))
+        return fail(ctx, NEDDF_EINVAL, "raycast_grid_query: NULL cell_start, items or outputs, or an item count outside [0, 2^31)");
+    DeviceGuard guard_(ctx->device);
+    launch_raycast_grid_query(g, d_ray_orig, d_ray_dir, n_rays, d_vertices, n_vertices, d_triangles, n_triangles, d_cell_start, d_items, n_items, t_min,
+                              t_max, d_t, d_triangle, d_b1, d_b2, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}

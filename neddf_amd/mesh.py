@@ -220,10 +220,12 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_ply(path):
+def read_ply(path, properties=False):
     """(vertices float32 [V, 3], triangles int32 [T, 3]) as numpy arrays from a PLY file with the elements write_ply produces: `vertex`
     with scalar properties among which x, y, z (normals, colours and others are skipped) and `face` with one list property of 3 indices
-    per face -- binary little-endian, as write_ply writes its three variants, or ASCII.  ValueError on anything else."""
+    per face -- binary little-endian, as write_ply writes its three variants, or ASCII.  ValueError on anything else.
+    properties=True: (vertices, triangles, normals, colors) -- normals float32 [V, 3] from nx, ny, nz and colors float32 [V, 3] from red,
+    green, blue as write_ply takes them (B, G, R order, value / 255 for an integer property), each None when the file lacks it."""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.find(b"end_header\n")
@@ -267,6 +269,9 @@ def read_ply(path):
             raise ValueError("read_ply: %s: only triangles are supported (a face with %d vertices found)" % (path, int(faces["n"][faces["n"] != 3][0])))
         verts = np.stack([rec[k].astype(np.float32) for k in "xyz"], axis=1) if nv else np.zeros((0, 3), np.float32)
         tris = faces["i"].astype(np.int32)
+
+        def column(k):
+            return rec[k].astype(np.float32)
     else:
         rows = body.decode("ascii", "replace").split("\n")
         rows = [r.split() for r in rows if r.strip()]
@@ -277,12 +282,24 @@ def read_ply(path):
             if any(len(r) != len(names) for r in rows[:nv]):
                 raise ValueError("a vertex line with the wrong number of values")
             verts = np.array([[float(r[c]) for c in col] for r in rows[:nv]], np.float32).reshape(nv, 3)
+
+            def column(k):
+                return np.array([float(r[names.index(k)]) for r in rows[:nv]], np.float32)
             if any(len(r) != 4 or int(r[0]) != 3 for r in rows[nv:nv + nf]):
                 raise ValueError("only triangles `3 i j k` are supported")
             tris = np.array([[int(x) for x in r[1:]] for r in rows[nv:nv + nf]], np.int64).reshape(nf, 3).astype(np.int32)
         except ValueError as e:
             raise ValueError("read_ply: %s: %s" % (path, e)) from None
-    return np.ascontiguousarray(verts), np.ascontiguousarray(tris.reshape(nf, 3))
+    verts, tris = np.ascontiguousarray(verts), np.ascontiguousarray(tris.reshape(nf, 3))
+    if not properties:
+        return verts, tris
+    normals = colors = None
+    if all(k in names for k in ("nx", "ny", "nz")):
+        normals = np.stack([column(k) for k in ("nx", "ny", "nz")], axis=1).reshape(nv, 3)
+    if all(k in names for k in ("red", "green", "blue")):
+        types = dict(vprops)
+        colors = np.stack([column(k) / np.float32(1.0 if types[k][0] == "f" else 255.0) for k in ("blue", "green", "red")], axis=1).reshape(nv, 3)
+    return verts, tris, normals, colors
 
 
 def surface_area(vertices, triangles):

@@ -516,6 +516,83 @@ class NeRFRender(BaseNeuralRender):
                 out = {k: v.reshape(h, w, 3) if v.dim() == 2 else v.reshape(h, w) for k, v in out.items()}
         return {k: out[k] for k in target_types}
 
+    MESH_TARGETS = ("depth", "transmittance", "triangle", "normal", "color")
+
+    def render_image_mesh(self, width: int, height: int, camera: Camera, vertices: Tensor, triangles: Tensor,
+                          target_types: Iterable[RenderTarget], normals: Optional[Tensor] = None, colors: Optional[Tensor] = None,
+                          downsampling: int = 1, pixel_range=None, method: str = "grid", background: float = 0.0, grid=None) -> Dict[str, Tensor]:
+        """A view of a triangle mesh (vertices float32 [V, 3], triangles int32 or int64 [T, 3] on the camera's device; not a
+        reference method): render_image_traced's world-space rays -- the same pixels -- meet the mesh between dist_near and
+        dist_far inside the library (raycast.cast_rays: the first watertight hit, method "grid" or "brute", the same bits).
+        Targets, [h, w, 3] or [h, w]:
+
+            depth          t on HIT pixels, 0 elsewhere
+            transmittance  0 on HIT pixels, 1 elsewhere (the hit mask)
+            triangle       int32: the triangle hit, -1 elsewhere
+            normal         the vertex `normals` [V, 3] interpolated at the hit when given, otherwise the face's geometric normal;
+                           normalised, turned to face the ray, 0 elsewhere
+            color          the vertex `colors` [V, 3] interpolated at the hit, `background` elsewhere (raises without colors)
+
+        pixel_range=(lo, hi) renders that slab of the row-major pixel index and returns flat tensors.  grid: the mesh's
+        raycast.build_grid, to be built once for many views (None: built here).  Interpolation and normals are torch gathers over
+        the hit pixels.  ray_space='ndc' raises.  No network is evaluated, no random number drawn."""
+        from .raycast import cast_rays
+        target_types = list(target_types)
+        unknown = [k for k in target_types if k not in self.MESH_TARGETS]
+        if unknown:
+            raise ValueError("render_image_mesh: unknown target(s) %s; it offers %s" % (unknown, list(self.MESH_TARGETS)))
+        if self.ray_space != "world":
+            raise NotImplementedError("render_image_mesh casts world-space rays: ray_space=%r is not supported" % (self.ray_space,))
+        if "color" in target_types and colors is None:
+            raise ValueError("render_image_mesh: the color target needs vertex colors")
+        for name, a in (("normals", normals), ("colors", colors)):
+            if a is not None and (a.dim() != 2 or tuple(a.shape) != tuple(vertices.shape)):
+                raise ValueError("render_image_mesh: %s must be [V, 3] like the vertices (got %s)" % (name, tuple(a.shape)))
+        with torch.no_grad():
+            dev = camera.device
+            w, h = width // downsampling, height // downsampling
+            us = torch.arange(w, device=dev).reshape(1, w).expand(h, w).reshape(-1) * downsampling
+            vs = torch.arange(h, device=dev).reshape(h, 1).expand(h, w).reshape(-1) * downsampling
+            lo, hi = (0, w * h) if pixel_range is None else pixel_range
+            uv = torch.stack([us, vs], 1)[lo:hi]
+            n = uv.shape[0]
+            rd, ro = self._ctx(dev).raygen(uv, camera.descriptor())
+            hits = cast_rays(ro, rd, vertices, triangles, t_min=self.dist_near, t_max=self.dist_far, method=method, grid=grid)
+            hit = hits["triangle"] >= 0
+            out: Dict[str, Tensor] = {}
+            if "depth" in target_types:
+                out["depth"] = torch.where(hit, hits["t"], torch.zeros_like(hits["t"]))
+            if "transmittance" in target_types:
+                out["transmittance"] = torch.where(hit, torch.zeros_like(hits["t"]), torch.ones_like(hits["t"]))
+            if "triangle" in target_types:
+                out["triangle"] = hits["triangle"]
+            wide = [k for k in ("color", "normal") if k in target_types]
+            if wide:
+                idx = hit.nonzero().squeeze(1)
+                corners = triangles[hits["triangle"][idx].long()].long()                 # [n_hit, 3] vertex indices
+                b1, b2 = hits["b1"][idx, None], hits["b2"][idx, None]
+
+                def interpolate(a):
+                    a = a.to(torch.float32)
+                    a0 = a[corners[:, 0]]
+                    return a0 + b1 * (a[corners[:, 1]] - a0) + b2 * (a[corners[:, 2]] - a0)
+                if "color" in wide:
+                    out["color"] = torch.as_tensor(background, dtype=torch.float32, device=dev).expand(n, 3).contiguous()
+                    out["color"][idx] = interpolate(colors)
+                if "normal" in wide:
+                    out["normal"] = torch.zeros(n, 3, device=dev)
+                    if normals is not None:
+                        nrm = interpolate(normals)
+                    else:
+                        p0 = vertices[corners[:, 0]]
+                        nrm = torch.cross(vertices[corners[:, 1]] - p0, vertices[corners[:, 2]] - p0, dim=1)
+                    nrm = torch.nn.functional.normalize(nrm, dim=1)
+                    away = (nrm * rd[idx]).sum(dim=1, keepdim=True) > 0
+                    out["normal"][idx] = torch.where(away, -nrm, nrm)
+            if pixel_range is None:
+                out = {k: v.reshape(h, w, 3) if v.dim() == 2 else v.reshape(h, w) for k, v in out.items()}
+        return {k: out[k] for k in target_types}
+
     def render_field_slice(self, slice_t: float = 0.0, render_size: float = 1.1, render_resolution: int = 128,
                            colormap: bool = True):
         """nerf_render.py:263-336: z = slice_t plane of the fine network's fields as uint8 images (debug view).
