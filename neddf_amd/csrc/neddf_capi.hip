@@ -599,7 +599,14 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
     // apart) and refills it: at 2^21 points a 65 536-ray x 128-sample call was four launch pairs, at 2^23 it is one -- fp32 +0.8 %,
     // split fp16 +0.7 %, bf16 +2.8 % (profiles/r04_launch_size.txt).  The hand-off buffers grow with it (1 088 B per point
     // eval-minimal: 9.1 GB at 2^23 of the 288 GB); NEDDF_FIELD_CHUNK_LOG2 overrides.
-    static const int chunk_log2 = [] { const char *e = getenv("NEDDF_FIELD_CHUNK_LOG2"); int v = e ? atoi(e) : 23; return v < 16 ? 16 : (v > 25 ? 25 : v); }();
+    static const int chunk_env = [] { const char *e = getenv("NEDDF_FIELD_CHUNK_LOG2"); int v = e && *e ? atoi(e) : 0; return !v ? 0 : (v < 16 ? 16 : (v > 25 ? 25 : v)); }();
+    const int chunk_log2 = chunk_env ? chunk_env : 23;
+    // The three-term fp32 DISTANCE kernel is the exception: its L2 hit rate FALLS with the launch size (per 2^23 points: 83 % of the
+    // TCC requests hit in 2^19-point launches, 74 % at 2^21, 65 % at 2^23; fabric reads 42 / 83 / 125 M KB) and it is fastest in
+    // launches of 2^20 points (profiles/r09_alignment.txt, r09_launch_size_ab.txt).  The colour kernel behind it and every other policy
+    // still prefer the large launch.  So a chunk's distance kernel runs as sub-launches of 2^20 points into the chunk's hand-off, and
+    // the colour kernel once over the chunk.  With NEDDF_FIELD_CHUNK_LOG2 set, both kernels take launches of that size as before.
+    const int64_t ddf_sub = (use3 && !chunk_env) ? ((int64_t)1 << 20) : ((int64_t)1 << 25);
     const int64_t chunk_cap = full ? (1 << 19) : ((int64_t)1 << chunk_log2);
     int64_t chunk = N < chunk_cap ? N : chunk_cap;
     // The hand-off of one launch (features + per-point record: 1 088 B per point eval-minimal at width 256, 9.1 GB at 2^23 points,
@@ -647,8 +654,6 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
         HIPCHK(hipMemsetAsync(a.sched, 0, kSchedInts * sizeof(int), s));
         if (reverse) {          // one scalar's gradient: reverse mode, 64 or 32 points per tile (field_kernels.hip ddf_rev_kernel)
             const int pts = ddf_rev_points(dt, wid), wgs = ddf_rev_wgs_per_cu(dt, wid) * ctx->cus;
-            const int64_t tiles = (n + pts - 1) / pts;
-            const int grid = (int)(tiles < wgs ? tiles : wgs);
             if (int rc = ensure(ctx, ctx->rev_scratch, (size_t)wgs * ddf_rev_scratch_floats_per_wg(a.n_layers, pts, wid) * sizeof(float))) return rc;
             a.rev_scratch = (float *)ctx->rev_scratch.p;
 #ifdef NEDDF_STAMP
@@ -658,7 +663,22 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
             HIPCHK(hipMemsetAsync(d_stamps, 0, stamp_bytes, s));
             a.stamps = d_stamps;
 #endif
-            STAGE(ctx, s, NEDDF_STAGE_DDF, launch_ddf_rev(a, grid, s));
+            for (int64_t so = 0; so < n; so += ddf_sub) {       // (one launch, except for the three-term policy: see ddf_sub)
+                DdfArgs b = a;
+                b.n_points = n - so < ddf_sub ? n - so : ddf_sub;
+                if (so) {
+                    if (use_rays) b.rays.base = a.rays.base + so;
+                    else { b.pos = a.pos + so * 3; b.dir = a.dir + so * 3; b.var = a.var + so * 3; }
+                    if (a.features) b.features = a.features + (size_t)so * fr * wid;
+                    b.ptaux = a.ptaux + (size_t)so * kPtAux;
+                    if (a.distance) b.distance = a.distance + so;
+                    if (a.density) b.density = a.density + so;
+                    if (a.aux_grad) b.aux_grad = a.aux_grad + so;
+                    HIPCHK(hipMemsetAsync(b.sched, 0, kSchedInts * sizeof(int), s));
+                }
+                const int64_t stiles = (b.n_points + pts - 1) / pts;
+                STAGE(ctx, s, NEDDF_STAGE_DDF, launch_ddf_rev(b, (int)(stiles < wgs ? stiles : wgs), s));
+            }
 #ifdef NEDDF_STAMP
             if (const char *path = getenv("NEDDF_STAMP_FILE")) {        // the LAST launch's stamps (a diagnostic build: synchronising here is fine)
                 HIPCHK(hipStreamSynchronize(s));
