@@ -735,6 +735,74 @@ int neddf_raycast_grid_query(neddf_ctx *ctx, const float *d_ray_orig, const floa
                              const int32_t *d_cell_start, const int32_t *d_items, int64_t n_items, float t_min, float t_max, float *d_t,
                              int32_t *d_triangle, float *d_b1, float *d_b2, void *stream);
 
+/* ---- point-to-mesh distance (additive to ABI v7; no reference counterpart: its evaluation compares images only) ------
+ * The closest point of an indexed mesh (d_vertices [V][3] float, d_triangles [T][3] int32) to every query (d_queries [Q][3] float):
+ * d_d2 [Q] float, the squared distance; d_triangle [Q] int32, the closest triangle; d_b1, d_b2 [Q] float -- the closest point is
+ * p0 + b1 (p1 - p0) + b2 (p2 - p0).  Every operation below is ONE rounded fp32 operation (no fused multiply-add; `/` is the correctly
+ * rounded division); dot(x, y) = (x0 y0 + x1 y1) + x2 y2; tests/pointmesh_check.py restates it in numpy bit for bit.
+ *   per valid triangle (indices in [0, V), finite vertices; a, b, c its corners):
+ *       e0 = b - a, e1 = c - a, e2 = c - b;  g00 = dot(e0, e0), g01 = dot(e0, e1), g11 = dot(e1, e1), g22 = dot(e2, e2);
+ *       r00 = 1 / g00, r11 = 1 / g11, r22 = 1 / g22;  f = e1 - (g01 * r00) * e0 per axis (e1 without its part along e0), gpp = dot(f, f),
+ *       rpp = 1 / gpp -- the only four divisions, none per pair
+ *   per (query p, triangle):  ap = p - a, bp = p - b, d1 = dot(e0, ap), d2 = dot(e1, ap), d3 = dot(e2, bp);
+ *       clamp01(u) = u > 0 ? (u < 1 ? u : 1) : 0 (a NaN gives 0: a zero-length edge, r = inf and h = 0, gives its start point)
+ *       edge candidates (s, e, h, r) = (a, e0, d1, r00), (b, e2, d3, r22), (a, e1, d2, r11):  u = clamp01(h * r), q = s + u * e per axis (a
+ *           rounded product, then a rounded sum), d = p - q, D2 = dot(d, d); (b1, b2) = (u, 0), (1 - u, u), (0, u)
+ *       interior candidate:  solve(x, h) = (v, w) with w = dot(f, x) * rpp, v = (h - w * g01) * r00.  (v, w) = solve(ap, d1);
+ *           q = (a + v * e0) + w * e1, d = p - q; ONE step of iterative refinement: (dv, dw) = solve(d, dot(e0, d)), v = v + dv,
+ *           w = w + dw, and q, d again.  It exists when gpp > 0, v > 0, w > 0 and v + w < 1;  D2 = dot(d, d), (b1, b2) = (v, w).
+ *           (Solving the 2 x 2 Gram system by its determinant g00 * g11 - g01 * g01 squares the triangle's aspect ratio in the error
+ *           of (v, w): measured against fp64, samples of a marching-cubes mesh then lie up to 80 * 2^-24 off their OWN triangles, and
+ *           2500 * 2^-24 at an aspect of 1:300.  Orthogonalising first -- a QR step in place of the normal equations -- makes the
+ *           amplification linear, and the refinement squares what is left: within 4 * 2^-24 down to an aspect of 1:10000.  Thinner
+ *           triangles may lose the candidate; the edge candidates are then within the triangle's height of the truth.)
+ *       corner candidate:  d = p - c, D2 = dot(d, d), (b1, b2) = (0, 1).  The corners a and b are reached without rounding by u = 0 of
+ *           the edges ab and bc; c is reached by no edge candidate exactly (u = g * (1 / g) may round below 1, and a + 1 * (c - a) need
+ *           not give c back), so without this candidate a mesh vertex would be at distance 0 of only SOME of its triangles
+ *       the pair's result starts at (+inf, 0, 0) and is replaced by the interior candidate, then by the edge candidates in the order
+ *           ab, bc, ac, then by the corner candidate, each when its D2 is strictly smaller: a D2 that is NaN (or +inf) never replaces
+ *           anything.  A mesh vertex is therefore at distance exactly 0 of every triangle it is a corner of, and the lowest one wins
+ *   per query:  the smallest D2 wins, among equal D2 the LOWEST triangle index (best starts at (+inf, -1, 0, 0); a pair replaces it
+ *       when D2 < best, or D2 == best and its index is below the current one, -1 counting as highest): the result does not depend on
+ *       the visiting order or on how often a triangle is met.  A query with a non-finite coordinate: (NaN, -1, NaN, NaN).  No valid
+ *       triangle: (+inf, -1, 0, 0).
+ * Every candidate is a point of the triangle up to rounding -- a clamped point of a segment or a convex combination of the corners --
+ * so a sliver or a degenerate triangle cannot give a gross underestimate: at worst it loses its interior candidate, and the edge
+ * candidates are then within the triangle's smallest height of the truth.
+ * Every entry point: NEDDF_EINVAL for a negative count or a NULL array it needs, NEDDF_EUNSUPPORTED from 2^31 queries, triangles or
+ * vertices on (indices are int32).
+ * neddf_point_mesh_brute: one lane per query visits every triangle; the per-triangle constants are computed once per 256-triangle tile
+ * and staged through LDS -- the yardstick of the grid and the method for small meshes.  Q == 0 and T == 0 are legal. */
+int neddf_point_mesh_brute(neddf_ctx *ctx, const float *d_queries, int64_t n_queries, const float *d_vertices, int64_t n_vertices,
+                           const int32_t *d_triangles, int64_t n_triangles, float *d_d2, int32_t *d_triangle, float *d_b1, float *d_b2, void *stream);
+/* neddf_point_mesh_brute's bits, for any box, any cell counts and any queries, through the lists neddf_raycast_grid_build made of the
+ * same mesh, box, cells and pad (n_items = its *h_n_items; the pad limit and every other parameter rule are the build's): no build and
+ * no list format of its own.  A prepare launch writes the per-triangle constants into a table in the context's workspace (80 bytes
+ * per triangle), then one lane per query visits the overflow list and the Chebyshev shells r = 0, 1, 2, ... of cells around the
+ * query's (clamped) cell, as neddf_nn_grid_query does, and stops after shell r once (r * safe_cell)^2 > best D2 strictly and
+ * (r * safe_cell)^2 >= 1e-30, safe_cell = 0.99 * the smallest cell edge among the axes with an extent, or when the shell has left the
+ * grid on all sides.  A triangle listed in several visited cells is evaluated again, which the tie rule makes harmless.
+ *
+ * THE EQUALITY ARGUMENT.  Let the walk stop after shell r >= 1 with best D2 = B, and let a listed triangle be unvisited.
+ *   (1) On some axis its whole listed cell range lies outside [c - r, c + r], c the query's cell.  cell() is monotone and the range
+ *       covers cell(min3 - 2 pad) .. cell(max3 + 2 pad), so every point of the triangle lies in a cell at least r + 1 from c along that
+ *       axis; cell()'s steps lie within 2^-12 cells of the ideal ones (neddf_nn_grid_build), also for a query outside the box that was
+ *       clamped.  Every point of the triangle is therefore more than (r - 2^-12) e from the query, e the smallest cell edge.
+ *   (2) A candidate's D2 comes from a point q that carries an ABSOLUTE error: per axis the rounding of the edge (2^-24 |e|, |e| <= 2 W),
+ *       of each product and of each sum (2^-24 W each, W the largest |coordinate| of the widened box wlo .. whi, which holds every
+ *       vertex of a listed triangle) -- at most nine such terms for the interior candidate, five for an edge candidate, none for the corner; over three
+ *       axes less than 2^-20 W < 2^-19 W.  d = p - q and dot(d, d) add relative errors only, below 2^-21 of the distance.  The computed
+ *       distance of the unvisited triangle is therefore above (r - 2^-12) e (1 - 2^-21) - 2^-19 W.
+ *   (3) The walk stopped because (0.99 r e)^2, computed with relative error below 2^-22, exceeds B.  The unvisited D2 exceeds B as
+ *       well -- no tie, no smaller value -- when r e (0.01 - 2^-12 - 2^-20) > 2^-19 W; the bracket exceeds 2^-7, so e >= 2^-12 W would
+ *       do.  The query walks the shells only when e >= 2^-10 W (a margin of four); otherwise it visits every list once, the
+ *       overflow list included, which is the brute kernel's set of valid triangles.
+ * The overflow list is visited before the shells in either case.  Visiting more triangles, or one twice, never changes the result. */
+int neddf_point_mesh_grid_query(neddf_ctx *ctx, const float *d_queries, int64_t n_queries, const float *d_vertices, int64_t n_vertices,
+                                const int32_t *d_triangles, int64_t n_triangles, const double *h_lo, const double *h_hi, const int *h_cells, float pad,
+                                const int32_t *d_cell_start, const int32_t *d_items, int64_t n_items, float *d_d2, int32_t *d_triangle, float *d_b1,
+                                float *d_b2, void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

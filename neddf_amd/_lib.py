@@ -168,6 +168,9 @@ SYMBOLS = [
     ("neddf_raycast_grid_build", C.c_int, [_vp, _vp, _i64, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), C.c_float, _vp, _vp, _i64, C.POINTER(_i64), _vp]),
     ("neddf_raycast_grid_query", C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), C.c_float, _vp, _vp, _i64,
                                            C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_point_mesh_brute", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_point_mesh_grid_query", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), C.c_float, _vp, _vp, _i64,
+                                              _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _lib = None
@@ -642,6 +645,26 @@ class Context:
                                                      _ptr(items) if items.numel() else None, items.shape[0], float(t_min), float(t_max),
                                                      _ptr(t), _ptr(j), _ptr(b1), _ptr(b2), self.stream()))
         return t, j, b1, b2
+
+    # ------------------------------------------------------------------ point-to-mesh distance
+    def point_mesh_brute(self, queries, vertices, triangles):
+        """The closest point of the mesh to every query by brute force (neddf_point_mesh_brute): (d2 float32 [Q], triangle int32 [Q],
+        b1, b2 float32 [Q])."""
+        d2, j, b1, b2 = self._hit_buffers(queries.shape[0], queries.device)
+        self.check(self.lib.neddf_point_mesh_brute(self.h, _ptr(queries), queries.shape[0], _ptr(vertices), vertices.shape[0], _ptr(triangles),
+                                                   triangles.shape[0], _ptr(d2), _ptr(j), _ptr(b1), _ptr(b2), self.stream()))
+        return d2, j, b1, b2
+
+    def point_mesh_grid_query(self, queries, vertices, triangles, lo, hi, cells, pad, cell_start, items):
+        """The closest point of the mesh to every query through the ray-casting grid (neddf_point_mesh_grid_query): point_mesh_brute's
+        result, bit for bit."""
+        blo, bhi, bc = self._grid_args(lo, hi, cells)
+        d2, j, b1, b2 = self._hit_buffers(queries.shape[0], queries.device)
+        self.check(self.lib.neddf_point_mesh_grid_query(self.h, _ptr(queries), queries.shape[0], _ptr(vertices), vertices.shape[0],
+                                                        _ptr(triangles), triangles.shape[0], blo, bhi, bc, float(pad), _ptr(cell_start),
+                                                        _ptr(items) if items.numel() else None, items.shape[0], _ptr(d2), _ptr(j), _ptr(b1),
+                                                        _ptr(b2), self.stream()))
+        return d2, j, b1, b2
 
     def composite(self, dists, dens, col, max_dist):
         require_device(dists, "dists")

@@ -371,6 +371,19 @@ void launch_raycast_grid_query(const RcGrid &g, const float *ro, const float *rd
                                const int32_t *cell_start, const int32_t *items, int64_t n_items, float t_min, float t_max, float *t, int32_t *triangle,
                                float *b1, float *b2, hipStream_t s);
 
+// Point-to-mesh distance (pointmesh_kernels.hip): the closest point of the closest triangle to every query, by brute force and through
+// the lists of the ray-casting grid.
+struct PmGrid {
+    NnGrid nn;
+    int walk;                            // 1: Chebyshev shells with the stopping rule; 0: every list once (include/neddf_hip.h says when)
+};
+void launch_point_mesh_brute(const float *q, int64_t nq, const float *v, int64_t V, const int32_t *tri, int64_t T, float *d2, int32_t *triangle, float *b1,
+                             float *b2, hipStream_t s);
+// table [20 T] floats, 16-byte aligned (workspace): the per-triangle constants, written by a prepare launch in front of the query
+void launch_point_mesh_grid_query(const PmGrid &g, const float *q, int64_t nq, const float *v, int64_t V, const int32_t *tri, int64_t T, float *table,
+                                  const int32_t *cell_start, const int32_t *items, int64_t n_items, float *d2, int32_t *triangle, float *b1, float *b2,
+                                  hipStream_t s);
+
 void launch_linear_grad(const float *x, const float *J, int64_t n, int cin, int ldx, int cout_block, int ksteps, const float *wp,
                         const float *bias, float *y, float *G, int ldo, int nvalid, int accumulate, int grid, hipStream_t s);
 void launch_op_activation(int kind, const float *x, const float *J, int64_t N, int C, float *y, float *G, hipStream_t s);

@@ -2192,3 +2192,47 @@ int neddf_raycast_grid_query(neddf_ctx *ctx, const float *d_ray_orig, const floa
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// ---- point-to-mesh distance (pointmesh_kernels.hip) ----
+int neddf_point_mesh_brute(neddf_ctx *ctx, const float *d_queries, int64_t n_queries, const float *d_vertices, int64_t n_vertices,
+                           const int32_t *d_triangles, int64_t n_triangles, float *d_d2, int32_t *d_triangle, float *d_b1, float *d_b2, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = rc_counts_ok(ctx, n_queries, d_queries, d_queries, n_vertices, d_vertices, n_triangles, d_triangles, 0.f, "point_mesh_brute")) return rc;
+    if (n_queries > 0 && (!d_d2 || !d_triangle || !d_b1 || !d_b2)) return fail(ctx, NEDDF_EINVAL, "point_mesh_brute: NULL outputs");
+    DeviceGuard guard_(ctx->device);
+    launch_point_mesh_brute(d_queries, n_queries, d_vertices, n_vertices, d_triangles, n_triangles, d_d2, d_triangle, d_b1, d_b2, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_point_mesh_grid_query(neddf_ctx *ctx, const float *d_queries, int64_t n_queries, const float *d_vertices, int64_t n_vertices,
+                                const int32_t *d_triangles, int64_t n_triangles, const double *h_lo, const double *h_hi, const int *h_cells, float pad,
+                                const int32_t *d_cell_start, const int32_t *d_items, int64_t n_items, float *d_d2, int32_t *d_triangle, float *d_b1,
+                                float *d_b2, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = rc_counts_ok(ctx, n_queries, d_queries, d_queries, n_vertices, d_vertices, n_triangles, d_triangles, pad, "point_mesh_grid_query")) return rc;
+    RcGrid rg;
+    if (int rc = rc_grid(ctx, h_lo, h_hi, h_cells, pad, &rg, "point_mesh_grid_query")) return rc;
+    if (!d_cell_start || n_items < 0 || n_items > 0x7fffffff || (n_items > 0 && !d_items) || (n_queries > 0 && (!d_d2 || !d_triangle || !d_b1 || !d_b2)))
+        return fail(ctx, NEDDF_EINVAL, "point_mesh_grid_query: NULL cell_start, items or outputs, or an item count outside [0, 2^31)");
+    PmGrid g;
+    g.nn = rg.nn;
+    // the shells are walked when the smallest cell edge is at least 2^-10 of the largest |coordinate| of the widened box (the header's
+    // equality argument, part 3); a grid without any extent is one cell
+    float inv_max = 0.f;
+    double w = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        inv_max = std::max(inv_max, rg.nn.inv_cell[a]);
+        w = std::max(w, std::max(std::fabs((double)rg.wlo[a]), std::fabs((double)rg.whi[a])));
+    }
+    g.walk = (inv_max == 0.f || 1.0 / (double)inv_max >= 0x1p-10 * w) ? 1 : 0;
+    DeviceGuard guard_(ctx->device);
+    if (n_queries > 0 && n_triangles > 0)
+        if (int rc = ensure(ctx, ctx->geom_ws, (size_t)n_triangles * 20 * sizeof(float))) return rc;
+    launch_point_mesh_grid_query(g, d_queries, n_queries, d_vertices, n_vertices, d_triangles, n_triangles, (float *)ctx->geom_ws.p, d_cell_start, d_items,
+                                 n_items, d_d2, d_triangle, d_b1, d_b2, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}

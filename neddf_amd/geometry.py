@@ -1,9 +1,11 @@
-"""Distances between point clouds and between meshes on the GPU: exact nearest neighbours (a uniform grid, or brute force), Chamfer
-and Hausdorff distance, precision / recall / F-score at a threshold.
+"""Distances between point clouds and between meshes on the GPU: exact nearest neighbours (a uniform grid, or brute force), the exact
+distance from points to a mesh's triangles, Chamfer and Hausdorff distance, precision / recall / F-score at a threshold, and a check of
+a distance field against the mesh of one of its level sets.
 
 The reference's evaluation compares images (PSNR, SSIM: metrics.py); the distance between two SURFACES is what tells how far a sparse
 extraction, an operand policy or a clean-up moved the level set.  Sampling (mesh.sample_surface) and the nearest-neighbour search are
-HIP kernels (include/neddf_hip.h neddf_mesh_sample_*, neddf_nn_brute, neddf_nn_grid_build, neddf_nn_grid_query); the reductions over
+HIP kernels (include/neddf_hip.h neddf_mesh_sample_*, neddf_nn_brute, neddf_nn_grid_build, neddf_nn_grid_query), and so is the
+point-to-triangle search (neddf_point_mesh_brute, neddf_point_mesh_grid_query over raycast.build_grid's lists); the reductions over
 the per-point distances are torch fp64 on the device.
 """
 import torch
@@ -11,9 +13,10 @@ import torch
 from ._lib import Context, NeddfError
 from .mesh import sample_surface, surface_area
 
-# targets per grid cell of nearest()'s default grid: a placeholder until the sweep 1, 2, 4, 8, 16 at 10^6 x 10^6 points of
-# tools/time_mesh_distance.py (profiles/mesh_distance_cost.json) has been run on the device -- the fastest value goes here
-POINTS_PER_CELL = 4
+# targets per grid cell of nearest()'s default grid: the fastest of the sweep 1, 2, 4, 8, 16 of tools/time_mesh_distance.py on the MI355X
+# (profiles/mesh_distance_cost.json: 10^6 x 10^6 points, build + query 1.3 ms at 1 against 2.8 ms at 4 and 4.7 ms at 16; 1 is the sweep's
+# best and its edge).  Results are bit-identical for any value.
+POINTS_PER_CELL = 1
 MAX_CELLS_PER_AXIS, MAX_CELLS = 1024, 1 << 24           # the library's limits (neddf_nn_grid_build)
 
 
@@ -128,13 +131,76 @@ def cloud_distance(a, b, tau=None, method="grid", return_samples=False):
     return out
 
 
-def mesh_distance(mesh_a, mesh_b, n=None, density=None, seed=0, tau=None, method="grid", return_samples=False):
-    """cloud_distance between area-weighted samples of two device meshes, each (vertices float32 [V, 3], triangles int32 [T, 3]).
+def _grid_of(what, v, t, grid):
+    """`grid` validated as cast_rays validates it, or build_grid's default grid of the mesh."""
+    from .raycast import MeshGrid, build_grid
+    if grid is None:
+        return build_grid(v, t)
+    if not isinstance(grid, MeshGrid) or grid.n_vertices != v.shape[0] or grid.n_triangles != t.shape[0] or grid.cell_start.device != v.device:
+        raise NeddfError("%s: grid must be the MeshGrid build_grid made of this mesh" % what)
+    return grid
 
-    Both meshes are sampled with the SAME density and seed (mesh.sample_surface), so identical meshes give identical samples and every
-    distance is exactly 0.  Exactly one of `density` (samples per unit area) and `n` is given; n is turned into a density by the mean
-    of the two areas, so each mesh gets about n points.  return_samples=True adds points_a / points_b, triangle_a / triangle_b and the
-    per-sample distances and indices of cloud_distance: where the two surfaces differ, and by how much."""
+
+def point_mesh_distance(queries, vertices, triangles, method="grid", grid=None):
+    """The exact distance from every query (float32 [Q, 3]) to the SURFACE of a device mesh (vertices float32 [V, 3], triangles int32
+    or int64 [T, 3]) -- to its closest triangle, not to its closest vertex or sample -- as a dict:
+
+      distance  float32 [Q]: torch.sqrt of the library's squared distance; +inf without a valid triangle
+      triangle  int64 [Q]: the closest triangle, -1 for none
+      b1, b2    float32 [Q]: the closest point is p0 + b1 (p1 - p0) + b2 (p2 - p0) (closest_points evaluates it); 0 for none
+
+    The arithmetic is specified operation by operation (include/neddf_hip.h neddf_point_mesh_brute; tests/pointmesh_check.py restates it
+    in numpy bit for bit): among equal squared distances the lowest triangle index wins, so method="grid" and method="brute" return the
+    same bits.  A query with a non-finite coordinate gets (NaN, -1, NaN, NaN); a triangle with an index outside [0, V) or a non-finite
+    vertex is never found.  method="grid" walks the uniform grid of raycast.build_grid (`grid`: the MeshGrid of this mesh, built here
+    with build_grid's defaults when None -- build it once for many calls); queries far from the surface walk many shells of cells
+    and are correspondingly slower.  `grid` is ignored by method="brute"."""
+    from .raycast import _mesh
+    q = _points("point_mesh_distance", "queries", queries)
+    v, t = _mesh("point_mesh_distance", vertices, triangles)
+    if q.device != v.device:
+        raise NeddfError("point_mesh_distance: queries and mesh must live on one device (got %s, %s)" % (q.device, v.device))
+    if method not in ("grid", "brute"):
+        raise NeddfError("point_mesh_distance: method must be 'grid' or 'brute' (got %r)" % (method,))
+    ctx = Context.get(q.device)
+    if method == "brute":
+        if grid is not None:
+            _grid_of("point_mesh_distance", v, t, grid)
+        d2, j, b1, b2 = ctx.point_mesh_brute(q, v, t)
+    else:
+        grid = _grid_of("point_mesh_distance", v, t, grid)
+        d2, j, b1, b2 = ctx.point_mesh_grid_query(q, v, t, grid.lo, grid.hi, grid.cells, grid.pad, grid.cell_start, grid.items)
+    return {"distance": torch.sqrt(d2), "triangle": j.long(), "b1": b1, "b2": b2}
+
+
+def closest_points(vertices, triangles, result):
+    """p0 + b1 (p1 - p0) + b2 (p2 - p0) float32 [Q, 3] of a point_mesh_distance result, in torch; NaN rows where triangle is -1."""
+    j, b1, b2 = result["triangle"], result["b1"], result["b2"]
+    ok = j >= 0
+    p = vertices[triangles.long()[j.clamp_min(0)]]
+    out = p[:, 0] + b1[:, None] * (p[:, 1] - p[:, 0]) + b2[:, None] * (p[:, 2] - p[:, 0])
+    return torch.where(ok[:, None], out, torch.full_like(out, float("nan")))
+
+
+def mesh_distance(mesh_a, mesh_b, n=None, density=None, seed=0, tau=None, method="grid", return_samples=False, to="samples"):
+    """Distances between two device meshes, each (vertices float32 [V, 3], triangles int32 [T, 3]), from area-weighted samples of both
+    (cloud_distance's dict).
+
+    Both meshes are sampled with the SAME density and seed (mesh.sample_surface).  Exactly one of `density` (samples per unit area) and
+    `n` is given; n is turned into a density by the mean of the two areas, so each mesh gets about n points.
+
+    to="samples" (the default): cloud_distance between the two sample sets.  Identical meshes give identical samples and every distance
+    is exactly 0 -- the mode for asking WHETHER two meshes are the same -- but two meshes that differ at all are a sample spacing
+    apart (about 3e-3 at 10^5 samples on a unit-sized object), whatever their true distance.
+    to="surface": every sample of one mesh is measured against the other mesh's TRIANGLES (point_mesh_distance), the figure
+    reconstruction papers report and the one without a sampling floor -- the mode for asking HOW FAR two different meshes are apart.
+    Identical meshes then give rounding-level distances (a few 2^-24 of the coordinates), not exact zeros.  The dict has the same keys.
+
+    return_samples=True adds points_a / points_b, triangle_a / triangle_b and the per-sample distances a_to_b / b_to_a and indices
+    a_to_b_index / b_to_a_index: sample indices with to="samples"; with to="surface" triangle indices of the other mesh, and
+    a_to_b_b1 / a_to_b_b2 / b_to_a_b1 / b_to_a_b2, the closest point's barycentric pair (closest_points)."""
+    if to not in ("samples", "surface"):
+        raise NeddfError("mesh_distance: to must be 'samples' or 'surface' (got %r)" % (to,))
     if (density is None) == (n is None):
         raise NeddfError("mesh_distance: exactly one of density and n must be given")
     (va, ta), (vb, tb) = mesh_a, mesh_b
@@ -148,11 +214,104 @@ def mesh_distance(mesh_a, mesh_b, n=None, density=None, seed=0, tau=None, method
         density = int(n) / area if area > 0.0 else 0.0
     pa, ia = sample_surface(va, ta, density=density, seed=seed)
     pb, ib = sample_surface(vb, tb, density=density, seed=seed)
-    out = cloud_distance(pa, pb, tau=tau, method=method, return_samples=return_samples)
+    if to == "samples":
+        out = cloud_distance(pa, pb, tau=tau, method=method, return_samples=return_samples)
+    else:
+        if tau is not None and not float(tau) >= 0.0:
+            raise NeddfError("mesh_distance: tau must not be negative (got %r)" % (tau,))
+        rab = point_mesh_distance(pa, vb, tb, method=method)
+        rba = point_mesh_distance(pb, va, ta, method=method)
+        mab, xab, pab, _, bad_a = _one_way(rab["distance"], rab["triangle"], tau)
+        mba, xba, pba, _, bad_b = _one_way(rba["distance"], rba["triangle"], tau)
+        out = {"a_to_b_mean": mab, "b_to_a_mean": mba, "chamfer": 0.5 * (mab + mba),
+               "hausdorff": max(xab, xba) if xab == xab and xba == xba else float("nan"), "a_to_b_max": xab, "b_to_a_max": xba,
+               "n_a": int(pa.shape[0]), "n_b": int(pb.shape[0]), "invalid_a": bad_a, "invalid_b": bad_b}
+        if tau is not None:
+            out["precision"], out["recall"] = pab, pba
+            out["fscore"] = 2.0 * pab * pba / (pab + pba) if pab + pba > 0.0 else (0.0 if pab == pab and pba == pba else float("nan"))
+        if return_samples:
+            out.update(a_to_b=rab["distance"], b_to_a=rba["distance"], a_to_b_index=rab["triangle"], b_to_a_index=rba["triangle"],
+                       a_to_b_b1=rab["b1"], a_to_b_b2=rab["b2"], b_to_a_b1=rba["b1"], b_to_a_b2=rba["b2"])
     out["density"] = float(density)
     if return_samples:
         out.update(points_a=pa, points_b=pb, triangle_a=ia, triangle_b=ib)
     return out
 
 
-__all__ = ["nearest", "cloud_distance", "mesh_distance", "default_cells", "POINTS_PER_CELL"]
+GOLDEN_STEP, PLASTIC_STEP = 0.6180339887498949, 0.7548776662466927      # the offsets' low-discrepancy sequence and its shift per seed
+
+
+def level_set_check(distance_fn, vertices, triangles, threshold, band, n=100000, seed=0, min_distance=None, method="grid", grid=None,
+                    return_samples=False):
+    """How well a field is a DISTANCE field around one of its level sets: (vertices, triangles) is the mesh of the level set
+    D = threshold (extract_mesh), distance_fn(p [M, 3]) -> D [M] the field (trace.sphere_trace's contract), and |D(p) - threshold| is
+    set against the exact distance d(p) from p to the mesh (point_mesh_distance) at about n points within `band` of it.
+
+    The points: x_k, triangle ids = sample_surface(n=n, seed=seed); n_k the unit face normal in torch fp32; the offset
+    s_k = band * (2 frac((k + 1) * 0.6180339887498949 + seed * 0.7548776662466927) - 1) in fp64 (deterministic: no torch generator is
+    touched); p_k = x_k + s_k n_k in fp32.  With e_k = |D_k - threshold| - d_k the dict holds
+
+      n, band, invalid                    the points, the band, and how many D_k were not finite (left out of everything below)
+      mean_error, mean_abs_error, rms_error, max_abs_error     of e_k
+      slope_median, slope_p99, slope_max, n_slope              of |D_k - threshold| / d_k over the points with d_k >= min_distance
+                                          (default band / 8): 1 for a distance field, above 1 where the field oversteps
+      suggested_step_scale                min(1, 1 / slope_p99): the sphere tracer's step_scale that keeps 99 % of the steps short of
+                                          the surface; the same number bounds extract_mesh's `lipschitz`
+
+    Every figure carries the mesh's own error: the level set lies within marching cubes' interpolation error of its mesh, which the
+    slope's min_distance keeps small against d_k.  Reductions are torch fp64 on the device.  return_samples=True adds points,
+    mesh_distance and field_distance (float32, all n points)."""
+    from .raycast import _mesh
+    if not callable(distance_fn):
+        raise NeddfError("level_set_check: distance_fn must be callable: pos [M, 3] -> distances [M]")
+    v, t = _mesh("level_set_check", vertices, triangles)
+    band, threshold = float(band), float(threshold)
+    if not (band > 0.0 and band < float("inf")):
+        raise NeddfError("level_set_check: band must be positive and finite (got %r)" % (band,))
+    min_distance = band / 8.0 if min_distance is None else float(min_distance)
+    if not min_distance > 0.0:
+        raise NeddfError("level_set_check: min_distance must be positive (got %r)" % (min_distance,))
+    x, tid = sample_surface(v, t, n=int(n), seed=seed)
+    p = v[t.long()[tid.long()]]
+    nrm = torch.linalg.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    nrm = nrm / nrm.norm(dim=1, keepdim=True).clamp_min(1e-30)
+    k = torch.arange(1, x.shape[0] + 1, device=x.device, dtype=torch.float64)
+    s = band * (2.0 * torch.frac(k * GOLDEN_STEP + float(int(seed)) * PLASTIC_STEP) - 1.0)
+    pts = (x + s.float()[:, None] * nrm).contiguous()
+    d = point_mesh_distance(pts, v, t, method=method, grid=grid)["distance"]
+    with torch.no_grad():
+        D = distance_fn(pts)
+    if not isinstance(D, torch.Tensor) or D.device != pts.device or D.numel() != pts.shape[0]:
+        raise NeddfError("level_set_check: distance_fn must return one distance per point on the points' device")
+    D = D.reshape(-1).float()
+    ok = torch.isfinite(D) & torch.isfinite(d)
+    m = int(ok.sum().item())
+    nan = float("nan")
+    out = {"n": int(pts.shape[0]), "band": band, "invalid": int(pts.shape[0]) - m}
+    f = (D.double() - threshold).abs()[ok]
+    dd = d.double()[ok]
+    e = f - dd
+    if m:
+        out.update(mean_error=float(e.mean().item()), mean_abs_error=float(e.abs().mean().item()),
+                   rms_error=float((e * e).mean().sqrt().item()), max_abs_error=float(e.abs().max().item()))
+    else:
+        out.update(mean_error=nan, mean_abs_error=nan, rms_error=nan, max_abs_error=nan)
+    far = dd >= min_distance
+    n_slope = int(far.sum().item())
+    out["n_slope"] = n_slope
+    if n_slope:
+        slope = f[far] / dd[far]
+        if n_slope <= 1 << 24:
+            p99 = float(torch.quantile(slope, 0.99).item())
+        else:                                                       # (torch.quantile refuses more than 2^24 elements)
+            p99 = float(slope.sort().values[int(0.99 * (n_slope - 1))].item())
+        out.update(slope_median=float(slope.median().item()), slope_p99=p99, slope_max=float(slope.max().item()))
+        out["suggested_step_scale"] = min(1.0, 1.0 / out["slope_p99"]) if out["slope_p99"] > 0.0 else 1.0
+    else:
+        out.update(slope_median=nan, slope_p99=nan, slope_max=nan, suggested_step_scale=nan)
+    if return_samples:
+        out.update(points=pts, mesh_distance=d, field_distance=D)
+    return out
+
+
+__all__ = ["nearest", "cloud_distance", "mesh_distance", "point_mesh_distance", "closest_points", "level_set_check", "default_cells", "POINTS_PER_CELL"]

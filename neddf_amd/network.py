@@ -272,6 +272,27 @@ class BaseNeuralField(ABC, nn.Module):
                 timings["colors"] = t4 - t3
         return tuple(out) if (normals or colors) else (verts, tris)
 
+    def level_set_check(self, vertices: Tensor, triangles: Tensor, threshold: float = 0.0275, band: Optional[float] = None, **kw):
+        """geometry.level_set_check of this field's distance (NeuS: sdf) against (vertices, triangles), the mesh extract_mesh made of
+        its `threshold` level set: how far |D(p) - threshold| is from the exact distance of p to that mesh at points within `band`
+        of it, and the slope figures that give the sphere tracer's step_scale and extract_mesh's `lipschitz` a measured value.
+        The field is evaluated as render_image_traced evaluates its hit points (forward_surface, var = 0; the distance ignores
+        the direction).  band=None: four lattice steps of extract_mesh's default resolution and cube, 4 * 2.2 / 63.  Further
+        keywords (n, seed, min_distance, method, grid, return_samples) are geometry.level_set_check's.  NeRF fields raise."""
+        from .geometry import level_set_check
+        if not self._has_surface():
+            raise NotImplementedError("%s fields have no distance or sdf to check against a level set" % type(self).__name__)
+        if band is None:
+            band = 4.0 * 2.0 * 1.1 / (64 - 1)
+
+        def distance_fn(pos):
+            with torch.no_grad():
+                view = torch.tensor([1.0, 0.0, 0.0], device=pos.device).expand_as(pos).contiguous()
+                o = self.forward_surface(Sampling(pos[None], view[None], torch.zeros_like(pos)[None]), want=("distance",))
+            return (o["distance"] if "distance" in o else o["sdf"])[0]
+
+        return level_set_check(distance_fn, vertices, triangles, threshold, band, **kw)
+
     def _has_surface(self) -> bool:
         """True for fields with a distance / sdf trunk, whose position gradient is the surface normal (NeDDF, NeuS)."""
         return False

@@ -1,6 +1,6 @@
 """`python neddf/scripts/extract_mesh.py <run_dir> [--epoch 2000] [--resolution 64] [--threshold 0.0275] [--field distance]
 [--cube-range 1.1] [--normals [field|geometric]] [--colors] [--min-component N] [--keep-largest [K]] [--sparse [B]] [--band W]
-[--lipschitz L] [--brick-dilate D]` -- the reference's mesh export (neddf/scripts/fields_visualizer.py:528-566, generate_mesh: voxelize
+[--lipschitz L] [--brick-dilate D] [--check-distance [BAND]]` -- the reference's mesh export (neddf/scripts/fields_visualizer.py:528-566, generate_mesh: voxelize
 "distance" on a 64^3 cube of half-width 1.1, marching cubes at 0.0275, export) without its Open3D viewer.  The run is
 loaded as run_eval loads it (`<run_dir>/.hydra/config.yaml`, `models/model_{epoch:05}.pth`); the mesh of
 `trainer.neural_render.get_network()` is written to `<run_dir>/mesh/mesh_{resolution}_threshold{threshold}.ply` (the
@@ -14,7 +14,11 @@ removed and the clean-up time.
 --sparse [B] (B = 8 when omitted) evaluates the field only on the bricks of B^3 cells that can hold the level set, picked from the
 field's values at the brick corners: a corner within --band of the threshold keeps a brick (default: --lipschitz, 1 when omitted,
 times half the brick's diagonal; a density needs an explicit --band), --brick-dilate grows the set.  The mesh and the file are the
-dense run's whenever no brick the surface crosses was left out; one more line reports the active and the total number of bricks."""
+dense run's whenever no brick the surface crosses was left out; one more line reports the active and the total number of bricks.
+--check-distance [BAND] (distance and sdf fields) measures the field against the mesh just extracted (BaseNeuralField.level_set_check:
+|D(p) - threshold| against the exact distance from p to the mesh at points within BAND of it; BAND = four lattice steps of this run's
+resolution when omitted) and prints the result as ONE JSON line after everything else.  Without the option nothing new runs."""
+import json
 from argparse import ArgumentParser
 from pathlib import Path
 
@@ -41,6 +45,8 @@ def build_parser() -> ArgumentParser:
     parser.add_argument("--band", type=float, default=None, help="a brick corner this close to the threshold keeps its brick")
     parser.add_argument("--lipschitz", type=float, default=1.0, help="the default band is this times half the brick's diagonal")
     parser.add_argument("--brick-dilate", type=int, default=0, metavar="D", help="grow the set of kept bricks by D bricks (0..4)")
+    parser.add_argument("--check-distance", type=float, nargs="?", const=0.0, default=None, metavar="BAND",
+                        help="check the field against the exact distance to the extracted mesh within BAND of it (four lattice steps when omitted)")
     return parser
 
 
@@ -81,6 +87,11 @@ def main(argv=None) -> Path:
         print("components: %d found, %d kept, triangles removed: %d, clean-up: %.3f s"
               % (times["components"], times["components_kept"], times["triangles_removed"], times["clean"]))
     print("wrote %s" % path)
+    if args.check_distance is not None:
+        if args.field == "density":
+            raise SystemExit("--check-distance needs a distance or sdf field")
+        band = args.check_distance if args.check_distance > 0.0 else 4.0 * 2.0 * args.cube_range / max(args.resolution - 1, 1)
+        print(json.dumps(network.level_set_check(verts, tris, threshold=args.threshold, band=band)))
     return path
 
 
