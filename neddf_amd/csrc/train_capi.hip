@@ -57,6 +57,29 @@ bool split_fused()
     return on;
 }
 
+// NEDDF_TRAIN_UNFUSED=1: one GEMM kernel per layer (the round-1 routes) instead of the fused layer stacks, kept for A/B measurements
+bool train_unfused()
+{
+    static const bool on = [] { const char *e = getenv("NEDDF_TRAIN_UNFUSED"); return e && atoi(e) != 0; }();
+    return on;
+}
+
+// workspace plans: the next n floats at offset o, every piece starting at a multiple of 64 floats
+size_t take(size_t &o, size_t n)
+{
+    const size_t at = o;
+    o += (n + 63) & ~(size_t)63;
+    return at;
+}
+
+// layers 1 .. n_layers - 1 that read cat([hidden state, encoding]); a fused stack holds one such partial product
+int skip_layers(const neddf_field_desc &d, int n_layers)
+{
+    int n = 0;
+    for (int l = 1; l < n_layers; ++l) n += in_skips(d, l - 1) ? 1 : 0;
+    return n;
+}
+
 int train_supported(neddf_ctx *ctx, const Field &f)
 {
     if (f.d.layer_width % kWidth != 0 || f.d.layer_width < kWidth || f.d.layer_width > 2 * kWidth ||
@@ -80,13 +103,12 @@ int make_plan(neddf_ctx *ctx, int slot, int64_t N, int n_tensors, Plan &p)
     p.N = N; p.R = 4 * N;
     p.WH = f.d.layer_width;
     size_t o = 0;
-    auto take = [&](size_t n) { size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
-    p.o_pes = take((size_t)p.R * kLdPe);
-    p.o_xa = take((size_t)p.R * p.ldxa);
-    p.o_pt = take((size_t)N * kTrainPt);
-    p.o_cr = take((size_t)p.R * kLdNarrow);
-    for (int l = 0; l < p.n_trunk; ++l) { p.o_z[l] = take((size_t)p.R * p.WH); p.o_h[l] = take((size_t)p.R * p.WH); }
-    for (int l = 0; l < p.n_col; ++l) { p.o_zc[l] = take((size_t)p.R * p.WH); p.o_hc[l] = take((size_t)p.R * p.WH); }
+    p.o_pes = take(o, (size_t)p.R * kLdPe);
+    p.o_xa = take(o, (size_t)p.R * p.ldxa);
+    p.o_pt = take(o, (size_t)N * kTrainPt);
+    p.o_cr = take(o, (size_t)p.R * kLdNarrow);
+    for (int l = 0; l < p.n_trunk; ++l) { p.o_z[l] = take(o, (size_t)p.R * p.WH); p.o_h[l] = take(o, (size_t)p.R * p.WH); }
+    for (int l = 0; l < p.n_col; ++l) { p.o_zc[l] = take(o, (size_t)p.R * p.WH); p.o_hc[l] = take(o, (size_t)p.R * p.WH); }
     p.total = o;
     return 0;
 }
@@ -127,6 +149,153 @@ int amax_begin(neddf_ctx *ctx, int split, AmaxSlots &m, hipStream_t s)
     return 0;
 }
 
+// ---- the per-layer routes' products in 256 x 256 blocks ------------------------------------------------------------------
+// A layer's weight (WeightView) or weight gradient (GradView): input k, output n at w[k * sk + n * sn].  NeDDF stores [in, out]
+// (strides (out_total, 1)), nn.Linear -- NeRF, NeuS -- [out, in] (strides (1, in_total)).
+struct WeightView { const float *w; int64_t sk, sn; };
+struct GradView { float *w; int64_t sk, sn; };
+
+// Every product of a per-layer route, one kernel launch per 256 x 256 block: K blocks accumulate in the output, the activation (forward)
+// or its backward runs with the last one.  The backward pass keeps dZ of the layer in flight in dA ([rows, WH], max |dA| in *mA under the
+// split-fp16 policy) and writes the next one to dB.
+struct Blocks {
+    int sp, cus;                // operand policy (1: split fp16), compute units
+    hipStream_t s;
+    float *wp;                  // one packed 256 x 256 weight block
+    int64_t rows;               // N value rows, or 4 N (value, Jacobian) rows
+    int WH, NBK, nout;          // row stride of dA / dB, its 256-column blocks, and the valid columns of dA among them
+    float *dA = nullptr, *dB = nullptr;
+    AmaxSlots am;
+    float *mA = nullptr, *mB = nullptr;
+
+    Blocks(const neddf_ctx *ctx, int sp_, hipStream_t s_, int64_t rows_, int WH_) : sp(sp_), cus(ctx->cus), s(s_), wp((float *)ctx->tpack.p), rows(rows_) { cols(WH_, WH_); }
+    void cols(int WH_, int nout_) { WH = WH_; NBK = WH_ / kWidth; nout = nout_; }
+
+    // Z[rows, ldz] (+)= X[rows, Kin] x W[k_off .. k_off + Kin, 0 .. nout_valid) (+ bias on rows r % period == 0); H = a(Z) when act_kind >= 0.
+    // Kin <= 256: one K block of `kload` loaded columns (pad columns are zero); otherwise Kin is a multiple of 256.
+    void forward(const float *X, int ldx, int kload, int Kin, WeightView W, int k_off, int nout_valid, const float *bias, int period,
+                 float *Z, int ldz, int acc0, int act_kind, float *H) const
+    {
+        const int KB = Kin <= kWidth ? 1 : Kin / kWidth, kc = Kin <= kWidth ? Kin : kWidth, kl = Kin <= kWidth ? kload : kWidth;
+        const int NB = (nout_valid + kWidth - 1) / kWidth;
+        for (int nb = 0; nb < NB; ++nb)
+            for (int kb = 0; kb < KB; ++kb) {
+                const bool last = kb == KB - 1;
+                const int nv = nout_valid - nb * kWidth < kWidth ? nout_valid - nb * kWidth : kWidth;
+                launch_pack(sp, W.w, W.sk, W.sn, k_off + kb * kWidth, nb * kWidth, kc, nv, kWidth, wp, s);
+                launch_rows_gemm(sp, X + kb * kWidth, rows, ldx, kl, wp, gemm_ksteps(kc, sp), (kb == 0 && bias) ? bias + nb * kWidth : nullptr, period,
+                                 Z + nb * kWidth, ldz, (acc0 || kb > 0) ? 1 : 0, last ? act_kind : -1, (last && H) ? H + nb * kWidth : nullptr, cus, s);
+            }
+    }
+
+    // gW[k_off + k, n] += sum_r X[r, k] dA[r, n] for k < Kin (as in forward), n < nout; with the first K block gB[n] += sum of dA[r, n]
+    // over the rows r % period == 0
+    void dw(const float *X, int ldx, int Kin, GradView gW, int k_off, float *gB, int period) const
+    {
+        const int KB = Kin <= kWidth ? 1 : Kin / kWidth, kc = Kin <= kWidth ? Kin : kWidth;
+        for (int nb = 0; nb < NBK; ++nb)
+            for (int kb = 0; kb < KB; ++kb) {
+                const int nv = nout - nb * kWidth < kWidth ? nout - nb * kWidth : kWidth;
+                launch_dw(sp, X + kb * kWidth, ldx, kc, dA + nb * kWidth, WH, rows, gW.w + (k_off + kb * kWidth) * gW.sk + (int64_t)nb * kWidth * gW.sn,
+                          gW.sk, gW.sn, nv, (kb == 0 && gB) ? gB + nb * kWidth : nullptr, period, cus, s, mA, am.dw_tmp);
+            }
+    }
+
+    // dB[rows, WH] = dA x W[k_off .. k_off + WH, :]^T, then the activation backward with Zprev on groups of `period` rows, which leaves
+    // max |dB| in *mOut.  act_kind < 0: no activation (Zprev and mOut unused).  The plain blocks carry no bias, so their period is not
+    // read (rows_gemm_kernel uses it for the bias rows and in the activation epilogues only): they pass 1.
+    void backward(WeightView W, int k_off, int period, int act_kind, const float *Zprev, float *mOut)
+    {
+        for (int nb = 0; nb < NBK; ++nb)
+            for (int kb = 0; kb < NBK; ++kb) {
+                launch_pack(sp, W.w, W.sn, W.sk, kb * kWidth, k_off + nb * kWidth, kWidth, kWidth, kWidth, wp, s);        // W^T block
+                if (kb == NBK - 1 && act_kind >= 0)
+                    launch_rows_gemm_actback(sp, dA + kb * kWidth, rows, WH, kWidth, wp, gemm_ksteps(kWidth, sp), period, act_kind, Zprev + nb * kWidth,
+                                             dB + nb * kWidth, WH, cus, s, mA, mOut, kb > 0);
+                else
+                    launch_rows_gemm(sp, dA + kb * kWidth, rows, WH, kWidth, wp, gemm_ksteps(kWidth, sp), nullptr, 1, dB + nb * kWidth, WH, kb > 0, -1, nullptr,
+                                     cus, s, mA);
+            }
+        mB = mOut;
+    }
+    // the gradient matrix backward() wrote becomes the one in flight
+    void swap() { float *t = dA; dA = dB; dB = t; mA = mB; }
+
+    // heads of 1 .. 4 columns on a WH-wide input, one launch per 256-column block kb of it (x_pm: X is point-major, where column block
+    // kb starts 4 x 256 kb floats into a point).  Y[rows, kLdNarrow] = X . w (+ bias on rows r % period == 0):
+    void narrow_forward(const float *X, NarrowW w, int period, float *Y, int x_pm = 0) const
+    {
+        const NarrowW w0 = w;
+        for (int kb = 0; kb < NBK; ++kb) {
+            for (int c = 0; c < w.nc; ++c) { w.w[c] = w0.w[c] + (size_t)kb * kWidth * w.wstride; w.b[c] = kb == 0 ? w0.b[c] : nullptr; }
+            launch_narrow_forward(X + (x_pm ? 4 : 1) * kb * kWidth, WH, rows, w, period, Y, kLdNarrow, s, x_pm, kb > 0);
+        }
+    }
+    // block kb of dZ[rows, WH] = activation backward with Zprev of ((accumulate ? dH : 0) + sum_c G[., c] w_c), max |dZ| to *mOut
+    void narrow_backward_act(int kb, const float *G, NarrowW w, const float *dH, int accumulate, int act_kind, int period, const float *Zprev,
+                             float *dZ, float *mOut) const
+    {
+        for (int c = 0; c < w.nc; ++c) w.w[c] += (size_t)kb * kWidth * w.wstride;
+        launch_narrow_backward_act(G, kLdNarrow, rows, w, dH ? dH + kb * kWidth : nullptr, accumulate, act_kind, period, Zprev + kb * kWidth,
+                                   dZ + kb * kWidth, WH, s, mOut);
+    }
+    // block kb of the heads' weight gradients (column c: gw[c][k * wstride]) and, with block 0, their bias gradients
+    void narrow_dw(int kb, const float *X, const float *G, int nc, float *const *gw, int wstride, float *const *gb, int period) const
+    {
+        float *wk[4] = { nullptr, nullptr, nullptr, nullptr };
+        for (int c = 0; c < nc; ++c) wk[c] = gw[c] + (size_t)kb * kWidth * wstride;
+        launch_narrow_dw(X + kb * kWidth, WH, G, kLdNarrow, rows, nc, wk, wstride, kb == 0 ? gb : nullptr, period, kWidth, s);
+    }
+};
+
+// the forward's sample inputs and the input-gradient outputs of neddf_train_field_backward_inputs (NULL: parameter gradients only --
+// then not one launch, allocation or byte of the backward passes differs from what it was before these outputs existed)
+struct InputGrads {
+    const float *pos, *dir, *var;
+    float *g_pos, *g_dir, *g_var;
+};
+
+// The per-layer routes reuse dA / dB from layer to layer, so the gradient matrices of the layers that read an encoding are copied
+// aside as they appear, for launch_enc_input_grad: `seg` describes the row-major matrix dZ ([seg.rows x N, seg.ld]) and its weight segment
+struct KeptGrads {
+    EncGradArgs eg{};
+    float *at = nullptr;        // room for the next copy
+};
+int keep(neddf_ctx *ctx, KeptGrads &k, int64_t N, const float *dZ, EncGradSeg seg, hipStream_t s)
+{
+    const size_t n = (size_t)N * seg.rows * seg.ld;
+    HIPCHK(hipMemcpyAsync(k.at, dZ, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    seg.dZ = k.at;
+    k.eg.seg[k.eg.n_seg++] = seg;
+    k.at += n;
+    return 0;
+}
+
+void enc_input_grad(EncGradArgs &e, int64_t N, const EncodeDesc &enc, const InputGrads &ig, hipStream_t s)
+{
+    e.N = N; e.enc = enc;
+    e.pos = ig.pos; e.dir = ig.dir; e.var = ig.var;
+    e.g_pos = ig.g_pos; e.g_dir = ig.g_dir; e.g_var = ig.g_var;
+    launch_enc_input_grad(e, s);
+}
+
+// Packed weight fragments of a fused layer stack, one `stride`-float slot per matrix.  batch: the fp32 fragments of a stack in one
+// launch (flush() after the last pack; split fp16 always goes matrix by matrix)
+struct StackPacker {
+    int sp, batch;
+    hipStream_t s;
+    float *at;
+    size_t stride;
+    PackBatch pb;
+    float *next() { float *r = at; at += stride; return r; }
+    void pack(const float *src, int64_t sk, int64_t sn, int k_off, int n_off, int kcount, int ncount, int nout, float *dst)
+    {
+        if (batch && !sp) pb.add(src, sk, sn, k_off, n_off, kcount, ncount, nout, dst, s);
+        else launch_pack(sp, src, sk, sn, k_off, n_off, kcount, ncount, nout, dst, s);
+    }
+    void flush() { pb.flush(s); }
+};
+
 // ---- plain NeRF field (nerf.py:107-165): value rows only, nn.Linear weights [out, in] -------------------------------
 struct NerfPlan {
     int E, Ed, Cpe, Cdir, n, i_dens, i_c0, i_c1, in_c0;
@@ -146,13 +315,12 @@ int make_nerf_plan(neddf_ctx *ctx, int slot, int64_t N, int n_tensors, NerfPlan 
     if (n_tensors >= 0 && n_tensors != p.n + 3) return fail(ctx, NEDDF_EINVAL, "NeRF: wrong tensor count");
     p.N = N;
     size_t o = 0;
-    auto take = [&](size_t n) { size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
-    p.o_pe = take((size_t)N * kLdPe);
-    p.o_ed = take((size_t)N * kLdDir);
-    p.o_zd = take((size_t)N * kLdNarrow);
-    p.o_zc = take((size_t)N * kWidth);
-    p.o_hc = take((size_t)N * kWidth);
-    for (int l = 0; l < p.n; ++l) { p.o_z[l] = take((size_t)N * p.WH); p.o_h[l] = take((size_t)N * p.WH); }
+    p.o_pe = take(o, (size_t)N * kLdPe);
+    p.o_ed = take(o, (size_t)N * kLdDir);
+    p.o_zd = take(o, (size_t)N * kLdNarrow);
+    p.o_zc = take(o, (size_t)N * kWidth);
+    p.o_hc = take(o, (size_t)N * kWidth);
+    for (int l = 0; l < p.n; ++l) { p.o_z[l] = take(o, (size_t)N * p.WH); p.o_h[l] = take(o, (size_t)N * p.WH); }
     p.total = o;
     return 0;
 }
@@ -165,56 +333,40 @@ int nerf_forward(neddf_ctx *ctx, int slot, const float *const *W, const float *c
     NerfPlan p;
     if (int rc = make_nerf_plan(ctx, slot, N, n_tensors, p)) return rc;
     const Field &f = ctx->field[slot];
-    const int act = f.d.activation, cus = ctx->cus, WH = p.WH, NBK = WH / kWidth, HC = p.HC;
+    const int act = f.d.activation, WH = p.WH, HC = p.HC;
     const int sp = f.d.weight_dtype == NEDDF_DTYPE_F16_SPLIT;
     if (int rc = ensure(ctx, ctx->tpack, 2 * kPackFloats * sizeof(float))) return rc;
     if (int rc = ensure(ctx, ctx->ttmp, ((size_t)N * kLdNarrow + kWidth) * sizeof(float))) return rc;
-    float *wp = (float *)ctx->tpack.p;
     float *CR = (float *)ctx->ttmp.p, *bias_c0 = CR + (size_t)N * kLdNarrow;
     float *PE = ws + p.o_pe, *Ed = ws + p.o_ed;
     EncodeDesc enc;
     fill_enc(enc, f);
     launch_pe_values(pos, dir, var, N, enc, PE, kLdPe, Ed, kLdDir, s);
     const int kpe = (p.Cpe + 3) & ~3, kdir = (p.Cdir + 3) & ~3;
-    // Z[N, ldz] (+)= X[N, Kin] x (input columns k_off .. of the [nrows_out, in_total] weight)^T for output rows 0 .. nout_valid (padded to a
-    // multiple of 256): Kin <= 256 is one K block of `kload` loaded columns, otherwise Kin = WH
-    auto gemm_fw = [&](const float *X, int ldx, int kload, int Kin, const float *Wsrc, int in_total, int k_off, int nout_valid, const float *bias,
-                       float *Z, int ldz, int acc0, int act_kind, float *H) {
-        const int KB = Kin <= kWidth ? 1 : Kin / kWidth, kc = Kin <= kWidth ? Kin : kWidth, kl = Kin <= kWidth ? kload : kWidth;
-        const int NB = (nout_valid + kWidth - 1) / kWidth;
-        for (int nb = 0; nb < NB; ++nb)
-            for (int kb = 0; kb < KB; ++kb) {
-                const bool last = kb == KB - 1;
-                const int nv = nout_valid - nb * kWidth < kWidth ? nout_valid - nb * kWidth : kWidth;
-                launch_pack(sp, Wsrc, 1, in_total, k_off + kb * kWidth, nb * kWidth, kc, nv, kWidth, wp, s);
-                launch_rows_gemm(sp, X + kb * kWidth, N, ldx, kl, wp, gemm_ksteps(kc, sp), (kb == 0 && bias) ? bias + nb * kWidth : nullptr, 1,
-                                 Z + nb * kWidth, ldz, (acc0 || kb > 0) ? 1 : 0, last ? act_kind : -1, (last && H) ? H + nb * kWidth : nullptr, cus, s);
-            }
-    };
+    const Blocks b(ctx, sp, s, N, WH);
     for (int l = 0; l < p.n; ++l) {             // nerf.py:151-155
         float *Z = ws + p.o_z[l], *H = ws + p.o_h[l];
         const bool wide = l > 0 && in_skips(f.d, l - 1);
-        const int in_total = l == 0 ? p.Cpe : (wide ? WH + p.Cpe : WH);
-        if (l == 0) gemm_fw(PE, kLdPe, kpe, p.Cpe, W[0], in_total, 0, WH, B[0], Z, WH, 0, act, H);
-        else if (!wide) gemm_fw(ws + p.o_h[l - 1], WH, WH, WH, W[l], in_total, 0, WH, B[l], Z, WH, 0, act, H);
+        const WeightView Wl{ W[l], 1, l == 0 ? p.Cpe : (wide ? WH + p.Cpe : WH) };
+        if (l == 0) b.forward(PE, kLdPe, kpe, p.Cpe, Wl, 0, WH, B[0], 1, Z, WH, 0, act, H);
+        else if (!wide) b.forward(ws + p.o_h[l - 1], WH, WH, WH, Wl, 0, WH, B[l], 1, Z, WH, 0, act, H);
         else {          // cat([hx, embed_pos]): the hidden state feeds input columns 0 .. WH-1, the encoding WH ..
-            gemm_fw(ws + p.o_h[l - 1], WH, WH, WH, W[l], in_total, 0, WH, B[l], Z, WH, 0, -1, nullptr);
-            gemm_fw(PE, kLdPe, kpe, p.Cpe, W[l], in_total, WH, WH, nullptr, Z, WH, 1, act, H);
+            b.forward(ws + p.o_h[l - 1], WH, WH, WH, Wl, 0, WH, B[l], 1, Z, WH, 0, -1, nullptr);
+            b.forward(PE, kLdPe, kpe, p.Cpe, Wl, WH, WH, nullptr, 1, Z, WH, 1, act, H);
         }
     }
     const float *Hlast = ws + p.o_h[p.n - 1];
-    for (int kb = 0; kb < NBK; ++kb) {
-        NarrowW dens{};
-        dens.nc = 1; dens.wstride = 1; dens.kcount = kWidth;
-        dens.w[0] = W[p.i_dens] + kb * kWidth; dens.b[0] = kb == 0 ? B[p.i_dens] : nullptr;
-        launch_narrow_forward(Hlast + kb * kWidth, WH, N, dens, 1, ws + p.o_zd, kLdNarrow, s, 0, kb > 0);
-    }
+    NarrowW dens{};
+    dens.nc = 1; dens.wstride = 1; dens.kcount = kWidth;
+    dens.w[0] = W[p.i_dens]; dens.b[0] = B[p.i_dens];
+    b.narrow_forward(Hlast, dens, 1, ws + p.o_zd);
     if (density) launch_density_head(f.d.density_activation, ws + p.o_zd, kLdNarrow, N, nullptr, density, 1, s);
     // colour head: Linear(WH + dir, WH / 2) -> ReLU -> Linear(WH / 2, 3); the WH / 2 outputs are one 256-column block (zero weights beyond them)
     HIPCHK(hipMemsetAsync(bias_c0, 0, kWidth * sizeof(float), s));
     HIPCHK(hipMemcpyAsync(bias_c0, B[p.i_c0], (size_t)HC * sizeof(float), hipMemcpyDeviceToDevice, s));
-    gemm_fw(Hlast, WH, WH, WH, W[p.i_c0], p.in_c0, 0, HC, bias_c0, ws + p.o_zc, kWidth, 0, -1, nullptr);
-    gemm_fw(Ed, kLdDir, kdir, p.Cdir, W[p.i_c0], p.in_c0, WH, HC, nullptr, ws + p.o_zc, kWidth, 1, NEDDF_ACT_RELU, ws + p.o_hc);
+    const WeightView Wc0{ W[p.i_c0], 1, p.in_c0 };
+    b.forward(Hlast, WH, WH, WH, Wc0, 0, HC, bias_c0, 1, ws + p.o_zc, kWidth, 0, -1, nullptr);
+    b.forward(Ed, kLdDir, kdir, p.Cdir, Wc0, WH, HC, nullptr, 1, ws + p.o_zc, kWidth, 1, NEDDF_ACT_RELU, ws + p.o_hc);
     NarrowW c1{};
     c1.nc = 3; c1.wstride = 1; c1.kcount = HC;
     for (int c = 0; c < 3; ++c) { c1.w[c] = W[p.i_c1] + c * HC; c1.b[c] = B[p.i_c1] + c; }
@@ -224,40 +376,23 @@ int nerf_forward(neddf_ctx *ctx, int slot, const float *const *W, const float *c
     return 0;
 }
 
-// the forward's sample inputs and the input-gradient outputs of neddf_train_field_backward_inputs (NULL: parameter gradients only --
-// then not one launch, allocation or byte of the pass below differs from what it was before these outputs existed)
-struct InputGrads {
-    const float *pos, *dir, *var;
-    float *g_pos, *g_dir, *g_var;
-};
-
 int nerf_backward(neddf_ctx *ctx, int slot, const float *const *W, int n_tensors, int64_t N, float *ws, const float *g_density,
                   const float *g_color, float *const *gW, float *const *gB, const InputGrads *ig, hipStream_t s)
 {
     NerfPlan p;
     if (int rc = make_nerf_plan(ctx, slot, N, n_tensors, p)) return rc;
     const Field &f = ctx->field[slot];
-    const int act = f.d.activation, cus = ctx->cus, WH = p.WH, NBK = WH / kWidth, HC = p.HC;
+    const int act = f.d.activation, WH = p.WH, NBK = WH / kWidth, HC = p.HC;
     const int sp = f.d.weight_dtype == NEDDF_DTYPE_F16_SPLIT;
     if (int rc = ensure(ctx, ctx->tpack, 2 * kPackFloats * sizeof(float))) return rc;
-    // input gradients (ig): this route reuses dA / dB from layer to layer, so the gradient matrices of the layers that read an encoding
-    // (the colour head's first layer, layer 0, the layers after a skip) are copied aside as they appear, for launch_enc_input_grad
-    int n_keep = 0;
-    if (ig) {
-        n_keep = 2;
-        for (int l = 1; l < p.n; ++l) n_keep += in_skips(f.d, l - 1) ? 1 : 0;
-    }
+    // input gradients (ig) keep the gradient matrices of the colour head's first layer, of layer 0 and of the layers after a skip
+    const int n_keep = ig ? 2 + skip_layers(f.d, p.n) : 0;
     if (int rc = ensure(ctx, ctx->ttmp, (size_t)N * ((2 + n_keep) * WH + 2 * kLdNarrow) * sizeof(float))) return rc;
-    float *wp = (float *)ctx->tpack.p;
-    float *dA = (float *)ctx->ttmp.p, *dB = dA + (size_t)N * WH, *GC = dB + (size_t)N * WH, *GD = GC + (size_t)N * kLdNarrow;
-    float *keep_at = GD + (size_t)N * kLdNarrow;
-    EncGradArgs eg{};
-    auto keep = [&](const float *dZ, int ld, int nk, const float *Wseg, int64_t sk, int ncols, int col0) -> int {
-        HIPCHK(hipMemcpyAsync(keep_at, dZ, (size_t)N * ld * sizeof(float), hipMemcpyDeviceToDevice, s));
-        eg.seg[eg.n_seg++] = EncGradSeg{ keep_at, 0, 1, ld, nk, Wseg, 1, sk, ncols, col0, 1 };
-        keep_at += (size_t)N * ld;
-        return 0;
-    };
+    Blocks b(ctx, sp, s, N, WH);
+    b.dA = (float *)ctx->ttmp.p; b.dB = b.dA + (size_t)N * WH;
+    float *GC = b.dB + (size_t)N * WH, *GD = GC + (size_t)N * kLdNarrow;
+    KeptGrads kept;
+    kept.at = GD + (size_t)N * kLdNarrow;
     const float *PE = ws + p.o_pe, *Ed = ws + p.o_ed, *Hlast = ws + p.o_h[p.n - 1];
     HIPCHK(hipMemsetAsync(GC, 0, (size_t)N * 2 * kLdNarrow * sizeof(float), s));      // GC and GD
     if (g_color) launch_copy3(g_color, 3, GC, kLdNarrow, N, s);
@@ -265,71 +400,57 @@ int nerf_backward(neddf_ctx *ctx, int slot, const float *const *W, int n_tensors
     NarrowW c1{};
     c1.nc = 3; c1.wstride = 1; c1.kcount = HC;
     for (int c = 0; c < 3; ++c) c1.w[c] = W[p.i_c1] + c * HC;
-    AmaxSlots am;
-    if (int rc = amax_begin(ctx, sp, am, s)) return rc;
-    float *mA = am.take();          // max |dA| of the gradient matrix currently in dA
-    launch_narrow_backward_act(GC, kLdNarrow, N, c1, nullptr, 0, NEDDF_ACT_RELU, 1, ws + p.o_zc, dA, kWidth, s, mA);
-    if (ig) if (int rc = keep(dA, kWidth, HC, W[p.i_c0] + WH, p.in_c0, p.Cdir, p.Cpe)) return rc;       // embed_dir columns of the colour head
+    if (int rc = amax_begin(ctx, sp, b.am, s)) return rc;
+    b.mA = b.am.take();
+    launch_narrow_backward_act(GC, kLdNarrow, N, c1, nullptr, 0, NEDDF_ACT_RELU, 1, ws + p.o_zc, b.dA, kWidth, s, b.mA);
+    b.cols(kWidth, HC);
+    if (ig)         // embed_dir columns of the colour head
+        if (int rc = keep(ctx, kept, N, b.dA, EncGradSeg{ nullptr, 0, 1, kWidth, HC, W[p.i_c0] + WH, 1, p.in_c0, p.Cdir, p.Cpe, 1 }, s)) return rc;
     {
         float *wc[3] = { gW[p.i_c1], gW[p.i_c1] + HC, gW[p.i_c1] + 2 * HC }, *bc[3] = { gB[p.i_c1], gB[p.i_c1] + 1, gB[p.i_c1] + 2 };
         launch_narrow_dw(ws + p.o_hc, kWidth, GC, kLdNarrow, N, 3, wc, 1, bc, 1, HC, s);
     }
-    // first colour layer (weights [WH / 2, WH + dir]): weight gradients per 256-row block of the hidden input, then dHlast = dA x W_c0[:, 0:WH]
-    for (int kb = 0; kb < NBK; ++kb)
-        launch_dw(sp, Hlast + kb * kWidth, WH, kWidth, dA, kWidth, N, gW[p.i_c0] + kb * kWidth, 1, p.in_c0, HC, kb == 0 ? gB[p.i_c0] : nullptr, 1, cus, s, mA, am.dw_tmp);
-    launch_dw(sp, Ed, kLdDir, p.Cdir, dA, kWidth, N, gW[p.i_c0] + WH, 1, p.in_c0, HC, nullptr, 1, cus, s, mA, am.dw_tmp);
+    // first colour layer (weights [WH / 2, WH + dir]): weight gradients, then dHlast = dA x W_c0[:, 0:WH]
+    const GradView gWc0{ gW[p.i_c0], 1, p.in_c0 };
+    b.dw(Hlast, WH, WH, gWc0, 0, gB[p.i_c0], 1);
+    b.dw(Ed, kLdDir, p.Cdir, gWc0, WH, nullptr, 1);
+    // (not through backward(): the K side of this product is the one [N, 256] block with WH / 2 loaded columns, where backward() takes
+    // K = WH columns in 256-column blocks of a [N, WH] matrix -- other strides and loaded widths in the launches)
     for (int nb = 0; nb < NBK; ++nb) {
-        launch_pack(sp, W[p.i_c0], p.in_c0, 1, 0, nb * kWidth, HC, kWidth, kWidth, wp, s);     // rows = the WH / 2 outputs, columns = hidden inputs of block nb
-        launch_rows_gemm(sp, dA, N, kWidth, HC, wp, gemm_ksteps(HC, sp), nullptr, 1, dB + nb * kWidth, WH, 0, -1, nullptr, cus, s, mA);
+        launch_pack(sp, W[p.i_c0], p.in_c0, 1, 0, nb * kWidth, HC, kWidth, kWidth, b.wp, s);     // rows = the WH / 2 outputs, columns = hidden inputs of block nb
+        launch_rows_gemm(sp, b.dA, N, kWidth, HC, b.wp, gemm_ksteps(HC, sp), nullptr, 1, b.dB + nb * kWidth, WH, 0, -1, nullptr, b.cus, s, b.mA);
     }
     // density head, then the last trunk activation: dA = dZ of the last trunk layer ([N, WH] from here on)
+    b.cols(WH, WH);
     if (g_density) launch_density_head(f.d.density_activation, ws + p.o_zd, kLdNarrow, N, g_density, GD, kLdNarrow, s);
-    mA = am.take();
+    b.mA = b.am.take();
+    NarrowW dens{};
+    dens.nc = 1; dens.wstride = 1; dens.kcount = kWidth;
+    dens.w[0] = W[p.i_dens];
+    float *wd[1] = { gW[p.i_dens] }, *bd[1] = { gB[p.i_dens] };
     for (int kb = 0; kb < NBK; ++kb) {
-        NarrowW dens{};
-        dens.nc = 1; dens.wstride = 1; dens.kcount = kWidth;
-        dens.w[0] = W[p.i_dens] + kb * kWidth;
-        launch_narrow_backward_act(GD, kLdNarrow, N, dens, dB + kb * kWidth, 1, act, 1, ws + p.o_z[p.n - 1] + kb * kWidth, dA + kb * kWidth, WH, s, mA);
-        float *wd[1] = { gW[p.i_dens] + kb * kWidth }, *bd[1] = { gB[p.i_dens] };
-        launch_narrow_dw(Hlast + kb * kWidth, WH, GD, kLdNarrow, N, 1, wd, 1, kb == 0 ? bd : nullptr, 1, kWidth, s);
+        b.narrow_backward_act(kb, GD, dens, b.dB, 1, act, 1, ws + p.o_z[p.n - 1], b.dA, b.mA);
+        b.narrow_dw(kb, Hlast, GD, 1, wd, 1, bd, 1);
     }
-    // trunk
-    auto dw_blocks = [&](const float *X, int ldx, int Kin, float *gWl, int in_total, int col_off, float *gBl) {       // gW[n, col_off + k] += dA^T X
-        const int KB = Kin <= kWidth ? 1 : Kin / kWidth, kc = Kin <= kWidth ? Kin : kWidth;
-        for (int nb = 0; nb < NBK; ++nb)
-            for (int kb = 0; kb < KB; ++kb)
-                launch_dw(sp, X + kb * kWidth, ldx, kc, dA + nb * kWidth, WH, N, gWl + (size_t)nb * kWidth * in_total + col_off + kb * kWidth, 1, in_total, kWidth,
-                          (kb == 0 && gBl) ? gBl + nb * kWidth : nullptr, 1, cus, s, mA, am.dw_tmp);
-    };
-    for (int l = p.n - 1; l >= 0; --l) {
+    for (int l = p.n - 1; l >= 0; --l) {        // trunk
         const bool wide = l > 0 && in_skips(f.d, l - 1);
         const int in_total = l == 0 ? p.Cpe : (wide ? WH + p.Cpe : WH);
-        if (ig && (l == 0 || wide)) if (int rc = keep(dA, WH, WH, W[l] + (l == 0 ? 0 : WH), in_total, p.Cpe, 0)) return rc;
+        const GradView gWl{ gW[l], 1, in_total };
+        if (ig && (l == 0 || wide))
+            if (int rc = keep(ctx, kept, N, b.dA, EncGradSeg{ nullptr, 0, 1, WH, WH, W[l] + (l == 0 ? 0 : WH), 1, in_total, p.Cpe, 0, 1 }, s)) return rc;
         if (l == 0) {
-            dw_blocks(PE, kLdPe, p.Cpe, gW[0], in_total, 0, gB[0]);
+            b.dw(PE, kLdPe, p.Cpe, gWl, 0, gB[0], 1);
             break;
         }
-        dw_blocks(ws + p.o_h[l - 1], WH, WH, gW[l], in_total, 0, gB[l]);
-        if (wide) dw_blocks(PE, kLdPe, p.Cpe, gW[l], in_total, WH, nullptr);
-        float *mB = am.take();
-        for (int nb = 0; nb < NBK; ++nb)             // dB[:, nb] = actback(Z_{l-1}[:, nb]; sum_kb dA[:, kb] x W[kb rows, nb columns])
-            for (int kb = 0; kb < NBK; ++kb) {
-                launch_pack(sp, W[l], in_total, 1, kb * kWidth, nb * kWidth, kWidth, kWidth, kWidth, wp, s);
-                if (kb == NBK - 1)
-                    launch_rows_gemm_actback(sp, dA + kb * kWidth, N, WH, kWidth, wp, gemm_ksteps(kWidth, sp), 1, act, ws + p.o_z[l - 1] + nb * kWidth,
-                                             dB + nb * kWidth, WH, cus, s, mA, mB, kb > 0);
-                else
-                    launch_rows_gemm(sp, dA + kb * kWidth, N, WH, kWidth, wp, gemm_ksteps(kWidth, sp), nullptr, 1, dB + nb * kWidth, WH, kb > 0, -1, nullptr, cus, s, mA);
-            }
-        float *t = dA; dA = dB; dB = t;
-        mA = mB;
+        b.dw(ws + p.o_h[l - 1], WH, WH, gWl, 0, gB[l], 1);
+        if (wide) b.dw(PE, kLdPe, p.Cpe, gWl, WH, nullptr, 1);
+        b.backward(WeightView{ W[l], 1, in_total }, 0, 1, act, ws + p.o_z[l - 1], b.am.take());
+        b.swap();
     }
     if (ig) {
-        eg.N = N;
-        fill_enc(eg.enc, f);
-        eg.pos = ig->pos; eg.dir = ig->dir; eg.var = ig->var;
-        eg.g_pos = ig->g_pos; eg.g_dir = ig->g_dir; eg.g_var = ig->g_var;
-        launch_enc_input_grad(eg, s);
+        EncodeDesc enc;
+        fill_enc(enc, f);
+        enc_input_grad(kept.eg, N, enc, *ig, s);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -360,13 +481,12 @@ int make_neus_plan(neddf_ctx *ctx, int slot, int64_t N, int n_tensors, NeusPlan 
     if (n_tensors >= 0 && n_tensors != p.n_sdf + p.n_col + 2) return fail(ctx, NEDDF_EINVAL, "NeuS: wrong tensor count");
     p.N = N; p.R = 4 * N;
     size_t o = 0;
-    auto take = [&](size_t n) { size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
-    p.o_pe = take((size_t)p.R * kLdPe);
-    p.o_ed = take((size_t)N * kLdDir);
-    p.o_xa = take((size_t)N * p.ldxa);
-    p.o_zo = take((size_t)N * kLdNarrow);
-    for (int l = 0; l < p.n_sdf; ++l) { p.o_z[l] = take((size_t)p.R * p.WH); p.o_h[l] = take((size_t)p.R * p.WH); }
-    for (int l = 0; l < p.n_col; ++l) { p.o_zc[l] = take((size_t)N * p.WH); p.o_hc[l] = take((size_t)N * p.WH); }
+    p.o_pe = take(o, (size_t)p.R * kLdPe);
+    p.o_ed = take(o, (size_t)N * kLdDir);
+    p.o_xa = take(o, (size_t)N * p.ldxa);
+    p.o_zo = take(o, (size_t)N * kLdNarrow);
+    for (int l = 0; l < p.n_sdf; ++l) { p.o_z[l] = take(o, (size_t)p.R * p.WH); p.o_h[l] = take(o, (size_t)p.R * p.WH); }
+    for (int l = 0; l < p.n_col; ++l) { p.o_zc[l] = take(o, (size_t)N * p.WH); p.o_hc[l] = take(o, (size_t)N * p.WH); }
     p.total = o;
     return 0;
 }
@@ -388,11 +508,12 @@ int neus_forward(neddf_ctx *ctx, int slot, const float *const *W, const float *c
     NeusPlan p;
     if (int rc = make_neus_plan(ctx, slot, N, n_tensors, p)) return rc;
     const Field &f = ctx->field[slot];
-    const int act = f.d.activation, cus = ctx->cus, WH = p.WH, NBK = WH / kWidth;
+    const int act = f.d.activation, WH = p.WH;
     const int sp = f.d.weight_dtype == NEDDF_DTYPE_F16_SPLIT;
-    if (int rc = ensure(ctx, ctx->tpack, 2 * kPackFloats * sizeof(float))) return rc;
+    // the sdf trunk as one fused layer stack (256 wide, one skip partial), every other product block by block
+    const bool fused = !train_unfused() && skip_layers(f.d, p.n_sdf) <= 1 && WH == kWidth;
+    if (int rc = ensure(ctx, ctx->tpack, (size_t)(fused ? kMaxLayers + 2 : 2) * kPackFloats * sizeof(float))) return rc;
     if (int rc = ensure(ctx, ctx->ttmp, ((size_t)p.R * kLdPe + (size_t)N * 4) * sizeof(float))) return rc;
-    float *wp = (float *)ctx->tpack.p;
     float *PEs = (float *)ctx->ttmp.p, *var0 = PEs + (size_t)p.R * kLdPe;
     float *PE = ws + p.o_pe, *Ed = ws + p.o_ed;
     // plain PositionalEncoding (neus.py:118-119): no variance weights, no low-pass schedule
@@ -402,58 +523,40 @@ int neus_forward(neddf_ctx *ctx, int slot, const float *const *W, const float *c
     for (int i = 0; i < 10; ++i) enc.lowpass[i] = 1.0f;
     launch_pe_rows(pos, dir, var0, N, enc, PEs, PE, kLdPe, Ed, kLdDir, s);
     const int kpe = (p.Cpe + 3) & ~3;
-    int n_wide = 0;
-    for (int l = 1; l < p.n_sdf; ++l) n_wide += in_skips(f.d, l - 1) ? 1 : 0;
-    static const bool unfused = [] { const char *e = getenv("NEDDF_TRAIN_UNFUSED"); return e && atoi(e) != 0; }();
-    // Z[rows, WH] (+)= X[rows, Kin] x (input columns k_off .. of the [WH, in_total] weight)^T, 256 x 256 blocks: Kin <= 256 is one K
-    // block of `kload` loaded columns, otherwise Kin = WH; K blocks accumulate in Z, the activation runs with the last one
-    auto gemm_fw = [&](const float *X, int64_t rows, int ldx, int kload, int Kin, const float *Wsrc, int in_total, int k_off, const float *bias,
-                       int period, float *Z, int acc0, int act_kind, float *H) {
-        const int KB = Kin <= kWidth ? 1 : Kin / kWidth, kc = Kin <= kWidth ? Kin : kWidth, kl = Kin <= kWidth ? kload : kWidth;
-        for (int nb = 0; nb < NBK; ++nb)
-            for (int kb = 0; kb < KB; ++kb) {
-                const bool last = kb == KB - 1;
-                launch_pack(sp, Wsrc, 1, in_total, k_off + kb * kWidth, nb * kWidth, kc, kWidth, kWidth, wp, s);
-                launch_rows_gemm(sp, X + kb * kWidth, rows, ldx, kl, wp, gemm_ksteps(kc, sp), (kb == 0 && bias) ? bias + nb * kWidth : nullptr, period,
-                                 Z + nb * kWidth, WH, (acc0 || kb > 0) ? 1 : 0, last ? act_kind : -1, (last && H) ? H + nb * kWidth : nullptr, cus, s);
-            }
-    };
-    if (!unfused && n_wide <= 1 && WH == kWidth) {      // the sdf trunk (neus.py:121-125) as one fused layer stack (train_kernels.h MlpForwardArgs)
-        if (int rc = ensure(ctx, ctx->tpack, (size_t)(kMaxLayers + 2) * kPackFloats * sizeof(float))) return rc;
-        wp = (float *)ctx->tpack.p;
-        float *pack_at = wp;
-        auto next_pack = [&]() { float *r = pack_at; pack_at += kPackFloats; return r; };
+    Blocks b(ctx, sp, s, p.R, WH);
+    if (fused) {        // neus.py:121-125 (train_kernels.h MlpForwardArgs); one pack launch per matrix
+        StackPacker pk{ sp, 0, s, b.wp, kPackFloats, {} };
         MlpForwardArgs m{};
         m.R = p.R; m.X0 = PE; m.ld0 = kLdPe; m.kload0 = kpe; m.ksteps0 = gemm_ksteps(p.Cpe, sp);
         m.n_layers = p.n_sdf; m.skip_layer = -1; m.act_kind = act;
-        float *w0 = next_pack();
-        launch_pack(sp, W[0], 1, p.Cpe, 0, 0, p.Cpe, kWidth, kWidth, w0, s);
+        float *w0 = pk.next();
+        pk.pack(W[0], 1, p.Cpe, 0, 0, p.Cpe, kWidth, kWidth, w0);
         m.wp0 = w0;
         for (int l = 0; l < p.n_sdf; ++l) {
             const bool wide = l > 0 && in_skips(f.d, l - 1);
             const int in_total = l == 0 ? p.Cpe : (wide ? kWidth + p.Cpe : kWidth);
             m.bias[l] = B[l]; m.Z[l] = ws + p.o_z[l]; m.H[l] = ws + p.o_h[l];
             if (l == 0) continue;
-            float *wl = next_pack();
-            launch_pack(sp, W[l], 1, in_total, 0, 0, kWidth, kWidth, kWidth, wl, s);       // cat([hx, embed_pos]): hidden state first
+            float *wl = pk.next();
+            pk.pack(W[l], 1, in_total, 0, 0, kWidth, kWidth, kWidth, wl);       // cat([hx, embed_pos]): hidden state first
             m.wp[l] = wl;
             if (wide) {
-                float *wsk = next_pack();
-                launch_pack(sp, W[l], 1, in_total, kWidth, 0, p.Cpe, kWidth, kWidth, wsk, s);
+                float *wsk = pk.next();
+                pk.pack(W[l], 1, in_total, kWidth, 0, p.Cpe, kWidth, kWidth, wsk);
                 m.skip_layer = l; m.wp_skip = wsk;
             }
         }
-        launch_mlp_forward(sp, m, cus, s);
+        launch_mlp_forward(sp, m, b.cus, s);
     } else
     for (int l = 0; l < p.n_sdf; ++l) {             // neus.py:121-125
         float *Z = ws + p.o_z[l], *H = ws + p.o_h[l];
         const bool wide = l > 0 && in_skips(f.d, l - 1);
-        const int in_total = l == 0 ? p.Cpe : (wide ? WH + p.Cpe : WH);
-        if (l == 0) gemm_fw(PE, p.R, kLdPe, kpe, p.Cpe, W[0], in_total, 0, B[0], 4, Z, 0, act, H);
-        else if (!wide) gemm_fw(ws + p.o_h[l - 1], p.R, WH, WH, WH, W[l], in_total, 0, B[l], 4, Z, 0, act, H);
+        const WeightView Wl{ W[l], 1, l == 0 ? p.Cpe : (wide ? WH + p.Cpe : WH) };
+        if (l == 0) b.forward(PE, kLdPe, kpe, p.Cpe, Wl, 0, WH, B[0], 4, Z, WH, 0, act, H);
+        else if (!wide) b.forward(ws + p.o_h[l - 1], WH, WH, WH, Wl, 0, WH, B[l], 4, Z, WH, 0, act, H);
         else {          // cat([hx, embed_pos]): hidden state first
-            gemm_fw(ws + p.o_h[l - 1], p.R, WH, WH, WH, W[l], in_total, 0, B[l], 4, Z, 0, -1, nullptr);
-            gemm_fw(PE, p.R, kLdPe, kpe, p.Cpe, W[l], in_total, WH, nullptr, 4, Z, 1, act, H);
+            b.forward(ws + p.o_h[l - 1], WH, WH, WH, Wl, 0, WH, B[l], 4, Z, WH, 0, -1, nullptr);
+            b.forward(PE, kLdPe, kpe, p.Cpe, Wl, WH, WH, nullptr, 4, Z, WH, 1, act, H);
         }
     }
     NeusPointArgs a;
@@ -461,22 +564,22 @@ int neus_forward(neddf_ctx *ctx, int slot, const float *const *W, const float *c
     a.pos = pos; a.sdf = sdf; a.density = density; a.color = color;
     launch_neus_head_forward(a, s);
     // colour trunk on value rows (neus.py:146-152): the features are the value rows of the last sdf layer (row stride 4 x WH)
+    b.rows = N;
     const float *Hlast = ws + p.o_h[p.n_sdf - 1];
     for (int l = 0; l < p.n_col; ++l) {
         float *Z = ws + p.o_zc[l], *H = ws + p.o_hc[l];
-        const float *Wl = W[p.n_sdf + l], *Bl = B[p.n_sdf + l];
+        const float *Bl = B[p.n_sdf + l];
+        const WeightView Wl{ W[p.n_sdf + l], 1, l == 0 ? p.in_c0 : WH };
         if (l == 0) {
-            gemm_fw(ws + p.o_xa, N, p.ldxa, p.ldxa, p.Ca, Wl, p.in_c0, 0, Bl, 1, Z, 0, -1, nullptr);
-            gemm_fw(Hlast, N, 4 * WH, WH, WH, Wl, p.in_c0, p.Ca, nullptr, 1, Z, 1, act, H);
+            b.forward(ws + p.o_xa, p.ldxa, p.ldxa, p.Ca, Wl, 0, WH, Bl, 1, Z, WH, 0, -1, nullptr);
+            b.forward(Hlast, 4 * WH, WH, WH, Wl, p.Ca, WH, nullptr, 1, Z, WH, 1, act, H);
         } else
-            gemm_fw(ws + p.o_hc[l - 1], N, WH, WH, WH, Wl, WH, 0, Bl, 1, Z, 0, act, H);
+            b.forward(ws + p.o_hc[l - 1], WH, WH, WH, Wl, 0, WH, Bl, 1, Z, WH, 0, act, H);
     }
-    for (int kb = 0; kb < NBK; ++kb) {
-        NarrowW cout{};
-        cout.nc = 3; cout.wstride = 1; cout.kcount = kWidth;
-        for (int c = 0; c < 3; ++c) { cout.w[c] = W[p.i_cout] + c * WH + kb * kWidth; cout.b[c] = kb == 0 ? B[p.i_cout] + c : nullptr; }
-        launch_narrow_forward(ws + p.o_hc[p.n_col - 1] + kb * kWidth, WH, N, cout, 1, ws + p.o_zo, kLdNarrow, s, 0, kb > 0);
-    }
+    NarrowW cout{};
+    cout.nc = 3; cout.wstride = 1; cout.kcount = kWidth;
+    for (int c = 0; c < 3; ++c) { cout.w[c] = W[p.i_cout] + c * WH; cout.b[c] = B[p.i_cout] + c; }
+    b.narrow_forward(ws + p.o_hc[p.n_col - 1], cout, 1, ws + p.o_zo);
     if (color) launch_neus_color_forward(a, s);
     HIPCHK(hipGetLastError());
     return 0;
@@ -488,89 +591,64 @@ int neus_backward(neddf_ctx *ctx, int slot, const float *const *W, int n_tensors
     NeusPlan p;
     if (int rc = make_neus_plan(ctx, slot, N, n_tensors, p)) return rc;
     const Field &f = ctx->field[slot];
-    const int act = f.d.activation, act4 = neus_backward_act_kind(act), cus = ctx->cus, WH = p.WH, NBK = WH / kWidth;
+    const int act = f.d.activation, act4 = neus_backward_act_kind(act), WH = p.WH, NBK = WH / kWidth;
     const int sp = f.d.weight_dtype == NEDDF_DTYPE_F16_SPLIT;
     if (int rc = ensure(ctx, ctx->tpack, 2 * kPackFloats * sizeof(float))) return rc;
     if (int rc = ensure(ctx, ctx->ttmp, ((size_t)p.R * 2 * WH + (size_t)N * 2 * kLdNarrow) * sizeof(float))) return rc;
-    float *wp = (float *)ctx->tpack.p;
-    float *dA = (float *)ctx->ttmp.p, *dB = dA + (size_t)p.R * WH, *GC = dB + (size_t)p.R * WH, *DG = GC + (size_t)N * kLdNarrow;
+    Blocks b(ctx, sp, s, N, WH);
+    b.dA = (float *)ctx->ttmp.p; b.dB = b.dA + (size_t)p.R * WH;
+    float *GC = b.dB + (size_t)p.R * WH, *DG = GC + (size_t)N * kLdNarrow;
     const float *PE = ws + p.o_pe, *Hlast = ws + p.o_h[p.n_sdf - 1];
     NeusPointArgs a;
     neus_point_args(a, f, p, W, ws);
     a.g_sdf = g_sdf; a.g_density = g_density; a.g_color = g_color;
     a.GC = GC; a.g_variance = gW[p.i_var];
     launch_neus_color_backward(a, s);               // GC = g_color a'(ZC); variance gradient
-    AmaxSlots am;
-    if (int rc = amax_begin(ctx, sp, am, s)) return rc;
-    float *mA = am.take();          // max |dA| of the gradient matrix currently in dA
-    // gW[n, col_off + k] += dA[rows, WH]^T X[rows, Kin] in 256 x 256 blocks (+ the bias gradient with the first K block)
-    auto dw_blocks = [&](const float *X, int64_t rows, int ldx, int Kin, float *gWl, int in_total, int col_off, float *gBl, int period) {
-        const int KB = Kin <= kWidth ? 1 : Kin / kWidth, kc = Kin <= kWidth ? Kin : kWidth;
-        for (int nb = 0; nb < NBK; ++nb)
-            for (int kb = 0; kb < KB; ++kb)
-                launch_dw(sp, X + kb * kWidth, ldx, kc, dA + nb * kWidth, WH, rows, gWl + (size_t)nb * kWidth * in_total + col_off + kb * kWidth, 1, in_total, kWidth,
-                          (kb == 0 && gBl) ? gBl + nb * kWidth : nullptr, period, cus, s, mA, am.dw_tmp);
-    };
-    // dB[rows, WH] = actback(Zprev; dA x (input columns k_off .. k_off + WH of the [WH, in_total] weight)) (act_kind < 0: no activation)
-    auto gemm_bw = [&](int64_t rows, const float *Wsrc, int in_total, int k_off, int period, int act_kind, const float *Zprev, float *mB) {
-        for (int nb = 0; nb < NBK; ++nb)
-            for (int kb = 0; kb < NBK; ++kb) {
-                launch_pack(sp, Wsrc, in_total, 1, kb * kWidth, k_off + nb * kWidth, kWidth, kWidth, kWidth, wp, s);      // rows = outputs, columns = inputs
-                if (kb == NBK - 1 && act_kind >= 0)
-                    launch_rows_gemm_actback(sp, dA + kb * kWidth, rows, WH, kWidth, wp, gemm_ksteps(kWidth, sp), period, act_kind, Zprev + nb * kWidth,
-                                             dB + nb * kWidth, WH, cus, s, mA, mB, kb > 0);
-                else
-                    launch_rows_gemm(sp, dA + kb * kWidth, rows, WH, kWidth, wp, gemm_ksteps(kWidth, sp), nullptr, 1, dB + nb * kWidth, WH, kb > 0, -1, nullptr, cus, s, mA);
-            }
-    };
-    // colour trunk, value rows ([N, WH] matrices; dA holds dZ of the layer in flight)
+    if (int rc = amax_begin(ctx, sp, b.am, s)) return rc;
+    b.mA = b.am.take();
+    // colour trunk, value rows ([N, WH] matrices)
+    NarrowW cout{};
+    cout.nc = 3; cout.wstride = 1; cout.kcount = kWidth;
+    for (int c = 0; c < 3; ++c) cout.w[c] = W[p.i_cout] + c * WH;
+    float *wc[3] = { gW[p.i_cout], gW[p.i_cout] + WH, gW[p.i_cout] + 2 * WH }, *bc[3] = { gB[p.i_cout], gB[p.i_cout] + 1, gB[p.i_cout] + 2 };
     for (int kb = 0; kb < NBK; ++kb) {
-        NarrowW cout{};
-        cout.nc = 3; cout.wstride = 1; cout.kcount = kWidth;
-        for (int c = 0; c < 3; ++c) cout.w[c] = W[p.i_cout] + c * WH + kb * kWidth;
-        launch_narrow_backward_act(GC, kLdNarrow, N, cout, nullptr, 0, act, 1, ws + p.o_zc[p.n_col - 1] + kb * kWidth, dA + kb * kWidth, WH, s, mA);
-        float *wc[3] = { gW[p.i_cout] + kb * kWidth, gW[p.i_cout] + WH + kb * kWidth, gW[p.i_cout] + 2 * WH + kb * kWidth };
-        float *bc[3] = { gB[p.i_cout], gB[p.i_cout] + 1, gB[p.i_cout] + 2 };
-        launch_narrow_dw(ws + p.o_hc[p.n_col - 1] + kb * kWidth, WH, GC, kLdNarrow, N, 3, wc, 1, kb == 0 ? bc : nullptr, 1, kWidth, s);
+        b.narrow_backward_act(kb, GC, cout, nullptr, 0, act, 1, ws + p.o_zc[p.n_col - 1], b.dA, b.mA);
+        b.narrow_dw(kb, ws + p.o_hc[p.n_col - 1], GC, 3, wc, 1, bc, 1);
     }
     for (int l = p.n_col - 1; l >= 1; --l) {
-        dw_blocks(ws + p.o_hc[l - 1], N, WH, WH, gW[p.n_sdf + l], WH, 0, gB[p.n_sdf + l], 1);
-        float *mB = am.take();
-        gemm_bw(N, W[p.n_sdf + l], WH, 0, 1, act, ws + p.o_zc[l - 1], mB);
-        float *t = dA; dA = dB; dB = t;
-        mA = mB;
+        b.dw(ws + p.o_hc[l - 1], WH, WH, GradView{ gW[p.n_sdf + l], 1, WH }, 0, gB[p.n_sdf + l], 1);
+        b.backward(WeightView{ W[p.n_sdf + l], 1, WH }, 0, 1, act, ws + p.o_zc[l - 1], b.am.take());
+        b.swap();
     }
     {   // first colour layer: weights [WH, pos 3 | embed_dir | gradient 3 | features WH]
         const float *W0 = W[p.n_sdf];
-        float *gW0 = gW[p.n_sdf];
-        dw_blocks(ws + p.o_xa, N, p.ldxa, p.Ca, gW0, p.in_c0, 0, gB[p.n_sdf], 1);
-        dw_blocks(Hlast, N, 4 * WH, WH, gW0, p.in_c0, p.Ca, nullptr, 1);
+        const GradView gW0{ gW[p.n_sdf], 1, p.in_c0 };
+        b.dw(ws + p.o_xa, p.ldxa, p.Ca, gW0, 0, gB[p.n_sdf], 1);
+        b.dw(Hlast, 4 * WH, WH, gW0, p.Ca, nullptr, 1);
         // of the small inputs only the normal depends on parameters: DG[n, k] = dA[n, :] . W0[:, 3 + Cdir + k]
-        for (int kb = 0; kb < NBK; ++kb) {
-            NarrowW wn{};
-            wn.nc = 3; wn.wstride = p.in_c0; wn.kcount = kWidth;
-            for (int c = 0; c < 3; ++c) wn.w[c] = W0 + (size_t)kb * kWidth * p.in_c0 + 3 + p.Cdir + c;
-            launch_narrow_forward(dA + kb * kWidth, WH, N, wn, 1, DG, kLdNarrow, s, 0, kb > 0);
-        }
-        gemm_bw(N, W0, p.in_c0, p.Ca, 1, -1, nullptr, nullptr);      // dF
+        NarrowW wn{};
+        wn.nc = 3; wn.wstride = p.in_c0; wn.kcount = kWidth;
+        for (int c = 0; c < 3; ++c) wn.w[c] = W0 + 3 + p.Cdir + c;
+        b.narrow_forward(b.dA, wn, 1, DG);
+        b.backward(WeightView{ W0, 1, p.in_c0 }, p.Ca, 1, -1, nullptr, nullptr);      // dF, left in dB
     }
     // heads: dZ of the last sdf layer on (value, Jacobian) rows
-    mA = am.take();
-    a.dF = dB; a.DG = DG; a.lddg = kLdNarrow; a.dZ = dA; a.amax_out = mA;
+    b.rows = p.R;
+    b.mA = b.am.take();
+    a.dF = b.dB; a.DG = DG; a.lddg = kLdNarrow; a.dZ = b.dA; a.amax_out = b.mA;
     launch_neus_head_backward(a, s);
     for (int l = p.n_sdf - 1; l >= 0; --l) {
         const bool wide = l > 0 && in_skips(f.d, l - 1);
         const int in_total = l == 0 ? p.Cpe : (wide ? WH + p.Cpe : WH);
+        const GradView gWl{ gW[l], 1, in_total };
         if (l == 0) {
-            dw_blocks(PE, p.R, kLdPe, p.Cpe, gW[0], in_total, 0, gB[0], 4);
+            b.dw(PE, kLdPe, p.Cpe, gWl, 0, gB[0], 4);
             break;
         }
-        dw_blocks(ws + p.o_h[l - 1], p.R, WH, WH, gW[l], in_total, 0, gB[l], 4);
-        if (wide) dw_blocks(PE, p.R, kLdPe, p.Cpe, gW[l], in_total, WH, nullptr, 4);
-        float *mB = am.take();
-        gemm_bw(p.R, W[l], in_total, 0, 4, act4, ws + p.o_z[l - 1], mB);
-        float *t = dA; dA = dB; dB = t;
-        mA = mB;
+        b.dw(ws + p.o_h[l - 1], WH, WH, gWl, 0, gB[l], 4);
+        if (wide) b.dw(PE, kLdPe, p.Cpe, gWl, WH, nullptr, 4);
+        b.backward(WeightView{ W[l], 1, in_total }, 0, 4, act4, ws + p.o_z[l - 1], b.am.take());
+        b.swap();
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -620,88 +698,55 @@ int neddf_train_field_forward(neddf_ctx *ctx, int slot, const float *const *W, c
     const size_t packf = (size_t)p.WH * p.WH;       // one packed hidden x hidden matrix (kPackFloats at width 256)
     if (int rc = ensure(ctx, ctx->tpack, (size_t)(kMaxLayers + 2) * packf * sizeof(float))) return rc;
     if (int rc = ensure(ctx, ctx->ttmp, ((size_t)p.R * (kLdPe + kLdNarrow) + (size_t)N * kLdDir) * sizeof(float))) return rc;
-    float *wp = (float *)ctx->tpack.p;
     float *PEu = (float *)ctx->ttmp.p, *Ed = PEu + (size_t)p.R * kLdPe, *ZH = Ed + (size_t)N * kLdDir;
     float *PEs = ws + p.o_pes;
     TrainPointArgs a;
     point_args(a, f, p, ws);
     launch_pe_rows(pos, dir, var, N, a.enc, PEs, PEu, kLdPe, Ed, kLdDir, s);
-    // NEDDF_TRAIN_UNFUSED=1: one GEMM kernel per layer (the round-1 forward), kept for A/B measurements
-    static const bool unfused = [] { const char *e = getenv("NEDDF_TRAIN_UNFUSED"); return e && atoi(e) != 0; }();
     const int kpe = (p.Cpe + 3) & ~3;       // loaded width of the encoding matrix (pad columns are zero)
-    float *pack_at = wp;
-    auto next_pack = [&]() { float *r = pack_at; pack_at += packf; return r; };
-    // weight fragments of a fused stack: fp32 in one launch per stack (PackBatch), split fp16 matrix by matrix
-    PackBatch pb;
-    auto pack = [&](const float *src, int64_t sk, int64_t sn, int k_off, int n_off, int kcount, int ncount, int nout, float *dst) {
-        if (sp) launch_pack(1, src, sk, sn, k_off, n_off, kcount, ncount, nout, dst, s);
-        else pb.add(src, sk, sn, k_off, n_off, kcount, ncount, nout, dst, s);
-    };
-    // distance trunk (neddf.py:206-218); the fused kernel holds one skip partial, architectures with more take the per-layer route
-    int n_wide = 0;
-    for (int l = 1; l < p.n_trunk; ++l) n_wide += in_skips(f.d, l - 1) ? 1 : 0;
-    // fp32 policy, both stacks fused: the hidden states are kept point-major (train_kernels.h MlpForwardArgs.point_major), the layout of
-    // the fused backward (neddf_train_field_backward takes that route under the same condition)
-    const int WH = p.WH, NBK = WH / kWidth;      // hidden width the kernels see, in 256-column blocks
-    // the fused chains are 256 wide, and -- round 5, fp32 policy -- 512 wide for the fields that train padded to 512 (wide_fused)
-    const bool fused = !unfused && n_wide <= 1 && (WH == kWidth || (WH == 2 * kWidth && wide_fused() && (!sp || split_fused())));
-    // (round 5: the split-fp16 policy takes the same fused, point-major route; NEDDF_TRAIN_SPLIT_FUSED=0 keeps its per-layer backward
-    // and the row-major matrices that reads -- the A/B partner)
+    const int WH = p.WH;                    // hidden width the kernels see
+    const Blocks b(ctx, sp, s, p.R, WH);
+    StackPacker pk{ sp, 1, s, b.wp, packf, {} };
+    // distance trunk (neddf.py:206-218); the fused kernel holds one skip partial, architectures with more take the per-layer route.
+    // The fused chains are 256 wide, and -- round 5 -- 512 wide for the fields that train padded to 512 (wide_fused)
+    const bool fused = !train_unfused() && skip_layers(f.d, p.n_trunk) <= 1 &&
+                       (WH == kWidth || (WH == 2 * kWidth && wide_fused() && (!sp || split_fused())));
+    // both stacks fused: the hidden states are kept point-major (train_kernels.h MlpForwardArgs.point_major), the layout of the fused
+    // backward (neddf_train_field_backward takes that route under the same condition).  Round 5: the split-fp16 policy takes the same
+    // route; NEDDF_TRAIN_SPLIT_FUSED=0 keeps its per-layer backward and the row-major matrices that reads -- the A/B partner
     const int pm = (fused && (!sp || split_fused())) ? 1 : 0;
-    // Z[R, WH] (+)= X[R, Kin] x (rows k_off .. k_off + Kin of the [in, WH] weight) (+ bias on value rows); H = a(Z) when act_kind >= 0.
-    // Kin <= 256: one K block of `kload` loaded columns; otherwise Kin = WH in 256-row blocks.  Every block is one rows_gemm launch:
-    // K blocks accumulate in Z, the activation runs with the last one
-    auto gemm_fw = [&](const float *X, int ldx, int kload, int Kin, const float *Wsrc, int k_off, const float *bias, float *Z, int acc0,
-                       int act_kind, float *H) {
-        const int KB = Kin <= kWidth ? 1 : Kin / kWidth, kc = Kin <= kWidth ? Kin : kWidth, kl = Kin <= kWidth ? kload : kWidth;
-        for (int nb = 0; nb < NBK; ++nb)
-            for (int kb = 0; kb < KB; ++kb) {
-                const bool last = kb == KB - 1;
-                launch_pack(sp, Wsrc, WH, 1, k_off + kb * kWidth, nb * kWidth, kc, kWidth, kWidth, wp, s);
-                launch_rows_gemm(sp, X + kb * kWidth, p.R, ldx, kl, wp, gemm_ksteps(kc, sp), (kb == 0 && bias) ? bias + nb * kWidth : nullptr, 4,
-                                 Z + nb * kWidth, WH, (acc0 || kb > 0) ? 1 : 0, last ? act_kind : -1, (last && H) ? H + nb * kWidth : nullptr, ctx->cus, s);
-            }
-    };
-    // Y[R, kLdNarrow] = X[R, WH] . (nc narrow columns) + bias: one narrow_forward launch per 256-column block of X
-    auto narrow_fw = [&](const float *X, NarrowW w, float *Y, int x_pm) {
-        const float *w0[4] = { w.w[0], w.w[1], w.w[2], w.w[3] }, *b0[4] = { w.b[0], w.b[1], w.b[2], w.b[3] };
-        for (int kb = 0; kb < NBK; ++kb) {
-            for (int c = 0; c < w.nc; ++c) { w.w[c] = w0[c] + (size_t)kb * kWidth * w.wstride; w.b[c] = kb == 0 ? b0[c] : nullptr; }
-            // (column block kb of a point-major matrix starts 4 x 256 kb floats into a point)
-            launch_narrow_forward(X + (x_pm ? 4 : 1) * kb * kWidth, WH, p.R, w, 4, Y, kLdNarrow, s, x_pm, kb > 0);
-        }
-    };
     if (fused) {
         MlpForwardArgs m{};
         m.R = p.R; m.X0 = PEs; m.ld0 = kLdPe; m.kload0 = kpe; m.ksteps0 = gemm_ksteps(p.Cpe, sp);
         m.n_layers = p.n_trunk; m.skip_layer = -1; m.act_kind = act; m.point_major = pm; m.width = WH;
-        float *w0 = next_pack();
-        pack(W[0], WH, 1, 0, 0, p.Cpe, WH, WH, w0);
+        float *w0 = pk.next();
+        pk.pack(W[0], WH, 1, 0, 0, p.Cpe, WH, WH, w0);
         m.wp0 = w0;
         for (int l = 0; l < p.n_trunk; ++l) {
             const bool wide = l > 0 && in_skips(f.d, l - 1);
             m.bias[l] = B[l]; m.Z[l] = ws + p.o_z[l]; m.H[l] = ws + p.o_h[l];
             if (l == 0) continue;
-            float *wl = next_pack();
-            pack(W[l], WH, 1, wide ? p.Cpe : 0, 0, WH, WH, WH, wl);
+            float *wl = pk.next();
+            pk.pack(W[l], WH, 1, wide ? p.Cpe : 0, 0, WH, WH, WH, wl);
             m.wp[l] = wl;
             if (wide) {         // hx = cat([embed_pos_scaled, hx]): the encoding feeds rows 0 .. Cpe-1 of the weight
-                float *wsk = next_pack();
-                pack(W[l], WH, 1, 0, 0, p.Cpe, WH, WH, wsk);
+                float *wsk = pk.next();
+                pk.pack(W[l], WH, 1, 0, 0, p.Cpe, WH, WH, wsk);
                 m.skip_layer = l; m.wp_skip = wsk;
             }
         }
-        pb.flush(s);
+        pk.flush();
         launch_mlp_forward(sp, m, ctx->cus, s);
     } else {
         for (int l = 0; l < p.n_trunk; ++l) {
             float *Z = ws + p.o_z[l], *H = ws + p.o_h[l];
             const bool wide = l > 0 && in_skips(f.d, l - 1);
-            if (l == 0) gemm_fw(PEs, kLdPe, kpe, p.Cpe, W[0], 0, B[0], Z, 0, act, H);
-            else if (!wide) gemm_fw(ws + p.o_h[l - 1], WH, WH, WH, W[l], 0, B[l], Z, 0, act, H);
+            const WeightView Wl{ W[l], WH, 1 };
+            if (l == 0) b.forward(PEs, kLdPe, kpe, p.Cpe, Wl, 0, WH, B[0], 4, Z, WH, 0, act, H);
+            else if (!wide) b.forward(ws + p.o_h[l - 1], WH, WH, WH, Wl, 0, WH, B[l], 4, Z, WH, 0, act, H);
             else {              // hx = cat([embed_pos_scaled, hx]): the encoding feeds rows 0 .. Cpe-1 of the weight
-                gemm_fw(ws + p.o_h[l - 1], WH, WH, WH, W[l], p.Cpe, B[l], Z, 0, -1, nullptr);
-                gemm_fw(PEs, kLdPe, kpe, p.Cpe, W[l], 0, nullptr, Z, 1, act, H);
+                b.forward(ws + p.o_h[l - 1], WH, WH, WH, Wl, p.Cpe, WH, B[l], 4, Z, WH, 0, -1, nullptr);
+                b.forward(PEs, kLdPe, kpe, p.Cpe, Wl, 0, WH, nullptr, 4, Z, WH, 1, act, H);
             }
         }
     }
@@ -710,7 +755,7 @@ int neddf_train_field_forward(neddf_ctx *ctx, int slot, const float *const *W, c
     heads.nc = 2; heads.wstride = 1; heads.kcount = kWidth;
     heads.w[0] = W[p.i_ddf]; heads.w[1] = W[p.i_aux];
     heads.b[0] = B[p.i_ddf]; heads.b[1] = B[p.i_aux];
-    narrow_fw(Hlast, heads, ZH, pm);
+    b.narrow_forward(Hlast, heads, 4, ZH, pm);
     a.ZH = ZH; a.PEu = PEu; a.Ed = Ed;
     a.distance = distance; a.density = density; a.aux_grad = aux_grad;
     launch_point_forward(a, s);
@@ -719,34 +764,35 @@ int neddf_train_field_forward(neddf_ctx *ctx, int slot, const float *const *W, c
         MlpForwardArgs m{};
         m.R = p.R; m.X0 = ws + p.o_xa; m.ld0 = p.ldxa; m.kload0 = p.ldxa; m.ksteps0 = gemm_ksteps(p.Ca, sp);
         m.X1 = Hlast; m.n_layers = p.n_col; m.skip_layer = -1; m.act_kind = act; m.point_major = pm; m.width = WH;
-        pack_at = wp;           // same stream: the trunk kernel is done with the buffer when these packs run
-        float *w0 = next_pack(), *w1 = next_pack();
-        pack(W[p.n_trunk], WH, 1, 0, 0, p.Ca, WH, WH, w0);
-        pack(W[p.n_trunk], WH, 1, p.Ca, 0, WH, WH, WH, w1);
+        pk.at = b.wp;           // same stream: the trunk kernel is done with the buffer when these packs run
+        float *w0 = pk.next(), *w1 = pk.next();
+        pk.pack(W[p.n_trunk], WH, 1, 0, 0, p.Ca, WH, WH, w0);
+        pk.pack(W[p.n_trunk], WH, 1, p.Ca, 0, WH, WH, WH, w1);
         m.wp0 = w0; m.wp1 = w1;
         for (int l = 0; l < p.n_col; ++l) {
             m.bias[l] = B[p.n_trunk + l]; m.Z[l] = ws + p.o_zc[l]; m.H[l] = ws + p.o_hc[l];
             if (l == 0) continue;
-            float *wl = next_pack();
-            pack(W[p.n_trunk + l], WH, 1, 0, 0, WH, WH, WH, wl);
+            float *wl = pk.next();
+            pk.pack(W[p.n_trunk + l], WH, 1, 0, 0, WH, WH, WH, wl);
             m.wp[l] = wl;
         }
-        pb.flush(s);
+        pk.flush();
         launch_mlp_forward(sp, m, ctx->cus, s);
     } else {
         for (int l = 0; l < p.n_col; ++l) {
             float *Z = ws + p.o_zc[l], *H = ws + p.o_hc[l];
-            const float *Wl = W[p.n_trunk + l], *Bl = B[p.n_trunk + l];
+            const float *Bl = B[p.n_trunk + l];
+            const WeightView Wl{ W[p.n_trunk + l], WH, 1 };
             if (l == 0) {       // [embed_pos | embed_dir | normal | features] (neddf.py:243)
-                gemm_fw(ws + p.o_xa, p.ldxa, p.ldxa, p.Ca, Wl, 0, Bl, Z, 0, -1, nullptr);
-                gemm_fw(Hlast, WH, WH, WH, Wl, p.Ca, nullptr, Z, 1, act, H);
-            } else gemm_fw(ws + p.o_hc[l - 1], WH, WH, WH, Wl, 0, Bl, Z, 0, act, H);
+                b.forward(ws + p.o_xa, p.ldxa, p.ldxa, p.Ca, Wl, 0, WH, Bl, 4, Z, WH, 0, -1, nullptr);
+                b.forward(Hlast, WH, WH, WH, Wl, p.Ca, WH, nullptr, 4, Z, WH, 1, act, H);
+            } else b.forward(ws + p.o_hc[l - 1], WH, WH, WH, Wl, 0, WH, Bl, 4, Z, WH, 0, act, H);
         }
     }
     NarrowW cout{};
     cout.nc = 3; cout.wstride = 3; cout.kcount = kWidth;
     for (int c = 0; c < 3; ++c) { cout.w[c] = W[p.i_cout] + c; cout.b[c] = B[p.i_cout] + c; }
-    narrow_fw(ws + p.o_hc[p.n_col - 1], cout, ws + p.o_cr, pm);
+    b.narrow_forward(ws + p.o_hc[p.n_col - 1], cout, 4, ws + p.o_cr, pm);
     a.color = color; a.penalty = penalty;
     launch_penalty_forward(a, s);
     HIPCHK(hipGetLastError());
@@ -787,32 +833,25 @@ static int field_backward(neddf_ctx *ctx, int slot, const float *const *W, const
     const int sp = f.d.weight_dtype == NEDDF_DTYPE_F16_SPLIT;      // GEMM operands as two fp16 terms (tile_engine.h)
     // fp32 MFMA policy: the input-gradient chain of each layer stack is ONE kernel (train_kernels.h MlpBackwardArgs); every dZ_l keeps
     // its own matrix for the weight-gradient products.  NEDDF_TRAIN_UNFUSED=1 and the split-fp16 policy take the per-layer route below.
-    static const bool unfused = [] { const char *e = getenv("NEDDF_TRAIN_UNFUSED"); return e && atoi(e) != 0; }();
-    int n_wide = 0;
-    for (int l = 1; l < p.n_trunk; ++l) n_wide += in_skips(f.d, l - 1) ? 1 : 0;
+    const int n_wide = skip_layers(f.d, p.n_trunk);
     const int WH = p.WH, NBK = WH / kWidth;
-    if ((!sp || split_fused()) && !unfused && n_wide <= 1 && (WH == kWidth || (WH == 2 * kWidth && wide_fused()))) {      // (= the forward's condition for point-major hidden states)
+    if ((!sp || split_fused()) && !train_unfused() && n_wide <= 1 && (WH == kWidth || (WH == 2 * kWidth && wide_fused()))) {      // (= the forward's condition for point-major hidden states)
         const int nT = p.n_trunk, nC = p.n_col;
         const size_t slot = (size_t)p.R * WH, packf = (size_t)WH * WH;
         const int B4 = 4 * kWidth;      // a 256-column block of a point-major [R, WH] matrix starts B4 x (block index) floats into a point
         if (int rc = ensure(ctx, ctx->tpack, (size_t)(nT + nC + 1) * packf * sizeof(float))) return rc;
         if (int rc = ensure(ctx, ctx->ttmp, ((size_t)(nT + nC + 1) * slot + (size_t)p.R * 2 * kLdNarrow) * sizeof(float))) return rc;
-        float *tb = (float *)ctx->ttmp.p, *pack_at = (float *)ctx->tpack.p;
+        float *tb = (float *)ctx->ttmp.p;
         auto dZc = [&](int l) { return tb + (size_t)l * slot; };
         auto dZt = [&](int l) { return tb + (size_t)(nC + l) * slot; };
         float *dFeat = tb + (size_t)(nC + nT) * slot, *GZH = dFeat + slot, *GCR = GZH + (size_t)p.R * kLdNarrow;
-        auto next_pack = [&]() { float *r = pack_at; pack_at += packf; return r; };
         const float *PEs = ws + p.o_pes;
         TrainPointArgs a;
         point_args(a, f, p, ws);
         a.g_distance = g_distance; a.g_density = g_density; a.g_color = g_color; a.g_penalty = g_penalty; a.g_aux = g_aux_grad;
         a.GZH = GZH; a.GCR = GCR;
         launch_point_backward(a, s);
-        PackBatch pbk;         // the transposed weight fragments of a chain: one launch per chain (fp32; split fp16: matrix by matrix)
-        auto pack_t = [&](const float *src, int64_t sk, int64_t sn, int k_off, int n_off, int kcount, int ncount, int nout, float *dst) {
-            if (sp) launch_pack(1, src, sk, sn, k_off, n_off, kcount, ncount, nout, dst, s);
-            else pbk.add(src, sk, sn, k_off, n_off, kcount, ncount, nout, dst, s);
-        };
+        StackPacker pk{ sp, 1, s, (float *)ctx->tpack.p, packf, {} };       // the transposed weight fragments of both chains
         DwJobs dwj{};          // the weight-gradient products of this pass, job-parallel: one launch per kMaxDwJobs of them (launch_dw_jobs)
         dwj.R = p.R;
         // split fp16: every gradient matrix leaves max |dZ| in a device scalar (the chain kernel publishes it), its weight-gradient
@@ -872,11 +911,11 @@ static int field_backward(neddf_ctx *ctx, int slot, const float *const *W, const
             for (int c = 0; c < 3; ++c) m.top_w[c] = cout.w[c];
             m.top_Z = ws + p.o_zc[nC - 1]; m.top_out = dZc(nC - 1); m.amax_top = mZc[nC - 1];
             for (int l = 1; l < nC; ++l) {
-                float *wl = next_pack();
-                pack_t(W[nT + l], 1, WH, 0, 0, WH, WH, WH, wl);             // W_l^T
+                float *wl = pk.next();
+                pk.pack(W[nT + l], 1, WH, 0, 0, WH, WH, WH, wl);             // W_l^T
                 m.wT[l] = wl; m.Z[l - 1] = ws + p.o_zc[l - 1]; m.dZ[l - 1] = dZc(l - 1); m.amax_dZ[l - 1] = mZc[l - 1];
             }
-            pbk.flush(s);
+            pk.flush();
             launch_mlp_backward(sp, m, ctx->cus, s);
         }
         for (int l = nC - 1; l >= 1; --l) dw_hidden(ws + p.o_hc[l - 1], dZc(l), mZc[l], gW[nT + l], gB[nT + l]);
@@ -891,19 +930,19 @@ static int field_backward(neddf_ctx *ctx, int slot, const float *const *W, const
             m.R = p.R; m.n_layers = nT; m.act_kind = act; m.width = WH;
             // prologue: dZ of the last trunk layer = activation backward of (gradient of the features from the colour trunk -- only the
             // feature segment of its first layer propagates: the small colour inputs carry no parameters -- + the distance / aux heads)
-            float *wf = next_pack();
-            pack_t(W[nT], 1, WH, 0, p.Ca, WH, WH, WH, wf);                  // (feature rows of W_c0)^T
+            float *wf = pk.next();
+            pk.pack(W[nT], 1, WH, 0, p.Ca, WH, WH, WH, wf);                  // (feature rows of W_c0)^T
             m.top_src = dZc(0); m.top_wT = wf;
             m.top_G = GZH; m.top_ldg = kLdNarrow; m.top_nc = 2; m.top_wstride = 1;
             m.top_w[0] = W[p.i_ddf]; m.top_w[1] = W[p.i_aux];
             m.top_Z = ws + p.o_z[nT - 1]; m.top_out = dZt(nT - 1); m.amax_top = mZt[nT - 1];
             for (int l = 1; l < nT; ++l) {
                 const bool wide = in_skips(f.d, l - 1);
-                float *wl = next_pack();
-                pack_t(W[l], 1, WH, 0, wide ? p.Cpe : 0, WH, WH, WH, wl);   // (hidden rows of W_l)^T
+                float *wl = pk.next();
+                pk.pack(W[l], 1, WH, 0, wide ? p.Cpe : 0, WH, WH, WH, wl);   // (hidden rows of W_l)^T
                 m.wT[l] = wl; m.Z[l - 1] = ws + p.o_z[l - 1]; m.dZ[l - 1] = dZt(l - 1); m.amax_dZ[l - 1] = mZt[l - 1];
             }
-            pbk.flush(s);
+            pk.flush();
             launch_mlp_backward(sp, m, ctx->cus, s);
         }
         for (int l = nT - 1; l >= 0; --l) {
@@ -915,145 +954,87 @@ static int field_backward(neddf_ctx *ctx, int slot, const float *const *W, const
         flush_dw();
         if (ig) {       // every dZ of the pass is still in its own matrix: the encoding segments' input gradients read them in place
             EncGradArgs e{};
-            e.N = N; e.enc = a.enc;
-            e.pos = ig->pos; e.dir = ig->dir; e.var = ig->var;
-            e.g_pos = ig->g_pos; e.g_dir = ig->g_dir; e.g_var = ig->g_var;
             for (int l = 0; l < nT; ++l)
                 if (l == 0 || in_skips(f.d, l - 1)) e.seg[e.n_seg++] = EncGradSeg{ dZt(l), 1, 4, WH, WH, W[l], WH, 1, p.Cpe, 0, 0 };
             e.seg[e.n_seg++] = EncGradSeg{ dZc(0), 1, 4, WH, WH, W[nT], WH, 1, p.Cpe + p.Cdir, 0, 1 };
-            launch_enc_input_grad(e, s);
+            enc_input_grad(e, N, a.enc, *ig, s);
         }
         HIPCHK(hipGetLastError());
         return 0;
     }
     // per-layer route: dA / dB are reused from layer to layer, so the gradient matrices the input gradients need (layer 0, the skip
     // layers, colour layer 0) are copied aside as they appear
-    int n_keep = 0;
-    if (ig) {
-        n_keep = 2;
-        for (int l = 1; l < p.n_trunk; ++l) n_keep += in_skips(f.d, l - 1) ? 1 : 0;
-    }
+    const int n_keep = ig ? 2 + n_wide : 0;
     if (int rc = ensure(ctx, ctx->tpack, 2 * kPackFloats * sizeof(float))) return rc;
     if (int rc = ensure(ctx, ctx->ttmp, (size_t)p.R * ((2 + n_keep) * WH + 2 * kLdNarrow) * sizeof(float))) return rc;
-    float *wp = (float *)ctx->tpack.p;
-    float *dA = (float *)ctx->ttmp.p, *dB = dA + (size_t)p.R * WH, *GZH = dB + (size_t)p.R * WH, *GCR = GZH + (size_t)p.R * kLdNarrow;
-    float *keep_at = GCR + (size_t)p.R * kLdNarrow;
-    EncGradArgs eg{};
-    auto keep = [&](const float *dZ, const float *Wl, int ncols, int target) -> int {      // copy dZ aside and register its segment
-        HIPCHK(hipMemcpyAsync(keep_at, dZ, (size_t)p.R * WH * sizeof(float), hipMemcpyDeviceToDevice, s));
-        eg.seg[eg.n_seg++] = EncGradSeg{ keep_at, 0, 4, WH, WH, Wl, WH, 1, ncols, 0, target };
-        keep_at += (size_t)p.R * WH;
-        return 0;
-    };
+    Blocks b(ctx, sp, s, p.R, WH);
+    b.dA = (float *)ctx->ttmp.p; b.dB = b.dA + (size_t)p.R * WH;
+    float *GZH = b.dB + (size_t)p.R * WH, *GCR = GZH + (size_t)p.R * kLdNarrow;
+    KeptGrads kept;
+    kept.at = GCR + (size_t)p.R * kLdNarrow;
     const float *PEs = ws + p.o_pes;
     TrainPointArgs a;
     point_args(a, f, p, ws);
     a.g_distance = g_distance; a.g_density = g_density; a.g_color = g_color; a.g_penalty = g_penalty; a.g_aux = g_aux_grad;
     a.GZH = GZH; a.GCR = GCR;
     launch_point_backward(a, s);
-    AmaxSlots am;
-    if (int rc = amax_begin(ctx, sp, am, s)) return rc;
-    // Every product of this route is cut into 256 x 256 blocks (NBK = 1 at hidden width 256, 2 at 512).  dA always holds dZ of the layer
-    // in flight ([R, WH]); every activation backward is fused into the kernel that produces its upstream gradient.
-    // dW[row_off + k, n] += X[R, Kin]^T dA (+ db): Kin <= 256 (an encoding segment) or Kin = WH
-    auto dw_blocks = [&](const float *X, int ldx, int Kin, float *gWl, int row_off, float *gBl, const float *mA) {
-        const int KB = Kin <= kWidth ? 1 : Kin / kWidth, kc = Kin <= kWidth ? Kin : kWidth;
-        for (int nb = 0; nb < NBK; ++nb)
-            for (int kb = 0; kb < KB; ++kb)
-                launch_dw(sp, X + kb * kWidth, ldx, kc, dA + nb * kWidth, WH, p.R, gWl + (size_t)(row_off + kb * kWidth) * WH + nb * kWidth, WH, 1, kWidth,
-                          (kb == 0 && gBl) ? gBl + nb * kWidth : nullptr, 4, ctx->cus, s, mA, am.dw_tmp);
-    };
-    // dB[R, WH] = [activation backward with Zprev of] dA x (rows row_off .. row_off + WH of the [in, WH] weight)^T: K blocks accumulate
-    // in dB, the activation backward runs with the last one
-    auto gemm_bw = [&](const float *Wsrc, int row_off, int act_kind, const float *Zprev, const float *mIn, float *mOut) {
-        for (int nb = 0; nb < NBK; ++nb)
-            for (int kb = 0; kb < NBK; ++kb) {
-                launch_pack(sp, Wsrc, 1, WH, kb * kWidth, row_off + nb * kWidth, kWidth, kWidth, kWidth, wp, s);        // W^T block
-                if (Zprev && kb == NBK - 1)
-                    launch_rows_gemm_actback(sp, dA + kb * kWidth, p.R, WH, kWidth, wp, gemm_ksteps(kWidth, sp), 4, act_kind, Zprev + nb * kWidth,
-                                             dB + nb * kWidth, WH, ctx->cus, s, mIn, mOut, kb > 0);
-                else
-                    launch_rows_gemm(sp, dA + kb * kWidth, p.R, WH, kWidth, wp, gemm_ksteps(kWidth, sp), nullptr, 4, dB + nb * kWidth, WH, kb > 0, -1, nullptr,
-                                     ctx->cus, s, mIn);
-            }
-    };
-    // dZ[R, WH] = activation backward with Zprev of ((accumulate ? dH : 0) + sum_c G[., c] w_c), and the narrow columns' weight gradients
-    auto narrow_bw_act = [&](const float *G, NarrowW w, const float *dH, int accumulate, const float *Zprev, float *dZ, float *mOut) {
-        const float *w0[4] = { w.w[0], w.w[1], w.w[2], w.w[3] };
-        for (int kb = 0; kb < NBK; ++kb) {
-            for (int c = 0; c < w.nc; ++c) w.w[c] = w0[c] + (size_t)kb * kWidth * w.wstride;
-            launch_narrow_backward_act(G, kLdNarrow, p.R, w, dH ? dH + kb * kWidth : nullptr, accumulate, act, 4, Zprev + kb * kWidth, dZ + kb * kWidth, WH, s, mOut);
-        }
-    };
-    auto narrow_dw = [&](const float *X, const float *G, int nc, float *const *w, int wstride, float *const *b) {
-        for (int kb = 0; kb < NBK; ++kb) {
-            float *wk[4] = { nullptr, nullptr, nullptr, nullptr };
-            for (int c = 0; c < nc; ++c) wk[c] = w[c] + (size_t)kb * kWidth * wstride;
-            launch_narrow_dw(X + kb * kWidth, WH, G, kLdNarrow, p.R, nc, wk, wstride, kb == 0 ? b : nullptr, 4, kWidth, s);
-        }
-    };
+    if (int rc = amax_begin(ctx, sp, b.am, s)) return rc;
+    // every activation backward is fused into the kernel that produces its upstream gradient
     // colour head: LinearGradFunction.backward (linear.py:62-88) on [HC | JC] rows
     NarrowW cout{};
     cout.nc = 3; cout.wstride = 3; cout.kcount = kWidth;
     for (int c = 0; c < 3; ++c) cout.w[c] = W[p.i_cout] + c;
     const float *HClast = ws + p.o_hc[p.n_col - 1];
-    float *mA = am.take();          // max |dA| of the gradient matrix currently in dA
-    narrow_bw_act(GCR, cout, nullptr, 0, ws + p.o_zc[p.n_col - 1], dA, mA);
+    b.mA = b.am.take();
+    for (int kb = 0; kb < NBK; ++kb) b.narrow_backward_act(kb, GCR, cout, nullptr, 0, act, 4, ws + p.o_zc[p.n_col - 1], b.dA, b.mA);
     {
         float *wc[3] = { gW[p.i_cout], gW[p.i_cout] + 1, gW[p.i_cout] + 2 }, *bc[3] = { gB[p.i_cout], gB[p.i_cout] + 1, gB[p.i_cout] + 2 };
-        narrow_dw(HClast, GCR, 3, wc, 3, bc);
+        for (int kb = 0; kb < NBK; ++kb) b.narrow_dw(kb, HClast, GCR, 3, wc, 3, bc, 4);
     }
     const float *Hlast = ws + p.o_h[p.n_trunk - 1];
     for (int l = p.n_col - 1; l >= 0; --l) {
-        const float *Wl = W[p.n_trunk + l];
-        float *gWl = gW[p.n_trunk + l], *gBl = gB[p.n_trunk + l];
+        const WeightView Wl{ W[p.n_trunk + l], WH, 1 };
+        const GradView gWl{ gW[p.n_trunk + l], WH, 1 };
+        float *gBl = gB[p.n_trunk + l];
         if (l > 0) {
-            dw_blocks(ws + p.o_hc[l - 1], WH, WH, gWl, 0, gBl, mA);
-            float *mB = am.take();
-            gemm_bw(Wl, 0, act, ws + p.o_zc[l - 1], mA, mB);
-            mA = mB;
+            b.dw(ws + p.o_hc[l - 1], WH, WH, gWl, 0, gBl, 4);
+            b.backward(Wl, 0, 4, act, ws + p.o_zc[l - 1], b.am.take());
         } else {
-            dw_blocks(ws + p.o_xa, p.ldxa, p.Ca, gWl, 0, gBl, mA);
-            dw_blocks(Hlast, WH, WH, gWl, p.Ca, nullptr, mA);
-            if (ig) if (int rc = keep(dA, Wl, p.Cpe + p.Cdir, 1)) return rc;
+            b.dw(ws + p.o_xa, p.ldxa, p.Ca, gWl, 0, gBl, 4);
+            b.dw(Hlast, WH, WH, gWl, p.Ca, nullptr, 4);
+            if (ig) if (int rc = keep(ctx, kept, N, b.dA, EncGradSeg{ nullptr, 0, 4, WH, WH, Wl.w, WH, 1, p.Cpe + p.Cdir, 0, 1 }, s)) return rc;
             // the small colour inputs (encodings, detached normal) carry no parameters: only the feature segment propagates
-            gemm_bw(Wl, p.Ca, -1, nullptr, mA, nullptr);
+            b.backward(Wl, p.Ca, 4, -1, nullptr, nullptr);
         }
-        float *t = dA; dA = dB; dB = t;
+        b.swap();
     }
     // dA = gradient of the trunk features from the colour trunk; add the distance / aux heads, then the last trunk activation
     NarrowW heads{};
     heads.nc = 2; heads.wstride = 1; heads.kcount = kWidth;
     heads.w[0] = W[p.i_ddf]; heads.w[1] = W[p.i_aux];
-    mA = am.take();
-    narrow_bw_act(GZH, heads, dA, 1, ws + p.o_z[p.n_trunk - 1], dA, mA);
+    b.mA = b.am.take();
+    for (int kb = 0; kb < NBK; ++kb) b.narrow_backward_act(kb, GZH, heads, b.dA, 1, act, 4, ws + p.o_z[p.n_trunk - 1], b.dA, b.mA);
     {
         float *wh[2] = { gW[p.i_ddf], gW[p.i_aux] }, *bh[2] = { gB[p.i_ddf], gB[p.i_aux] };
-        narrow_dw(Hlast, GZH, 2, wh, 1, bh);
+        for (int kb = 0; kb < NBK; ++kb) b.narrow_dw(kb, Hlast, GZH, 2, wh, 1, bh, 4);
     }
     // distance trunk
     for (int l = p.n_trunk - 1; l >= 0; --l) {
         const bool wide = l > 0 && in_skips(f.d, l - 1);
-        if (ig && (l == 0 || wide)) if (int rc = keep(dA, W[l], p.Cpe, 0)) return rc;
+        const GradView gWl{ gW[l], WH, 1 };
+        if (ig && (l == 0 || wide)) if (int rc = keep(ctx, kept, N, b.dA, EncGradSeg{ nullptr, 0, 4, WH, WH, W[l], WH, 1, p.Cpe, 0, 0 }, s)) return rc;
         if (l == 0) {
-            dw_blocks(PEs, kLdPe, p.Cpe, gW[0], 0, gB[0], mA);
+            b.dw(PEs, kLdPe, p.Cpe, gWl, 0, gB[0], 4);
             break;
         }
-        if (wide) {
-            dw_blocks(PEs, kLdPe, p.Cpe, gW[l], 0, gB[l], mA);
-            dw_blocks(ws + p.o_h[l - 1], WH, WH, gW[l], p.Cpe, nullptr, mA);
-        } else dw_blocks(ws + p.o_h[l - 1], WH, WH, gW[l], 0, gB[l], mA);
-        float *mB = am.take();
-        gemm_bw(W[l], wide ? p.Cpe : 0, act, ws + p.o_z[l - 1], mA, mB);
-        float *t = dA; dA = dB; dB = t;
-        mA = mB;
+        if (wide) {             // hx = cat([embed_pos_scaled, hx])
+            b.dw(PEs, kLdPe, p.Cpe, gWl, 0, gB[l], 4);
+            b.dw(ws + p.o_h[l - 1], WH, WH, gWl, p.Cpe, nullptr, 4);
+        } else b.dw(ws + p.o_h[l - 1], WH, WH, gWl, 0, gB[l], 4);
+        b.backward(WeightView{ W[l], WH, 1 }, wide ? p.Cpe : 0, 4, act, ws + p.o_z[l - 1], b.am.take());
+        b.swap();
     }
-    if (ig) {
-        eg.N = N; eg.enc = a.enc;
-        eg.pos = ig->pos; eg.dir = ig->dir; eg.var = ig->var;
-        eg.g_pos = ig->g_pos; eg.g_dir = ig->g_dir; eg.g_var = ig->g_var;
-        launch_enc_input_grad(eg, s);
-    }
+    if (ig) enc_input_grad(kept.eg, N, a.enc, *ig, s);
     HIPCHK(hipGetLastError());
     return 0;
 }
