@@ -803,6 +803,68 @@ int neddf_point_mesh_grid_query(neddf_ctx *ctx, const float *d_queries, int64_t 
                                 const int32_t *d_cell_start, const int32_t *d_items, int64_t n_items, float *d_d2, int32_t *d_triangle, float *d_b1,
                                 float *d_b2, void *stream);
 
+/* ---- a BVH over the triangles, and the point-to-mesh distance through it (additive to ABI v7; no reference counterpart) ------
+ * neddf_point_mesh_brute's bits for ANY query, near the surface or far from it, through a linear BVH (Karras 2012) of the mesh.  The
+ * per-pair arithmetic, the per-triangle constants and the tie rule are the block's above; only the set of visited triangles differs.
+ * Three steps: neddf_bvh_keys, an ascending sort of the keys by the caller (they are distinct, so every correct sort gives one order),
+ * neddf_bvh_build.  Argument rules as above: NEDDF_EINVAL for a negative count or a NULL array that is needed, NEDDF_EUNSUPPORTED from
+ * 2^31 queries, triangles or vertices on.  T == 0 and Q == 0 are legal everywhere.
+ *
+ * neddf_bvh_keys: d_keys int64 [T].  A triangle is valid by the rule above (indices in [0, V), finite vertices).  A valid one:
+ *     centre = (min3 + max3) * 0.5 per axis (one rounded fp32 sum, an exact halving); cell per axis by neddf_nn_grid_build's cell
+ *     function with 1024 cells over the box h_lo .. h_hi (HOST doubles, finite, hi >= lo; any box gives a correct tree -- the cell
+ *     function clamps -- the bounds of the valid triangles' vertices the best one); code = the 30-bit Morton code of (cx, cy, cz), bit
+ *     3 b + a of the code = bit b of the cell along axis a; key = code << 32 | j.  An invalid one: key = 2^62 | j -- it sorts behind
+ *     every valid triangle and stays in the tree (which therefore always has T leaves) with an EMPTY box, which is never entered.
+ * neddf_bvh_build, from the keys sorted ascending -- THE TREE, for this and any later traversal (ray casting through it is not built):
+ *     d_leaf_triangle int32 [T]      the triangle of leaf k: the low 32 bits of sorted key k (Morton order)
+ *     d_children int32 [T - 1][2]    left and right child of internal node i (NULL allowed for T <= 1); c >= 0 is internal node c, c < 0
+ *                                    is leaf ~c.  Node 0 is the root; T == 1 has no internal node, the root is leaf 0.  Node i covers a
+ *                                    contiguous range of leaves, the left child the lower part; depth <= 62 (62 key bits can differ).
+ *                                    delta(i, j) = the number of leading bits that the 64-bit keys i and j share, -1 for j outside [0, T)
+ *     d_boxes float [2 T - 1][6]     (lo.xyz, hi.xyz): internal node i at row i, leaf k at row T - 1 + k, so row 0 is the root's.  A
+ *                                    leaf's box is the exact min / max of its corners, (+inf x 3, -inf x 3) for an invalid triangle;
+ *                                    a node's is the min / max of its children's: exact fp32, independent of timing although the
+ *                                    boxes are fitted bottom-up with one integer atomic counter per node (the second arriver goes on)
+ * neddf_point_mesh_bvh_query: n_leaves must equal n_triangles (NEDDF_EINVAL: a tree of another mesh is refused, not followed).  One
+ * lane per query, depth first.  A box (node or leaf) against query p, every operation ONE rounded fp32 operation:
+ *     gap_a = max(max(lo_a - p_a, p_a - hi_a), 0) per axis;  lb = sqrt(dot(gap, gap));  m = f * lb - s;  m2 = m * m
+ *     f = 1 - 2^-16;  s = 2^-18 * W, W = the largest |coordinate| of the root box
+ *     the box is SKIPPED when it is empty (lo.x > hi.x), or when m > 0 and m2 > best D2 strictly and 1e-30 <= m2 < +inf
+ * Of two children that are not skipped, the one with the smaller m2 (m <= 0 counting as 0) is entered first, the left one on a tie;
+ * the other waits on a stack and is tested again, against the best of that moment, when its turn comes.  A leaf that is entered is
+ * evaluated with its ORIGINAL triangle index.  d_visits int32 [Q] (NULL allowed): the leaves evaluated per query (0 for a non-finite
+ * query) -- tests/bvh_check.py restates keys, tree and traversal in numpy and reproduces this count exactly.  Child and triangle
+ * indices are checked before they are followed and a query handles at most 2 T nodes: a corrupt tree gives a wrong answer, no hang.
+ *
+ * THE EQUALITY ARGUMENT.  Let a box be skipped by the rule with best D2 = B, and let a valid triangle lie below it.
+ *   (1) Boxes are exact min / max of vertex coordinates, so every point of the triangle lies in the box, and its true distance d from
+ *       p is at least L, the true distance from p to the box.  The computed lb: each gap is one subtraction (relative error 2^-24; the
+ *       max with 0 is exact), dot(gap, gap) is three products and two sums of non-negative terms (relative error below 5 * 2^-24 in
+ *       all, the gaps' included), the square root halves that and adds 2^-24: lb <= L (1 + 2^-22).  Underflow only lowers lb.
+ *   (2) m = f * lb - s and m2 = m * m add three roundings: with m > 0, sqrt(m2) <= (f L (1 + 2^-22) - s) (1 + 2^-23)
+ *       <= L (1 - 2^-16 + 2^-21) - s ((x - s) (1 + e) <= x (1 + e) - s: the roundings only shrink the part of s).  s = 2^-18 W is a
+ *       scaling by a power of two, exact.
+ *   (3) Step (2) of the grid's argument above: a candidate's computed distance is above d (1 - 2^-21) - 2^-19 W, W the largest
+ *       |coordinate| of a box that holds every vertex of the triangles in question -- here the root box, which holds every valid one.
+ *   (4) So sqrt(computed D2) - sqrt(m2) > L (2^-16 - 2^-20) + (2^-18 - 2^-19) W > 0: the skipped triangle's D2 exceeds m2,
+ *       which exceeds B strictly -- no tie and no smaller value among the skipped, at a relative margin of 2^-16 against roundings of
+ *       2^-21.  1e-30 <= m2 keeps the margin above the absolute error of a D2 whose products underflow (3 * 2^-126); m2 < +inf
+ *       leaves alone the range where the bound itself has overflowed.
+ *   (5) best only decreases, so a box skipped once would be skipped later too; visiting more triangles never changes the result (the
+ *       tie rule).  Hence the bits are the brute kernel's, whatever the order.
+ * (The grid's factor 0.99 would not do here: 100 mesh sizes away everything is within 1 % of everything else, and a query would
+ * visit most of the mesh.  Where rounding dominates -- a mesh of size 2^-8 at offset 1000, s as large as the mesh -- nearly every
+ * triangle is visited, as the grid stops walking there.) */
+int neddf_bvh_keys(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles, const double *h_lo,
+                   const double *h_hi, int64_t *d_keys, void *stream);
+int neddf_bvh_build(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                    const int64_t *d_sorted_keys, int32_t *d_leaf_triangle, int32_t *d_children, float *d_boxes, void *stream);
+int neddf_point_mesh_bvh_query(neddf_ctx *ctx, const float *d_queries, int64_t n_queries, const float *d_vertices, int64_t n_vertices,
+                               const int32_t *d_triangles, int64_t n_triangles, const int32_t *d_leaf_triangle, const int32_t *d_children,
+                               const float *d_boxes, int64_t n_leaves, float *d_d2, int32_t *d_triangle, float *d_b1, float *d_b2, int32_t *d_visits,
+                               void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -171,6 +171,9 @@ SYMBOLS = [
     ("neddf_point_mesh_brute", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("neddf_point_mesh_grid_query", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), C.c_float, _vp, _vp, _i64,
                                               _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_bvh_keys", C.c_int, [_vp, _vp, _i64, _vp, _i64, _dp, _dp, _vp, _vp]),
+    ("neddf_bvh_build", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_point_mesh_bvh_query", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _lib = None
@@ -665,6 +668,37 @@ class Context:
                                                         _ptr(items) if items.numel() else None, items.shape[0], _ptr(d2), _ptr(j), _ptr(b1),
                                                         _ptr(b2), self.stream()))
         return d2, j, b1, b2
+
+    def bvh_keys(self, vertices, triangles, lo, hi):
+        """The sort keys of the triangles (neddf_bvh_keys): int64 [T], Morton code of the box centre << 32 | triangle index."""
+        blo, bhi, _ = self._grid_args(lo, hi, (1, 1, 1))
+        keys = torch.empty(triangles.shape[0], device=vertices.device, dtype=torch.int64)
+        self.check(self.lib.neddf_bvh_keys(self.h, _ptr(vertices), vertices.shape[0], _ptr(triangles), triangles.shape[0], blo, bhi,
+                                           _ptr(keys) if keys.numel() else None, self.stream()))
+        return keys
+
+    def bvh_build(self, vertices, triangles, sorted_keys):
+        """The tree over the keys sorted ascending (neddf_bvh_build): (leaf_triangle int32 [T], children int32 [max(T - 1, 0), 2], boxes
+        float32 [max(2 T - 1, 0), 6])."""
+        n, dev = triangles.shape[0], vertices.device
+        leaf = torch.empty(n, device=dev, dtype=torch.int32)
+        children = torch.empty(max(n - 1, 0), 2, device=dev, dtype=torch.int32)
+        boxes = torch.empty(max(2 * n - 1, 0), 6, device=dev, dtype=torch.float32)
+        self.check(self.lib.neddf_bvh_build(self.h, _ptr(vertices), vertices.shape[0], _ptr(triangles), n, _ptr(sorted_keys) if n else None,
+                                            _ptr(leaf) if n else None, _ptr(children) if n > 1 else None, _ptr(boxes) if n else None, self.stream()))
+        return leaf, children, boxes
+
+    def point_mesh_bvh_query(self, queries, vertices, triangles, leaf_triangle, children, boxes, return_visits=False):
+        """The closest point of the mesh to every query through the BVH (neddf_point_mesh_bvh_query): point_mesh_brute's result, bit for
+        bit; with return_visits a fifth tensor, the leaves evaluated per query (int32 [Q])."""
+        d2, j, b1, b2 = self._hit_buffers(queries.shape[0], queries.device)
+        visits = torch.empty(queries.shape[0], device=queries.device, dtype=torch.int32) if return_visits else None
+        self.check(self.lib.neddf_point_mesh_bvh_query(self.h, _ptr(queries), queries.shape[0], _ptr(vertices), vertices.shape[0], _ptr(triangles),
+                                                       triangles.shape[0], _ptr(leaf_triangle) if leaf_triangle.numel() else None,
+                                                       _ptr(children) if children.numel() else None, _ptr(boxes) if boxes.numel() else None,
+                                                       leaf_triangle.shape[0], _ptr(d2), _ptr(j), _ptr(b1), _ptr(b2),
+                                                       _ptr(visits) if return_visits else None, self.stream()))
+        return (d2, j, b1, b2, visits) if return_visits else (d2, j, b1, b2)
 
     def composite(self, dists, dens, col, max_dist):
         require_device(dists, "dists")

@@ -383,6 +383,19 @@ void launch_point_mesh_brute(const float *q, int64_t nq, const float *v, int64_t
 void launch_point_mesh_grid_query(const PmGrid &g, const float *q, int64_t nq, const float *v, int64_t V, const int32_t *tri, int64_t T, float *table,
                                   const int32_t *cell_start, const int32_t *items, int64_t n_items, float *d2, int32_t *triangle, float *b1, float *b2,
                                   hipStream_t s);
+// the table alone: [20 T] floats, 16-byte aligned (nothing is launched for T <= 0)
+void launch_point_mesh_prepare(const float *v, int64_t V, const int32_t *tri, int64_t T, float *table, hipStream_t s);
+
+// A linear BVH over the triangles and the point-to-mesh query through it (bvh_kernels.hip; include/neddf_hip.h states the arrays).
+// keys int64 [T]: Morton code of the box centre (g: 1024 cells per axis) << 32 | triangle index; bit 62 set for an invalid triangle
+void launch_bvh_keys(const NnGrid &g, const float *v, int64_t V, const int32_t *tri, int64_t T, int64_t *keys, hipStream_t s);
+// keys sorted ascending -> leaf_tri [T], children [T - 1][2], boxes [2 T - 1][6]; parent [2 T - 1] and counter [T - 1] are workspace
+void launch_bvh_build(const int64_t *keys, const float *v, int64_t V, const int32_t *tri, int64_t T, int32_t *leaf_tri, int32_t *children, float *boxes,
+                      int32_t *parent, int32_t *counter, hipStream_t s);
+// table [20 T] floats (workspace, written by a prepare launch in front of the query); visits [nq] or NULL
+void launch_point_mesh_bvh_query(const float *q, int64_t nq, const float *v, int64_t V, const int32_t *tri, int64_t T, float *table, const int32_t *leaf_tri,
+                                 const int32_t *children, const float *boxes, float *d2, int32_t *triangle, float *b1, float *b2, int32_t *visits,
+                                 hipStream_t s);
 
 void launch_linear_grad(const float *x, const float *J, int64_t n, int cin, int ldx, int cout_block, int ksteps, const float *wp,
                         const float *bias, float *y, float *G, int ldo, int nvalid, int accumulate, int grid, hipStream_t s);

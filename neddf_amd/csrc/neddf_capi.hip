@@ -2236,3 +2236,64 @@ int neddf_point_mesh_grid_query(neddf_ctx *ctx, const float *d_queries, int64_t 
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// ---- a BVH over the triangles, and the point-to-mesh distance through it (bvh_kernels.hip) ----
+int neddf_bvh_keys(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles, const double *h_lo,
+                   const double *h_hi, int64_t *d_keys, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = rc_counts_ok(ctx, 0, nullptr, nullptr, n_vertices, d_vertices, n_triangles, d_triangles, 0.f, "bvh_keys")) return rc;
+    if (!h_lo || !h_hi) return fail(ctx, NEDDF_EINVAL, "bvh_keys: NULL box");
+    if (n_triangles > 0 && !d_keys) return fail(ctx, NEDDF_EINVAL, "bvh_keys: NULL keys");
+    NnGrid g;
+    for (int a = 0; a < 3; ++a) {               // nn_grid's cells, 1024 per axis (its limit of 2^24 cells in all is the lists', not the cell function's)
+        if (!std::isfinite(h_lo[a]) || !std::isfinite(h_hi[a]) || !(h_hi[a] >= h_lo[a])) return fail(ctx, NEDDF_EINVAL, "bvh_keys: a finite box with hi >= lo expected");
+        const double ext = h_hi[a] - h_lo[a];
+        g.n[a] = kNnMaxAxis;
+        g.lo[a] = (float)h_lo[a];
+        g.inv_cell[a] = ext > 0.0 ? (float)((double)kNnMaxAxis / ext) : 0.f;
+        if (!std::isfinite(g.lo[a]) || !std::isfinite(g.inv_cell[a])) return fail(ctx, NEDDF_EINVAL, "bvh_keys: the box does not fit fp32");
+    }
+    g.safe_cell = 0.f;
+    DeviceGuard guard_(ctx->device);
+    launch_bvh_keys(g, d_vertices, n_vertices, d_triangles, n_triangles, d_keys, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_bvh_build(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                    const int64_t *d_sorted_keys, int32_t *d_leaf_triangle, int32_t *d_children, float *d_boxes, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = rc_counts_ok(ctx, 0, nullptr, nullptr, n_vertices, d_vertices, n_triangles, d_triangles, 0.f, "bvh_build")) return rc;
+    if (n_triangles > 0 && (!d_sorted_keys || !d_leaf_triangle || !d_boxes || (n_triangles > 1 && !d_children)))
+        return fail(ctx, NEDDF_EINVAL, "bvh_build: NULL keys, leaf_triangle, children or boxes");
+    if (n_triangles == 0) return 0;
+    DeviceGuard guard_(ctx->device);
+    if (int rc = ensure(ctx, ctx->geom_ws, (size_t)(3 * n_triangles) * sizeof(int32_t))) return rc;
+    int32_t *parent = (int32_t *)ctx->geom_ws.p, *counter = parent + (2 * n_triangles - 1);
+    launch_bvh_build(d_sorted_keys, d_vertices, n_vertices, d_triangles, n_triangles, d_leaf_triangle, d_children, d_boxes, parent, counter,
+                     (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_point_mesh_bvh_query(neddf_ctx *ctx, const float *d_queries, int64_t n_queries, const float *d_vertices, int64_t n_vertices,
+                               const int32_t *d_triangles, int64_t n_triangles, const int32_t *d_leaf_triangle, const int32_t *d_children,
+                               const float *d_boxes, int64_t n_leaves, float *d_d2, int32_t *d_triangle, float *d_b1, float *d_b2, int32_t *d_visits,
+                               void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = rc_counts_ok(ctx, n_queries, d_queries, d_queries, n_vertices, d_vertices, n_triangles, d_triangles, 0.f, "point_mesh_bvh_query")) return rc;
+    if (n_leaves != n_triangles) return fail(ctx, NEDDF_EINVAL, "point_mesh_bvh_query: the tree's leaves are not this mesh's triangles (n_leaves != n_triangles)");
+    if (n_triangles > 0 && (!d_leaf_triangle || !d_boxes || (n_triangles > 1 && !d_children)))
+        return fail(ctx, NEDDF_EINVAL, "point_mesh_bvh_query: NULL leaf_triangle, children or boxes");
+    if (n_queries > 0 && (!d_d2 || !d_triangle || !d_b1 || !d_b2)) return fail(ctx, NEDDF_EINVAL, "point_mesh_bvh_query: NULL outputs");
+    DeviceGuard guard_(ctx->device);
+    if (n_queries > 0 && n_triangles > 0)
+        if (int rc = ensure(ctx, ctx->geom_ws, (size_t)n_triangles * 20 * sizeof(float))) return rc;
+    launch_point_mesh_bvh_query(d_queries, n_queries, d_vertices, n_vertices, d_triangles, n_triangles, (float *)ctx->geom_ws.p, d_leaf_triangle, d_children,
+                                d_boxes, d_d2, d_triangle, d_b1, d_b2, d_visits, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}

@@ -5,8 +5,9 @@ a distance field against the mesh of one of its level sets.
 The reference's evaluation compares images (PSNR, SSIM: metrics.py); the distance between two SURFACES is what tells how far a sparse
 extraction, an operand policy or a clean-up moved the level set.  Sampling (mesh.sample_surface) and the nearest-neighbour search are
 HIP kernels (include/neddf_hip.h neddf_mesh_sample_*, neddf_nn_brute, neddf_nn_grid_build, neddf_nn_grid_query), and so is the
-point-to-triangle search (neddf_point_mesh_brute, neddf_point_mesh_grid_query over raycast.build_grid's lists); the reductions over
-the per-point distances are torch fp64 on the device.
+point-to-triangle search (neddf_point_mesh_brute, neddf_point_mesh_grid_query over raycast.build_grid's lists,
+neddf_point_mesh_bvh_query through bvh.build_bvh's tree -- the one for queries anywhere in the volume, which distance_field_check
+asks); the reductions over the per-point distances are torch fp64 on the device.
 """
 import torch
 
@@ -141,7 +142,7 @@ def _grid_of(what, v, t, grid):
     return grid
 
 
-def point_mesh_distance(queries, vertices, triangles, method="grid", grid=None):
+def point_mesh_distance(queries, vertices, triangles, method="grid", grid=None, bvh=None):
     """The exact distance from every query (float32 [Q, 3]) to the SURFACE of a device mesh (vertices float32 [V, 3], triangles int32
     or int64 [T, 3]) -- to its closest triangle, not to its closest vertex or sample -- as a dict:
 
@@ -154,19 +155,27 @@ def point_mesh_distance(queries, vertices, triangles, method="grid", grid=None):
     same bits.  A query with a non-finite coordinate gets (NaN, -1, NaN, NaN); a triangle with an index outside [0, V) or a non-finite
     vertex is never found.  method="grid" walks the uniform grid of raycast.build_grid (`grid`: the MeshGrid of this mesh, built here
     with build_grid's defaults when None -- build it once for many calls); queries far from the surface walk many shells of cells
-    and are correspondingly slower.  `grid` is ignored by method="brute"."""
+    and are correspondingly slower.  `grid` is ignored by method="brute".  method="bvh" descends a bounding-volume hierarchy of the
+    triangles (`bvh`: the MeshBVH of this mesh, bvh.build_bvh, built here when None) and returns the same bits again: its cost barely
+    depends on how far the query is from the surface, so it is the method for queries anywhere in the volume."""
+    from .bvh import bvh_of
     from .raycast import _mesh
     q = _points("point_mesh_distance", "queries", queries)
     v, t = _mesh("point_mesh_distance", vertices, triangles)
     if q.device != v.device:
         raise NeddfError("point_mesh_distance: queries and mesh must live on one device (got %s, %s)" % (q.device, v.device))
-    if method not in ("grid", "brute"):
-        raise NeddfError("point_mesh_distance: method must be 'grid' or 'brute' (got %r)" % (method,))
+    if method not in ("grid", "brute", "bvh"):
+        raise NeddfError("point_mesh_distance: method must be 'grid', 'brute' or 'bvh' (got %r)" % (method,))
     ctx = Context.get(q.device)
+    if grid is not None and method != "grid":
+        _grid_of("point_mesh_distance", v, t, grid)
+    if bvh is not None and method != "bvh":
+        bvh_of("point_mesh_distance", v, t, bvh)
     if method == "brute":
-        if grid is not None:
-            _grid_of("point_mesh_distance", v, t, grid)
         d2, j, b1, b2 = ctx.point_mesh_brute(q, v, t)
+    elif method == "bvh":
+        bvh = bvh_of("point_mesh_distance", v, t, bvh)
+        d2, j, b1, b2 = ctx.point_mesh_bvh_query(q, v, t, bvh.leaf_triangle, bvh.children, bvh.boxes)
     else:
         grid = _grid_of("point_mesh_distance", v, t, grid)
         d2, j, b1, b2 = ctx.point_mesh_grid_query(q, v, t, grid.lo, grid.hi, grid.cells, grid.pad, grid.cell_start, grid.items)
@@ -242,7 +251,7 @@ GOLDEN_STEP, PLASTIC_STEP = 0.6180339887498949, 0.7548776662466927      # the of
 
 
 def level_set_check(distance_fn, vertices, triangles, threshold, band, n=100000, seed=0, min_distance=None, method="grid", grid=None,
-                    return_samples=False):
+                    return_samples=False, bvh=None):
     """How well a field is a DISTANCE field around one of its level sets: (vertices, triangles) is the mesh of the level set
     D = threshold (extract_mesh), distance_fn(p [M, 3]) -> D [M] the field (trace.sphere_trace's contract), and |D(p) - threshold| is
     set against the exact distance d(p) from p to the mesh (point_mesh_distance) at about n points within `band` of it.
@@ -278,7 +287,7 @@ def level_set_check(distance_fn, vertices, triangles, threshold, band, n=100000,
     k = torch.arange(1, x.shape[0] + 1, device=x.device, dtype=torch.float64)
     s = band * (2.0 * torch.frac(k * GOLDEN_STEP + float(int(seed)) * PLASTIC_STEP) - 1.0)
     pts = (x + s.float()[:, None] * nrm).contiguous()
-    d = point_mesh_distance(pts, v, t, method=method, grid=grid)["distance"]
+    d = point_mesh_distance(pts, v, t, method=method, grid=grid, bvh=bvh)["distance"]
     with torch.no_grad():
         D = distance_fn(pts)
     if not isinstance(D, torch.Tensor) or D.device != pts.device or D.numel() != pts.shape[0]:
@@ -314,4 +323,106 @@ def level_set_check(distance_fn, vertices, triangles, threshold, band, n=100000,
     return out
 
 
-__all__ = ["nearest", "cloud_distance", "mesh_distance", "point_mesh_distance", "closest_points", "level_set_check", "default_cells", "POINTS_PER_CELL"]
+# the volume's low-discrepancy sequence: the additive recurrence with (1 / g, 1 / g^2, 1 / g^3), g the real root of x^4 = x + 1
+R3_STEPS = (0.8191725133961645, 0.6710436067037893, 0.5497004779019702)
+
+
+def _quantile(x, q):
+    """torch.quantile, which refuses more than 2^24 elements, or the sorted element at that rank."""
+    n = int(x.numel())
+    return float(torch.quantile(x, q).item()) if n <= 1 << 24 else float(x.sort().values[int(q * (n - 1))].item())
+
+
+def distance_field_check(distance_fn, vertices, triangles, threshold, box=None, n=100000, seed=0, bins=8, method="bvh", return_samples=False):
+    """How well a field is a DISTANCE field in the whole volume -- level_set_check's question without its band: (vertices, triangles)
+    is the mesh of the level set D = threshold (extract_mesh), distance_fn(p [M, 3]) -> D [M] the field, and F = |D(p) - threshold| is
+    set against the exact distance d(p) from p to the mesh (point_mesh_distance; method="bvh" by default: the queries are far from
+    the surface, where the grid walks many shells) at n points of `box`, and reported BY DISTANCE from the surface.
+
+    box = (lo, hi): by default the bounds of the mesh's valid triangles widened on every side by a quarter of their diagonal.  The
+    points: u_k = frac((k + 1) * (0.8191725133961645, 0.6710436067037893, 0.5497004779019702) + seed * 0.7548776662466927) per axis, k =
+    0 .. n - 1, in fp64 (a low-discrepancy sequence; deterministic: no torch generator is touched), p_k = lo + u_k (hi - lo) rounded
+    to fp32.  With e_k = F_k - d_k the dict holds
+
+      n, box, invalid                     the points, the box, and how many D_k or d_k were not finite (left out of everything below)
+      mean_error, mean_abs_error, rms_error, max_abs_error     of e_k
+      max_distance                        the largest d_k
+      bins                                a list of `bins` dicts over equal-width ranges of d up to max_distance, each with lo, hi, count,
+                                          mean_error, mean_abs_error, and slope_median, slope_p99, n_slope of F_k / d_k over its points
+                                          with d_k >= max_distance / (8 bins) -- an eighth of a bin, what band / 8 is to level_set_check:
+                                          closer to the surface the mesh's own error dominates the quotient (NaN for an empty bin)
+      suggested_step_scale                min(1, 1 / the largest slope_p99 of any bin): level_set_check's formula on the worst range
+
+    Reductions are torch fp64 on the device.  return_samples=True adds points, mesh_distance and field_distance (float32, all n)."""
+    from .bvh import valid_bounds
+    from .raycast import _mesh
+    if not callable(distance_fn):
+        raise NeddfError("distance_field_check: distance_fn must be callable: pos [M, 3] -> distances [M]")
+    v, t = _mesh("distance_field_check", vertices, triangles)
+    n, bins, threshold = int(n), int(bins), float(threshold)
+    if n < 1 or bins < 1:
+        raise NeddfError("distance_field_check: n and bins must be positive (got %r, %r)" % (n, bins))
+    if box is None:
+        lo, hi = valid_bounds(v, t)
+        pad = 0.25 * sum((h - l) ** 2 for l, h in zip(lo, hi)) ** 0.5
+        lo, hi = [l - pad for l in lo], [h + pad for h in hi]
+    else:
+        try:
+            lo, hi = [float(x) for x in box[0]], [float(x) for x in box[1]]
+        except (TypeError, ValueError, IndexError):
+            raise NeddfError("distance_field_check: box must be (lo, hi) with 3 numbers each (got %r)" % (box,)) from None
+        if len(lo) != 3 or len(hi) != 3 or not all(l <= h and abs(l) < float("inf") and abs(h) < float("inf") for l, h in zip(lo, hi)):
+            raise NeddfError("distance_field_check: box must be (lo, hi) with 3 finite numbers each and lo <= hi (got %r)" % (box,))
+    k = torch.arange(1, n + 1, device=v.device, dtype=torch.float64)
+    step = torch.tensor(R3_STEPS, device=v.device, dtype=torch.float64)
+    u = torch.frac(k[:, None] * step[None, :] + float(int(seed)) * PLASTIC_STEP)
+    lo_t, hi_t = (torch.tensor(x, device=v.device, dtype=torch.float64) for x in (lo, hi))
+    pts = (lo_t[None, :] + u * (hi_t - lo_t)[None, :]).float().contiguous()
+    d = point_mesh_distance(pts, v, t, method=method)["distance"]
+    with torch.no_grad():
+        D = distance_fn(pts)
+    if not isinstance(D, torch.Tensor) or D.device != pts.device or D.numel() != n:
+        raise NeddfError("distance_field_check: distance_fn must return one distance per point on the points' device")
+    D = D.reshape(-1).float()
+    ok = torch.isfinite(D) & torch.isfinite(d)
+    m = int(ok.sum().item())
+    nan = float("nan")
+    out = {"n": n, "box": (tuple(lo), tuple(hi)), "invalid": n - m}
+    f = (D.double() - threshold).abs()[ok]
+    dd = d.double()[ok]
+    e = f - dd
+
+    def errors(x):
+        if not x.numel():
+            return dict(mean_error=nan, mean_abs_error=nan)
+        return dict(mean_error=float(x.mean().item()), mean_abs_error=float(x.abs().mean().item()))
+
+    out.update(errors(e))
+    out.update(rms_error=float((e * e).mean().sqrt().item()) if m else nan, max_abs_error=float(e.abs().max().item()) if m else nan)
+    d_max = float(dd.max().item()) if m else nan
+    out["max_distance"] = d_max
+    width = d_max / bins if m else nan
+    which = (dd / width).floor().long().clamp(0, bins - 1) if m and width > 0.0 else torch.zeros_like(dd, dtype=torch.long)
+    rows, worst = [], nan
+    for b in range(bins):
+        sel = which == b
+        row = dict(lo=b * width, hi=(b + 1) * width, count=int(sel.sum().item()))
+        row.update(errors(e[sel]))
+        far = sel & (dd >= width / 8.0) & (dd > 0.0)
+        row["n_slope"] = int(far.sum().item())
+        if row["n_slope"]:
+            slope = f[far] / dd[far]
+            row.update(slope_median=float(slope.median().item()), slope_p99=_quantile(slope, 0.99))
+            worst = row["slope_p99"] if not worst == worst else max(worst, row["slope_p99"])
+        else:
+            row.update(slope_median=nan, slope_p99=nan)
+        rows.append(row)
+    out["bins"] = rows
+    out["suggested_step_scale"] = (min(1.0, 1.0 / worst) if worst > 0.0 else 1.0) if worst == worst else nan
+    if return_samples:
+        out.update(points=pts, mesh_distance=d, field_distance=D)
+    return out
+
+
+__all__ = ["nearest", "cloud_distance", "mesh_distance", "point_mesh_distance", "closest_points", "level_set_check", "distance_field_check",
+           "default_cells", "POINTS_PER_CELL"]

@@ -284,14 +284,24 @@ class BaseNeuralField(ABC, nn.Module):
             raise NotImplementedError("%s fields have no distance or sdf to check against a level set" % type(self).__name__)
         if band is None:
             band = 4.0 * 2.0 * 1.1 / (64 - 1)
+        return level_set_check(self._surface_distance, vertices, triangles, threshold, band, **kw)
 
-        def distance_fn(pos):
-            with torch.no_grad():
-                view = torch.tensor([1.0, 0.0, 0.0], device=pos.device).expand_as(pos).contiguous()
-                o = self.forward_surface(Sampling(pos[None], view[None], torch.zeros_like(pos)[None]), want=("distance",))
-            return (o["distance"] if "distance" in o else o["sdf"])[0]
+    def _surface_distance(self, pos: Tensor) -> Tensor:
+        """The distance (NeuS: sdf) at pos [M, 3] as render_image_traced evaluates its hit points: forward_surface, var = 0."""
+        with torch.no_grad():
+            view = torch.tensor([1.0, 0.0, 0.0], device=pos.device).expand_as(pos).contiguous()
+            o = self.forward_surface(Sampling(pos[None], view[None], torch.zeros_like(pos)[None]), want=("distance",))
+        return (o["distance"] if "distance" in o else o["sdf"])[0]
 
-        return level_set_check(distance_fn, vertices, triangles, threshold, band, **kw)
+    def distance_field_check(self, vertices: Tensor, triangles: Tensor, threshold: float = 0.0275, **kw):
+        """geometry.distance_field_check of this field's distance (NeuS: sdf) against (vertices, triangles), the mesh extract_mesh
+        made of its `threshold` level set: level_set_check's question asked in the WHOLE volume -- how far |D(p) - threshold| is from
+        the exact distance of p to the mesh, and its slope, by distance from the surface.  Further keywords (box, n, seed, bins, method,
+        return_samples) are geometry.distance_field_check's.  NeRF fields raise."""
+        from .geometry import distance_field_check
+        if not self._has_surface():
+            raise NotImplementedError("%s fields have no distance or sdf to check against a mesh" % type(self).__name__)
+        return distance_field_check(self._surface_distance, vertices, triangles, threshold, **kw)
 
     def _has_surface(self) -> bool:
         """True for fields with a distance / sdf trunk, whose position gradient is the surface normal (NeDDF, NeuS)."""

@@ -1,4 +1,4 @@
-"""`python neddf/scripts/compare_mesh.py A.ply B.ply [--samples N | --density D] [--seed S] [--tau T] [--method grid|brute] [--exact]` -- the
+"""`python neddf/scripts/compare_mesh.py A.ply B.ply [--samples N | --density D] [--seed S] [--tau T] [--method grid|brute|bvh] [--exact]` -- the
 distance between two triangle meshes (no reference counterpart: its evaluation compares images): both are read (neddf_amd.mesh.read_ply:
 the files extract_mesh.py writes, or ASCII PLY), uploaded, sampled on the device with one density and seed, and compared by
 neddf_amd.geometry.mesh_distance.  Prints ONE JSON line: a_to_b_mean, b_to_a_mean, chamfer, hausdorff, a_to_b_max, b_to_a_max, n_a, n_b,
@@ -20,7 +20,8 @@ def build_parser() -> ArgumentParser:
     how.add_argument("--density", type=float, default=None, metavar="D", help="D surface samples per unit area")
     parser.add_argument("--seed", type=int, default=0, help="seed of the sampling (32 bits)")
     parser.add_argument("--tau", type=float, default=None, help="distance threshold of precision / recall / F-score")
-    parser.add_argument("--method", default="grid", choices=["grid", "brute"], help="nearest-neighbour search")
+    parser.add_argument("--method", default="grid", choices=["grid", "brute", "bvh"],
+                        help="nearest-neighbour search; bvh (with --exact only): the triangles' bounding-volume hierarchy")
     parser.add_argument("--exact", action="store_true", help="measure samples against the other mesh's triangles, not its samples")
     return parser
 
@@ -38,6 +39,8 @@ def parse_args(argv=None):
         parser.error("--tau must not be negative")
     if not 0 <= args.seed < 2 ** 32:
         parser.error("--seed must fit 32 bits")
+    if args.method == "bvh" and not args.exact:
+        parser.error("--method bvh searches triangles: it needs --exact")
     return args
 
 

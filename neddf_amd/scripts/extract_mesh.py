@@ -1,6 +1,6 @@
 """`python neddf/scripts/extract_mesh.py <run_dir> [--epoch 2000] [--resolution 64] [--threshold 0.0275] [--field distance]
 [--cube-range 1.1] [--normals [field|geometric]] [--colors] [--min-component N] [--keep-largest [K]] [--sparse [B]] [--band W]
-[--lipschitz L] [--brick-dilate D] [--check-distance [BAND]]` -- the reference's mesh export (neddf/scripts/fields_visualizer.py:528-566, generate_mesh: voxelize
+[--lipschitz L] [--brick-dilate D] [--check-distance [BAND]] [--check-volume [N]]` -- the reference's mesh export (neddf/scripts/fields_visualizer.py:528-566, generate_mesh: voxelize
 "distance" on a 64^3 cube of half-width 1.1, marching cubes at 0.0275, export) without its Open3D viewer.  The run is
 loaded as run_eval loads it (`<run_dir>/.hydra/config.yaml`, `models/model_{epoch:05}.pth`); the mesh of
 `trainer.neural_render.get_network()` is written to `<run_dir>/mesh/mesh_{resolution}_threshold{threshold}.ply` (the
@@ -17,7 +17,10 @@ times half the brick's diagonal; a density needs an explicit --band), --brick-di
 dense run's whenever no brick the surface crosses was left out; one more line reports the active and the total number of bricks.
 --check-distance [BAND] (distance and sdf fields) measures the field against the mesh just extracted (BaseNeuralField.level_set_check:
 |D(p) - threshold| against the exact distance from p to the mesh at points within BAND of it; BAND = four lattice steps of this run's
-resolution when omitted) and prints the result as ONE JSON line after everything else.  Without the option nothing new runs."""
+resolution when omitted) and prints the result as ONE JSON line after everything else.  Without the option nothing new runs.
+--check-volume [N] (distance and sdf fields) is its whole-volume counterpart (BaseNeuralField.distance_field_check: N points, 100 000
+when omitted, spread over the mesh's bounds widened by a quarter of their diagonal; the error and the slope by distance from the
+surface, through the triangles' BVH) and prints ONE more JSON line, after --check-distance's."""
 import json
 from argparse import ArgumentParser
 from pathlib import Path
@@ -47,6 +50,8 @@ def build_parser() -> ArgumentParser:
     parser.add_argument("--brick-dilate", type=int, default=0, metavar="D", help="grow the set of kept bricks by D bricks (0..4)")
     parser.add_argument("--check-distance", type=float, nargs="?", const=0.0, default=None, metavar="BAND",
                         help="check the field against the exact distance to the extracted mesh within BAND of it (four lattice steps when omitted)")
+    parser.add_argument("--check-volume", type=int, nargs="?", const=100000, default=None, metavar="N",
+                        help="check the field against the exact distance to the extracted mesh at N points of the whole volume (100000 when omitted)")
     return parser
 
 
@@ -92,6 +97,10 @@ def main(argv=None) -> Path:
             raise SystemExit("--check-distance needs a distance or sdf field")
         band = args.check_distance if args.check_distance > 0.0 else 4.0 * 2.0 * args.cube_range / max(args.resolution - 1, 1)
         print(json.dumps(network.level_set_check(verts, tris, threshold=args.threshold, band=band)))
+    if args.check_volume is not None:
+        if args.field == "density":
+            raise SystemExit("--check-volume needs a distance or sdf field")
+        print(json.dumps(network.distance_field_check(verts, tris, threshold=args.threshold, n=args.check_volume)))
     return path
 
 
