@@ -106,6 +106,13 @@ __device__ __forceinline__ void act_grad(float x, float &y, float &dy)
     }
 }
 
+// F.relu / nn.ReLU as torch evaluates them: NaN for NaN.  `x > 0 ? x : 0` and fmaxf(x, 0) (v_max_f32 returns its other operand for a
+// NaN) both return 0 there, which turns a diverged field into a finite one.  The comparison that is FALSE for a NaN selects x: one
+// v_cmp + one v_cndmask and the same bits for every other input (-0 included).  hipcc turned the `>` form into a single v_max_f32
+// behind arithmetic: one instruction more per element of a NeRF ReLU layer, +0.3 % on a 2^20-point evaluation (docs/lab_notebook.md).
+// v_max_f32 / v_med3_f32 drop the NaN in either float mode and v_max_i32 on the bits keeps only NaNs with a clear sign bit.
+__device__ __forceinline__ float relu_keep_nan(float x) { return x <= 0.f ? 0.f : x; }
+
 template <int KIND, int MODE = 0>
 __device__ __forceinline__ float act_val(float x)
 {
@@ -115,7 +122,7 @@ __device__ __forceinline__ float act_val(float x)
         float e2 = __builtin_amdgcn_exp2f(ex * 2.8853900817779268f);
         return x * fmaf(-2.0f, __builtin_amdgcn_rcpf(e2 + 1.0f), 1.0f);
     }
-    if (KIND == 0) return x > 0.f ? x : 0.f;            // F.relu
+    if (KIND == 0) return relu_keep_nan(x);             // F.relu
     if (KIND == 1) return x > 0.f ? x : 0.01f * x;       // F.leaky_relu
     return x * tanh_nonneg(fast_exp(__builtin_amdgcn_fmed3f(x, -3.0e38f, 80.0f)));      // nn_module/tanh_exp.py:28-31; x > 20 -> x exactly, see act_grad
 }
@@ -251,18 +258,23 @@ __device__ __forceinline__ void softplus_grad(float z, float &y, float &dy)
 }
 
 // the same two head activations on the raw transcendental units (kFast policies: bf16 operands -- their error, ~1e-6 relative, is three
-// orders of magnitude below the policy's rounding); the library expf / logf / tanhf above are ~40 instructions each
+// orders of magnitude below the policy's rounding); the library expf / logf / tanhf above are ~40 instructions each.
+// v_med3_f32 returns a finite value for a NaN, so the clamped exponent cannot carry one: a NaN pre-activation is put back by a
+// select (one v_cmp and one or two v_cndmask per POINT, in the head tail), as softplus_grad / sigmoid_grad and the reference keep it.
 __device__ __forceinline__ void softplus_grad_fast(float z, float &y, float &dy)
 {
-    const bool big = z > 20.0f;
+    const bool big = z > 20.0f, nan = z != z;
     const float e = fast_exp(__builtin_amdgcn_fmed3f(z, -80.0f, 20.0f));
     y = big ? z : __builtin_amdgcn_logf(1.0f + e) * 0.6931471805599453f;
     dy = big ? 1.0f : e * __builtin_amdgcn_rcpf(1.0f + e);          // 1 / (1 + e^-z)
+    y = nan ? z : y;
+    dy = nan ? z : dy;
 }
 __device__ __forceinline__ void sigmoid_grad_fast(float a, float &y, float &dy)
 {
     const float e = fast_exp(__builtin_amdgcn_fmed3f(-a, -80.0f, 80.0f));
-    const float t = __builtin_amdgcn_rcpf(1.0f + e);                // (1 + tanh(a / 2)) / 2
+    float t = __builtin_amdgcn_rcpf(1.0f + e);                      // (1 + tanh(a / 2)) / 2
+    t = a != a ? a : t;
     y = t;
     dy = t * (1 - t);
 }
@@ -315,7 +327,10 @@ __device__ __forceinline__ float exp_acc(float x)
     const float t = x * 1.44269502162933349609375f;
     const float r = fmaf(x, 1.44269502162933349609375f, -t) + x * 1.925963033500011e-8f;
     const float e = __builtin_amdgcn_exp2f(t);
-    return fmaf(e, r * 0.693147182464599609375f, e);
+    // Where the product x log2(e) leaves the fp32 range (x = -inf: a variance of +inf, or 4^e var beyond ~2e38) the carried error r is
+    // inf - inf = NaN, and 0 * NaN would poison a weight that is exactly 0 in the reference (exp(-inf), sampling.py:71).  e == 0 is
+    // false for a NaN, so a NaN variance still gives a NaN weight; for every other x the value is fmaf(0, r, 0) = 0 either way.
+    return e == 0.f ? 0.f : fmaf(e, r * 0.693147182464599609375f, e);
 }
 
 // Ray.get_sampling_cones ray.py:128-194 / get_sampling_points ray.py:88-126 for sample j of a ray whose S distances start at d: the

@@ -1130,16 +1130,16 @@ __global__ __launch_bounds__(64 * NW, WPS * NW / 4) void col_trunk_kernel(const 
                 float rest = 3 * aux * Dinv;
                 float sc = aux * dgn * D;
                 pen[0] = sc * ((d2 - rest) * (d2 - rest));
-                float t1 = fmaxf(-1.0f + dDdt, 0.f);
+                float t1 = relu_keep_nan(-1.0f + dDdt);
                 pen[1] = t1 * t1;
-                float a1 = fmaxf(-4.6f - z, 0.f), a2 = fmaxf(-a.distance_range_max + z, 0.f);
+                float a1 = relu_keep_nan(-4.6f - z), a2 = relu_keep_nan(-a.distance_range_max + z);
                 pen[2] = (a1 + a2) * (a1 + a2);
-                float b1 = fmaxf(-4.6f - az, 0.f), b2 = fmaxf(-4.6f + az, 0.f);
+                float b1 = relu_keep_nan(-4.6f - az), b2 = relu_keep_nan(-4.6f + az);
                 pen[3] = (b1 + b2) * (b1 + b2);
                 pen[4] = 0.f; pen[5] = 0.f;
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    float c1 = fmaxf(-0.0f - c[0][k], 0.f), c2 = fmaxf(-1.0f + c[0][k], 0.f);
+                    float c1 = relu_keep_nan(-0.0f - c[0][k]), c2 = relu_keep_nan(-1.0f + c[0][k]);
                     pen[4] += (c1 + c2) * (c1 + c2);
                     float s = c[RPP > 1 ? 1 : 0][k] * pa[PA_DG0] + c[RPP > 2 ? 2 : 0][k] * pa[PA_DG1] + c[RPP > 3 ? 3 : 0][k] * pa[PA_DG2];
                     pen[5] += s * s;

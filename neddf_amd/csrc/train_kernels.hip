@@ -1590,15 +1590,15 @@ __global__ void penalty_forward_kernel(TrainPointArgs a)
     float d2 = pt[TP_AGG0] * pt[TP_ND0] + pt[TP_AGG0 + 1] * pt[TP_ND0 + 1] + pt[TP_AGG0 + 2] * pt[TP_ND0 + 2];
     float rest = 3 * aux * Dinv;
     pen[0] = (aux * pt[TP_DGN] * D) * ((d2 - rest) * (d2 - rest));
-    float t1 = fmaxf(-1.0f + pt[TP_DDDT], 0.f);
+    float t1 = relu_keep_nan(-1.0f + pt[TP_DDDT]);
     pen[1] = t1 * t1;
-    float a1 = fmaxf(-4.6f - pt[TP_ZD0], 0.f), a2 = fmaxf(-a.distance_range_max + pt[TP_ZD0], 0.f);
+    float a1 = relu_keep_nan(-4.6f - pt[TP_ZD0]), a2 = relu_keep_nan(-a.distance_range_max + pt[TP_ZD0]);
     pen[2] = (a1 + a2) * (a1 + a2);
-    float b1 = fmaxf(-4.6f - pt[TP_ZA0], 0.f), b2 = fmaxf(-4.6f + pt[TP_ZA0], 0.f);
+    float b1 = relu_keep_nan(-4.6f - pt[TP_ZA0]), b2 = relu_keep_nan(-4.6f + pt[TP_ZA0]);
     pen[3] = (b1 + b2) * (b1 + b2);
     pen[4] = 0.f; pen[5] = 0.f;
     for (int k = 0; k < 3; ++k) {
-        float c1 = fmaxf(-0.0f - c[0][k], 0.f), c2 = fmaxf(-1.0f + c[0][k], 0.f);
+        float c1 = relu_keep_nan(-0.0f - c[0][k]), c2 = relu_keep_nan(-1.0f + c[0][k]);
         pen[4] += (c1 + c2) * (c1 + c2);
         float s = c[1][k] * pt[TP_DG0] + c[2][k] * pt[TP_DG0 + 1] + c[3][k] * pt[TP_DG0 + 2];
         pen[5] += s * s;
@@ -1642,20 +1642,20 @@ __global__ void point_backward_kernel(TrainPointArgs a)
     g_aux += -g_d2 * 3 * Dinv;
     for (int i = 0; i < 3; ++i) { g_agg[i] = g_d2 * nd[i]; g_nd[i] = g_d2 * agg[i]; }
     // pen1 = relu(dDdt - 1)^2
-    g_dDdt += gpen[1] * 2 * fmaxf(dDdt - 1.0f, 0.f);
+    g_dDdt += gpen[1] * 2 * relu_keep_nan(dDdt - 1.0f);
     // pen2, pen3: range penalties on the raw head outputs
     {
         float a1 = -4.6f - zd0, a2 = zd0 - a.distance_range_max;
-        float t = fmaxf(a1, 0.f) + fmaxf(a2, 0.f);
+        float t = relu_keep_nan(a1) + relu_keep_nan(a2);
         g_zd0 += gpen[2] * 2 * t * ((a2 > 0.f ? 1.f : 0.f) - (a1 > 0.f ? 1.f : 0.f));
         float b1 = -4.6f - za0, b2 = za0 - 4.6f;
-        float t2 = fmaxf(b1, 0.f) + fmaxf(b2, 0.f);
+        float t2 = relu_keep_nan(b1) + relu_keep_nan(b2);
         g_za0 += gpen[3] * 2 * t2 * ((b2 > 0.f ? 1.f : 0.f) - (b1 > 0.f ? 1.f : 0.f));
     }
     // pen4 (colour range), pen5 (colour constraint, distance_grad detached), colour itself
     for (int k = 0; k < 3; ++k) {
         float c1 = -c[0][k], c2 = c[0][k] - 1.0f;
-        float t = fmaxf(c1, 0.f) + fmaxf(c2, 0.f);
+        float t = relu_keep_nan(c1) + relu_keep_nan(c2);
         g_c[0][k] = (a.g_color ? a.g_color[n * 3 + k] : 0.f) + gpen[4] * 2 * t * ((c2 > 0.f ? 1.f : 0.f) - (c1 > 0.f ? 1.f : 0.f));
         float sk = c[1][k] * dg[0] + c[2][k] * dg[1] + c[3][k] * dg[2];
         for (int i = 0; i < 3; ++i) g_c[1 + i][k] = gpen[5] * 2 * sk * dg[i];

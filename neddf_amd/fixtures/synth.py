@@ -322,3 +322,87 @@ def pose_route_inputs(case):
     rng = np.random.default_rng(seed_ups)
     ups = OrderedDict((k, rng.standard_normal((rays, samples) + ((3,) if k == "color" else ())).astype(np.float32)) for k in FIELD_KEYS[kind])
     return pos, d, var, ups
+
+
+# ---------------------------------------------------------------- non-finite inputs and weights (tests/golden/nonfinite.npz)
+# name -> (field kind, constructor keywords); every network is 128 wide, its state is `arch_state(kind, kw, NONFINITE_STATE_SEED)`
+NONFINITE_STATE_SEED = 47
+_NF_NEDDF = dict(embed_pos_rank=6, embed_dir_rank=4, ddf_layer_count=6, ddf_layer_width=128, col_layer_count=3, col_layer_width=128,
+                 d_near=0.01, skips=[2], lowpass_alpha_offset=10)
+_NF_NERF = dict(embed_pos_rank=6, embed_dir_rank=4, layer_count=6, layer_width=128, skips=[2], lowpass_alpha_offset=10)
+_NF_NEUS = dict(embed_pos_rank=6, embed_dir_rank=4, sdf_layer_count=6, sdf_layer_width=128, col_layer_count=3, col_layer_width=128,
+                init_variance=0.3, skips=[2])
+NONFINITE_NETS = OrderedDict([
+    ("neddf_relu", ("neddf", dict(_NF_NEDDF, activation_type="ReLU", density_activation_type="ReLU"))),
+    # every penalty term switched on, range_color included (neddf.py:271-294)
+    ("neddf_tanhexp", ("neddf", dict(_NF_NEDDF, activation_type="tanhExp", density_activation_type="ReLU",
+                                     penalty_weight={"constraints_aux_grad": 0.05, "constraints_dDdt": 1.0, "constraints_color": 0.0001,
+                                                     "range_distance": 1.0, "range_aux_grad": 1.0, "range_color": 0.1}))),
+    ("neddf_leaky", ("neddf", dict(_NF_NEDDF, activation_type="LeakyReLU", density_activation_type="LeakyReLU"))),
+    ("neddf_skips", ("neddf", dict(_NF_NEDDF, activation_type="tanhExp", density_activation_type="ReLU", skips=[1, 3]))),
+    ("nerf_relu", ("nerf", dict(_NF_NERF, activation_type="ReLU", density_activation_type="ReLU"))),
+    ("nerf_tanhexp", ("nerf", dict(_NF_NERF, activation_type="tanhExp", density_activation_type="ReLU"))),
+    ("neus_relu", ("neus", dict(_NF_NEUS, activation_type="ReLU"))),
+    ("neus_tanhexp", ("neus", dict(_NF_NEUS, activation_type="tanhExp"))),
+])
+NONFINITE_POINTS = 229               # three 64-row tiles and a ragged 37
+NONFINITE_POINT_SEED = 53
+# poisoned rows: both sides of every 64-row tile edge and of the 128-row edge of the bf16 tiles, the first and the last row
+NONFINITE_ROWS = (0, 63, 64, 65, 127, 128, 191, 192, 228)
+_NAN, _INF = float("nan"), float("inf")
+# one per row, in order: (array, coordinate or None for all three, value) pairs
+NONFINITE_INPUT_POISONS = (
+    (("pos", 0, _NAN),), (("pos", 1, _INF),), (("pos", 2, -_INF),),
+    (("dir", 0, _NAN),), (("dir", 1, _INF),),
+    (("var", 2, _NAN),), (("var", 0, -_INF),),
+    (("var", None, _INF),),
+    (("var", None, _INF), ("pos", 1, _NAN)),
+)
+# weight poisons: name -> per field kind (tensor, index, value).  `trunk_*` sit in a hidden layer of the distance / density / sdf
+# trunk, `color_nan` in the colour trunk only, `head_bias_nan` is the output bias of the distance (NeRF: density, NeuS: sdf) head.
+NONFINITE_WEIGHT_POISONS = OrderedDict([
+    ("trunk_nan", {"neddf": ("layers_ddf.2.weight", (5, 7), _NAN), "nerf": ("layers.2.weight", (7, 5), _NAN),
+                   "neus": ("layers_sdf.2.weight", (7, 5), _NAN)}),
+    ("color_nan", {"neddf": ("layers_col.1.weight", (3, 9), _NAN), "nerf": ("outL_color.0.weight", (9, 3), _NAN),
+                   "neus": ("layers_col.1.weight", (9, 3), _NAN)}),
+    ("head_bias_nan", {"neddf": ("layer_ddf_out.bias", (0,), _NAN), "nerf": ("outL_density.bias", (0,), _NAN),
+                       "neus": ("layers_sdf.5.bias", (0,), _NAN)}),
+    ("trunk_inf", {"neddf": ("layers_ddf.2.weight", (5, 7), _INF), "nerf": ("layers.2.weight", (7, 5), _INF),
+                   "neus": ("layers_sdf.2.weight", (7, 5), _INF)}),
+])
+
+
+def nonfinite_inputs():
+    """(clean, poisoned): two (pos, dir, var) triples of shape [NONFINITE_POINTS, 1, 3]; the poisoned one carries
+    NONFINITE_INPUT_POISONS on NONFINITE_ROWS and equals the clean one everywhere else."""
+    clean = random_sampling(NONFINITE_POINTS, 1, NONFINITE_POINT_SEED, cone=True)
+    bad = dict(zip(("pos", "dir", "var"), (a.copy() for a in clean)))
+    for row, poisons in zip(NONFINITE_ROWS, NONFINITE_INPUT_POISONS):
+        for name, coord, value in poisons:
+            bad[name][row, 0, slice(None) if coord is None else coord] = value
+    return clean, (bad["pos"], bad["dir"], bad["var"])
+
+
+def nonfinite_upstream(kind, seed=59):
+    """Upstream gradients [NONFINITE_POINTS, 1(, 3)] for every output key of a field of `kind`, standard normal."""
+    rng = np.random.default_rng(seed)
+    return OrderedDict((k, rng.standard_normal((NONFINITE_POINTS, 1) + ((3,) if k == "color" else ())).astype(np.float32))
+                       for k in FIELD_KEYS[kind])
+
+
+def nonfinite_state(net, poison=None):
+    """The state dict of NONFINITE_NETS[net], with one entry of NONFINITE_WEIGHT_POISONS applied when `poison` names it."""
+    kind, kw = NONFINITE_NETS[net]
+    sd = arch_state(kind, dict(kw), NONFINITE_STATE_SEED)
+    if poison is not None:
+        key, idx, value = NONFINITE_WEIGHT_POISONS[poison][kind]
+        w = np.array(sd[key], np.float32, copy=True)
+        w[idx] = value
+        sd[key] = w
+    return sd
+
+
+def float_class(a):
+    """0 finite, 1 NaN, 2 +Inf, 3 -Inf, per element."""
+    a = np.asarray(a)
+    return (np.isnan(a) * 1 + np.isposinf(a) * 2 + np.isneginf(a) * 3).astype(np.uint8)

@@ -112,7 +112,7 @@ static inline float v_tanh_nonneg(float u)
 }
 static inline float act_val(int kind, float x)
 {
-    if (kind == ORC_RELU) return x > 0.f ? x : 0.f;
+    if (kind == ORC_RELU) return x <= 0.f ? 0.f : x;       /* F.relu keeps NaN */
     if (kind == ORC_LEAKY) return x > 0.f ? x : 0.01f * x;
     const float xc = x > 20.0f ? 20.0f : x;
     const float y = x * v_tanh_nonneg(v_exp(xc));

@@ -268,9 +268,12 @@ int orc_sample_pdf(const float *dists, float *weights, const float *U, int B, in
 
 /* ------------------------------------------------------------------------ */
 /* activations */
+/* F.relu / nn.ReLU return NaN for NaN (x > 0 ? x : 0 would return 0): the comparison that is false for NaN selects x */
+static inline float orc_relu(float x) { return x <= 0.f ? 0.f : x; }
+
 static inline float orc_act(int kind, float x)
 {
-    if (kind == ORC_RELU) return x > 0.f ? x : 0.f;              /* F.relu */
+    if (kind == ORC_RELU) return orc_relu(x);                    /* F.relu */
     if (kind == ORC_LEAKY) return x > 0.f ? x : 0.01f * x;        /* F.leaky_relu */
     /* tanhExp nn_module/tanh_exp.py:15-33 */
     if (x > 20.0f) return x;
@@ -637,18 +640,18 @@ void orc_neddf_forward(const orc_neddf_t *net, const float *pos, const float *di
                 float rest = 3 * aux * Dinv;
                 float scale = aux * dgn_[p] * D;
                 pen[0] = scale * ((d2 - rest) * (d2 - rest));
-                float t1 = -1.0f + dDdt_[p]; t1 = t1 > 0 ? t1 : 0;
+                float t1 = orc_relu(-1.0f + dDdt_[p]);
                 pen[1] = t1 * t1;
-                float a1 = -4.6f - hd[0]; a1 = a1 > 0 ? a1 : 0;
-                float a2 = -net->distance_range_max + hd[0]; a2 = a2 > 0 ? a2 : 0;
+                float a1 = orc_relu(-4.6f - hd[0]);
+                float a2 = orc_relu(-net->distance_range_max + hd[0]);
                 pen[2] = (a1 + a2) * (a1 + a2);
-                float b1 = -4.6f - ax[0]; b1 = b1 > 0 ? b1 : 0;
-                float b2 = -4.6f + ax[0]; b2 = b2 > 0 ? b2 : 0;
+                float b1 = orc_relu(-4.6f - ax[0]);
+                float b2 = orc_relu(-4.6f + ax[0]);
                 pen[3] = (b1 + b2) * (b1 + b2);
                 pen[4] = 0.f;
                 for (int k = 0; k < 3; ++k) {
-                    float c1 = -0.0f - c4[k]; c1 = c1 > 0 ? c1 : 0;
-                    float c2 = -1.0f + c4[k]; c2 = c2 > 0 ? c2 : 0;
+                    float c1 = orc_relu(-0.0f - c4[k]);
+                    float c2 = orc_relu(-1.0f + c4[k]);
                     pen[4] += (c1 + c2) * (c1 + c2);
                 }
                 pen[5] = 0.f;
@@ -736,7 +739,7 @@ void orc_nerf_forward(const orc_nerf_t *net, const float *pos, const float *dir,
                     h[cin + 3 * Ed + e * 3 + d] = cosf(p);
                 }
             orc_linear_t(h, net->col0_w, net->col0_b, cin + Cdir, W / 2, o);
-            for (int j = 0; j < W / 2; ++j) o[j] = o[j] > 0.f ? o[j] : 0.f;   /* nn.ReLU */
+            for (int j = 0; j < W / 2; ++j) o[j] = orc_relu(o[j]);   /* nn.ReLU */
             orc_linear_t(o, net->col1_w, net->col1_b, W / 2, 3, color + 3 * n);
         }
         free(pe); free(h); free(o);
@@ -761,7 +764,7 @@ typedef struct {
 /* value + derivative of the plain activations NeuS uses (nn.ReLU / tanhExp) */
 static inline void orc_act_plain_grad(int kind, float x, float *y, float *dy)
 {
-    if (kind == ORC_RELU) { *y = x > 0.f ? x : 0.f; *dy = x > 0.f ? 1.f : 0.f; return; }
+    if (kind == ORC_RELU) { *y = orc_relu(x); *dy = x <= 0.f ? 0.f : 1.f; return; }     /* threshold_backward: NaN passes the gradient on */
     orc_act_grad(ORC_TANHEXP, x, y, dy);
 }
 

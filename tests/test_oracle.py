@@ -440,3 +440,47 @@ def test_eval_harness_outputs_vs_reference(bunny_weights):
     _uint8_gate(dpt, g["cam0_depth"], "depth image")
     assert len(np.unique(g["cam0_rgb"])) > 50 and len(np.unique(g["cam0_depth"])) > 20      # the frame is not flat
     assert abs(peak_signal_noise_ratio(rgb, g["cam0_rgb_gt"]) - float(g["cam0_psnr"])) < 0.01
+
+
+# ----------------------------------------------------------------- NaN / Inf propagation (tests/golden/nonfinite.npz)
+def _nonfinite_oracle(name, poison):
+    kind, kw = synth.NONFINITE_NETS[name]
+    return {"neddf": orc.NeDDFOracle, "nerf": orc.NeRFOracle, "neus": orc.NeuSOracle}[kind](synth.nonfinite_state(name, poison), **kw)
+
+
+def check_nonfinite(got, g, pre, keys, rtol, atol, what):
+    """Class (finite / NaN / +Inf / -Inf) equal to the reference's on every kept element, and the kept finite elements at the gate."""
+    for k in keys:
+        want, keep = g[pre + k], g[pre + "keep_" + k]
+        have = np.asarray(got[k]).reshape(want.shape)
+        cg, cw = synth.float_class(have), synth.float_class(want)
+        bad = keep & (cg != cw)
+        assert not bad.any(), "%s %s: class differs on %d elements, first at %s: got %s, reference %s" % (
+            what, k, int(bad.sum()), tuple(np.argwhere(bad)[0]), have[bad][:4], want[bad][:4])
+        fin = keep & (cw == 0)
+        assert fin.any() or (cw != 0).all(), (what, k)
+        if fin.any():
+            assert_close(have[fin], want[fin], rtol, atol, "%s %s" % (what, k))
+
+
+@pytest.mark.parametrize("name", list(synth.NONFINITE_NETS))
+def test_oracle_nonfinite_propagation(name):
+    """The checker itself against the REFERENCE where a value is not finite (gen_nonfinite_goldens.py): nine poisoned points among 229
+    (NaN / +-Inf positions, directions and variances) and four poisoned weights.  F.relu, nn.ReLU and the relu(...) of the penalty
+    terms return NaN for NaN; a restatement as `x > 0 ? x : 0` returns 0 and turns a diverged field into a finite one."""
+    g = golden("nonfinite.npz")
+    kind, _ = synth.NONFINITE_NETS[name]
+    clean, bad = synth.nonfinite_inputs()
+    for a, k in zip(bad, ("pos", "dir", "var")):
+        assert np.array_equal(a, g[k], equal_nan=True)
+    for case in ["input"] + list(synth.NONFINITE_WEIGHT_POISONS):
+        net = _nonfinite_oracle(name, None if case == "input" else case)
+        pts = bad if case == "input" else clean
+        for mode, it in (("eval", -1), ("train", 2500)):
+            pre = "%s/%s/%s/" % (name, case, mode)
+            if pre + synth.FIELD_KEYS[kind][0] not in g.files:
+                assert kind != "neddf" and mode == "train"
+                continue
+            net.set_iter(it)
+            o = net.forward(*pts)
+            check_nonfinite(o, g, pre, synth.FIELD_KEYS[kind], 1e-4, 1e-5, pre)
