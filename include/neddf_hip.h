@@ -865,6 +865,101 @@ int neddf_point_mesh_bvh_query(neddf_ctx *ctx, const float *d_queries, int64_t n
                                const float *d_boxes, int64_t n_leaves, float *d_d2, int32_t *d_triangle, float *d_b1, float *d_b2, int32_t *d_visits,
                                void *stream);
 
+/* ---- mesh simplification by vertex clustering (additive to ABI v7; no reference counterpart: its users decimated in Open3D) ------
+ * Opt-in: a grid of cells is laid over the mesh, the vertices of a cell become one vertex, the triangles that collapse go.  Integer
+ * structure by count / scan / write, every floating-point step ONE rounded operation in a fixed order (no fused multiply-add, no float
+ * atomic): one answer per input on every run; tests/simplify_check.py restates all of it in numpy bit for bit.  The steps, with the
+ * caller's sorts between them (the keys of each sort are distinct or the sort is stable, so every correct sort gives one order):
+ *     neddf_mesh_simplify_keys -> sort ascending -> neddf_mesh_simplify_clusters -> [neddf_mesh_simplify_pairs -> sort ascending] ->
+ *     neddf_mesh_simplify_place [-> neddf_mesh_simplify_attributes] -> neddf_mesh_simplify_triangles -> order by triple ->
+ *     neddf_mesh_simplify_unique -> neddf_mesh_compact(representatives, mapped triangles, keep flags)
+ * Input: d_vertices float [V][3], d_triangles int32 [T][3].  V == 0, T == 0 and a result without any triangle are legal everywhere.
+ * Every entry point: NEDDF_EINVAL for a negative count, a NULL array it needs or a parameter outside its range, NEDDF_EUNSUPPORTED from
+ * 2^31 vertices or triangles on.  An index read from a sorted array is checked before it is followed: arrays that are not what the
+ * earlier steps made give a wrong answer, never an access outside them.
+ *
+ * GRID.  h_cells = (gx, gy, gz), each in [1, 1024], over the box h_lo .. h_hi (HOST doubles, finite, hi >= lo; mesh.simplify_mesh's
+ * default: the bounds of the finite vertices).  The cell of a coordinate is neddf_nn_grid_build's cell function unchanged: lo =
+ * (float)h_lo, inv_cell = (float)(cells / (h_hi - h_lo)) with the quotient in double, 0 for an axis without extent; f = (p - lo) *
+ * inv_cell in two rounded fp32 operations; cell = f >= cells ? cells - 1 : (f > 0 ? (int)f : 0) -- points outside the box are clamped
+ * into its border cells.  No per-cell array exists, so that build's limit of 2^24 cells in all does not apply.
+ * KEYS (neddf_mesh_simplify_keys: d_keys int64 [V]).  A finite vertex i: ((cz gy + cy) gx + cx) << 32 | i.  A vertex with a non-finite
+ * coordinate: 2^62 | i.  The keys are distinct.
+ * CLUSTERS (neddf_mesh_simplify_clusters, from the keys sorted ascending).  A cluster is a run of keys with equal high words; a key with
+ * bit 62 set is a run of its own (a non-finite vertex is never merged).  Its members appear in ascending vertex index, its head is
+ * its lowest vertex index, and clusters are numbered in the order of their heads: when no two vertices share a cell, cluster i is
+ * vertex i and the whole simplification is the identity.  d_vertex_cluster int32 [V]: the cluster of every vertex; d_cluster_range
+ * int32 [capacity V][2]: the [begin, end) of cluster c among the sorted keys, the first C rows written; *h_n_clusters = C (HOST; the
+ * call synchronises `stream` once).
+ * PLACEMENT (neddf_mesh_simplify_place: d_out float [C][3]).  A cluster of ONE member, finite or not, gets that vertex' bits.  Otherwise
+ *   NEDDF_SIMPLIFY_MEAN:  per axis the members are summed in fp64 in ascending member order (the sum starts at +0.0),
+ *       m = sum / (double)count, the result rounded once to fp32.
+ *   NEDDF_SIMPLIFY_QUADRIC:  m as above, unrounded.  For every VALID triangle (indices in [0, V), finite corners) with at least one
+ *       corner in the cluster, once each, in ascending triangle index, the ones that will collapse included -- the pairs of
+ *       neddf_mesh_simplify_pairs sorted ascending -- with p0, p1, p2 its corners converted to fp64:
+ *           u = p1 - p0, w = p2 - p0;  n = (u.y w.z - u.z w.y, u.z w.x - u.x w.z, u.x w.y - u.y w.x)
+ *           a00 += n.x n.x, a01 += n.x n.y, a02 += n.x n.z, a11 += n.y n.y, a12 += n.y n.z, a22 += n.z n.z
+ *           d = (n.x (p0.x - m.x) + n.y (p0.y - m.y)) + n.z (p0.z - m.z);  r += n * d per axis
+ *       n is deliberately not normalised: the weight is the squared area, there is no square root, and the only divisions are the
+ *       solve's.  Then (A + lambda I) y = r by the adjugate:
+ *           tr = (a00 + a11) + a22;  lambda = (regularisation * tr) / 3;  b00 = a00 + lambda, b11 = a11 + lambda, b22 = a22 + lambda
+ *           c00 = b11 b22 - a12 a12;  c01 = a02 a12 - a01 b22;  c02 = a01 a12 - a02 b11
+ *           c11 = b00 b22 - a02 a02;  c12 = a01 a02 - b00 a12;  c22 = b00 b11 - a01 a01
+ *           det = (b00 c00 + a01 c01) + a02 c02
+ *           y0 = ((c00 r0 + c01 r1) + c02 r2) / det;  y1 = ((c01 r0 + c11 r1) + c12 r2) / det;  y2 = ((c02 r0 + c12 r1) + c22 r2) / det
+ *       x = m + y; x = m instead when tr is 0 or non-finite, det is 0 or non-finite, or a component of y is non-finite.  Each axis of x
+ *       is then clamped to the [min, max] of the members' coordinates on that axis (max(x, min) first, then min(., max)) and rounded
+ *       to fp32.  regularisation (finite, >= 0; mesh.simplify_mesh's default 2^-10) is a knob, not a tolerance: it pulls x towards m
+ *       where the planes of a flat cluster leave a direction undetermined.
+ *   neddf_mesh_simplify_pairs: every valid triangle contributes one pair per DISTINCT cluster among its corners, cluster << 32 |
+ *       triangle, by count / scan / write in triangle order (within a triangle in corner order); *h_n_pairs = their number (HOST, one
+ *       synchronise); nothing is written while d_pairs is NULL or pair_cap is below it (the counting call).
+ * ATTRIBUTES (neddf_mesh_simplify_attributes: d_attributes float [V][k] -> d_out float [C][k], 1 <= k <= 1024; normals, colours).  Under
+ * either placement: a cluster of one member gets its bits; otherwise each column is the fp64 mean in member order as above, rounded
+ * once to fp32, a NaN result written as 0x7fc00000.  Nothing is renormalised.
+ * TRIANGLES (neddf_mesh_simplify_triangles: d_mapped int32 [T][3], d_lowest int32 [T], d_keys int64 [T]).  A triangle with an index
+ * outside [0, V) is dropped (a non-finite corner does NOT drop it: that vertex is its own cluster).  The corners are replaced by their
+ * clusters, d_mapped; a triangle with two equal clusters is dropped.  The rest are rotated cyclically so that the lowest cluster
+ * comes first, which keeps the orientation: the rotated triple (a, b, c) is the triangle's IDENTITY, d_lowest = a, d_keys = b << 31 |
+ * c.  A dropped one: (-1, -1, -1), -1 and -1.  d_mapped keeps the input's corner order -- the rotation decides which triangles are
+ * the same, it does not reorder the output -- so that a simplification that merges nothing returns the triangles as they came.
+ *   neddf_mesh_simplify_unique: d_order int64 [T] lists the triangles by ascending (a, b, c), equal triples by ascending index (a
+ *   STABLE sort by d_keys, then a stable sort by d_lowest); d_keep_triangle [T] bytes: 1 for the first of every run of equal triples
+ *   that is not a dropped one -- among triangles with the same rotated triple only the lowest original index survives.  Opposite
+ *   orientations are different triples and both stay.
+ * COMPACTION.  neddf_mesh_compact over (d_out of _place as vertices, d_mapped as triangles, d_keep_triangle) drops the clusters that
+ * no surviving triangle references and renumbers the rest in order; survivors keep the input order.  With its vertex map M over the
+ * clusters, vertex_map[v] = M[d_vertex_cluster[v]] (or -1) and triangle_map[t] = the rank of t among the kept triangles (or -1).
+ *
+ * THE DISPLACEMENT BOUND.  Let e_a = (h_hi_a - h_lo_a) / cells_a be the cell edges and D = sqrt(e_x^2 + e_y^2 + e_z^2) the diagonal.
+ *   (1) A representative lies in the per-axis [min, max] of its members: the mean of numbers lies between them, the clamp enforces
+ *       it for the quadric, and the final rounding to fp32 is monotone while min and max are fp32 numbers themselves.
+ *   (2) The members of a cluster share a cell.  The cell function's steps lie within 2^-12 cells of the ideal ones
+ *       (neddf_nn_grid_build), and its edge 1 / inv_cell within 2^-24 of e_a, so two coordinates INSIDE the box with one cell index
+ *       differ by less than (1 + 2^-11 + 2^-23) e_a.  (Points outside the box are clamped into the border cells and may lie further
+ *       apart: the bound is for a box that holds the mesh, as the default does.  An axis without extent has e_a = 0 and one cell.)
+ *   (3) Hence an input vertex with vertex_map >= 0 lies within (1 + 2^-10) D of its output vertex.
+ *   (4) Every output triangle is the image of an input triangle whose corners moved by at most that much; the point with the same
+ *       barycentric coordinates moved by a convex combination of the three displacements, so every point of the output surface lies
+ *       within (1 + 2^-10) D of the input surface.
+ * Nothing is promised in the other direction: a component smaller than a cell vanishes, and that is what clustering means. */
+enum { NEDDF_SIMPLIFY_MEAN = 0, NEDDF_SIMPLIFY_QUADRIC = 1 };
+int neddf_mesh_simplify_keys(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const double *h_lo, const double *h_hi, const int *h_cells,
+                             int64_t *d_keys, void *stream);
+int neddf_mesh_simplify_clusters(neddf_ctx *ctx, const int64_t *d_sorted_keys, int64_t n_vertices, int32_t *d_vertex_cluster, int32_t *d_cluster_range,
+                                 int64_t *h_n_clusters, void *stream);
+int neddf_mesh_simplify_pairs(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                              const int32_t *d_vertex_cluster, int64_t *d_pairs, int64_t pair_cap, int64_t *h_n_pairs, void *stream);
+int neddf_mesh_simplify_place(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int64_t *d_sorted_keys, const int32_t *d_cluster_range,
+                              int64_t n_clusters, int placement, double regularisation, const int32_t *d_triangles, int64_t n_triangles,
+                              const int64_t *d_sorted_pairs, int64_t n_pairs, float *d_out, void *stream);
+int neddf_mesh_simplify_attributes(neddf_ctx *ctx, const float *d_attributes, int64_t n_vertices, int n_columns, const int64_t *d_sorted_keys,
+                                   const int32_t *d_cluster_range, int64_t n_clusters, float *d_out, void *stream);
+int neddf_mesh_simplify_triangles(neddf_ctx *ctx, const int32_t *d_triangles, int64_t n_triangles, int64_t n_vertices, const int32_t *d_vertex_cluster,
+                                  int32_t *d_mapped, int32_t *d_lowest, int64_t *d_keys, void *stream);
+int neddf_mesh_simplify_unique(neddf_ctx *ctx, const int32_t *d_lowest, const int64_t *d_keys, int64_t n_triangles, const int64_t *d_order,
+                               unsigned char *d_keep_triangle, void *stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

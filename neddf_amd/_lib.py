@@ -174,7 +174,15 @@ SYMBOLS = [
     ("neddf_bvh_keys", C.c_int, [_vp, _vp, _i64, _vp, _i64, _dp, _dp, _vp, _vp]),
     ("neddf_bvh_build", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("neddf_point_mesh_bvh_query", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_mesh_simplify_keys", C.c_int, [_vp, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), _vp, _vp]),
+    ("neddf_mesh_simplify_clusters", C.c_int, [_vp, _vp, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    ("neddf_mesh_simplify_pairs", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(_i64), _vp]),
+    ("neddf_mesh_simplify_place", C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_int, C.c_double, _vp, _i64, _vp, _i64, _vp, _vp]),
+    ("neddf_mesh_simplify_attributes", C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _i64, _vp, _vp]),
+    ("neddf_mesh_simplify_triangles", C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_mesh_simplify_unique", C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
 ]
+SIMPLIFY_PLACEMENTS = {"mean": 0, "quadric": 1}         # NEDDF_SIMPLIFY_*
 
 _lib = None
 
@@ -699,6 +707,82 @@ class Context:
                                                        leaf_triangle.shape[0], _ptr(d2), _ptr(j), _ptr(b1), _ptr(b2),
                                                        _ptr(visits) if return_visits else None, self.stream()))
         return (d2, j, b1, b2, visits) if return_visits else (d2, j, b1, b2)
+
+    # ------------------------------------------------------------------ mesh simplification (mesh.simplify_mesh orders the steps)
+    def mesh_simplify_keys(self, vertices, lo, hi, cells):
+        """The sort keys of the vertices (neddf_mesh_simplify_keys): int64 [V], cell << 32 | index, 2^62 | index for a non-finite one."""
+        blo, bhi, bc = self._grid_args(lo, hi, cells)
+        keys = torch.empty(vertices.shape[0], device=vertices.device, dtype=torch.int64)
+        self.check(self.lib.neddf_mesh_simplify_keys(self.h, _ptr(vertices) if keys.numel() else None, vertices.shape[0], blo, bhi, bc,
+                                                     _ptr(keys) if keys.numel() else None, self.stream()))
+        return keys
+
+    def mesh_simplify_clusters(self, sorted_keys):
+        """The clusters of the keys sorted ascending (neddf_mesh_simplify_clusters): (vertex_cluster int32 [V], cluster_range int32 [C, 2])."""
+        n, dev = sorted_keys.shape[0], sorted_keys.device
+        cluster = torch.empty(n, device=dev, dtype=torch.int32)
+        rng = torch.empty(n, 2, device=dev, dtype=torch.int32)
+        c = _i64(0)
+        self.check(self.lib.neddf_mesh_simplify_clusters(self.h, _ptr(sorted_keys) if n else None, n, _ptr(cluster) if n else None,
+                                                         _ptr(rng) if n else None, C.byref(c), self.stream()))
+        return cluster, rng[:c.value]
+
+    def mesh_simplify_pairs(self, vertices, triangles, vertex_cluster):
+        """The (cluster, triangle) pairs of the valid triangles (neddf_mesh_simplify_pairs), by a counting call and a writing call of
+        exactly that size: int64 [P], cluster << 32 | triangle, triangle-major."""
+        n = _i64(0)
+
+        def call(pairs):
+            self.check(self.lib.neddf_mesh_simplify_pairs(self.h, _ptr(vertices) if vertices.numel() else None, vertices.shape[0],
+                                                          _ptr(triangles) if triangles.numel() else None, triangles.shape[0],
+                                                          _ptr(vertex_cluster) if vertex_cluster.numel() else None, _ptr(pairs),
+                                                          0 if pairs is None else pairs.shape[0], C.byref(n), self.stream()))
+        call(None)
+        pairs = torch.empty(n.value, device=vertices.device, dtype=torch.int64)
+        if n.value:
+            call(pairs)
+        return pairs
+
+    def mesh_simplify_place(self, vertices, sorted_keys, cluster_range, placement, regularisation, triangles, sorted_pairs):
+        """The representative of every cluster (neddf_mesh_simplify_place): float32 [C, 3]."""
+        c = cluster_range.shape[0]
+        out = torch.empty(c, 3, device=vertices.device, dtype=torch.float32)
+        has_pairs = sorted_pairs is not None and sorted_pairs.numel() > 0
+        self.check(self.lib.neddf_mesh_simplify_place(self.h, _ptr(vertices) if c else None, vertices.shape[0], _ptr(sorted_keys) if c else None,
+                                                      _ptr(cluster_range) if c else None, c, int(placement), float(regularisation),
+                                                      _ptr(triangles) if has_pairs else None, triangles.shape[0],
+                                                      _ptr(sorted_pairs) if has_pairs else None, sorted_pairs.shape[0] if has_pairs else 0,
+                                                      _ptr(out) if c else None, self.stream()))
+        return out
+
+    def mesh_simplify_attributes(self, attributes, sorted_keys, cluster_range):
+        """The per-cluster mean of every column of float32 [V, k] attributes (neddf_mesh_simplify_attributes): float32 [C, k]."""
+        c, k = cluster_range.shape[0], attributes.shape[1]
+        out = torch.empty(c, k, device=attributes.device, dtype=torch.float32)
+        self.check(self.lib.neddf_mesh_simplify_attributes(self.h, _ptr(attributes) if c else None, attributes.shape[0], k,
+                                                           _ptr(sorted_keys) if c else None, _ptr(cluster_range) if c else None, c,
+                                                           _ptr(out) if c else None, self.stream()))
+        return out
+
+    def mesh_simplify_triangles(self, triangles, n_vertices, vertex_cluster):
+        """Corners -> clusters (neddf_mesh_simplify_triangles): (mapped int32 [T, 3] in corner order, lowest int32 [T], keys int64 [T]:
+        the triple rotated to its lowest cluster is (lowest, keys >> 31, keys & (2^31 - 1))); -1 for a dropped triangle."""
+        n, dev = triangles.shape[0], triangles.device
+        mapped = torch.empty(n, 3, device=dev, dtype=torch.int32)
+        lowest = torch.empty(n, device=dev, dtype=torch.int32)
+        keys = torch.empty(n, device=dev, dtype=torch.int64)
+        self.check(self.lib.neddf_mesh_simplify_triangles(self.h, _ptr(triangles) if n else None, n, int(n_vertices),
+                                                          _ptr(vertex_cluster) if vertex_cluster.numel() else None, _ptr(mapped) if n else None,
+                                                          _ptr(lowest) if n else None, _ptr(keys) if n else None, self.stream()))
+        return mapped, lowest, keys
+
+    def mesh_simplify_unique(self, lowest, keys, order):
+        """uint8 [T]: 1 for the first of every run of equal rotated triples along `order` (neddf_mesh_simplify_unique)."""
+        n = lowest.shape[0]
+        keep = torch.empty(n, device=lowest.device, dtype=torch.uint8)
+        self.check(self.lib.neddf_mesh_simplify_unique(self.h, _ptr(lowest) if n else None, _ptr(keys) if n else None, n,
+                                                       _ptr(order) if n else None, _ptr(keep) if n else None, self.stream()))
+        return keep
 
     def composite(self, dists, dens, col, max_dist):
         require_device(dists, "dists")

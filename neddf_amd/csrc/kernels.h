@@ -397,6 +397,28 @@ void launch_point_mesh_bvh_query(const float *q, int64_t nq, const float *v, int
                                  const int32_t *children, const float *boxes, float *d2, int32_t *triangle, float *b1, float *b2, int32_t *visits,
                                  hipStream_t s);
 
+// Mesh simplification by vertex clustering (simplify_kernels.hip; include/neddf_hip.h states the contract).
+// keys int64 [V]: cell of g (neddf_nn_grid_build's cell function) << 32 | vertex index; 2^62 | index for a non-finite vertex
+void launch_simplify_keys(const NnGrid &g, const float *v, int64_t V, int64_t *keys, hipStream_t s);
+// keys sorted ascending -> vertex_cluster [V], cluster_range [C][2] (the [begin, end) of each cluster in the sorted keys); workspace:
+// head_of_vertex [V] bytes, run_start [V + 1], sblk / vblk [mc_blocks(V) + 1] each, sblk[mc_blocks(V)] = the number of clusters afterwards
+void launch_simplify_clusters(const int64_t *keys, int64_t V, unsigned char *head_of_vertex, int32_t *run_start, int64_t *sblk, int64_t *vblk,
+                              int32_t *vertex_cluster, int32_t *cluster_range, hipStream_t s);
+// the (cluster, triangle) pairs of the valid triangles: pblk [mc_blocks(T) + 1], pblk[mc_blocks(T)] = the number of pairs afterwards;
+// pairs [that number] = cluster << 32 | triangle, triangle-major
+void launch_simplify_pair_count(const float *v, int64_t V, const int32_t *tri, int64_t T, const int32_t *vertex_cluster, int64_t *pblk, hipStream_t s);
+void launch_simplify_pair_write(const float *v, int64_t V, const int32_t *tri, int64_t T, const int32_t *vertex_cluster, const int64_t *pblk, int64_t *pairs,
+                                hipStream_t s);
+// out [C][3]: the representative of every cluster; quadric != 0 reads the pairs sorted ascending
+void launch_simplify_place(const int64_t *keys, int64_t V, const int32_t *cluster_range, int64_t C, const float *v, const int32_t *tri, int64_t T,
+                           const int64_t *pairs, int64_t P, int quadric, double reg, float *out, hipStream_t s);
+// attr [V][K] -> out [C][K]
+void launch_simplify_attributes(const int64_t *keys, int64_t V, const int32_t *cluster_range, int64_t C, const float *attr, int K, float *out, hipStream_t s);
+// mapped [T][3], lowest [T], key [T]; then, with order [T] = the triangles sorted by (lowest, key) (ties by index), keep [T]
+void launch_simplify_triangles(const int32_t *tri, int64_t T, int64_t V, const int32_t *vertex_cluster, int32_t *mapped, int32_t *lowest, int64_t *key,
+                               hipStream_t s);
+void launch_simplify_unique(const int32_t *lowest, const int64_t *key, int64_t T, const int64_t *order, unsigned char *keep, hipStream_t s);
+
 void launch_linear_grad(const float *x, const float *J, int64_t n, int cin, int ldx, int cout_block, int ksteps, const float *wp,
                         const float *bias, float *y, float *G, int ldo, int nvalid, int accumulate, int grid, hipStream_t s);
 void launch_op_activation(int kind, const float *x, const float *J, int64_t N, int C, float *y, float *G, hipStream_t s);

@@ -2297,3 +2297,134 @@ int neddf_point_mesh_bvh_query(neddf_ctx *ctx, const float *d_queries, int64_t n
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// ---- mesh simplification by vertex clustering (simplify_kernels.hip) ----
+static int simplify_counts_ok(neddf_ctx *ctx, int64_t V, int64_t T, const char *what)
+{
+    if (V < 0 || T < 0) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": negative count");
+    if (V >= ((int64_t)1 << 31) || T >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, std::string(what) + ": 2^31 vertices or triangles or more (indices are int32)");
+    return 0;
+}
+
+int neddf_mesh_simplify_keys(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const double *h_lo, const double *h_hi, const int *h_cells,
+                             int64_t *d_keys, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = simplify_counts_ok(ctx, n_vertices, 0, "mesh_simplify_keys")) return rc;
+    if (!h_lo || !h_hi || !h_cells) return fail(ctx, NEDDF_EINVAL, "mesh_simplify_keys: NULL box or cells");
+    if (n_vertices > 0 && (!d_vertices || !d_keys)) return fail(ctx, NEDDF_EINVAL, "mesh_simplify_keys: NULL vertices or keys");
+    NnGrid g;
+    for (int a = 0; a < 3; ++a) {               // nn_grid's cells (its limit of 2^24 cells in all is the lists', not the cell function's)
+        if (h_cells[a] < 1 || h_cells[a] > kNnMaxAxis) return fail(ctx, NEDDF_EINVAL, "mesh_simplify_keys: 1 to 1024 cells per axis");
+        if (!std::isfinite(h_lo[a]) || !std::isfinite(h_hi[a]) || !(h_hi[a] >= h_lo[a])) return fail(ctx, NEDDF_EINVAL, "mesh_simplify_keys: a finite box with hi >= lo expected");
+        const double ext = h_hi[a] - h_lo[a];
+        g.n[a] = h_cells[a];
+        g.lo[a] = (float)h_lo[a];
+        g.inv_cell[a] = ext > 0.0 ? (float)((double)h_cells[a] / ext) : 0.f;
+        if (!std::isfinite(g.lo[a]) || !std::isfinite(g.inv_cell[a])) return fail(ctx, NEDDF_EINVAL, "mesh_simplify_keys: the box does not fit fp32");
+    }
+    g.safe_cell = 0.f;
+    DeviceGuard guard_(ctx->device);
+    launch_simplify_keys(g, d_vertices, n_vertices, d_keys, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_mesh_simplify_clusters(neddf_ctx *ctx, const int64_t *d_sorted_keys, int64_t n_vertices, int32_t *d_vertex_cluster, int32_t *d_cluster_range,
+                                 int64_t *h_n_clusters, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    const int64_t V = n_vertices;
+    if (int rc = simplify_counts_ok(ctx, V, 0, "mesh_simplify_clusters")) return rc;
+    if (!h_n_clusters || (V > 0 && (!d_sorted_keys || !d_vertex_cluster || !d_cluster_range)))
+        return fail(ctx, NEDDF_EINVAL, "mesh_simplify_clusters: NULL keys, vertex clusters, cluster ranges or count");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nb = mc_blocks(V);
+    if (int rc = ensure(ctx, ctx->cc_parent, (size_t)(V + 1) * sizeof(int32_t))) return rc;
+    if (int rc = ensure(ctx, ctx->cc_used, (size_t)(V > 0 ? V : 1))) return rc;
+    if (int rc = ensure(ctx, ctx->cc_blk, (size_t)(2 * nb + 2) * sizeof(int64_t))) return rc;
+    int64_t *sblk = (int64_t *)ctx->cc_blk.p, *vblk = sblk + nb + 1;
+    launch_simplify_clusters(d_sorted_keys, V, (unsigned char *)ctx->cc_used.p, (int32_t *)ctx->cc_parent.p, sblk, vblk, d_vertex_cluster, d_cluster_range, s);
+    return read_totals(ctx, s, { { h_n_clusters, sblk + nb } });
+}
+
+int neddf_mesh_simplify_pairs(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                              const int32_t *d_vertex_cluster, int64_t *d_pairs, int64_t pair_cap, int64_t *h_n_pairs, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    const int64_t V = n_vertices, T = n_triangles;
+    if (int rc = simplify_counts_ok(ctx, V, T, "mesh_simplify_pairs")) return rc;
+    if (!h_n_pairs || (V > 0 && (!d_vertices || !d_vertex_cluster)) || (T > 0 && !d_triangles))
+        return fail(ctx, NEDDF_EINVAL, "mesh_simplify_pairs: NULL vertices, triangles, vertex clusters or count");
+    DeviceGuard guard_(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nb = mc_blocks(T);
+    if (int rc = ensure(ctx, ctx->cc_blk, (size_t)(nb + 1) * sizeof(int64_t))) return rc;
+    int64_t *pblk = (int64_t *)ctx->cc_blk.p;
+    launch_simplify_pair_count(d_vertices, V, d_triangles, T, d_vertex_cluster, pblk, s);
+    if (int rc = read_totals(ctx, s, { { h_n_pairs, pblk + nb } })) return rc;
+    if (!d_pairs || pair_cap < *h_n_pairs) return 0;                 // the counting call
+    launch_simplify_pair_write(d_vertices, V, d_triangles, T, d_vertex_cluster, pblk, d_pairs, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_mesh_simplify_place(neddf_ctx *ctx, const float *d_vertices, int64_t n_vertices, const int64_t *d_sorted_keys, const int32_t *d_cluster_range,
+                              int64_t n_clusters, int placement, double regularisation, const int32_t *d_triangles, int64_t n_triangles,
+                              const int64_t *d_sorted_pairs, int64_t n_pairs, float *d_out, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    const int64_t V = n_vertices, T = n_triangles, C = n_clusters;
+    if (int rc = simplify_counts_ok(ctx, V, T, "mesh_simplify_place")) return rc;
+    if (C < 0 || C > V || n_pairs < 0 || n_pairs > 3 * T) return fail(ctx, NEDDF_EINVAL, "mesh_simplify_place: 0 <= clusters <= vertices and 0 <= pairs <= 3 triangles expected");
+    if (placement != NEDDF_SIMPLIFY_MEAN && placement != NEDDF_SIMPLIFY_QUADRIC) return fail(ctx, NEDDF_EINVAL, "mesh_simplify_place: unknown placement");
+    if (!(regularisation >= 0.0) || !std::isfinite(regularisation)) return fail(ctx, NEDDF_EINVAL, "mesh_simplify_place: the regularisation must be finite and not negative");
+    if (C > 0 && (!d_vertices || !d_sorted_keys || !d_cluster_range || !d_out)) return fail(ctx, NEDDF_EINVAL, "mesh_simplify_place: NULL vertices, keys, ranges or output");
+    if (placement == NEDDF_SIMPLIFY_QUADRIC && n_pairs > 0 && (!d_triangles || !d_sorted_pairs))
+        return fail(ctx, NEDDF_EINVAL, "mesh_simplify_place: NULL triangles or pairs");
+    DeviceGuard guard_(ctx->device);
+    launch_simplify_place(d_sorted_keys, V, d_cluster_range, C, d_vertices, d_triangles, T, d_sorted_pairs, n_pairs, placement == NEDDF_SIMPLIFY_QUADRIC,
+                          regularisation, d_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_mesh_simplify_attributes(neddf_ctx *ctx, const float *d_attributes, int64_t n_vertices, int n_columns, const int64_t *d_sorted_keys,
+                                   const int32_t *d_cluster_range, int64_t n_clusters, float *d_out, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    const int64_t V = n_vertices, C = n_clusters;
+    if (int rc = simplify_counts_ok(ctx, V, 0, "mesh_simplify_attributes")) return rc;
+    if (C < 0 || C > V || n_columns < 1 || n_columns > 1024) return fail(ctx, NEDDF_EINVAL, "mesh_simplify_attributes: 0 <= clusters <= vertices and 1 to 1024 columns expected");
+    if (C > 0 && (!d_attributes || !d_sorted_keys || !d_cluster_range || !d_out)) return fail(ctx, NEDDF_EINVAL, "mesh_simplify_attributes: NULL attributes, keys, ranges or output");
+    DeviceGuard guard_(ctx->device);
+    launch_simplify_attributes(d_sorted_keys, V, d_cluster_range, C, d_attributes, n_columns, d_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_mesh_simplify_triangles(neddf_ctx *ctx, const int32_t *d_triangles, int64_t n_triangles, int64_t n_vertices, const int32_t *d_vertex_cluster,
+                                  int32_t *d_mapped, int32_t *d_lowest, int64_t *d_keys, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = simplify_counts_ok(ctx, n_vertices, n_triangles, "mesh_simplify_triangles")) return rc;
+    if ((n_triangles > 0 && (!d_triangles || !d_mapped || !d_lowest || !d_keys)) || (n_triangles > 0 && n_vertices > 0 && !d_vertex_cluster))
+        return fail(ctx, NEDDF_EINVAL, "mesh_simplify_triangles: NULL triangles, vertex clusters or outputs");
+    DeviceGuard guard_(ctx->device);
+    launch_simplify_triangles(d_triangles, n_triangles, n_vertices, d_vertex_cluster, d_mapped, d_lowest, d_keys, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_mesh_simplify_unique(neddf_ctx *ctx, const int32_t *d_lowest, const int64_t *d_keys, int64_t n_triangles, const int64_t *d_order,
+                               unsigned char *d_keep_triangle, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = simplify_counts_ok(ctx, 0, n_triangles, "mesh_simplify_unique")) return rc;
+    if (n_triangles > 0 && (!d_lowest || !d_keys || !d_order || !d_keep_triangle)) return fail(ctx, NEDDF_EINVAL, "mesh_simplify_unique: NULL triples, order or keep flags");
+    DeviceGuard guard_(ctx->device);
+    launch_simplify_unique(d_lowest, d_keys, n_triangles, d_order, d_keep_triangle, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}

@@ -5,7 +5,9 @@ The reference meshes a trained field inside its Open3D viewer (neddf/scripts/fie
 PyMCubes -> .dae).  Here the grid evaluation and marching cubes are HIP kernels (include/neddf_hip.h neddf_field_grid,
 neddf_marching_cubes); BaseNeuralField.extract_mesh and neddf/scripts/extract_mesh.py are built on this module.  A level set of a
 trained field comes with small closed blobs in empty space and open shreds at the cube's faces: connected_components,
-compact_mesh and remove_small_components drop them on the device (neddf_mesh_components, neddf_mesh_compact).
+compact_mesh and remove_small_components drop them on the device (neddf_mesh_components, neddf_mesh_compact).  Marching cubes emits
+triangles at the lattice's density whether the surface is flat or not: simplify_mesh merges the vertices of every cell of a coarser
+grid on the device (neddf_mesh_simplify_*), in place of the decimation the reference's users ran in Open3D.
 """
 import numpy as np
 import torch
@@ -167,6 +169,109 @@ def remove_small_components(vertices, triangles, min_triangles=0, keep_largest=0
 
     Returns (vertices, triangles, vertex_map) as compact_mesh does."""
     return _clean(vertices, triangles, min_triangles, keep_largest)[0]
+
+
+def simplify_grid(bounds_lo, bounds_hi, cell=None, cells=None):
+    """The cell counts (gx, gy, gz) of simplify_mesh over a box: `cells` as given, or ceil(extent / cell) per axis and at least 1 for
+    an edge length `cell` in world units.  NeddfError unless exactly one of the two is given and every axis gets 1 to 1024 cells."""
+    if (cell is None) == (cells is None):
+        raise NeddfError("simplify_mesh: exactly one of cell and cells must be given")
+    if cells is None:
+        if not (float(cell) > 0.0 and float(cell) < float("inf")):
+            raise NeddfError("simplify_mesh: cell must be a positive edge length (got %r)" % (cell,))
+        need = [(float(h) - float(l)) / float(cell) for l, h in zip(bounds_lo, bounds_hi)]
+        if max(need) > 1024.0:
+            raise NeddfError("simplify_mesh: a cell of %g needs more than 1024 cells along an axis (extent / cell = %s)" % (float(cell), need))
+        cells = [max(1, int(np.ceil(x))) for x in need]
+    cells = tuple(int(c) for c in cells)
+    if len(cells) != 3 or min(cells) < 1 or max(cells) > 1024:
+        raise NeddfError("simplify_mesh: cells must be three counts in [1, 1024] (got %r)" % (cells,))
+    return cells
+
+
+def simplify_mesh(vertices, triangles, cell=None, cells=None, box=None, placement="mean", regularisation=2 ** -10, attributes=None, timings=None):
+    """Vertex clustering: a grid of `cells` = (gx, gy, gz) cells (or of cells with edge `cell`, in world units) is laid over `box` =
+    (lo, hi) -- the bounds of the finite vertices when None -- the vertices of each cell become one vertex, and the triangles that
+    collapse, and duplicates of a triangle, go (include/neddf_hip.h "mesh simplification" states every rule; tests/simplify_check.py
+    restates it in numpy bit for bit; the same call gives the same bits on every run).
+
+    placement "mean": the new vertex is the fp64 mean of the cell's vertices.  "quadric": the point that minimises the area-weighted
+    squared distance to the planes of the triangles around the cell's vertices, regularised towards the mean by `regularisation`
+    (a knob: 0 is legal) and clamped to the bounding box of the cell's vertices -- flat regions stay flat and edges stay sharp.
+    attributes: a float32 [V, k] tensor (normals, colours) or a list of them, averaged per cell and not renormalised.
+
+    Returns (vertices float32 [V', 3], triangles int32 [T', 3], vertex_map int32 [V]: the new index of every old vertex's cell or -1,
+    triangle_map int32 [T]: the new index of every surviving triangle or -1[, attributes: as given, [V', k] each]).  Every new vertex
+    lies within (1 + 2^-10) cell diagonals of the old vertices mapped to it, hence every point of the new surface that close to the
+    old one; components smaller than a cell vanish.  With cells so fine that no two vertices share one, the mesh comes back unchanged.
+    `timings` (a dict, optional) receives the wall time in seconds of "keys", "sort", "clusters", "placement", "triangles" and
+    "compaction", each ending in a device synchronise."""
+    import time
+    from ._lib import SIMPLIFY_PLACEMENTS
+    _device_mesh("simplify_mesh", vertices=vertices, triangles=triangles)
+    if placement not in SIMPLIFY_PLACEMENTS:
+        raise NeddfError("simplify_mesh: placement must be 'mean' or 'quadric' (got %r)" % (placement,))
+    if vertices.device != triangles.device:
+        raise NeddfError("simplify_mesh: vertices and triangles must live on one device (got %s, %s)" % (vertices.device, triangles.device))
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise NeddfError("simplify_mesh: vertices must be float32 [V, 3] (got %s %s)" % (vertices.dtype, tuple(vertices.shape)))
+    if not (float(regularisation) >= 0.0 and float(regularisation) < float("inf")):
+        raise NeddfError("simplify_mesh: the regularisation must be finite and not negative (got %r)" % (regularisation,))
+    single = isinstance(attributes, torch.Tensor)
+    attrs = [] if attributes is None else ([attributes] if single else list(attributes))
+    for a in attrs:
+        _device_mesh("simplify_mesh", attributes=a)
+        if a.dtype != torch.float32 or a.dim() != 2 or a.shape[0] != vertices.shape[0] or a.shape[1] < 1 or a.device != vertices.device:
+            raise NeddfError("simplify_mesh: attributes must be float32 [V, k] on the mesh's device (got %s %s)" % (a.dtype, tuple(a.shape)))
+    ctx = Context.get(vertices.device)
+    v = vertices.contiguous()
+    t = ctx._triangles(triangles, "simplify_mesh")
+    if box is None:
+        finite = v[torch.isfinite(v).all(dim=1)]
+        if finite.shape[0]:
+            lo, hi = finite.min(dim=0).values.double().tolist(), finite.max(dim=0).values.double().tolist()
+        else:
+            lo, hi = [0.0] * 3, [0.0] * 3
+    else:
+        lo, hi = [float(x) for x in box[0]], [float(x) for x in box[1]]
+        if len(lo) != 3 or len(hi) != 3:
+            raise NeddfError("simplify_mesh: box must be (lo, hi) of three coordinates each (got %r)" % (box,))
+    cells = simplify_grid(lo, hi, cell, cells)
+    marks = [time.perf_counter()]
+
+    def mark():
+        if timings is not None:
+            torch.cuda.synchronize(v.device)
+            marks.append(time.perf_counter())
+    keys = ctx.mesh_simplify_keys(v, lo, hi, cells)
+    mark()
+    keys = torch.sort(keys).values                      # distinct keys: one order (plumbing, as bvh.py sorts its keys)
+    mark()
+    cluster, crange = ctx.mesh_simplify_clusters(keys)
+    mark()
+    pairs = None
+    if placement == "quadric":
+        pairs = torch.sort(ctx.mesh_simplify_pairs(v, t, cluster)).values
+    rep = ctx.mesh_simplify_place(v, keys, crange, SIMPLIFY_PLACEMENTS[placement], regularisation, t, pairs)
+    rep_attrs = [ctx.mesh_simplify_attributes(a.contiguous(), keys, crange) for a in attrs]
+    mark()
+    mapped, lowest, tkeys = ctx.mesh_simplify_triangles(t, v.shape[0], cluster)
+    order = torch.sort(tkeys, stable=True).indices      # by (b, c), then by a: equal triples end up next to each other in index order
+    order = order[torch.sort(lowest[order], stable=True).indices]
+    keep = ctx.mesh_simplify_unique(lowest, tkeys, order.contiguous())
+    mark()
+    out_v, out_t, cmap = ctx.mesh_compact(rep, mapped, keep)
+    vmap = cmap[cluster.long()] if v.shape[0] else torch.empty(0, device=v.device, dtype=torch.int32)
+    tmap = torch.where(keep != 0, torch.cumsum(keep.to(torch.int32), 0, dtype=torch.int32) - 1, torch.full_like(keep, -1, dtype=torch.int32))
+    out_attrs = [a[cmap >= 0].contiguous() for a in rep_attrs]
+    mark()
+    if timings is not None:
+        for name, a, b in zip(("keys", "sort", "clusters", "placement", "triangles", "compaction"), marks[:-1], marks[1:]):
+            timings[name] = b - a
+    out = (out_v, out_t, vmap.contiguous(), tmap)
+    if attributes is None:
+        return out
+    return out + ((out_attrs[0] if single else out_attrs),)
 
 
 def _host(a, dtype):
@@ -344,4 +449,4 @@ def sample_surface(vertices, triangles, density=None, n=None, seed=0):
 
 
 __all__ = ["marching_cubes", "select_bricks", "marching_cubes_bricks", "vertex_normals", "connected_components", "compact_mesh", "remove_small_components", "write_ply",
-           "read_ply", "sample_surface", "surface_area"]
+           "read_ply", "sample_surface", "surface_area", "simplify_grid", "simplify_mesh"]

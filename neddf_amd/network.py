@@ -144,7 +144,7 @@ class BaseNeuralField(ABC, nn.Module):
     def extract_mesh(self, field_name: str = "distance", threshold: float = 0.0275, cube_range: float = 1.1,
                      resolution: int = 64, timings: Optional[Dict[str, float]] = None, normals=False, colors: bool = False,
                      min_component_triangles: int = 0, keep_largest: int = 0, brick: int = 0, band: Optional[float] = None,
-                     lipschitz: float = 1.0, brick_dilate: int = 0):
+                     lipschitz: float = 1.0, brick_dilate: int = 0, simplify_cell: float = 0.0, simplify_placement: str = "mean"):
         """Triangle mesh of the `threshold` level set of `field_name` in the cube [-cube_range, cube_range]^3 sampled at
         resolution^3 points -- the reference's generate_mesh (fields_visualizer.py:528-566: voxelize("distance", 1.1, 64),
         mcubes.marching_cubes(voxel, 0.0275)) with the grid evaluation and marching cubes on the GPU.
@@ -179,9 +179,18 @@ class BaseNeuralField(ABC, nn.Module):
         `lipschitz` per unit length -- a distance or sdf is 1-Lipschitz where it is exact, a trained one only roughly (raise
         `lipschitz` to be safer at the price of more bricks).  A density has no such bound: there `band` must be given.
         `timings` receives "coarse" (corner evaluation and selection), "grid" and "mcubes" (the brick stages), and the counts
-        "bricks" (all bricks of the lattice) and "bricks_active"."""
+        "bricks" (all bricks of the lattice) and "bricks_active".
+
+        simplify_cell (not in the reference, whose users decimated in Open3D; 0 = off): vertex clustering, mesh.simplify_mesh, with
+        cells of this edge length in world units over the bounds of the mesh and simplify_placement "mean" or "quadric".  It runs after
+        the clean-up and before normals and colours, so the field is evaluated at the vertices that remain.  `timings` receives the
+        stage's wall time ("simplify") and the counts it started from ("vertices_before", "triangles_before").  With 0 nothing new runs."""
         import time
-        from .mesh import _clean, marching_cubes, marching_cubes_bricks, select_bricks, vertex_normals
+        from .mesh import _clean, marching_cubes, marching_cubes_bricks, select_bricks, simplify_mesh, vertex_normals
+        if not float(simplify_cell) >= 0.0:
+            raise ValueError("extract_mesh: simplify_cell must not be negative (got %r)" % (simplify_cell,))
+        if simplify_placement not in ("mean", "quadric"):
+            raise ValueError("extract_mesh: simplify_placement must be 'mean' or 'quadric' (got %r)" % (simplify_placement,))
         brick = int(brick)
         if brick and not 2 <= brick <= 16:
             raise ValueError("extract_mesh: brick must be 0 (dense) or lie in [2, 16] (got %r)" % (brick,))
@@ -235,6 +244,12 @@ class BaseNeuralField(ABC, nn.Module):
                 (verts, tris, _), cleaned = _clean(verts, tris, min_component_triangles, keep_largest)
                 torch.cuda.synchronize(self.device)
                 t2 = time.perf_counter()
+            t_clean, before = t2, None
+            if float(simplify_cell) > 0.0:
+                before = (int(verts.shape[0]), int(tris.shape[0]))
+                verts, tris = simplify_mesh(verts, tris, cell=float(simplify_cell), placement=simplify_placement)[:2]
+                torch.cuda.synchronize(self.device)
+                t2 = time.perf_counter()
             out = [verts, tris]
             nrm = None
             if normals or colors:
@@ -264,8 +279,10 @@ class BaseNeuralField(ABC, nn.Module):
             if n_bricks is not None:
                 timings["coarse"], timings["bricks"], timings["bricks_active"] = t_coarse, n_bricks[0], n_bricks[1]
             if cleaned is not None:
-                timings["clean"] = t2 - t_mc
+                timings["clean"] = t_clean - t_mc
                 timings.update(cleaned)
+            if before is not None:
+                timings["simplify"], timings["vertices_before"], timings["triangles_before"] = t2 - t_clean, before[0], before[1]
             if normals:
                 timings["normals"] = t3 - t2
             if colors:

@@ -1,6 +1,6 @@
 """`python neddf/scripts/extract_mesh.py <run_dir> [--epoch 2000] [--resolution 64] [--threshold 0.0275] [--field distance]
 [--cube-range 1.1] [--normals [field|geometric]] [--colors] [--min-component N] [--keep-largest [K]] [--sparse [B]] [--band W]
-[--lipschitz L] [--brick-dilate D] [--check-distance [BAND]] [--check-volume [N]]` -- the reference's mesh export (neddf/scripts/fields_visualizer.py:528-566, generate_mesh: voxelize
+[--lipschitz L] [--brick-dilate D] [--simplify [K]] [--simplify-placement mean|quadric] [--check-distance [BAND]] [--check-volume [N]]` -- the reference's mesh export (neddf/scripts/fields_visualizer.py:528-566, generate_mesh: voxelize
 "distance" on a 64^3 cube of half-width 1.1, marching cubes at 0.0275, export) without its Open3D viewer.  The run is
 loaded as run_eval loads it (`<run_dir>/.hydra/config.yaml`, `models/model_{epoch:05}.pth`); the mesh of
 `trainer.neural_render.get_network()` is written to `<run_dir>/mesh/mesh_{resolution}_threshold{threshold}.ply` (the
@@ -20,7 +20,12 @@ dense run's whenever no brick the surface crosses was left out; one more line re
 resolution when omitted) and prints the result as ONE JSON line after everything else.  Without the option nothing new runs.
 --check-volume [N] (distance and sdf fields) is its whole-volume counterpart (BaseNeuralField.distance_field_check: N points, 100 000
 when omitted, spread over the mesh's bounds widened by a quarter of their diagonal; the error and the slope by distance from the
-surface, through the triangles' BVH) and prints ONE more JSON line, after --check-distance's."""
+surface, through the triangles' BVH) and prints ONE more JSON line, after --check-distance's.
+--simplify [K] (K = 2 when omitted) merges the vertices of every cell of K lattice steps, K * 2 cube_range / (resolution - 1), into one
+(mesh.simplify_mesh: the cell's mean, or with --simplify-placement quadric the point closest to the planes of the triangles around it),
+after the clean-up and before normals and colours; one more line reports the vertex and triangle counts before and after and the
+time.  With --check-distance or --check-volume the unsimplified mesh is extracted as well and one further line gives the largest
+distance from the simplified surface to it (geometry.mesh_distance, to="surface"); both checks then measure the simplified mesh."""
 import json
 from argparse import ArgumentParser
 from pathlib import Path
@@ -48,6 +53,10 @@ def build_parser() -> ArgumentParser:
     parser.add_argument("--band", type=float, default=None, help="a brick corner this close to the threshold keeps its brick")
     parser.add_argument("--lipschitz", type=float, default=1.0, help="the default band is this times half the brick's diagonal")
     parser.add_argument("--brick-dilate", type=int, default=0, metavar="D", help="grow the set of kept bricks by D bricks (0..4)")
+    parser.add_argument("--simplify", type=float, nargs="?", const=2.0, default=0.0, metavar="K",
+                        help="vertex clustering in cells of K lattice steps (K = 2 when omitted)")
+    parser.add_argument("--simplify-placement", default="mean", choices=["mean", "quadric"],
+                        help="the merged vertex: the cell's mean, or the point closest to the planes of the triangles around it")
     parser.add_argument("--check-distance", type=float, nargs="?", const=0.0, default=None, metavar="BAND",
                         help="check the field against the exact distance to the extracted mesh within BAND of it (four lattice steps when omitted)")
     parser.add_argument("--check-volume", type=int, nargs="?", const=100000, default=None, metavar="N",
@@ -68,6 +77,11 @@ def main(argv=None) -> Path:
         clean = dict(min_component_triangles=args.min_component, keep_largest=args.keep_largest)
     if args.sparse:
         clean = dict(clean, brick=args.sparse, band=args.band, lipschitz=args.lipschitz, brick_dilate=args.brick_dilate)
+    if args.simplify < 0.0:
+        raise SystemExit("--simplify needs a positive number of lattice steps")
+    if args.simplify:
+        plain = dict(clean)
+        clean = dict(clean, simplify_cell=args.simplify * 2.0 * args.cube_range / max(args.resolution - 1, 1), simplify_placement=args.simplify_placement)
     if args.normals or args.colors:
         want_n = True if args.normals == "auto" else (args.normals or False)
         res = list(network.extract_mesh(args.field, args.threshold, args.cube_range, args.resolution, timings=times,
@@ -91,7 +105,19 @@ def main(argv=None) -> Path:
     if "clean" in times:
         print("components: %d found, %d kept, triangles removed: %d, clean-up: %.3f s"
               % (times["components"], times["components_kept"], times["triangles_removed"], times["clean"]))
+    if "simplify" in times:
+        print("simplified (%s, cells of %g lattice steps): %d -> %d vertices, %d -> %d triangles, %.3f s"
+              % (args.simplify_placement, args.simplify, times["vertices_before"], verts.shape[0], times["triangles_before"], tris.shape[0],
+                 times["simplify"]))
     print("wrote %s" % path)
+    if args.simplify and (args.check_distance is not None or args.check_volume is not None):
+        from neddf_amd.geometry import mesh_distance
+        full = network.extract_mesh(args.field, args.threshold, args.cube_range, args.resolution, **plain)
+        if tris.shape[0] and full[1].shape[0]:
+            d = mesh_distance((verts, tris), full, n=100000, to="surface", method="bvh")
+            print("simplified -> unsimplified surface: max %.6g, mean %.6g over %d samples" % (d["a_to_b_max"], d["a_to_b_mean"], d["n_a"]))
+        else:
+            print("simplified -> unsimplified surface: no triangles to measure")
     if args.check_distance is not None:
         if args.field == "density":
             raise SystemExit("--check-distance needs a distance or sdf field")
