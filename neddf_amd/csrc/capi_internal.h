@@ -1,10 +1,12 @@
-// capi_internal.h -- context layout shared by the C-ABI translation units
-// (neddf_capi.hip: inference path, train_capi.hip: training step).  Not installed.
+// capi_internal.h -- context layout and helpers shared by the C-ABI translation units (neddf_capi.hip: context, fields, render, surface
+// extraction, occupancy, tracing; geom_capi.hip: meshes and point geometry; train_capi.hip: training step; comm_capi.hip: multi-GPU).
+// Not installed.
 #pragma once
 #include "../../include/neddf_hip.h"
 #include "kernels.h"
 
 #include <stdlib.h>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -99,13 +101,18 @@ struct neddf_ctx {
     DevBuf mc_mask, mc_vbase, mc_blk;         // neddf_marching_cubes: crossed-edge byte and first vertex id per lattice point, block bases
     DevBuf mc_nacc;              // neddf_mesh_vertex_normals: 64-bit fixed-point sums [3 V] + the scale word
     DevBuf cc_parent, cc_used, cc_blk;        // neddf_mesh_components / neddf_mesh_compact: parent (or new index) and used byte per vertex,
-                                              // block totals followed by the "changed" words of one batch of rounds
+                                              // block totals followed by the "changed" words of one batch of rounds.  Borrowed by
+                                              // neddf_mesh_simplify_clusters (run starts [V + 1], head byte per vertex, the block totals of
+                                              // its two scans) and neddf_mesh_simplify_pairs (cc_blk alone)
     int cc_rounds = 0;           // union-find rounds of the last neddf_mesh_components call
     DevBuf occ_cells, occ_blk;   // neddf_occupancy_build: two byte planes of R^3 cells; block totals of build / gather
     DevBuf brick_flags, brick_blk;            // neddf_brick_select: two byte planes of one flag per brick, block totals
     DevBuf brick_mask, brick_vbase;           // neddf_marching_cubes_bricks: owned crossed edges and first vertex id per brick lattice point
     DevBuf trace_blk, trace_ws;  // sphere tracing: block totals of the compactions; neddf_trace_field's index / points / distances / constant inputs
-    DevBuf geom_blk, geom_ws;    // neddf_mesh_sample_* / neddf_nn_grid_build: block totals; the cell of every target and the count of every cell
+    DevBuf geom_blk, geom_ws;    // geom_capi.hip, one call at a time.  geom_blk: the block totals of neddf_mesh_sample_*, neddf_nn_grid_build and
+                                 // neddf_raycast_grid_count / _build.  geom_ws: the cell of every target and the count of every cell
+                                 // (neddf_nn_grid_build), the pairs of every list (neddf_raycast_grid_*), the per-triangle table
+                                 // [kPmTableFloats T] (neddf_point_mesh_grid_query / _bvh_query), parents and counters (neddf_bvh_build)
     int64_t cull_samples = 0, cull_kept = 0;  // neddf_cull_stats: samples classified / kept by the culled render passes
     std::vector<GuardBand> carve_guards;      // NEDDF_GUARD=1: the bands behind the carves of the last render call
     bool timing = false;
@@ -169,6 +176,17 @@ static inline int ensure(neddf_ctx *ctx, DevBuf &b, size_t bytes)
     return 0;
 }
 
+// The end of every count -> scan pass: the launches before are checked, the grand totals (8 bytes each, behind their block bases; at
+// most three) and an optional flag word come back on the stream, then ONE synchronise.
+struct TotalRead { int64_t *host; const int64_t *dev; };
+static inline int read_totals(neddf_ctx *ctx, hipStream_t s, std::initializer_list<TotalRead> totals, int *h_flag = nullptr, const int *d_flag = nullptr)
+{
+    HIPCHK(hipGetLastError());
+    for (const TotalRead &t : totals) HIPCHK(hipMemcpyAsync(t.host, t.dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (h_flag) HIPCHK(hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
 
 static inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
 

@@ -379,11 +379,12 @@ struct PmGrid {
 };
 void launch_point_mesh_brute(const float *q, int64_t nq, const float *v, int64_t V, const int32_t *tri, int64_t T, float *d2, int32_t *triangle, float *b1,
                              float *b2, hipStream_t s);
-// table [20 T] floats, 16-byte aligned (workspace): the per-triangle constants, written by a prepare launch in front of the query
+constexpr int kPmTableFloats = 20;       // floats per triangle of the table below (pointmesh_device.h: kPmVec float4)
+// table [kPmTableFloats T] floats, 16-byte aligned (workspace): the per-triangle constants, written by a prepare launch in front of the query
 void launch_point_mesh_grid_query(const PmGrid &g, const float *q, int64_t nq, const float *v, int64_t V, const int32_t *tri, int64_t T, float *table,
                                   const int32_t *cell_start, const int32_t *items, int64_t n_items, float *d2, int32_t *triangle, float *b1, float *b2,
                                   hipStream_t s);
-// the table alone: [20 T] floats, 16-byte aligned (nothing is launched for T <= 0)
+// the table alone: [kPmTableFloats T] floats, 16-byte aligned (nothing is launched for T <= 0)
 void launch_point_mesh_prepare(const float *v, int64_t V, const int32_t *tri, int64_t T, float *table, hipStream_t s);
 
 // A linear BVH over the triangles and the point-to-mesh query through it (bvh_kernels.hip; include/neddf_hip.h states the arrays).
@@ -392,7 +393,7 @@ void launch_bvh_keys(const NnGrid &g, const float *v, int64_t V, const int32_t *
 // keys sorted ascending -> leaf_tri [T], children [T - 1][2], boxes [2 T - 1][6]; parent [2 T - 1] and counter [T - 1] are workspace
 void launch_bvh_build(const int64_t *keys, const float *v, int64_t V, const int32_t *tri, int64_t T, int32_t *leaf_tri, int32_t *children, float *boxes,
                       int32_t *parent, int32_t *counter, hipStream_t s);
-// table [20 T] floats (workspace, written by a prepare launch in front of the query); visits [nq] or NULL
+// table [kPmTableFloats T] floats (workspace, written by a prepare launch in front of the query); visits [nq] or NULL
 void launch_point_mesh_bvh_query(const float *q, int64_t nq, const float *v, int64_t V, const int32_t *tri, int64_t T, float *table, const int32_t *leaf_tri,
                                  const int32_t *children, const float *boxes, float *d2, int32_t *triangle, float *b1, float *b2, int32_t *visits,
                                  hipStream_t s);

@@ -7,6 +7,7 @@ namespace neddf {
 
 constexpr int kPmThreads = 256;          // queries per workgroup and triangles per LDS tile
 constexpr int kPmVec = 5;                // float4 per triangle
+static_assert(kPmTableFloats == 4 * kPmVec, "the table the C ABI sizes (kernels.h) is the one these kernels index");
 
 struct PmBest {
     float d2;

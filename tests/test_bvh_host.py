@@ -64,11 +64,12 @@ def test_null_and_negative_count_refusals():
     assert lib.neddf_bvh_keys(None, None, 0, None, 5, None, None, None, None) == -1
     assert lib.neddf_bvh_build(None, None, 3, None, -2, None, None, None, None, None) == -1
     assert lib.neddf_point_mesh_bvh_query(None, None, -1, None, 0, None, 4, None, None, None, 3, None, None, None, None, None, None) == -1
-    # the refusals themselves are in the source next to the point-mesh block's, by the same helper
-    capi = open(os.path.join(ROOT, "neddf_amd", "csrc", "neddf_capi.hip")).read()
+    # the refusals themselves are in the source next to the point-mesh block's, by the same mesh check (tests/test_gpu_capi_refusals.py
+    # holds every one of them to its code and text on the device)
+    capi = open(os.path.join(ROOT, "neddf_amd", "csrc", "geom_capi.hip")).read()
     for name in ("bvh_keys", "bvh_build", "point_mesh_bvh_query"):
-        assert 'rc_counts_ok(ctx, ' in capi and '"%s")' % name in capi, name
-    assert "n_leaves != n_triangles" in capi
+        assert 'mesh_counts_ok(ctx, n_vertices, d_vertices, n_triangles, d_triangles, "%s"' % name in capi, name
+    assert 'if (n_leaves != n_triangles) return fail(ctx, NEDDF_EINVAL, "point_mesh_bvh_query: ' in capi
 
 
 def test_python_layer_exports_and_refusals_without_a_device():
