@@ -816,7 +816,7 @@ int neddf_point_mesh_grid_query(neddf_ctx *ctx, const float *d_queries, int64_t 
  *     function clamps -- the bounds of the valid triangles' vertices the best one); code = the 30-bit Morton code of (cx, cy, cz), bit
  *     3 b + a of the code = bit b of the cell along axis a; key = code << 32 | j.  An invalid one: key = 2^62 | j -- it sorts behind
  *     every valid triangle and stays in the tree (which therefore always has T leaves) with an EMPTY box, which is never entered.
- * neddf_bvh_build, from the keys sorted ascending -- THE TREE, for this and any later traversal (ray casting through it is not built):
+ * neddf_bvh_build, from the keys sorted ascending -- THE TREE, for both traversals (points here, rays in neddf_raycast_bvh_query below):
  *     d_leaf_triangle int32 [T]      the triangle of leaf k: the low 32 bits of sorted key k (Morton order)
  *     d_children int32 [T - 1][2]    left and right child of internal node i (NULL allowed for T <= 1); c >= 0 is internal node c, c < 0
  *                                    is leaf ~c.  Node 0 is the root; T == 1 has no internal node, the root is leaf 0.  Node i covers a
@@ -864,6 +864,71 @@ int neddf_point_mesh_bvh_query(neddf_ctx *ctx, const float *d_queries, int64_t n
                                const int32_t *d_triangles, int64_t n_triangles, const int32_t *d_leaf_triangle, const int32_t *d_children,
                                const float *d_boxes, int64_t n_leaves, float *d_d2, int32_t *d_triangle, float *d_b1, float *d_b2, int32_t *d_visits,
                                void *stream);
+
+/* ---- rays through the BVH: first hit and any hit (additive to ABI v7; no reference counterpart) ------
+ * neddf_raycast_brute's bits with the same pad, for ANY rays and any pad >= 0, through the tree of neddf_bvh_build: one accelerator for
+ * the distance queries above and for ray casts.  The per-pair arithmetic (the hit definition of the ray-casting block) and the tie rule
+ * are unchanged; only the set of visited triangles differs.  n_leaves must equal n_triangles.  One lane per ray, depth first, the tree
+ * arrays validated and the walk bounded by 2 T nodes exactly as in neddf_point_mesh_bvh_query.
+ *
+ * THE BOX TEST, all fp64, every operation ONE rounded fp64 operation.  Per ray: rcp_a = 1 / (double)d_a for every axis with d_a != 0.
+ * Per box row (lo, hi) and axis a:
+ *     wl_a = (double)lo_a - 2 (double)pad,  wh_a = (double)hi_a + 2 (double)pad      (2 (double)pad is exact)
+ *     ta = (wl_a - o_a) * rcp_a,  tb = (wh_a - o_a) * rcp_a
+ *     an axis with d_a == 0 contributes no ta, tb; it EMPTIES the interval when o_a < wl_a or o_a > wh_a
+ *     te = max(t_min, max_a min(ta, tb)),  tx = min(t_max, min_a max(ta, tb))        (max / min that ignore a NaN operand: fmax, fmin)
+ * The box is SKIPPED when it is empty (lo.x > hi.x), when the interval is empty, !(te <= tx), or when te > (double)best t strictly.
+ * Of two children that are not skipped, the one with the smaller te is entered first, the left one on a tie; the other waits on the
+ * stack and is tested again, against the best of that moment, when it is popped.  A leaf that is entered is evaluated with its
+ * ORIGINAL triangle index (an invalid triangle has an empty box and is never evaluated).
+ *
+ * NO WALK.  With W = the largest |coordinate| of the root box (row 0, fp32, read on the device), a ray visits every valid triangle in
+ * index order -- the brute kernel's set -- instead of walking the tree when (fp64, one rounded operation each)
+ *     pad < 2^-16 W,  or  pad < 2^-126 (zero or subnormal),  or  max_a |o_a| > 2^21 pad - 2 (W + 2 pad).
+ * The first and the last are the grid's two conditions (what neddf_raycast_grid_* refuses or routes past its cells); here both are
+ * decided per ray on the device, so every pad >= 0 gives the right answer.  An all-invalid mesh has W = +inf: no walk, no visit.
+ *
+ * neddf_raycast_bvh_query: d_t, d_triangle, d_b1, d_b2 as neddf_raycast_brute writes them; a ray with a non-finite component or an
+ * all-zero direction gets (NaN, -1, NaN, NaN).  neddf_raycast_bvh_occluded: the ANY-HIT mode of the same kernel -- the ray stops at
+ * its first candidate (in the walk and in the every-triangle route alike); d_occluded uint8 [R] = 1 when there is one, which is
+ * exactly `d_triangle >= 0` of neddf_raycast_brute, 0 otherwise and for an invalid ray.  d_visits int32 [R] (NULL allowed): the leaves
+ * evaluated -- the valid triangles evaluated on the every-triangle route (all of them for the first hit), 0 for an invalid ray;
+ * tests/bvh_raycast_check.py restates the traversal in numpy and reproduces the count exactly.  R == 0 and T == 0 are legal;
+ * d_children may be NULL for T <= 1.  Before the first HIP call: NEDDF_EINVAL for a NULL context, a negative count, a NULL array that is
+ * needed, n_leaves != n_triangles, a pad that is negative or not finite; NEDDF_EUNSUPPORTED from 2^31 rays, triangles or vertices on.
+ *
+ * THE EQUALITY ARGUMENT.  Let a ray walk the tree, and let a valid triangle be a candidate of the brute kernel with computed parameter
+ * t (fp32, finite: an infinite t fails the box clause) and rounded hit point p.  W holds every coordinate of every valid triangle.
+ *   (1) The box clause: p lies within pad of the triangle's box B on every axis, up to the rounding of the bounds min3 - pad and
+ *       max3 + pad, at most 2^-24 (W + pad) <= (2^-8 + 2^-24) pad since W <= 2^16 pad.  So |p_a| <= W + 1.01 pad.
+ *   (2) The exact point p* = o + t d at the COMPUTED t lies within eps_p of p per axis: the rounding of the product (2^-24 |t d_a| <=
+ *       2^-24 (|p_a| (1 + 2^-23) + |o_a|)) and of the sum (2^-24 |p_a|), so eps_p <= 2^-24 (|o_a| + 2.01 |p_a|), plus at most 2^-149 where the
+ *       product underflows.  With |o_a| <= 2^21 pad - 2 W - 4 pad: eps_p <= 2^-24 (2^21 pad + 0.01 W) + 2^-149 <= pad / 8 + 2^-14 pad
+ *       (pad >= 2^-126 puts the underflow term below 2^-23 pad).
+ *   (3) Node boxes are exact min / max of vertex coordinates, so B lies inside the box of every ancestor, the leaf's own included.
+ *       wl and wh carry one fp64 rounding each, below 2^-52 (W + 2 pad) <= 2^-35 pad.  Hence on every axis
+ *       wl_a + 0.86 pad < p*_a < wh_a - 0.86 pad  (2 - 1 - 2^-8 - 1/8 - 2^-14 - 2^-35 > 0.86): the exact point lies inside every
+ *       ancestor's widened box with more than 0.8 pad to spare.
+ *   (4) An axis with d_a == 0 has p*_a = o_a, inside [wl_a, wh_a]: it does not empty the interval.  On an axis with d_a != 0, t lies
+ *       between the exact (wl_a - o_a) / d_a and (wh_a - o_a) / d_a and is more than 0.8 pad / |d_a| away from both.  The computed ta and tb
+ *       carry three fp64 roundings (the difference, the reciprocal, the product): below 2^-51 |wl_a - o_a| / |d_a| <= 2^-51 2^21 pad / |d_a|
+ *       = 2^-30 pad / |d_a| -- smaller by eight orders of magnitude.  And t_min <= t <= t_max by the candidate's own range clause, exactly
+ *       (a float converts to double without rounding).
+ *   (5) Hence (double)t lies inside the computed [te, tx] of every ancestor: no ancestor is skipped for an empty interval, and one that
+ *       is skipped with te > best t has t >= te > best t strictly -- the candidate neither ties nor wins.
+ *   (6) best t only decreases, so a box skipped once would be skipped later too, and a child dropped when its parent was handled would
+ *       have been dropped when popped.  Visiting more triangles, in any order, never changes the result (the tie rule).
+ * Hence the walk returns the brute kernel's bits; a ray that does not walk visits the brute kernel's set.  In the any-hit mode best t
+ * stays +inf until the ray stops, so no box that holds a candidate is skipped: the flag is 1 exactly when the brute kernel has a
+ * candidate at all, that is, when it reports a triangle. */
+int neddf_raycast_bvh_query(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_vertices, int64_t n_vertices,
+                            const int32_t *d_triangles, int64_t n_triangles, const int32_t *d_leaf_triangle, const int32_t *d_children,
+                            const float *d_boxes, int64_t n_leaves, float t_min, float t_max, float pad, float *d_t, int32_t *d_triangle, float *d_b1,
+                            float *d_b2, int32_t *d_visits, void *stream);
+int neddf_raycast_bvh_occluded(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_vertices,
+                               int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles, const int32_t *d_leaf_triangle,
+                               const int32_t *d_children, const float *d_boxes, int64_t n_leaves, float t_min, float t_max, float pad,
+                               uint8_t *d_occluded, int32_t *d_visits, void *stream);
 
 /* ---- mesh simplification by vertex clustering (additive to ABI v7; no reference counterpart: its users decimated in Open3D) ------
  * Opt-in: a grid of cells is laid over the mesh, the vertices of a cell become one vertex, the triangles that collapse go.  Integer

@@ -174,6 +174,10 @@ SYMBOLS = [
     ("neddf_bvh_keys", C.c_int, [_vp, _vp, _i64, _vp, _i64, _dp, _dp, _vp, _vp]),
     ("neddf_bvh_build", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("neddf_point_mesh_bvh_query", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_raycast_bvh_query", C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, C.c_float, C.c_float, C.c_float,
+                                          _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("neddf_raycast_bvh_occluded", C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, C.c_float, C.c_float, C.c_float,
+                                             _vp, _vp, _vp]),
     ("neddf_mesh_simplify_keys", C.c_int, [_vp, _vp, _i64, _dp, _dp, C.POINTER(C.c_int), _vp, _vp]),
     ("neddf_mesh_simplify_clusters", C.c_int, [_vp, _vp, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
     ("neddf_mesh_simplify_pairs", C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(_i64), _vp]),
@@ -707,6 +711,31 @@ class Context:
                                                        leaf_triangle.shape[0], _ptr(d2), _ptr(j), _ptr(b1), _ptr(b2),
                                                        _ptr(visits) if return_visits else None, self.stream()))
         return (d2, j, b1, b2, visits) if return_visits else (d2, j, b1, b2)
+
+    def _raycast_bvh_args(self, origins, dirs, vertices, triangles, leaf_triangle, children, boxes, t_min, t_max, pad):
+        return (self.h, _ptr(origins), _ptr(dirs), origins.shape[0], _ptr(vertices), vertices.shape[0], _ptr(triangles), triangles.shape[0],
+                _ptr(leaf_triangle) if leaf_triangle.numel() else None, _ptr(children) if children.numel() else None,
+                _ptr(boxes) if boxes.numel() else None, leaf_triangle.shape[0], float(t_min), float(t_max), float(pad))
+
+    def raycast_bvh_query(self, origins, dirs, vertices, triangles, leaf_triangle, children, boxes, t_min, t_max, pad, return_visits=False):
+        """The first hit of every ray through the BVH (neddf_raycast_bvh_query): raycast_brute's result, bit for bit; with return_visits
+        a fifth tensor, the leaves evaluated per ray (int32 [R])."""
+        t, j, b1, b2 = self._hit_buffers(origins.shape[0], origins.device)
+        visits = torch.empty(origins.shape[0], device=origins.device, dtype=torch.int32) if return_visits else None
+        self.check(self.lib.neddf_raycast_bvh_query(*self._raycast_bvh_args(origins, dirs, vertices, triangles, leaf_triangle, children, boxes,
+                                                                            t_min, t_max, pad),
+                                                    _ptr(t), _ptr(j), _ptr(b1), _ptr(b2), _ptr(visits) if return_visits else None, self.stream()))
+        return (t, j, b1, b2, visits) if return_visits else (t, j, b1, b2)
+
+    def raycast_bvh_occluded(self, origins, dirs, vertices, triangles, leaf_triangle, children, boxes, t_min, t_max, pad, return_visits=False):
+        """Whether every ray meets the mesh at all, through the BVH (neddf_raycast_bvh_occluded): uint8 [R], 1 where raycast_brute reports
+        a triangle; with return_visits a second tensor, the leaves evaluated per ray (int32 [R])."""
+        occ = torch.empty(origins.shape[0], device=origins.device, dtype=torch.uint8)
+        visits = torch.empty(origins.shape[0], device=origins.device, dtype=torch.int32) if return_visits else None
+        self.check(self.lib.neddf_raycast_bvh_occluded(*self._raycast_bvh_args(origins, dirs, vertices, triangles, leaf_triangle, children, boxes,
+                                                                               t_min, t_max, pad),
+                                                       _ptr(occ), _ptr(visits) if return_visits else None, self.stream()))
+        return (occ, visits) if return_visits else occ
 
     # ------------------------------------------------------------------ mesh simplification (mesh.simplify_mesh orders the steps)
     def mesh_simplify_keys(self, vertices, lo, hi, cells):

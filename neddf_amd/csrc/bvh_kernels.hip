@@ -7,6 +7,7 @@
 //   bvh_topology_kernel   one lane per internal node: Karras' construction over the sorted keys -- integers only
 //   bvh_fit_kernel        one lane per leaf: its box, then upwards; the second arriver at a node combines both children
 //   pm_bvh_kernel         one lane per query: depth-first, the nearer child first, a box skipped by the pruning rule below
+//   rc_bvh_kernel         one lane per ray: the same walk with the ray's slab test; first hit, or (any-hit) the first candidate
 //
 // INVALID TRIANGLES (an index outside [0, V) or a non-finite vertex: pm_constants' rule) stay in the tree, so that it always has T
 // leaves and its sizes can be checked against the mesh: their key has bit 62 set and sorts behind every valid one, their box is EMPTY
@@ -41,8 +42,15 @@
 // THE STACK holds at most depth + 1 <= 63 entries.  It lives in LDS as [level][lane] -- the lanes of a wave read one row, 64 distinct
 // banks -- 64 levels x 64 lanes x 4 B = 16 KB per one-wave workgroup, ten workgroups per CU.  No dynamically indexed private array: the
 // kernel's private segment size in the gfx950 code object's metadata is 0 bytes (.private_segment_fixed_size: 0, no scratch).
+//
+// RAYS (rc_bvh_kernel<any-hit>) walk the same arrays in the same shape -- one lane per ray, one wave per workgroup, the same LDS stack, the
+// same validation and the same 2 T bound -- with another pruning rule: an fp64 slab test of the ray against the box widened by 2 pad
+// (rb_skip; include/neddf_hip.h, neddf_raycast_bvh_query, states it and why the result has neddf_raycast_brute's bits).  The per-pair
+// arithmetic is raycast_device.h's, the one the brute and grid kernels use.  A ray for which the argument does not hold (a pad that is
+// small against the root box, an origin that is far away against pad) visits every triangle in index order instead.
 #include "kernels.h"
 #include "pointmesh_device.h"
+#include "raycast_device.h"
 
 namespace neddf {
 
@@ -257,6 +265,138 @@ __global__ void __launch_bounds__(kBvhThreads) pm_bvh_kernel(const float *q, int
     }
     pm_store(true, best, i, out_d2, out_j, out_b1, out_b2);
     if (out_visits) out_visits[i] = visits;
+}
+
+// ---- rays through the same tree (include/neddf_hip.h: neddf_raycast_bvh_query states the rule and the equality argument) ----
+struct RbRay {                      // what the box test needs of a ray, all fp64: origin, 1 / d per axis (unused where d == 0), [t_min, t_max]
+    double ox, oy, oz, rx, ry, rz;
+    bool zx, zy, zz;                // d_a == 0
+    double t0, t1;
+};
+
+// one axis of the slab test against the bounds widened by 2 pad: every operation one rounded fp64 operation
+__device__ __forceinline__ void rb_axis(float lo, float hi, double pad2, double o, double rcp, bool zero, double *te, double *tx, bool *out)
+{
+    const double wl = __dsub_rn((double)lo, pad2), wh = __dadd_rn((double)hi, pad2);
+    if (zero) {
+        *out = *out || o < wl || o > wh;
+    } else {
+        const double ta = __dmul_rn(__dsub_rn(wl, o), rcp), tb = __dmul_rn(__dsub_rn(wh, o), rcp);
+        *te = fmax(*te, fmin(ta, tb));
+        *tx = fmin(*tx, fmax(ta, tb));
+    }
+}
+
+// the pruning rule of the ray traversal: true when box `row` need not be entered; *key = te, what orders two children
+__device__ __forceinline__ bool rb_skip(const float *boxes, int64_t row, const RbRay &q, double pad2, float best_t, double *key)
+{
+    const float *b = boxes + 6 * row;
+    const float lx = b[0], ly = b[1], lz = b[2], hx = b[3], hy = b[4], hz = b[5];
+    double te = q.t0, tx = q.t1;
+    bool out = false;
+    rb_axis(lx, hx, pad2, q.ox, q.rx, q.zx, &te, &tx, &out);
+    rb_axis(ly, hy, pad2, q.oy, q.ry, q.zy, &te, &tx, &out);
+    rb_axis(lz, hz, pad2, q.oz, q.rz, q.zz, &te, &tx, &out);
+    *key = te;
+    return lx > hx || out || !(te <= tx) || te > (double)best_t;
+}
+
+// kAny == false: the first hit (out_t, out_j, out_b1, out_b2).  kAny == true: the ray stops at its first candidate, out_occ = 1 with one.
+template <bool kAny>
+__global__ void __launch_bounds__(kBvhThreads) rc_bvh_kernel(const float *ro, const float *rd, int64_t nr, const float *v, int64_t V, const int32_t *tri,
+                                                             int64_t T, const int32_t *leaf_tri, const int32_t *children, const float *boxes,
+                                                             float t_min, float t_max, float pad, float *out_t, int32_t *out_j, float *out_b1,
+                                                             float *out_b2, uint8_t *out_occ, int32_t *out_visits)
+{
+    __shared__ int32_t stack[kBvhStack][kBvhThreads];           // 16 KB, [level][lane]
+    const int lane = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * kBvhThreads + lane;
+    if (i >= nr) return;
+    RcRay r;
+    RcHit best{ __builtin_inff(), -1, 0.f, 0.f };
+    const bool ok = rc_ray_setup(ro[3 * i], ro[3 * i + 1], ro[3 * i + 2], rd[3 * i], rd[3 * i + 1], rd[3 * i + 2], &r);
+    int32_t visits = 0;
+    if (ok && T > 0) {
+        float w = 0.f;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) w = fmaxf(w, fabsf(boxes[a]));              // the root box is row 0 (inf when it is empty: no walk)
+        const double pd = (double)pad, wd = (double)w;
+        const double far = __dsub_rn(__dmul_rn(0x1p21, pd), __dmul_rn(2.0, __dadd_rn(wd, __dmul_rn(2.0, pd))));
+        const double omax = (double)fmaxf(fmaxf(fabsf(r.ox), fabsf(r.oy)), fabsf(r.oz));
+        const bool walk = pad >= 0x1p-126f && pd >= __dmul_rn(0x1p-16, wd) && omax <= far;
+        if (!walk) {
+            // the rounding of o + t d is not small against pad (or pad against the boxes' rounding): every triangle, as the brute kernel
+            for (int64_t j = 0; j < T; ++j) {
+                float p[9];
+                if (!rc_triangle(v, V, tri, j, p)) continue;
+                rc_visit(r, t_min, t_max, pad, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], (int32_t)j, &best);
+                ++visits;
+                if (kAny && best.j >= 0) break;
+            }
+        } else {
+            RbRay q;
+            q.ox = (double)r.ox; q.oy = (double)r.oy; q.oz = (double)r.oz;
+            q.zx = r.dx == 0.f; q.zy = r.dy == 0.f; q.zz = r.dz == 0.f;
+            q.rx = q.zx ? 0.0 : __ddiv_rn(1.0, (double)r.dx);
+            q.ry = q.zy ? 0.0 : __ddiv_rn(1.0, (double)r.dy);
+            q.rz = q.zz ? 0.0 : __ddiv_rn(1.0, (double)r.dz);
+            q.t0 = (double)t_min; q.t1 = (double)t_max;
+            const double pad2 = __dmul_rn(2.0, pd);
+            int32_t cur = T == 1 ? ~0 : 0;
+            double key;
+            bool have = !rb_skip(boxes, 0, q, pad2, best.t, &key);
+            int sp = 0;
+            for (int64_t step = 0; step < 2 * T; ++step) {
+                if (!have) {
+                    if (sp == 0) break;
+                    cur = stack[--sp][lane];
+                    if (rb_skip(boxes, bvh_row(cur, T), q, pad2, best.t, &key)) continue;          // (pushed entries were validated)
+                }
+                have = false;
+                if (cur < 0) {
+                    const int32_t j = leaf_tri[~cur];
+                    float p[9];
+                    if (j >= 0 && j < T && rc_triangle(v, V, tri, j, p)) {
+                        rc_visit(r, t_min, t_max, pad, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], j, &best);
+                        ++visits;
+                        if (kAny && best.j >= 0) break;
+                    }
+                    continue;
+                }
+                const int32_t c0 = children[2 * (int64_t)cur], c1 = children[2 * (int64_t)cur + 1];
+                const int64_t r0 = bvh_row(c0, T), r1 = bvh_row(c1, T);
+                double k0 = 0.0, k1 = 0.0;
+                const bool go0 = r0 >= 0 && !rb_skip(boxes, r0, q, pad2, best.t, &k0);
+                const bool go1 = r1 >= 0 && !rb_skip(boxes, r1, q, pad2, best.t, &k1);
+                if (go0 && go1) {
+                    const bool swap = k1 < k0;                       // the left child first on a tie
+                    if (sp < kBvhStack) stack[sp++][lane] = swap ? c0 : c1;
+                    cur = swap ? c1 : c0;
+                    have = true;
+                } else if (go0 || go1) {
+                    cur = go0 ? c0 : c1;
+                    have = true;
+                }
+            }
+        }
+    }
+    if (kAny) out_occ[i] = ok && best.j >= 0 ? 1 : 0;
+    else rc_store(ok, best, i, out_t, out_j, out_b1, out_b2);
+    if (out_visits) out_visits[i] = visits;
+}
+
+void launch_raycast_bvh(bool any_hit, const float *ro, const float *rd, int64_t nr, const float *v, int64_t V, const int32_t *tri, int64_t T,
+                        const int32_t *leaf_tri, const int32_t *children, const float *boxes, float t_min, float t_max, float pad, float *t,
+                        int32_t *triangle, float *b1, float *b2, uint8_t *occluded, int32_t *visits, hipStream_t s)
+{
+    if (nr <= 0) return;
+    const dim3 grid((unsigned)((nr + kBvhThreads - 1) / kBvhThreads));
+    if (any_hit)
+        hipLaunchKernelGGL(rc_bvh_kernel<true>, grid, dim3(kBvhThreads), 0, s, ro, rd, nr, v, V, tri, T, leaf_tri, children, boxes, t_min, t_max, pad, t,
+                           triangle, b1, b2, occluded, visits);
+    else
+        hipLaunchKernelGGL(rc_bvh_kernel<false>, grid, dim3(kBvhThreads), 0, s, ro, rd, nr, v, V, tri, T, leaf_tri, children, boxes, t_min, t_max, pad, t,
+                           triangle, b1, b2, occluded, visits);
 }
 
 void launch_bvh_keys(const NnGrid &g, const float *v, int64_t V, const int32_t *tri, int64_t T, int64_t *keys, hipStream_t s)

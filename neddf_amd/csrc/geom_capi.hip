@@ -1,6 +1,6 @@
 // geom_capi.hip -- C ABI of the mesh and point-geometry entry points (include/neddf_hip.h): vertex normals, connected components and
-// compaction, surface sampling, nearest neighbours, ray casting, point-to-mesh distance through the grid and the BVH, the BVH build and
-// mesh simplification.  What belongs here takes no field slot and never touches a Field, the render arena, stage timing or occupancy
+// compaction, surface sampling, nearest neighbours, ray casting, point-to-mesh distance through the grid and the BVH, the BVH build, rays
+// through the BVH and mesh simplification.  What belongs here takes no field slot and never touches a Field, the render arena, stage timing or occupancy
 // state: argument checks, workspaces of the context and launches on the caller's stream.
 #include "capi_internal.h"
 
@@ -458,6 +458,52 @@ int neddf_point_mesh_bvh_query(neddf_ctx *ctx, const float *d_queries, int64_t n
         if (int rc = ensure(ctx, ctx->geom_ws, (size_t)n_triangles * kPmTableFloats * sizeof(float))) return rc;
     launch_point_mesh_bvh_query(d_queries, n_queries, d_vertices, n_vertices, d_triangles, n_triangles, (float *)ctx->geom_ws.p, d_leaf_triangle, d_children,
                                 d_boxes, d_d2, d_triangle, d_b1, d_b2, d_visits, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- rays through the BVH (bvh_kernels.hip): the first hit and the any-hit flag share every check but the outputs' ----
+static int raycast_bvh_args_ok(neddf_ctx *ctx, const char *what, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_vertices,
+                               int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles, const int32_t *d_leaf_triangle,
+                               const int32_t *d_children, const float *d_boxes, int64_t n_leaves, float pad)
+{
+    if (int rc = mesh_counts_ok(ctx, n_vertices, d_vertices, n_triangles, d_triangles, what, n_rays, d_ray_orig && d_ray_dir)) return rc;
+    if (n_leaves != n_triangles) return fail(ctx, NEDDF_EINVAL, std::string(what) + ": the tree's leaves are not this mesh's triangles (n_leaves != n_triangles)");
+    if (n_triangles > 0 && (!d_leaf_triangle || !d_boxes || (n_triangles > 1 && !d_children)))
+        return fail(ctx, NEDDF_EINVAL, std::string(what) + ": NULL leaf_triangle, children or boxes");
+    return pad_ok(ctx, pad, what);
+}
+
+int neddf_raycast_bvh_query(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_vertices, int64_t n_vertices,
+                            const int32_t *d_triangles, int64_t n_triangles, const int32_t *d_leaf_triangle, const int32_t *d_children,
+                            const float *d_boxes, int64_t n_leaves, float t_min, float t_max, float pad, float *d_t, int32_t *d_triangle, float *d_b1,
+                            float *d_b2, int32_t *d_visits, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = raycast_bvh_args_ok(ctx, "raycast_bvh_query", d_ray_orig, d_ray_dir, n_rays, d_vertices, n_vertices, d_triangles, n_triangles,
+                                     d_leaf_triangle, d_children, d_boxes, n_leaves, pad))
+        return rc;
+    if (!outputs_ok(n_rays, d_t, d_triangle, d_b1, d_b2)) return fail(ctx, NEDDF_EINVAL, "raycast_bvh_query: NULL outputs");
+    DeviceGuard guard_(ctx->device);
+    launch_raycast_bvh(false, d_ray_orig, d_ray_dir, n_rays, d_vertices, n_vertices, d_triangles, n_triangles, d_leaf_triangle, d_children, d_boxes, t_min,
+                       t_max, pad, d_t, d_triangle, d_b1, d_b2, nullptr, d_visits, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int neddf_raycast_bvh_occluded(neddf_ctx *ctx, const float *d_ray_orig, const float *d_ray_dir, int64_t n_rays, const float *d_vertices,
+                               int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles, const int32_t *d_leaf_triangle,
+                               const int32_t *d_children, const float *d_boxes, int64_t n_leaves, float t_min, float t_max, float pad,
+                               uint8_t *d_occluded, int32_t *d_visits, void *stream)
+{
+    if (!ctx) return NEDDF_EINVAL;
+    if (int rc = raycast_bvh_args_ok(ctx, "raycast_bvh_occluded", d_ray_orig, d_ray_dir, n_rays, d_vertices, n_vertices, d_triangles, n_triangles,
+                                     d_leaf_triangle, d_children, d_boxes, n_leaves, pad))
+        return rc;
+    if (n_rays > 0 && !d_occluded) return fail(ctx, NEDDF_EINVAL, "raycast_bvh_occluded: NULL outputs");
+    DeviceGuard guard_(ctx->device);
+    launch_raycast_bvh(true, d_ray_orig, d_ray_dir, n_rays, d_vertices, n_vertices, d_triangles, n_triangles, d_leaf_triangle, d_children, d_boxes, t_min,
+                       t_max, pad, nullptr, nullptr, nullptr, nullptr, d_occluded, d_visits, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

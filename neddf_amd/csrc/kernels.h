@@ -397,6 +397,10 @@ void launch_bvh_build(const int64_t *keys, const float *v, int64_t V, const int3
 void launch_point_mesh_bvh_query(const float *q, int64_t nq, const float *v, int64_t V, const int32_t *tri, int64_t T, float *table, const int32_t *leaf_tri,
                                  const int32_t *children, const float *boxes, float *d2, int32_t *triangle, float *b1, float *b2, int32_t *visits,
                                  hipStream_t s);
+// rays through the tree: the first hit (t, triangle, b1, b2), or with any_hit the flag `occluded` [nr] alone; visits [nr] or NULL
+void launch_raycast_bvh(bool any_hit, const float *ro, const float *rd, int64_t nr, const float *v, int64_t V, const int32_t *tri, int64_t T,
+                        const int32_t *leaf_tri, const int32_t *children, const float *boxes, float t_min, float t_max, float pad, float *t,
+                        int32_t *triangle, float *b1, float *b2, uint8_t *occluded, int32_t *visits, hipStream_t s);
 
 // Mesh simplification by vertex clustering (simplify_kernels.hip; include/neddf_hip.h states the contract).
 // keys int64 [V]: cell of g (neddf_nn_grid_build's cell function) << 32 | vertex index; 2^62 | index for a non-finite vertex

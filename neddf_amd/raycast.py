@@ -5,6 +5,7 @@ What extract_mesh writes can be looked at from the dataset's cameras (NeRFRender
 next to the sphere-traced view of the same level set.  The hit is the watertight test of Woop, Benthin and Wald (JCGT 2013) with exactly
 specified fp32 arithmetic (include/neddf_hip.h neddf_raycast_brute; tests/raycast_check.py restates it in numpy bit for bit), and the
 grid returns the brute kernel's bits (neddf_raycast_grid_count / _build / _query).  Both are HIP kernels; this module is plumbing.
+A third route with the same bits, through the mesh's BVH, lives in neddf_amd.bvh (cast_rays, occluded, ambient_occlusion).
 """
 import math
 
@@ -125,7 +126,7 @@ def cast_rays(origins, dirs, vertices, triangles, t_min=0.0, t_max=float("inf"),
     if o.device != v.device or d.device != v.device:
         raise NeddfError("cast_rays: rays and mesh must live on one device (got %s, %s, %s)" % (o.device, d.device, v.device))
     if method not in ("grid", "brute"):
-        raise NeddfError("cast_rays: method must be 'grid' or 'brute' (got %r)" % (method,))
+        raise NeddfError("cast_rays: method must be 'grid' or 'brute' (got %r); rays through a MeshBVH are cast by neddf_amd.bvh.cast_rays" % (method,))
     if grid is not None:
         if not isinstance(grid, MeshGrid) or grid.n_vertices != v.shape[0] or grid.n_triangles != t.shape[0] or grid.cell_start.device != v.device:
             raise NeddfError("cast_rays: grid must be the MeshGrid build_grid made of this mesh")

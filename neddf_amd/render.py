@@ -516,11 +516,21 @@ class NeRFRender(BaseNeuralRender):
                 out = {k: v.reshape(h, w, 3) if v.dim() == 2 else v.reshape(h, w) for k, v in out.items()}
         return {k: out[k] for k in target_types}
 
-    MESH_TARGETS = ("depth", "transmittance", "triangle", "normal", "color")
+    MESH_TARGETS = ("depth", "transmittance", "triangle", "normal", "color", "ambient_occlusion")
+    MESH_TILE = 8
+
+    @staticmethod
+    def tile_order(w: int, h: int, tile: int, device) -> Tensor:
+        """int64 [w * h]: the row-major pixel indices ordered by tile x tile pixel tiles (tiles row-major, pixels row-major inside a
+        tile; partial tiles at the right and bottom edges) -- 64 consecutive entries are one 8 x 8 tile where the tile is whole."""
+        v, u = torch.meshgrid(torch.arange(h, device=device), torch.arange(w, device=device), indexing="ij")
+        key = (((v // tile) * ((w + tile - 1) // tile) + u // tile) * tile + v % tile) * tile + u % tile
+        return torch.argsort(key.reshape(-1))
 
     def render_image_mesh(self, width: int, height: int, camera: Camera, vertices: Tensor, triangles: Tensor,
                           target_types: Iterable[RenderTarget], normals: Optional[Tensor] = None, colors: Optional[Tensor] = None,
-                          downsampling: int = 1, pixel_range=None, method: str = "grid", background: float = 0.0, grid=None) -> Dict[str, Tensor]:
+                          downsampling: int = 1, pixel_range=None, method: str = "grid", background: float = 0.0, grid=None, bvh=None,
+                          tile: int = 0, ao_dirs: int = 16, ao_radius: Optional[float] = None) -> Dict[str, Tensor]:
         """A view of a triangle mesh (vertices float32 [V, 3], triangles int32 or int64 [T, 3] on the camera's device; not a
         reference method): render_image_traced's world-space rays -- the same pixels -- meet the mesh between dist_near and
         dist_far inside the library (raycast.cast_rays: the first watertight hit, method "grid" or "brute", the same bits).
@@ -532,12 +542,28 @@ class NeRFRender(BaseNeuralRender):
             normal         the vertex `normals` [V, 3] interpolated at the hit when given, otherwise the face's geometric normal;
                            normalised, turned to face the ray, 0 elsewhere
             color          the vertex `colors` [V, 3] interpolated at the hit, `background` elsewhere (raises without colors)
+            ambient_occlusion  [h, w]: bvh.ambient_occlusion (ao_dirs directions, radius ao_radius) at the hit points p0 + b1 (p1 - p0)
+                           + b2 (p2 - p0) with the `normal` target's normals, 1 elsewhere; needs `bvh`
 
         pixel_range=(lo, hi) renders that slab of the row-major pixel index and returns flat tensors.  grid: the mesh's
-        raycast.build_grid, to be built once for many views (None: built here).  Interpolation and normals are torch gathers over
-        the hit pixels.  ray_space='ndc' raises.  No network is evaluated, no random number drawn."""
+        raycast.build_grid, to be built once for many views (None: built here).  bvh: the mesh's bvh.build_bvh, or True to build it
+        here -- the rays then go through bvh.cast_rays (the same bits; not together with `grid` or method="brute").  tile=8 casts the
+        rays ordered by 8 x 8 pixel tiles (tile_order: one wave of the kernels is one tile) and scatters the results back: every pixel
+        keeps its bits, with every method; not together with pixel_range.  Interpolation and normals are torch gathers over the hit
+        pixels.  ray_space='ndc' raises.  No network is evaluated, no random number drawn."""
+        from . import bvh as bvh_module
         from .raycast import cast_rays
         target_types = list(target_types)
+        if tile not in (0, self.MESH_TILE):
+            raise ValueError("render_image_mesh: tile must be 0 or %d (got %r)" % (self.MESH_TILE, tile))
+        if tile and pixel_range is not None:
+            raise ValueError("render_image_mesh: tile orders the whole image; it cannot be combined with pixel_range")
+        if bvh is not None and bvh is not False and (grid is not None or method == "brute"):
+            raise ValueError("render_image_mesh: bvh casts the rays through the tree; it cannot be combined with grid or method='brute'")
+        if bvh is False:
+            bvh = None
+        if "ambient_occlusion" in target_types and bvh is None:
+            raise ValueError("render_image_mesh: the ambient_occlusion target needs bvh (a MeshBVH, or True)")
         unknown = [k for k in target_types if k not in self.MESH_TARGETS]
         if unknown:
             raise ValueError("render_image_mesh: unknown target(s) %s; it offers %s" % (unknown, list(self.MESH_TARGETS)))
@@ -557,7 +583,16 @@ class NeRFRender(BaseNeuralRender):
             uv = torch.stack([us, vs], 1)[lo:hi]
             n = uv.shape[0]
             rd, ro = self._ctx(dev).raygen(uv, camera.descriptor())
-            hits = cast_rays(ro, rd, vertices, triangles, t_min=self.dist_near, t_max=self.dist_far, method=method, grid=grid)
+            order = self.tile_order(w, h, tile, dev) if tile else None
+            co, cd = (ro, rd) if order is None else (ro[order].contiguous(), rd[order].contiguous())
+            if bvh is not None:
+                if bvh is True:
+                    bvh = bvh_module.build_bvh(vertices, triangles)
+                hits = bvh_module.cast_rays(co, cd, vertices, triangles, t_min=self.dist_near, t_max=self.dist_far, bvh=bvh)
+            else:
+                hits = cast_rays(co, cd, vertices, triangles, t_min=self.dist_near, t_max=self.dist_far, method=method, grid=grid)
+            if order is not None:
+                hits = {k: torch.empty_like(a).index_copy_(0, order, a) for k, a in hits.items()}
             hit = hits["triangle"] >= 0
             out: Dict[str, Tensor] = {}
             if "depth" in target_types:
@@ -566,7 +601,7 @@ class NeRFRender(BaseNeuralRender):
                 out["transmittance"] = torch.where(hit, torch.zeros_like(hits["t"]), torch.ones_like(hits["t"]))
             if "triangle" in target_types:
                 out["triangle"] = hits["triangle"]
-            wide = [k for k in ("color", "normal") if k in target_types]
+            wide = [k for k in ("color", "normal", "ambient_occlusion") if k in target_types]
             if wide:
                 idx = hit.nonzero().squeeze(1)
                 corners = triangles[hits["triangle"][idx].long()].long()                 # [n_hit, 3] vertex indices
@@ -579,8 +614,7 @@ class NeRFRender(BaseNeuralRender):
                 if "color" in wide:
                     out["color"] = torch.as_tensor(background, dtype=torch.float32, device=dev).expand(n, 3).contiguous()
                     out["color"][idx] = interpolate(colors)
-                if "normal" in wide:
-                    out["normal"] = torch.zeros(n, 3, device=dev)
+                if "normal" in wide or "ambient_occlusion" in wide:
                     if normals is not None:
                         nrm = interpolate(normals)
                     else:
@@ -588,7 +622,15 @@ class NeRFRender(BaseNeuralRender):
                         nrm = torch.cross(vertices[corners[:, 1]] - p0, vertices[corners[:, 2]] - p0, dim=1)
                     nrm = torch.nn.functional.normalize(nrm, dim=1)
                     away = (nrm * rd[idx]).sum(dim=1, keepdim=True) > 0
-                    out["normal"][idx] = torch.where(away, -nrm, nrm)
+                    nrm = torch.where(away, -nrm, nrm)
+                if "normal" in wide:
+                    out["normal"] = torch.zeros(n, 3, device=dev)
+                    out["normal"][idx] = nrm
+                if "ambient_occlusion" in wide:
+                    out["ambient_occlusion"] = torch.ones(n, device=dev)
+                    if idx.shape[0]:
+                        ao = bvh_module.ambient_occlusion(interpolate(vertices), nrm, vertices, triangles, n_dirs=ao_dirs, radius=ao_radius, bvh=bvh)
+                        out["ambient_occlusion"][idx] = ao
             if pixel_range is None:
                 out = {k: v.reshape(h, w, 3) if v.dim() == 2 else v.reshape(h, w) for k, v in out.items()}
         return {k: out[k] for k in target_types}

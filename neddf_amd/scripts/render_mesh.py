@@ -1,4 +1,5 @@
-"""`python neddf/scripts/render_mesh.py <run_dir> [--epoch 2000] [--mesh PATH.ply] [--compare-trace [THRESHOLD]] [--method grid|brute]` --
+"""`python neddf/scripts/render_mesh.py <run_dir> [--epoch 2000] [--mesh PATH.ply] [--compare-trace [THRESHOLD]] [--method grid|brute]
+[--bvh] [--tiles] [--ao [K]]` --
 views of an extracted mesh from the run's test cameras (no reference counterpart: the reference looks at its meshes in an Open3D
 viewer).  The run is loaded as extract_mesh.py loads it; the mesh is read with neddf_amd.mesh.read_ply, by default the newest file
 under `<run_dir>/mesh/`.  For every test camera NeRFRender.render_image_mesh casts the camera's rays -- the pixels of
@@ -6,7 +7,10 @@ render_image_traced and of the volume-rendered image -- at the mesh and `{id:03}
 the file has vertex colours, `{id:03}_rgb_mesh.png` go to `<run_dir>/render/`, scaled as the traced view's; one line per view gives
 the hit share and the time.  --compare-trace also sphere-traces the field at THRESHOLD (default: the one in the mesh's file name,
 `mesh_{resolution}_threshold{threshold}.ply`) and prints per view the share of pixels hit by both, by the mesh only and by the
-trace only, and the mean and maximum |t_mesh - t_traced| over the pixels hit by both."""
+trace only, and the mean and maximum |t_mesh - t_traced| over the pixels hit by both.  --bvh casts the rays through the mesh's BVH
+(neddf_amd.bvh: the same images, bit for bit) instead of --method's route, --tiles casts them ordered by 8 x 8 pixel tiles (the same
+images again), and --ao [K] (K directions, default 16; implies --bvh) also writes `{id:03}_ao_mesh.png`, the ambient occlusion at the
+hit points: a shaded look at the mesh."""
 import re
 from argparse import ArgumentParser
 from pathlib import Path
@@ -20,6 +24,10 @@ def build_parser() -> ArgumentParser:
     parser.add_argument("--compare-trace", type=float, nargs="?", const=float("nan"), default=None, metavar="THRESHOLD",
                         help="also sphere-trace the field at THRESHOLD (default: the one in the mesh's file name) and compare per pixel")
     parser.add_argument("--method", default="grid", choices=["grid", "brute"], help="ray casting through the grid or by brute force")
+    parser.add_argument("--bvh", action="store_true", help="cast the rays through the mesh's BVH instead of --method's route (the same images)")
+    parser.add_argument("--tiles", action="store_true", help="cast the rays ordered by 8 x 8 pixel tiles (the same images)")
+    parser.add_argument("--ao", type=int, nargs="?", const=16, default=None, metavar="K",
+                        help="also write {id:03}_ao_mesh.png: ambient occlusion from K directions (default 16); implies --bvh")
     return parser
 
 
@@ -56,6 +64,7 @@ def main(argv=None) -> list:
     import numpy as np
     import torch
 
+    from neddf_amd.bvh import build_bvh
     from neddf_amd.mesh import read_ply
     from neddf_amd.raycast import build_grid
     from neddf_amd.scripts.run_eval import load_config, load_trainer
@@ -70,8 +79,12 @@ def main(argv=None) -> list:
     render.set_iter(-1)
     dev = trainer.device
     verts, tris, normals, colors = (None if a is None else torch.from_numpy(a).to(dev) for a in read_ply(path, properties=True))
-    grid = build_grid(verts, tris) if args.method == "grid" else None
-    targets = ["depth", "transmittance", "normal"] + (["color"] if colors is not None else [])
+    use_bvh = args.bvh or args.ao is not None
+    if use_bvh and args.method != "grid":
+        raise SystemExit("render_mesh.py: --bvh and --ao cast the rays through the tree; leave --method at its default")
+    grid = build_grid(verts, tris) if args.method == "grid" and not use_bvh else None
+    bvh = build_bvh(verts, tris) if use_bvh else None
+    targets = ["depth", "transmittance", "normal"] + (["color"] if colors is not None else []) + (["ambient_occlusion"] if args.ao is not None else [])
     save_dir = output_dir / "render"
     save_dir.mkdir(exist_ok=True)
     print("mesh %s: %d vertices, %d triangles" % (path, verts.shape[0], tris.shape[0]))
@@ -82,7 +95,8 @@ def main(argv=None) -> list:
         h, w = trainer.dataset[camera_id]["rgb_images"].shape[:2]
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
-        images = render.render_image_mesh(w, h, camera, verts, tris, targets, normals=normals, colors=colors, method=args.method, grid=grid)
+        images = render.render_image_mesh(w, h, camera, verts, tris, targets, normals=normals, colors=colors, method=args.method, grid=grid, bvh=bvh,
+                                          tile=8 if args.tiles else 0, ao_dirs=args.ao if args.ao is not None else 16)
         torch.cuda.synchronize(dev)
         ms = 1e3 * (time.perf_counter() - t0)
         depth = torch.clamp((images["depth"] - 2.0) / 4.0 * 50000 / 256, 0, 255).cpu().numpy().astype(np.uint8)
@@ -91,6 +105,8 @@ def main(argv=None) -> list:
         imwrite_bgr(save_dir / "{:03}_normal_mesh.png".format(camera_id), np.ascontiguousarray(nrm[:, :, ::-1]))
         if colors is not None:
             imwrite_bgr(save_dir / "{:03}_rgb_mesh.png".format(camera_id), torch.clamp(images["color"] * 255, 0, 255).cpu().numpy().astype(np.uint8))
+        if args.ao is not None:
+            imwrite_bgr(save_dir / "{:03}_ao_mesh.png".format(camera_id), torch.clamp(images["ambient_occlusion"] * 255, 0, 255).cpu().numpy().astype(np.uint8))
         row = {"camera": camera_id, "hit_share": 1.0 - float(images["transmittance"].mean()), "ms": ms}
         print("mesh camera {}: hit share {:.4f}, {:.1f} ms".format(camera_id, row["hit_share"], ms))
         if threshold is not None:
