@@ -13,10 +13,23 @@
  *     pointer owned by the caller (a torch allocation); `h_` pointers are HOST.
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).  All
  *     stage calls are asynchronous on that stream; the caller synchronises.
+ *     The calls that hand a count back to the host say "synchronises `stream`"
+ *     in their comment: they wait for that stream (and for no other) to read it.
+ *     No other call blocks the host once the workspaces have grown to its sizes
+ *     (a workspace that has to grow is reallocated behind a device synchronise:
+ *     the first call of a new, larger size).
  *   - Return 0 on success, a negative NEDDF_E* code otherwise; never throws.
  *     neddf_last_error(ctx) returns a static/ctx-owned message.
- *   - One ctx per device; a ctx is not thread-safe, distinct ctxs are
- *     independent.  The ctx owns packed weights and scratch workspaces.
+ *   - A ctx belongs to one device and owns the packed weights and the scratch
+ *     workspaces (the field kernels' `scratch` and tile counters `sched`
+ *     included), which ALL its calls share.  Calls into one ctx may come from
+ *     different streams, but the caller must order them (an event, a stream
+ *     wait): two calls into one ctx that may run at the same time overwrite each
+ *     other's workspaces.  Unordered concurrent use needs one ctx per stream;
+ *     a device may have any number of them and distinct ctxs are independent.
+ *     A ctx is not thread-safe.  The one exception to "the caller orders" is
+ *     neddf_set_field: it waits for the last launch that reads the slot it
+ *     replaces, on whichever stream that was, and for nothing else.
  */
 #ifndef NEDDF_HIP_H
 #define NEDDF_HIP_H
@@ -230,6 +243,8 @@ int neddf_op_pe_weights(neddf_ctx *ctx, const float *d_var, int64_t N, int embed
 /* LinearGradFunction.forward (with_grad/linear.py:15-46) on the MFMA tile engine:
  * y = xW + b, G = JW.  h_W [Cin,Cout] / h_b [Cout] are HOST arrays (packed + uploaded
  * per call: this op is a test/compat entry point, the renderer keeps weights resident).
+ * Synchronises `stream` twice per block of weights: before the upload, which reuses the previous block's buffer, and after it,
+ * because the packed block is a host temporary.
  * Any Cin, Cout (round 4): K blocks of 256 input columns accumulate in the outputs, N blocks of 256 / 128 output columns. */
 int neddf_op_linear_grad(neddf_ctx *ctx, const float *d_x, const float *d_J, const float *h_W, const float *h_b,
                          int64_t N, int Cin, int Cout, float *d_y, float *d_G, void *stream);

@@ -253,7 +253,9 @@ def f32c(t):
 
 
 class Context:
-    """One neddf_ctx per device, shared by every module on that device."""
+    """A neddf_ctx.  Context.get(device) is the one every module on that device shares; its calls may come from different streams
+    as long as the caller orders them.  Work that runs unordered on another stream needs a context of its own, Context(index)
+    (include/neddf_hip.h, Conventions)."""
     _instances = {}
 
     @classmethod
