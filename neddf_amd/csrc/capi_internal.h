@@ -1,9 +1,10 @@
 // capi_internal.h -- context layout and helpers shared by the C-ABI translation units (neddf_capi.hip: context, fields, render, surface
 // extraction, occupancy, tracing; geom_capi.hip: meshes and point geometry; train_capi.hip: training step; comm_capi.hip: multi-GPU).
-// Not installed.
+// The host-only weight packer has its own header, field_pack.h (included here for roundup / in_skips).  Not installed.
 #pragma once
 #include "../../include/neddf_hip.h"
 #include "kernels.h"
+#include "field_pack.h"
 
 #include <stdlib.h>
 #include <initializer_list>
@@ -44,7 +45,7 @@ struct Field {
     ColArgs col{};
     NerfArgs nerf{};
     // NeDDF in fp32: the same network with three-term bf16 products (operands 3), taken by the eval-minimal route's reverse-mode
-    // distance kernel and colour kernel (NEDDF_F32_PRODUCTS, neddf_capi.hip)
+    // distance kernel and colour kernel (NEDDF_F32_PRODUCTS, field_pack.hip)
     bool has3 = false;
     DdfArgs ddf3{};
     ColArgs col3{};
@@ -121,6 +122,16 @@ struct neddf_ctx {
     CommState comm;
 };
 
+// Every DevBuf of a context (the fields' blobs and the communicator's staging aside): what neddf_destroy frees and the bounds probe
+// checks.  A workspace added to neddf_ctx joins this list.
+static inline std::vector<DevBuf *> workspaces(neddf_ctx *ctx)
+{
+    return { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack, &ctx->ttmp,
+             &ctx->tamax, &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc, &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk,
+             &ctx->occ_cells, &ctx->occ_blk, &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase, &ctx->trace_blk, &ctx->trace_ws,
+             &ctx->geom_blk, &ctx->geom_ws };
+}
+
 // hipEvent pair around one stage launch (only while neddf_set_timing is on); `which` = NEDDF_STAGE_*
 static inline void tick(neddf_ctx *ctx, hipStream_t s, int which, bool begin)
 {
@@ -186,14 +197,6 @@ static inline int read_totals(neddf_ctx *ctx, hipStream_t s, std::initializer_li
     if (h_flag) HIPCHK(hipMemcpyAsync(h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
-}
-
-static inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
-
-static inline bool in_skips(const neddf_field_desc &d, int id)
-{
-    for (int i = 0; i < d.n_skips; ++i) if (d.skips[i] == id) return true;
-    return false;
 }
 
 static inline void fill_enc(EncodeDesc &e, const Field &f)

@@ -38,7 +38,7 @@ enum { PA_R_DIR = 0, PA_R_POS = 8, PA_R_VAR = 11 };
 enum { PA_D = 0, PA_RHO = 1, PA_AUX = 2, PA_N0 = 3, PA_N1 = 4, PA_N2 = 5, PA_DDF_RAW = 6, PA_AUX_RAW = 7,
        PA_DG0 = 8, PA_DG1 = 9, PA_DG2 = 10, PA_AGG0 = 11, PA_AGG1 = 12, PA_AGG2 = 13, PA_DGN = 14, PA_DDDT = 15 };
 
-// One dense layer in "fragment-major" packing (see pack_layer() in neddf_capi.hip):
+// One dense layer in "fragment-major" packing (see pack_layer() in field_pack.hip):
 //   wp[(((wave*NT + t)*ksteps + S)*64 + lane)*4 + r] = W[k = 8S + 4*(lane>>5) + r][n = (wave*NT + t)*32 + (lane&31)]
 // so that one global_load_dwordx4 per lane yields the B operands of four
 // v_mfma_f32_32x32x2_f32 k-steps, and a wave's load is 1 KiB contiguous.

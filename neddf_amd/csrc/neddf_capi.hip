@@ -1,7 +1,8 @@
-// neddf_capi.hip -- C ABI of libneddf_hip.so (include/neddf_hip.h), the part around the fields: context, weight packing into MFMA
-// fragment order, workspaces, stage entry points, the fused render_rays orchestration (all launches on the caller's stream, no host
+// neddf_capi.hip -- C ABI of libneddf_hip.so (include/neddf_hip.h), the part around the fields: context, upload of the packed weights,
+// workspaces, stage entry points, the fused render_rays orchestration (all launches on the caller's stream, no host
 // round trip inside a call), and what evaluates a field or shares the render path's helpers: surface extraction, the occupancy tools
-// and sphere tracing.  Meshes and point geometry: geom_capi.hip; the training step: train_capi.hip; multi-GPU: comm_capi.hip.
+// and sphere tracing.  Weight packing into MFMA fragment order: field_pack.hip (host only); meshes and point geometry: geom_capi.hip;
+// the training step: train_capi.hip; multi-GPU: comm_capi.hip.
 #include "../../include/neddf_hip.h"
 #include "kernels.h"
 
@@ -27,493 +28,6 @@ static char g_err[256] = "no context";
 void neddf_comm_release(neddf_ctx *ctx);       // comm_capi.hip
 
 static int sched_flags() { return 2; }       // bit 1: dynamic tile queue (kernels.h DdfArgs::sched_flags)
-
-
-// ---------------------------------------------------------------------------
-// weight packing
-struct Src {
-    const float *w;
-    int rows, cols;       // logical [in][out]
-    bool transposed;      // storage is [out][in] (nn.Linear)
-    float at(int k, int n) const { return transposed ? w[(size_t)n * rows + k] : w[(size_t)k * cols + n]; }
-};
-
-// round-to-nearest-even fp32 -> bf16 bit pattern (what v_cvt_pk_bf16_f32 does on the device)
-static inline uint16_t bf16_bits(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);      // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-// fp32 -> IEEE half bit pattern, round to nearest even (toward_zero = false) or toward zero (true; never overflows to inf)
-static inline uint16_t f16_bits(float f, bool toward_zero)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    u &= 0x7fffffffu;
-    if (u >= 0x7f800000u) return (uint16_t)(sign | (u > 0x7f800000u ? 0x7e00u : (toward_zero ? 0x7bffu : 0x7c00u)));
-    if (u >= 0x477ff000u) {                                     // >= 65520: beyond the largest half
-        if (toward_zero || u < 0x477ff000u) return (uint16_t)(sign | 0x7bffu);
-        return (uint16_t)(sign | (toward_zero ? 0x7bffu : 0x7c00u));
-    }
-    if (u < 0x33000000u) return (uint16_t)sign;                 // < 2^-25: rounds to zero
-    int e = (int)(u >> 23) - 127;
-    uint32_t man = (u & 0x7fffffu) | 0x800000u;                 // 24-bit significand
-    int shift = e >= -14 ? 13 : 13 + (-14 - e);                 // bits dropped (subnormal halves drop more)
-    uint32_t q = man >> shift, rem = man & ((1u << shift) - 1), halfway = 1u << (shift - 1);
-    if (!toward_zero && (rem > halfway || (rem == halfway && (q & 1)))) ++q;
-    uint32_t h = e >= -14 ? (uint32_t)((e + 15) << 10) + (q - 0x400u) : q;      // q carries into the exponent on overflow
-    return (uint16_t)(sign | h);
-}
-
-static inline float f16_value(uint16_t h)
-{
-    const int e = (h >> 10) & 31, m = h & 0x3ff;
-    float v = e == 0 ? ldexpf((float)m, -24) : ldexpf((float)(m | 0x400), e - 25);
-    return (h & 0x8000) ? -v : v;
-}
-
-static inline float bf16_value(uint16_t b)
-{
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-// w = hi + mid + lo in bf16 (tile_engine.h OpsF32x3T): each term the bf16 rounding of what the previous ones left.  Exact for every
-// finite fp32 w that bf16 does not round up to infinity -- checked here for every packed weight, not assumed
-static inline bool bf16x3_split(float w, uint16_t t[3])
-{
-    t[0] = bf16_bits(w);
-    const float r1 = w - bf16_value(t[0]);
-    t[1] = bf16_bits(r1);
-    const float r2 = r1 - bf16_value(t[1]);
-    t[2] = bf16_bits(r2);
-    return bf16_value(t[2]) == r2 && (double)bf16_value(t[0]) + (double)bf16_value(t[1]) + (double)bf16_value(t[2]) == (double)w;
-}
-
-// fragment-major packing, see kernels.h LayerW.  kmap (engine column -> reference weight row, -1 = zero) is padded to
-// a whole number of super-steps: 8 k-values for fp32 fragments (4 floats per lane half), 16 for bf16 (8 per lane half).
-// (split_exact: cleared when a weight does not split exactly under operands 3)
-static size_t pack_layer(std::vector<float> &blob, const Src &src, std::vector<int> kmap, int nout, int operands, int *ksteps_out,
-                         bool *split_exact = nullptr)
-{
-    // operands == 2 (split fp16): two fp16 planes of 2^10 w (h toward zero, m = remainder to nearest), 32 bytes per lane and super-step
-    // operands == 3 (fp32 as three bf16 terms): planes hi, mid, lo of the 32x32x16 fragment, 48 bytes per lane and super-step
-    const int step = operands ? 16 : 8, half = step / 2, tiles = nout / 32, planes = operands == 2 ? 2 : (operands == 3 ? 3 : 1);     // nout: multiple of 32
-    while (kmap.size() % step) kmap.push_back(-1);
-    const int ks = (int)kmap.size() / step;
-    if (ksteps_out) *ksteps_out = ks;
-    size_t off = roundup((int)blob.size(), 64);
-    const size_t elems = (size_t)ks * step * nout;
-    blob.resize(off + (operands ? elems * planes / 2 : elems), 0.f);
-    float *dst = blob.data() + off;
-    uint16_t *dst16 = (uint16_t *)dst;
-    for (int tile = 0; tile < tiles; ++tile)            // tile-major: tile = wave * NT + t in the kernels
-            for (int S = 0; S < ks; ++S)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < half; ++r) {
-                        int n = tile * 32 + (lane & 31);
-                        int k = kmap[step * S + half * (lane >> 5) + r];
-                        float v = (k < 0 || n >= src.cols) ? 0.f : src.at(k, n);
-                        size_t frag = (((size_t)tile * ks + S) * 64 + lane);
-                        if (operands == 3) {
-                            uint16_t t[3];
-                            if (!bf16x3_split(v, t) && split_exact) *split_exact = false;
-                            for (int pl = 0; pl < 3; ++pl) dst16[(frag * 3 + pl) * half + r] = t[pl];
-                        } else if (operands == 2) {
-                            const float sv = v * 1024.0f;
-                            uint16_t h = f16_bits(sv, true);
-                            dst16[(frag * 2 + 0) * half + r] = h;
-                            dst16[(frag * 2 + 1) * half + r] = f16_bits(sv - f16_value(h), false);
-                        } else if (operands) dst16[frag * half + r] = bf16_bits(v);
-                        else dst[frag * half + r] = v;
-                    }
-    return off;
-}
-
-static size_t put(std::vector<float> &blob, const float *p, size_t n, size_t n_padded = 0)      // zero-padded to n_padded elements
-{
-    size_t off = roundup((int)blob.size(), 64);
-    blob.resize(off + (n_padded > n ? n_padded : n), 0.f);
-    memcpy(blob.data() + off, p, n * sizeof(float));
-    return off;
-}
-
-// engine columns of a hidden state of `width` features (zero-padded to the engine width wp) -> reference weight row base + k
-static std::vector<int> hidden_map(int width, int wp, int base)
-{
-    std::vector<int> m;
-    for (int k = 0; k < wp; ++k) m.push_back(k < width ? base + k : -1);
-    return m;
-}
-
-// engine width of a hidden width: the next multiple of 128 (four waves x 32-column MFMA tiles).  The padding columns carry zero
-// weights and biases, so they hold a(0) = 0 under every activation of the reference and feed zero rows downstream: exact.
-// A tile row also has to hold both encodings next to a 32-column block (enc_columns): a narrow network with long encodings takes the next
-// engine width that does
-static int enc_columns(const neddf_field_desc &d) { return 2 * roundup(3 * d.embed_pos_rank, 4) + 2 * roundup(3 * d.embed_dir_rank, 4) + 32; }
-static int engine_width(int width, const neddf_field_desc &d)
-{
-    int w = roundup(width, 128);
-    while (w < enc_columns(d)) w += 128;
-    return w;
-}
-
-// engine columns of the [sin half | cos half] encoding -> reference feature index base+...
-static void enc_map(std::vector<int> &m, int rank, int K, int base)
-{
-    for (int q = 0; q < K; ++q) m.push_back(q < 3 * rank ? base + q : -1);
-    for (int q = 0; q < K; ++q) m.push_back(q < 3 * rank ? base + 3 * rank + q : -1);
-}
-
-
-
-// How fp32 NeDDF fields take their products on the eval-minimal route (reverse-mode distance kernel + colour kernel), read once:
-//   NEDDF_F32_PRODUCTS=split3 (default)  three-term bf16 splits on v_mfma_f32_32x32x16_bf16 (tile_engine.h OpsF32x3T): fp32-accurate
-//   NEDDF_F32_PRODUCTS=mfma              v_mfma_f32_32x32x2_f32, the exact-fp32 route of earlier versions, bit for bit
-// The forward-mode kernels (full outputs, NEDDF_DDF_REVERSE=0), NeRF, NeuS and the training kernels take the fp32 MFMA either way.
-static bool f32_products_split3()
-{
-    static const bool v = [] {
-        const char *e = getenv("NEDDF_F32_PRODUCTS");
-        if (e && *e && strcmp(e, "mfma") != 0 && strcmp(e, "split3") != 0)
-            fprintf(stderr, "neddf: NEDDF_F32_PRODUCTS=%s is neither 'split3' nor 'mfma'; taking split3\n", e);
-        return !e || strcmp(e, "mfma") != 0;
-    }();
-    return v;
-}
-
-static int build_neddf(neddf_ctx *ctx, Field &f, const float *const *W, const float *const *B, int n_tensors)
-{
-    const neddf_field_desc &d = f.d;
-    const int E = d.embed_pos_rank, Ed = d.embed_dir_rank, n_trunk = d.layer_count - 1, n_col = d.col_layer_count - 1;
-    const int KH = roundup(3 * E, 4), KD = roundup(3 * Ed, 4), Cpe = 6 * E, Cdir = 6 * Ed;
-    const int operands = d.weight_dtype;      // 0 fp32, 1 bf16, 2 split fp16
-    const int Wd = d.layer_width, WP = engine_width(Wd, d);      // hidden width of the reference network / of the tile engine
-    if (d.col_layer_width != Wd)
-        return fail(ctx, NEDDF_EUNSUPPORTED, "NeDDF: col_layer_width must equal ddf_layer_width (the reference's layer_col_out takes ddf_layer_width inputs, "
-                                             "neddf.py:145: its own forward fails otherwise)");
-    if (n_tensors != n_trunk + n_col + 3) return fail(ctx, NEDDF_EINVAL, "NeDDF: wrong tensor count");
-    if (n_trunk < 1 || n_trunk > kMaxLayers || n_col < 1 || n_col > kMaxLayers) return fail(ctx, NEDDF_EUNSUPPORTED, "NeDDF: layer count out of range");
-    for (int i = 0; i < d.n_skips; ++i)
-        if (d.skips[i] < 0 || d.skips[i] >= n_trunk - 1)
-            return fail(ctx, NEDDF_EUNSUPPORTED, "NeDDF: skip index must address a trunk layer followed by another (the reference itself fails otherwise)");
-    // the argument blocks of one operand policy, their weights appended to `blob`; `resolve` sets their pointers once the blob is on the device
-    std::vector<float> blob;
-    auto pack = [&](int operands, DdfArgs &a, ColArgs &c, bool *exact, std::function<void(const float *)> &resolve) -> int {
-        a = DdfArgs{}; c = ColArgs{};
-        std::vector<size_t> o_wp(n_trunk), o_b(n_trunk), o_st;
-        std::vector<int> pe;
-        enc_map(pe, E, KH, 0);
-        a.n_layers = n_trunk; a.n_stash = 0;
-        for (int l = 0; l < n_trunk; ++l) {
-            bool wide = l > 0 && in_skips(d, l - 1);
-            int cin = l == 0 ? Cpe : (wide ? Wd + Cpe : Wd);
-            Src src{ W[l], cin, Wd, false };
-            std::vector<int> km;
-            a.layer[l].stash = -1;
-            if (l == 0) km = pe;
-            else km = hidden_map(Wd, WP, wide ? Cpe : 0);
-            o_wp[l] = pack_layer(blob, src, km, WP, operands, &a.layer[l].ksteps, exact);
-            if (wide) {
-                if (a.n_stash >= kMaxStash) return fail(ctx, NEDDF_EUNSUPPORTED, "NeDDF: more than 4 skip connections");
-                o_st.push_back(pack_layer(blob, src, pe, WP, operands, &a.stash[a.n_stash].ksteps, exact));
-                a.stash[a.n_stash].col0 = 0;
-                a.layer[l].stash = a.n_stash++;
-            }
-            o_b[l] = put(blob, B[l], Wd, WP);
-        }
-        const int i_ddf = n_trunk + n_col, i_aux = i_ddf + 1, i_cout = i_ddf + 2;
-        size_t o_wddf = put(blob, W[i_ddf], Wd, WP), o_waux = put(blob, W[i_aux], Wd, WP);
-        a.b_ddf_out = B[i_ddf][0]; a.b_aux_out = B[i_aux][0];
-        // Reverse-mode distance gradient (ddf_rev_kernel): the transposes.  dL/dH_{l-1} = g_l x (hidden rows of W_l)^T is a dense
-        // product with B[k][n] = W_l[row0 + n][k]; the gradient of the encoding collects g_0 x W_0^T and g_skip x (encoding rows of
-        // W_skip)^T, 64 engine columns wide (same [sin half | cos half] order as the forward encoding in LDS)
-        std::vector<size_t> o_wT(n_trunk, 0);
-        size_t o_wT_pe0 = 0, o_wT_pes[kMaxStash] = { 0 };
-        a.skip_layer = -1;
-        {
-            const std::vector<int> kall = hidden_map(Wd, WP, 0);
-            // narrow transposes: column n of the engine's encoding layout is reference row pe[n] (or padding)
-            auto pack_pe_T = [&](const float *Wl) {
-                std::vector<float> tmp((size_t)Wd * 64, 0.f);           // [k][n] row-major, n < 64
-                for (int n = 0; n < (int)pe.size() && n < 64; ++n)
-                    if (pe[n] >= 0)
-                        for (int k = 0; k < Wd; ++k) tmp[(size_t)k * 64 + n] = Wl[(size_t)pe[n] * Wd + k];
-                Src sn{ tmp.data(), Wd, 64, false };
-                return pack_layer(blob, sn, kall, 64, operands, nullptr, exact);
-            };
-            for (int l = 1; l < n_trunk; ++l) {
-                const bool wide = in_skips(d, l - 1);
-                // logical B[k][n] = W_l[(wide ? Cpe : 0) + n][k], W_l row-major [in][Wd]  ==  Src "transposed" with rows = Wd
-                Src st{ W[l] + (size_t)(wide ? Cpe : 0) * Wd, Wd, Wd, true };
-                o_wT[l] = pack_layer(blob, st, kall, WP, operands, nullptr, exact);
-                if (wide) { a.skip_layer = l; o_wT_pes[a.layer[l].stash] = pack_pe_T(W[l]); }
-            }
-            o_wT_pe0 = pack_pe_T(W[0]);
-        }
-        // colour trunk
-        std::vector<int> ka;
-        enc_map(ka, E, KH, 0);
-        enc_map(ka, Ed, KD, Cpe);
-        for (int k = 0; k < 3; ++k) ka.push_back(Cpe + Cdir + k);
-        std::vector<size_t> c_wp(n_col), c_b(n_col);
-        Src s0{ W[n_trunk], Cpe + Cdir + 3 + Wd, Wd, false };
-        size_t o_wa = pack_layer(blob, s0, ka, WP, operands, &c.ksteps_a, exact);
-        c.n_layers = n_col;
-        for (int l = 0; l < n_col; ++l) {
-            const std::vector<int> km = hidden_map(Wd, WP, l == 0 ? Cpe + Cdir + 3 : 0);
-            Src src{ W[n_trunk + l], l == 0 ? Cpe + Cdir + 3 + Wd : Wd, Wd, false };
-            c_wp[l] = pack_layer(blob, src, km, WP, operands, &c.layer[l].ksteps, exact);
-            c.layer[l].stash = -1;
-            c_b[l] = put(blob, B[n_trunk + l], Wd, WP);
-        }
-        size_t o_cout = put(blob, W[i_cout], (size_t)Wd * 3, (size_t)WP * 3);
-        for (int k = 0; k < 3; ++k) c.b_out[k] = B[i_cout][k];
-        resolve = [=, &a, &c](const float *base) {
-            for (int l = 0; l < n_trunk; ++l) { a.layer[l].wp = base + o_wp[l]; a.layer[l].bias = base + o_b[l]; }
-            for (int s = 0; s < a.n_stash; ++s) a.stash[s].wp = base + o_st[s];
-            a.w_ddf_out = base + o_wddf; a.w_aux_out = base + o_waux;
-            for (int l = 1; l < n_trunk; ++l) a.wT[l] = base + o_wT[l];
-            a.wT_pe0 = base + o_wT_pe0;
-            for (int st = 0; st < a.n_stash; ++st) a.wT_pe_skip[st] = base + o_wT_pes[st];
-            c.wp_a = base + o_wa;
-            for (int l = 0; l < n_col; ++l) { c.layer[l].wp = base + c_wp[l]; c.layer[l].bias = base + c_b[l]; }
-            c.w_out = base + o_cout;
-        };
-        a.ks_hidden = WP / (operands ? 16 : 8);
-        a.width = c.width = WP;
-        a.activation = c.activation = d.activation;
-        a.density_activation = d.density_activation;
-        a.d_near = d.d_near;
-        a.operands = c.operands = operands;
-        c.final_act = -1;
-        for (int k = 0; k < 6; ++k) { c.penalty_weight[k] = d.penalty_weight[k]; c.penalty_has[k] = d.penalty_has[k]; }
-        return 0;
-    };
-    std::function<void(const float *)> resolve, resolve3;
-    if (int rc = pack(operands, f.ddf, f.col, nullptr, resolve)) return rc;
-    // fp32 fields: the reverse-mode distance kernel and the colour kernel of the eval-minimal route take their products as three-term
-    // bf16 splits (operands 3, tile_engine.h OpsF32x3T) from a second packing of the same weights; the forward-mode kernels keep the first
-    f.has3 = false;
-    if (operands == NEDDF_DTYPE_F32 && f32_products_split3()) {
-        bool exact = true;
-        if (int rc = pack(3, f.ddf3, f.col3, &exact, resolve3)) return rc;
-        f.has3 = exact;
-    }
-    if (int rc = ensure(ctx, f.blob, blob.size() * sizeof(float))) return rc;
-    HIPCHK(hipMemcpy(f.blob.p, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
-    resolve((const float *)f.blob.p);
-    if (f.has3) resolve3((const float *)f.blob.p);
-    return 0;
-}
-
-// NeuS (neddf/network/neus.py): sdf trunk with Jacobian rows on the distance kernel (forward-mode replaces the
-// reference's torch.autograd.grad), colour trunk on the colour kernel.
-static int build_neus(neddf_ctx *ctx, Field &f, const float *const *W, const float *const *B, int n_tensors)
-{
-    const neddf_field_desc &d = f.d;
-    const int E = d.embed_pos_rank, Ed = d.embed_dir_rank, n_sdf = d.layer_count, n_col = d.col_layer_count;
-    const int KH = roundup(3 * E, 4), KD = roundup(3 * Ed, 4), Cpe = 6 * E, Cdir = 6 * Ed;
-    const int operands = d.weight_dtype;
-    // sdf and colour trunks may have different widths (neus.py:80-99); both run on one engine width, zero-padded
-    const int Ws = d.layer_width, Wc = d.col_layer_width, WP = engine_width(Ws > Wc ? Ws : Wc, d);
-    if (n_tensors != n_sdf + n_col + 2) return fail(ctx, NEDDF_EINVAL, "NeuS: wrong tensor count");
-    if (n_sdf < 1 || n_sdf > kMaxLayers || n_col < 1 || n_col > kMaxLayers) return fail(ctx, NEDDF_EUNSUPPORTED, "NeuS: layer count out of range");
-    if (d.activation == NEDDF_ACT_LEAKY) return fail(ctx, NEDDF_EUNSUPPORTED, "NeuS: activation must be ReLU or tanhExp");
-    for (int i = 0; i < d.n_skips; ++i)
-        if (d.skips[i] < 0 || d.skips[i] >= n_sdf - 1)
-            return fail(ctx, NEDDF_EUNSUPPORTED, "NeuS: skip index must address an sdf layer followed by another");
-    std::vector<float> blob;
-    DdfArgs &a = f.ddf;
-    ColArgs &c = f.col;
-    a = DdfArgs{}; c = ColArgs{};
-    std::vector<size_t> o_wp(n_sdf), o_b(n_sdf), o_st;
-    std::vector<int> pe;
-    enc_map(pe, E, KH, 0);
-    a.n_layers = n_sdf; a.n_stash = 0;
-    for (int l = 0; l < n_sdf; ++l) {
-        bool wide = l > 0 && in_skips(d, l - 1);
-        int cin = l == 0 ? Cpe : (wide ? Ws + Cpe : Ws);
-        Src src{ W[l], cin, Ws, true };
-        std::vector<int> km;
-        a.layer[l].stash = -1;
-        if (l == 0) km = pe;
-        else km = hidden_map(Ws, WP, 0);                            // cat([hx, embed_pos]): hidden state first
-        o_wp[l] = pack_layer(blob, src, km, WP, operands, &a.layer[l].ksteps);
-        if (wide) {
-            if (a.n_stash >= kMaxStash) return fail(ctx, NEDDF_EUNSUPPORTED, "NeuS: more than 4 skip connections");
-            std::vector<int> ps;
-            enc_map(ps, E, KH, Ws);
-            o_st.push_back(pack_layer(blob, src, ps, WP, operands, &a.stash[a.n_stash].ksteps));
-            a.stash[a.n_stash].col0 = 0;
-            a.layer[l].stash = a.n_stash++;
-        }
-        o_b[l] = put(blob, B[l], Ws, WP);
-    }
-    // Reverse-mode normal (ddf_rev_kernel): the sdf is feature 0 of the last activated layer, so the seed of the reverse pass is
-    // e_0 * y'_L -- the "distance head" of the kernel becomes the unit vector e_0 with zero bias, the aux head is zero -- and the
-    // transposes are read straight off nn.Linear's [out][in] storage: B[k][n] = W_l[k][n] for the hidden inputs n < 256 (hidden
-    // state first in NeuS's concatenation), the encoding inputs through the engine's column map
-    std::vector<size_t> o_wT(n_sdf, 0);
-    size_t o_wT_pe0 = 0, o_wT_pes[kMaxStash] = { 0 }, o_e0 = 0, o_zero = 0;
-    a.skip_layer = -1;
-    {
-        const std::vector<int> kall = hidden_map(Ws, WP, 0);
-        auto pack_pe_T = [&](const float *Wl, int cin, int base) {
-            std::vector<int> cols;
-            enc_map(cols, E, KH, base);
-            std::vector<float> tmp((size_t)Ws * 64, 0.f);           // [k][n] row-major, n < 64
-            for (int n = 0; n < (int)cols.size() && n < 64; ++n)
-                if (cols[n] >= 0)
-                    for (int k = 0; k < Ws; ++k) tmp[(size_t)k * 64 + n] = Wl[(size_t)k * cin + cols[n]];
-            Src sn{ tmp.data(), Ws, 64, false };
-            return pack_layer(blob, sn, kall, 64, operands, nullptr);
-        };
-        for (int l = 1; l < n_sdf; ++l) {
-            const bool wide = in_skips(d, l - 1);
-            // logical B[k][n] = W_l[k][n] over nn.Linear's [out][in] storage, hidden inputs n < Ws only
-            Src st{ W[l], Ws, wide ? Ws + Cpe : Ws, false };
-            std::vector<float> sq;                                   // pack_layer reads n < src.cols: cut the encoding inputs off
-            if (wide) {
-                sq.assign((size_t)Ws * Ws, 0.f);
-                for (int k = 0; k < Ws; ++k) memcpy(&sq[(size_t)k * Ws], W[l] + (size_t)k * (Ws + Cpe), (size_t)Ws * sizeof(float));
-                st = Src{ sq.data(), Ws, Ws, false };
-            }
-            o_wT[l] = pack_layer(blob, st, kall, WP, operands, nullptr);
-            if (wide) { a.skip_layer = l; o_wT_pes[a.layer[l].stash] = pack_pe_T(W[l], Ws + Cpe, Ws); }
-        }
-        o_wT_pe0 = pack_pe_T(W[0], Cpe, 0);
-        std::vector<float> e0(WP, 0.f), zero(WP, 0.f);
-        e0[0] = 1.0f;
-        o_e0 = put(blob, e0.data(), WP);
-        o_zero = put(blob, zero.data(), WP);
-    }
-    // colour trunk: engine columns [pos 3 | gradient 3 | pad 2 | dir sin KD | dir cos KD]
-    std::vector<int> ka;
-    for (int k = 0; k < 3; ++k) ka.push_back(k);
-    for (int k = 0; k < 3; ++k) ka.push_back(3 + Cdir + k);
-    ka.push_back(-1); ka.push_back(-1);
-    enc_map(ka, Ed, KD, 3);
-    const int in_col = 6 + Cdir + Ws;
-    Src s0{ W[n_sdf], in_col, Wc, true };
-    size_t o_wa = pack_layer(blob, s0, ka, WP, operands, &c.ksteps_a);
-    c.n_layers = n_col;
-    std::vector<size_t> c_wp(n_col), c_b(n_col);
-    for (int l = 0; l < n_col; ++l) {
-        const std::vector<int> km = l == 0 ? hidden_map(Ws, WP, 6 + Cdir) : hidden_map(Wc, WP, 0);
-        Src src{ W[n_sdf + l], l == 0 ? in_col : Wc, Wc, true };
-        c_wp[l] = pack_layer(blob, src, km, WP, operands, &c.layer[l].ksteps);
-        c.layer[l].stash = -1;
-        c_b[l] = put(blob, B[n_sdf + l], Wc, WP);
-    }
-    std::vector<float> wout((size_t)WP * 3, 0.f);         // [3][Wc] -> [WP][3]
-    for (int k = 0; k < Wc; ++k)
-        for (int o = 0; o < 3; ++o) wout[k * 3 + o] = W[n_sdf + n_col][(size_t)o * Wc + k];
-    size_t o_cout = put(blob, wout.data(), wout.size());
-    for (int k = 0; k < 3; ++k) c.b_out[k] = B[n_sdf + n_col][k];
-    if (int rc = ensure(ctx, f.blob, blob.size() * sizeof(float))) return rc;
-    HIPCHK(hipMemcpy(f.blob.p, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
-    const float *base = (const float *)f.blob.p;
-    for (int l = 0; l < n_sdf; ++l) { a.layer[l].wp = base + o_wp[l]; a.layer[l].bias = base + o_b[l]; }
-    for (int s = 0; s < a.n_stash; ++s) a.stash[s].wp = base + o_st[s];
-    c.wp_a = base + o_wa;
-    for (int l = 0; l < n_col; ++l) { c.layer[l].wp = base + c_wp[l]; c.layer[l].bias = base + c_b[l]; }
-    c.w_out = base + o_cout;
-    for (int l = 1; l < n_sdf; ++l) a.wT[l] = base + o_wT[l];
-    a.wT_pe0 = base + o_wT_pe0;
-    for (int st = 0; st < a.n_stash; ++st) a.wT_pe_skip[st] = base + o_wT_pes[st];
-    a.ks_hidden = WP / (operands ? 16 : 8);
-    a.width = c.width = WP;
-    a.w_ddf_out = base + o_e0; a.w_aux_out = base + o_zero;
-    a.b_ddf_out = 0.f; a.b_aux_out = 0.f;
-    a.activation = c.activation = d.activation;
-    a.neus = 1;
-    a.operands = c.operands = operands;
-    a.neus_v10 = W[n_sdf + n_col + 1][0] * 10.0f;
-    c.mode = 1;
-    c.final_act = d.activation;
-    return 0;
-}
-
-static int build_nerf(neddf_ctx *ctx, Field &f, const float *const *W, const float *const *B, int n_tensors)
-{
-    const neddf_field_desc &d = f.d;
-    const int E = d.embed_pos_rank, Ed = d.embed_dir_rank, n = d.layer_count;
-    const int KH = roundup(3 * E, 4), KD = roundup(3 * Ed, 4), Cpe = 6 * E, Cdir = 6 * Ed;
-    const int operands = d.weight_dtype, step = operands ? 16 : 8;
-    const int Wn = d.layer_width, WP = engine_width(Wn, d);
-    const int Wh = Wn / 2, HC = roundup(Wh > 0 ? Wh : 1, 128);      // colour head's hidden layer (nerf.py:99-103: layer_width // 2) and its engine width
-    if (n_tensors != n + 3) return fail(ctx, NEDDF_EINVAL, "NeRF: wrong tensor count");
-    if (n < 1 || n > kMaxLayers) return fail(ctx, NEDDF_EUNSUPPORTED, "NeRF: layer count out of range");
-    for (int i = 0; i < d.n_skips; ++i)
-        if (d.skips[i] < 0 || d.skips[i] >= n - 1)
-            return fail(ctx, NEDDF_EUNSUPPORTED, "NeRF: skip index must address a layer followed by another");
-    std::vector<float> blob;
-    NerfArgs &a = f.nerf;
-    a = NerfArgs{};
-    std::vector<int> pe;
-    enc_map(pe, E, KH, 0);
-    std::vector<size_t> o_wp(n), o_b(n), o_st;
-    a.n_layers = n; a.n_stash = 0;
-    for (int l = 0; l < n; ++l) {
-        bool wide = l > 0 && in_skips(d, l - 1);
-        int cin = l == 0 ? Cpe : (wide ? Wn + Cpe : Wn);
-        Src src{ W[l], cin, Wn, true };
-        std::vector<int> km;
-        a.layer[l].stash = -1;
-        if (l == 0) km = pe;
-        else km = hidden_map(Wn, WP, 0);                            // cat([hx, embed_pos]): hidden state first
-        o_wp[l] = pack_layer(blob, src, km, WP, operands, &a.layer[l].ksteps);
-        if (wide) {
-            if (a.n_stash >= kMaxStash - 1) return fail(ctx, NEDDF_EUNSUPPORTED, "NeRF: more than 3 skip connections");
-            std::vector<int> ps;
-            enc_map(ps, E, KH, Wn);
-            o_st.push_back(pack_layer(blob, src, ps, WP, operands, &a.stash[a.n_stash].ksteps));
-            a.stash[a.n_stash].col0 = 0;
-            a.layer[l].stash = a.n_stash++;
-        }
-        o_b[l] = put(blob, B[l], Wn, WP);
-    }
-    size_t o_wd = put(blob, W[n], Wn, WP);
-    a.b_density = B[n][0];
-    // colour head: Linear(layer_width + dir, layer_width // 2)
-    Src sc{ W[n + 1], Wn + Cdir, Wh, true };
-    const std::vector<int> km = hidden_map(Wn, WP, 0);
-    std::vector<int> kd;
-    enc_map(kd, Ed, KD, Wn);
-    size_t o_c0 = pack_layer(blob, sc, km, HC, operands, &a.col0.ksteps);
-    a.col_stash = a.n_stash;
-    size_t o_c0s = pack_layer(blob, sc, kd, HC, operands, &a.stash[a.n_stash].ksteps);
-    a.stash[a.n_stash].col0 = roundup(2 * KH, step);          // direction encoding: first super-step boundary after the position encoding
-    a.n_stash++;
-    size_t o_c0b = put(blob, B[n + 1], Wh, HC);
-    std::vector<float> w1((size_t)3 * HC, 0.f);               // [3][Wh] -> [3][HC]
-    for (int o = 0; o < 3; ++o) memcpy(&w1[(size_t)o * HC], W[n + 2] + (size_t)o * Wh, (size_t)Wh * sizeof(float));
-    size_t o_c1 = put(blob, w1.data(), w1.size());
-    for (int k = 0; k < 3; ++k) a.b_col1[k] = B[n + 2][k];
-
-    if (int rc = ensure(ctx, f.blob, blob.size() * sizeof(float))) return rc;
-    HIPCHK(hipMemcpy(f.blob.p, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
-    const float *base = (const float *)f.blob.p;
-    for (int l = 0; l < n; ++l) { a.layer[l].wp = base + o_wp[l]; a.layer[l].bias = base + o_b[l]; }
-    for (int s = 0; s + 1 < a.n_stash; ++s) a.stash[s].wp = base + o_st[s];
-    a.stash[a.col_stash].wp = base + o_c0s;
-    a.w_density = base + o_wd;
-    a.col0.wp = base + o_c0; a.col0.bias = base + o_c0b; a.col0.stash = a.col_stash;
-    a.w_col1 = base + o_c1;
-    a.activation = d.activation;
-    a.density_activation = d.density_activation;
-    a.operands = operands;
-    a.width = WP;
-    return 0;
-}
 
 // ---------------------------------------------------------------------------
 // the slot's packed weights were just read by work enqueued on `s`: neddf_set_field waits for exactly this before it repacks
@@ -777,11 +291,7 @@ void neddf_destroy(neddf_ctx *ctx)
         if (f.blob.p) (void)hipFree(f.blob.p);
         if (f.last_use) (void)hipEventDestroy(f.last_use);
     }
-    for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack, &ctx->ttmp, &ctx->tamax,
-                      &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc,
-                      &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk, &ctx->occ_cells, &ctx->occ_blk,
-                      &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase, &ctx->trace_blk, &ctx->trace_ws,
-                      &ctx->geom_blk, &ctx->geom_ws })
+    for (DevBuf *b : workspaces(ctx))
         if (b->p) (void)hipFree(b->base ? b->base : b->p);
     for (auto &e : ctx->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : ctx->pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -799,11 +309,7 @@ int neddf_debug_check_guards(neddf_ctx *ctx, int64_t *n_bands, int64_t *n_bad_by
     DeviceGuard guard_(ctx->device);
     HIPCHK(hipDeviceSynchronize());
     std::vector<GuardBand> bands = ctx->carve_guards;
-    for (DevBuf *b : { &ctx->features, &ctx->ptaux, &ctx->scratch, &ctx->arena, &ctx->flags, &ctx->rflags, &ctx->rev_scratch, &ctx->sched, &ctx->tpack,
-                       &ctx->ttmp, &ctx->tamax, &ctx->grid_pts, &ctx->mc_mask, &ctx->mc_vbase, &ctx->mc_blk, &ctx->mc_nacc,
-                      &ctx->cc_parent, &ctx->cc_used, &ctx->cc_blk, &ctx->occ_cells, &ctx->occ_blk,
-                      &ctx->brick_flags, &ctx->brick_blk, &ctx->brick_mask, &ctx->brick_vbase, &ctx->trace_blk, &ctx->trace_ws,
-                      &ctx->geom_blk, &ctx->geom_ws })
+    for (DevBuf *b : workspaces(ctx))
         if (b->base) {
             bands.push_back(GuardBand{ b->base, kGuardBytes });
             bands.push_back(GuardBand{ (char *)b->p + b->cap, kGuardBytes });
@@ -853,11 +359,13 @@ int neddf_set_field(neddf_ctx *ctx, int slot, const neddf_field_desc *desc, cons
     f.d = *desc;
     f.aux_grad_scale = 1.1f; f.distance_range_max = 2.0f;
     for (int i = 0; i < 10; ++i) f.lowpass[i] = 1.0f;
-    int rc = desc->kind == NEDDF_FIELD_NEDDF ? build_neddf(ctx, f, W, B, n)
-           : desc->kind == NEDDF_FIELD_NERF ? build_nerf(ctx, f, W, B, n)
-           : desc->kind == NEDDF_FIELD_NEUS ? build_neus(ctx, f, W, B, n)
-           : fail(ctx, NEDDF_EINVAL, "bad field kind");
-    if (rc) return rc;
+    PackedField pk;
+    if (int rc = pack_field(*desc, W, B, n, pk, ctx->err)) return rc;
+    if (int rc = ensure(ctx, f.blob, pk.blob.size() * sizeof(float))) return rc;
+    HIPCHK(hipMemcpy(f.blob.p, pk.blob.data(), pk.blob.size() * sizeof(float), hipMemcpyHostToDevice));
+    pk.resolve((const float *)f.blob.p);
+    f.ddf = pk.ddf; f.col = pk.col; f.nerf = pk.nerf;
+    f.ddf3 = pk.ddf3; f.col3 = pk.col3; f.has3 = pk.has3;
     f.valid = true;
     return 0;
 }

@@ -279,7 +279,7 @@ typedef OpsF16SplitT<256> OpsF16Split;
 // stashed in fp32, the activation mode.  A is read as 8 fp32 k-values per lane (two ds_read_b128) and split in prep(), ONCE
 // per super-step and M-tile (both column tiles take the same three terms; 44 vector instructions per 12 MFMAs at MT = NT = 2),
 // one super-step ahead: dense_mfma_split interleaves the split of super-step S + 1 with the MFMAs of S.  B is three
-// pre-split weight planes, 48 bytes per lane and super-step (neddf_capi.hip pack_layer,
+// pre-split weight planes, 48 bytes per lane and super-step (field_pack.hip pack_layer,
 // operands 3): half the weight bytes per MFMA of the bf16 policy.
 // (neither `OpsBF16` nor `OpsF16Split` may appear in this name: the benchmark tells the dtypes apart by those substrings)
 struct f32x8frag {
