@@ -1026,7 +1026,8 @@ __global__ __launch_bounds__(64 * NW, WPS * NW / 4) void col_trunk_kernel(const 
             __builtin_amdgcn_sched_barrier(0);
         }
         acc_init<MT, NT, ROWS4>(acc, a.layer[0].bias, wave, lane, Ops::kWScale);
-        dense<MT, NT, Ops>(acc, act_lane, (const frag *)a.wp_a + (size_t)wave * NT * a.ksteps_a * 64 + lane, a.ksteps_a);
+        // (both products of this kernel keep the split pipeline's over-read: tile_engine.h dense_pipeline OVERREAD)
+        dense<MT, NT, Ops, true>(acc, act_lane, (const frag *)a.wp_a + (size_t)wave * NT * a.ksteps_a * 64 + lane, a.ksteps_a);
         LayerPre<NT, Ops> pre;
         layer_prefetch<NT, Ops>(pre, a.layer[0].wp, nullptr, a.layer[0].ksteps, wave, lane);
         STAMP();                                    // 4: features requested, small-input product done
@@ -1065,7 +1066,7 @@ __global__ __launch_bounds__(64 * NW, WPS * NW / 4) void col_trunk_kernel(const 
         for (int l = 0; l < a.n_layers; ++l) {                     // neddf.py:254-256
             const LayerW &L = a.layer[l];
             if (l > 0) acc_init_pre<MT, NT, ROWS4, Ops>(acc, pre);
-            dense_pre<MT, NT, Ops>(acc, act_lane, (const frag *)L.wp + (size_t)wave * NT * L.ksteps * 64 + lane, L.ksteps, pre);
+            dense_pre<MT, NT, Ops, true>(acc, act_lane, (const frag *)L.wp + (size_t)wave * NT * L.ksteps * 64 + lane, L.ksteps, pre);
             if (l + 1 < a.n_layers)
                 layer_prefetch<NT, Ops>(pre, a.layer[l + 1].wp, a.layer[l + 1].bias, a.layer[l + 1].ksteps, wave, lane);
             STAMP();                                // layer l: 8 + 4l product done

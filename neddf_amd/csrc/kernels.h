@@ -23,12 +23,17 @@ constexpr size_t kStashFloatsPerWg = (size_t)kWaves * (4 * 2 * 4) * 64 * 4;
 // (device_math.h sample_moments: the stand-alone sampling kernel's own arithmetic, bit for bit) and hands them to the colour
 // kernel INSIDE the per-point record it writes anyway -- the [N, 3] x 3 sampling tensors (36 B per point written and 60 B read)
 // and the sampling launch disappear from neddf_render_rays' eval-minimal route.
+// Se < S: only the first Se samples of every ray are points of the launch, numbered compactly (point i = sample i % Se of ray i / Se, and
+// every per-point output is indexed by i).  The volume integral reads density / colour / normal of samples 0 .. S - 2 and of sample S - 1
+// its distance alone (render_kernels.hip composite_kernel), so a render pass whose per-sample arrays never leave the library evaluates
+// Se = S - 1 samples per ray (neddf_capi.hip render_pass).  A sample's moments do not depend on Se: dists keeps its row stride S.
 struct RaySrc {
     const float *rd = nullptr, *ro = nullptr, *view = nullptr, *dists = nullptr;   // [B, 3], [B, 3], [B, 3] or NULL, [B, S]
     int S = 0;              // samples per ray
+    int Se = 0;             // samples per ray that are evaluated: 1 .. S, or 0 for all S of them
     float r2 = 0.f;         // ray_radius^2 (cone sampling)
     int cone = 0;
-    int64_t base = 0;       // index of this launch's first point in the [B, S] grid
+    int64_t base = 0;       // index of this launch's first point in the [B, Se] grid
     double radius = -1.0;   // host side: the caller's ray radius as given (launch_sampling squares it itself), < 0 for point samples
 };
 
@@ -182,10 +187,11 @@ void launch_sampling(const float *rd, const float *ro, const float *view, const 
                      float *pos, float *dir, float *var, hipStream_t s);
 void launch_ndc(const float *rd, const float *ro, int64_t n, float width, float height, float fx, float fy, float near_, float *nd,
                 float *no, hipStream_t s);
+// ld: row stride of dens / col / nrm in samples (0: S; S - 1 where the field evaluated RaySrc::Se = S - 1 samples per ray)
 void launch_composite(const float *dists, const float *dens, const float *col, int64_t n, int S, float max_dist,
-                      float *w, float *depth, float *color, float *trans, int *nan_flag, hipStream_t s);
-// sum_j weight[b, j] * nrm[b, j] with launch_composite's weights (render_kernels.hip composite_normal_kernel); nrm [n, S, 3], normal [n, 3]
-void launch_composite_normal(const float *dists, const float *dens, const float *nrm, int64_t n, int S, float *normal, hipStream_t s);
+                      float *w, float *depth, float *color, float *trans, int *nan_flag, hipStream_t s, int ld = 0);
+// sum_j weight[b, j] * nrm[b, j] with launch_composite's weights (render_kernels.hip composite_normal_kernel); nrm [n, ld, 3], normal [n, 3]
+void launch_composite_normal(const float *dists, const float *dens, const float *nrm, int64_t n, int S, float *normal, hipStream_t s, int ld = 0);
 // [n, 3] position gradient / normal out of the per-point record of a distance-trunk launch (either may be NULL)
 void launch_surface_gather(const float *ptaux, int64_t n, int neus, float *dgrad, float *normal, hipStream_t s);
 void launch_integrate_penalty(const float *dists, const float *pen, int64_t n, int S, float *out, hipStream_t s);

@@ -49,8 +49,29 @@ struct UseMark {
     ~UseMark() { (void)mark_use(ctx, f, s); }
 };
 
-// rays != NULL (neddf_render_rays): the N points are the [B, S] sample grid of these rays; pos / dir / var are then WORKSPACE -- filled by
-// the sampling kernel when the route cannot take its points from the rays, untouched when it can (kernels.h RaySrc)
+// Eval-minimal NeDDF needs the gradient of one scalar (the distance) only: reverse mode halves the matrix work
+// (NEDDF_DDF_REVERSE=0 keeps the forward-mode Jacobian rows, which the penalties of the full mode need anyway)
+static bool ddf_reverse(const Field &f, bool full)
+{
+    static const bool rev_enabled = [] { const char *e = getenv("NEDDF_DDF_REVERSE"); return !e || atoi(e) != 0; }();
+    // (all three operand policies gain: fp32 27.5 vs 51.8 ms per 2^21 points, split fp16 12.4 vs 19.9 ms, bf16 6.4 vs 7.4 ms)
+    return rev_enabled && !full && (f.d.kind == NEDDF_FIELD_NEDDF || f.d.kind == NEDDF_FIELD_NEUS);
+}
+
+// Sample points straight from the rays (the cone moments in the field prologue): the reverse-mode distance
+// kernel derives them in its prologue and hands them to the colour kernel in the per-point record; NEDDF_RAYS_IN_FIELD=0 keeps the
+// sampling tensors (the A/B partner: tests/test_gpu_parity.py holds both routes bit-identical)
+// (read per call, a few times per frame: the bit-identity test flips it inside one process)
+// (a rays-sourced launch parks the sample position in the record's gradient slots, kernels.h PA_R_POS: not when the gradient is asked for)
+static bool rays_in_field(const Field &f, bool full, bool dgrad)
+{
+    const char *rif = getenv("NEDDF_RAYS_IN_FIELD");
+    return (!rif || atoi(rif) != 0) && ddf_reverse(f, full) && f.d.kind == NEDDF_FIELD_NEDDF && !dgrad;
+}
+
+// rays != NULL (neddf_render_rays): the N points are the [B, Se] grid of these rays' evaluated samples (Se = S unless the caller skips
+// each ray's last one, which only a rays_in_field() route can); pos / dir / var are then WORKSPACE -- filled by the sampling kernel when
+// the route cannot take its points from the rays, untouched when it can (kernels.h RaySrc)
 static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float *dir, const float *var, int64_t N,
                          int out_mode, float *distance, float *density, float *color, float *penalty, float *aux,
                          hipStream_t s, const RaySrc *rays = nullptr, float *dgrad = nullptr, float *normal = nullptr)
@@ -93,18 +114,10 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
     }
     const bool full = (out_mode == NEDDF_OUT_FULL) && penalty && f.d.kind == NEDDF_FIELD_NEDDF;
     const int fr = full ? 4 : 1;
-    // Eval-minimal NeDDF needs the gradient of one scalar (the distance) only: reverse mode halves the matrix work
-    // (NEDDF_DDF_REVERSE=0 keeps the forward-mode Jacobian rows, which the penalties of the full mode need anyway)
-    static const bool rev_enabled = [] { const char *e = getenv("NEDDF_DDF_REVERSE"); return !e || atoi(e) != 0; }();
-    // (all three operand policies gain: fp32 27.5 vs 51.8 ms per 2^21 points, split fp16 12.4 vs 19.9 ms, bf16 6.4 vs 7.4 ms)
-    const bool reverse = rev_enabled && !full && (f.d.kind == NEDDF_FIELD_NEDDF || f.d.kind == NEDDF_FIELD_NEUS);
-    // Sample points straight from the rays (the cone moments in the field prologue): the reverse-mode distance
-    // kernel derives them in its prologue and hands them to the colour kernel in the per-point record; NEDDF_RAYS_IN_FIELD=0 keeps the
-    // sampling tensors (the A/B partner: tests/test_gpu_parity.py holds both routes bit-identical)
-    // (read per call, a few times per frame: the bit-identity test flips it inside one process)
-    const char *rif = rays ? getenv("NEDDF_RAYS_IN_FIELD") : nullptr;
-    // (a rays-sourced launch parks the sample position in the record's gradient slots, kernels.h PA_R_POS: not when the gradient is asked for)
-    const bool use_rays = rays && (!rif || atoi(rif) != 0) && reverse && f.d.kind == NEDDF_FIELD_NEDDF && !dgrad;
+    const bool reverse = ddf_reverse(f, full);
+    const bool use_rays = rays && rays_in_field(f, full, dgrad != nullptr);
+    if (rays && !use_rays && rays->Se && rays->Se != rays->S)
+        return fail(ctx, NEDDF_EINVAL, "field_forward: the sampling tensors hold every sample of a ray (RaySrc::Se)");
     if (rays && !use_rays) sample_now();
     // fp32 products as three-term bf16 splits (f32_products_split3): the reverse-mode kernel and the colour kernel behind it only
     const bool use3 = f.has3 && reverse && f.d.kind == NEDDF_FIELD_NEDDF;
@@ -152,6 +165,7 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
         if (use_rays) {
             a.pos = a.dir = a.var = nullptr;
             a.rays = *rays;
+            if (!a.rays.Se) a.rays.Se = rays->S;
             a.rays.base = rays->base + off;
         }
         a.aux_grad_scale = f.aux_grad_scale;
@@ -617,11 +631,17 @@ static int render_pass(neddf_ctx *ctx, int slot, const float *rd, const float *r
         if (normal_out) STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite_normal(dists, dens, nrm, B, S, normal_out, s));
         return 0;
     }
-    int rc = field_forward(ctx, slot, pos, dir, var, B * S, want_pen ? NEDDF_OUT_FULL : NEDDF_OUT_MINIMAL, nullptr, dens, want_col ? col : nullptr,
+    // dens / col / nrm are workspaces of the callers (render_rays_impl, render_rays_single_impl) and the two compositors below are their only
+    // readers: of a ray's last sample they read the distance alone, so the field skips it where it takes its points from the rays (RaySrc::Se;
+    // the arrays are then [B, S - 1] rows).  The penalty route integrates a per-sample array of its own and keeps all S samples, and so
+    // does the sampling-tensor route (NeRF, NeuS, NEDDF_RAYS_IN_FIELD=0, NEDDF_DDF_REVERSE=0) and the culled pass above.
+    const int Se = !want_pen && rays_in_field(ctx->field[slot], false, false) ? S - 1 : S;
+    rays.Se = Se;
+    int rc = field_forward(ctx, slot, pos, dir, var, B * Se, want_pen ? NEDDF_OUT_FULL : NEDDF_OUT_MINIMAL, nullptr, dens, want_col ? col : nullptr,
                            want_pen ? pen : nullptr, nullptr, s, &rays, nullptr, normal_out ? nrm : nullptr);
     if (rc) return rc;
-    STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite(dists, dens, want_col ? col : nullptr, B, S, rp->max_dist, w_out, depth, color, trans, nan_flag, s));
-    if (normal_out) STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite_normal(dists, dens, nrm, B, S, normal_out, s));
+    STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite(dists, dens, want_col ? col : nullptr, B, S, rp->max_dist, w_out, depth, color, trans, nan_flag, s, Se));
+    if (normal_out) STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite_normal(dists, dens, nrm, B, S, normal_out, s, Se));
     if (want_pen) STAGE(ctx, s, NEDDF_STAGE_PENALTY, launch_integrate_penalty(dists, pen, B, S, pen_out, s));
     return 0;
 }

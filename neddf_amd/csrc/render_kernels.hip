@@ -159,14 +159,15 @@ __device__ __forceinline__ float wave_sum(float v)
 // fp64 (torch-CPU cumprod accumulates in double and rounds each output, N2).
 // col == NULL: weights only (the coarse pass of render_rays when nobody asked for
 // its pixels: only the resampling weights are consumed); depth / color / trans may then be NULL too.
+// ld: samples per ray STORED in dens / col (their row stride): S, or S - 1 where the field skipped the last one, which is never read here.
 __global__ __launch_bounds__(256) void composite_kernel(const float *dists, const float *dens, const float *col, int64_t n,
-                                                        int S, float max_dist, float *weight, float *depth, float *color,
+                                                        int S, int ld, float max_dist, float *weight, float *depth, float *color,
                                                         float *trans, int *nan_flag)
 {
     const int lane = threadIdx.x & 63;
     const int64_t b = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (b >= n) return;
-    const float *d = dists + b * S, *r = dens + b * S, *c = col ? col + b * S * 3 : nullptr;
+    const float *d = dists + b * S, *r = dens + b * ld, *c = col ? col + b * ld * 3 : nullptr;
     double carry = 1.0;               // T entering this 64-sample chunk
     float sd = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f;
     bool bad = false;
@@ -205,24 +206,25 @@ __global__ __launch_bounds__(256) void composite_kernel(const float *dists, cons
 }
 
 void launch_composite(const float *dists, const float *dens, const float *col, int64_t n, int S, float max_dist,
-                      float *w, float *depth, float *color, float *trans, int *nan_flag, hipStream_t s)
+                      float *w, float *depth, float *color, float *trans, int *nan_flag, hipStream_t s, int ld)
 {
     if (n <= 0) return;
-    hipLaunchKernelGGL(composite_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dists, dens, col, n, S, max_dist, w,
+    hipLaunchKernelGGL(composite_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dists, dens, col, n, S, ld ? ld : S, max_dist, w,
                        depth, color, trans, nan_flag);
 }
 
 // Normal render target: normal[b] = sum_j weight[b, j] * n[b, j] over the S - 1 intervals of composite_kernel, with composite_kernel's
 // own weights -- the same expressions in the same order (one wavefront per ray, the fp64 multiplicative wave scan, wave_sum's fixed
 // butterfly), so the weights are its weights bit for bit and two runs agree bitwise.  A kernel of its own: composite_kernel, and with
-// it colour / depth / transmittance / weight, is untouched by the target.  nrm [n, S, 3]: what the field hands to its colour trunk.
+// it colour / depth / transmittance / weight, is untouched by the target.  nrm [n, ld, 3]: what the field hands to its colour trunk
+// (ld as in composite_kernel).
 __global__ __launch_bounds__(256) void composite_normal_kernel(const float *dists, const float *dens, const float *nrm, int64_t n,
-                                                               int S, float *normal)
+                                                               int S, int ld, float *normal)
 {
     const int lane = threadIdx.x & 63;
     const int64_t b = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (b >= n) return;
-    const float *d = dists + b * S, *r = dens + b * S, *c = nrm + b * S * 3;
+    const float *d = dists + b * S, *r = dens + b * ld, *c = nrm + b * ld * 3;
     double carry = 1.0;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
     for (int base = 0; base < S - 1; base += 64) {
@@ -248,10 +250,10 @@ __global__ __launch_bounds__(256) void composite_normal_kernel(const float *dist
     if (lane == 0) { normal[3 * b + 0] = s0; normal[3 * b + 1] = s1; normal[3 * b + 2] = s2; }
 }
 
-void launch_composite_normal(const float *dists, const float *dens, const float *nrm, int64_t n, int S, float *normal, hipStream_t s)
+void launch_composite_normal(const float *dists, const float *dens, const float *nrm, int64_t n, int S, float *normal, hipStream_t s, int ld)
 {
     if (n <= 0) return;
-    hipLaunchKernelGGL(composite_normal_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dists, dens, nrm, n, S, normal);
+    hipLaunchKernelGGL(composite_normal_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dists, dens, nrm, n, S, ld ? ld : S, normal);
 }
 
 // The position gradient and the normal of the distance trunk, read back from the per-point record it leaves for the colour kernel

@@ -523,9 +523,9 @@ __device__ __forceinline__ void dense_pipeline3(f32x16 (&acc)[MT][NT], typename 
 template <class Ops>
 constexpr bool kSplitsA = !std::is_same<typename Ops::afrag, typename Ops::mfrag>::value;
 
+// the MFMAs of one super-step on terms already split.  On its own it is a product's LAST super-step, which has no successor to split.
 template <int MT, int NT, class Ops>
-__device__ __forceinline__ void dense_mfma_split(f32x16 (&acc)[MT][NT], const typename Ops::mfrag (&m)[MT], const typename Ops::bfrag (&b)[NT],
-                                                 const typename Ops::afrag (&an)[MT], typename Ops::mfrag (&mn)[MT])
+__device__ __forceinline__ void dense_mfma_last(f32x16 (&acc)[MT][NT], const typename Ops::mfrag (&m)[MT], const typename Ops::bfrag (&b)[NT])
 {
 #pragma unroll
     for (int r = 0; r < Ops::kSub; ++r)
@@ -533,6 +533,13 @@ __device__ __forceinline__ void dense_mfma_split(f32x16 (&acc)[MT][NT], const ty
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int t = 0; t < NT; ++t) acc[mt][t] = Ops::mfma(m[mt], b[t], acc[mt][t], r);
+}
+
+template <int MT, int NT, class Ops>
+__device__ __forceinline__ void dense_mfma_split(f32x16 (&acc)[MT][NT], const typename Ops::mfrag (&m)[MT], const typename Ops::bfrag (&b)[NT],
+                                                 const typename Ops::afrag (&an)[MT], typename Ops::mfrag (&mn)[MT])
+{
+    dense_mfma_last<MT, NT, Ops>(acc, m, b);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) mn[mt] = Ops::prep(an[mt]);
     constexpr int kMfma = Ops::kSub * MT * NT, kLead = MT * NT;
@@ -546,7 +553,10 @@ __device__ __forceinline__ void dense_mfma_split(f32x16 (&acc)[MT][NT], const ty
     }
 }
 
-template <int MT, int NT, class Ops = OpsF32>
+// OVERREAD (split policies only): keep the loop that requests, reads and splits one super-step past the last and drops it.  The colour
+// kernel asks for it: without the over-read its small-input product spills into its MFMA block and the kernel measured 1.9 % slower
+// (profiles/r10_dead_work_ab.txt); the distance kernel gains 1.4 % from the exact loop.
+template <int MT, int NT, class Ops = OpsF32, bool OVERREAD = false>
 __device__ __forceinline__ void dense_pipeline(f32x16 (&acc)[MT][NT], typename Ops::afrag (&a0)[MT], typename Ops::bfrag (&b0)[NT],
                                                const typename Ops::act_t *act_lane, const WeightStream &wl, int ksteps)
 {
@@ -561,21 +571,49 @@ __device__ __forceinline__ void dense_pipeline(f32x16 (&acc)[MT][NT], typename O
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) m0[mt] = Ops::prep(a0[mt]);     // the first super-step's split is the only one in the open
         const typename Ops::act_t *ap = act_lane;
-        for (int S = 0; S < ksteps; S += 2) {
-            const bool more = S + 1 < ksteps;
-            // (as below, A fragments up to two super-steps past the last are read and split, never used)
-            dense_load<MT, NT, Ops>(a1, b1, ap + Ops::kStep, wl, ksteps, more ? S + 1 : S);
+        if constexpr (OVERREAD) {
+            for (int S = 0; S < ksteps; S += 2) {
+                const bool more = S + 1 < ksteps;
+                // (as below, A fragments up to two super-steps past the last are read and split, never used)
+                dense_load<MT, NT, Ops>(a1, b1, ap + Ops::kStep, wl, ksteps, more ? S + 1 : S);
+                __builtin_amdgcn_sched_barrier(0);
+                dense_mfma_split<MT, NT, Ops>(acc, m0, b0, a1, m1);
+                __builtin_amdgcn_sched_barrier(0);
+                if (more) {
+                    dense_load<MT, NT, Ops>(a0, b0, ap + 2 * Ops::kStep, wl, ksteps, S + 2 < ksteps ? S + 2 : S);
+                    __builtin_amdgcn_sched_barrier(0);
+                    dense_mfma_split<MT, NT, Ops>(acc, m1, b1, a0, m0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                ap += 2 * Ops::kStep;
+            }
+            return;
+        }
+        // The loop covers the n = ksteps - 1 super-steps that have a successor: every request, LDS read and split is of a super-step of
+        // the product.  The last super-step's MFMAs then issue alone (dense_mfma_last), from the second register set: that is where an
+        // even ksteps (every product of the shipped 256-wide network: 16, 4 and 6 super-steps) leaves them; an odd one moves them over.
+        const int n = ksteps - 1;
+        for (int S = 0; S < n; S += 2) {
+            dense_load<MT, NT, Ops>(a1, b1, ap + Ops::kStep, wl, ksteps, S + 1);
             __builtin_amdgcn_sched_barrier(0);
             dense_mfma_split<MT, NT, Ops>(acc, m0, b0, a1, m1);
             __builtin_amdgcn_sched_barrier(0);
-            if (more) {
-                dense_load<MT, NT, Ops>(a0, b0, ap + 2 * Ops::kStep, wl, ksteps, S + 2 < ksteps ? S + 2 : S);
+            if (S + 1 < n) {
+                dense_load<MT, NT, Ops>(a0, b0, ap + 2 * Ops::kStep, wl, ksteps, S + 2);
                 __builtin_amdgcn_sched_barrier(0);
                 dense_mfma_split<MT, NT, Ops>(acc, m1, b1, a0, m0);
                 __builtin_amdgcn_sched_barrier(0);
             }
             ap += 2 * Ops::kStep;
         }
+        if (!(n & 1)) {
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) m1[mt] = m0[mt];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) b1[t] = b0[t];
+        }
+        dense_mfma_last<MT, NT, Ops>(acc, m1, b1);
+        __builtin_amdgcn_sched_barrier(0);
         return;
     }
     typename Ops::afrag a1[MT];
@@ -599,7 +637,7 @@ __device__ __forceinline__ void dense_pipeline(f32x16 (&acc)[MT][NT], typename O
     }
 }
 
-template <int MT, int NT, class Ops = OpsF32>
+template <int MT, int NT, class Ops = OpsF32, bool OVERREAD = false>
 __device__ __forceinline__ void dense_pre(f32x16 (&acc)[MT][NT], const typename Ops::act_t *act_lane, const typename Ops::bfrag *wl,
                                           int ksteps, const LayerPre<NT, Ops> &p)
 {
@@ -609,17 +647,17 @@ __device__ __forceinline__ void dense_pre(f32x16 (&acc)[MT][NT], const typename 
     for (int t = 0; t < NT; ++t) b0[t] = p.b[t];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) a0[mt] = Ops::load_a(act_lane + mt * 32 * Ops::kLd);
-    dense_pipeline<MT, NT, Ops>(acc, a0, b0, act_lane, weight_stream(wl), ksteps);
+    dense_pipeline<MT, NT, Ops, OVERREAD>(acc, a0, b0, act_lane, weight_stream(wl), ksteps);
 }
 
-template <int MT, int NT, class Ops = OpsF32>
+template <int MT, int NT, class Ops = OpsF32, bool OVERREAD = false>
 __device__ __forceinline__ void dense(f32x16 (&acc)[MT][NT], const typename Ops::act_t *act_lane, const typename Ops::bfrag *wl, int ksteps)
 {
     typename Ops::afrag a0[MT];
     typename Ops::bfrag b0[NT];
     const WeightStream w = weight_stream(wl);
     dense_load<MT, NT, Ops>(a0, b0, act_lane, w, ksteps, 0);
-    dense_pipeline<MT, NT, Ops>(acc, a0, b0, act_lane, w, ksteps);
+    dense_pipeline<MT, NT, Ops, OVERREAD>(acc, a0, b0, act_lane, w, ksteps);
 }
 
 // acc = act x W (no bias).  (Starting from the MFMA's zero constant instead of cleared accumulators -- no 16 v_mov per tile -- measured SLOWER under

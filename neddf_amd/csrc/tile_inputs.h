@@ -133,11 +133,12 @@ __device__ __forceinline__ void encode_dir(typename Ops::act_t *act, int col0, c
 #define STAMP_WALL(k) do { } while (0)
 #endif
 
-// position / variance / direction of point `gpt` of the [B, S] sample grid, straight from the rays (kernels.h RaySrc)
+// position / variance / direction of point `gpt` of the [B, Se] grid of evaluated samples, straight from the rays (kernels.h RaySrc):
+// sample j of ray b has the moments it has among all S samples of its ray, whatever Se is
 __device__ __forceinline__ void ray_point(const RaySrc &r, int64_t gpt, float (&pos)[3], float (&var)[3], float (&dir)[3])
 {
-    const int64_t b = gpt / r.S;
-    const int j = (int)(gpt - b * r.S);
+    const int64_t b = gpt / r.Se;
+    const int j = (int)(gpt - b * r.Se);
     float t_mu, t_var, r_var;
     if (r.cone) sample_moments<true>(r.dists + b * r.S, j, r.S, r.r2, t_mu, t_var, r_var);
     else sample_moments<false>(r.dists + b * r.S, j, r.S, r.r2, t_mu, t_var, r_var);
