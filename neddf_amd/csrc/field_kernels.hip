@@ -390,6 +390,8 @@ __global__ __launch_bounds__(kThreads, 2) void ddf_rev_kernel(const DdfArgs a)
     constexpr int NBLK = 2 * MT, BPW = NBLK >= NW ? NBLK / NW : 1;
     static_assert(BPW * NW == NBLK || NBLK < NW, "the encoding gradient's blocks must divide over the waves");
     constexpr int PARTS = THREADS / ROWS;               // threads per point in the tail
+    // L2 residency mechanisms of the three-term policy (tile_engine.h OpsF32x3L2T): last-use scratch loads non-temporal / periodic write-back
+    constexpr bool L2S = (kL2Of<Ops> & 1) != 0, L2WB = (kL2Of<Ops> & 2) != 0;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     act_t *act = (act_t *)smem;
     float *hd = (float *)(act + ROWS * LD);  // [2 k-halves][2 heads][ROWS] head dot products
@@ -509,6 +511,7 @@ __global__ __launch_bounds__(kThreads, 2) void ddf_rev_kernel(const DdfArgs a)
         __syncthreads();
         int next_tile = 0;
         if (tid == 0) next_tile = sched_next(a.sched, a.sched_flags, tile);
+        if constexpr (L2WB) l2_writeback_tick(a.sched, a.sched_flags >> kSchedL2PeriodShift, tid);
         // scaled integrated encoding (neddf.py:193-204), value rows; the factors of its Jacobian go to the scratch (or stay in LDS)
         // one (point, pair) item = the pair's sine / cosine value into the tile (and the encoding's own tile), its Jacobian factors into pjl / pj
         auto encode_item = [&](int p, int q, int e, float px, float vx) {
@@ -699,7 +702,7 @@ __global__ __launch_bounds__(kThreads, 2) void ddf_rev_kernel(const DdfArgs a)
                     if (parked) {
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
-                            f32x4v v = gpe_park[(i * 4 + g) * 64];
+                            f32x4v v = stream_get<L2S>(&gpe_park[(i * 4 + g) * 64]);
                             gs[0][0][4 * g] = v[0]; gs[0][0][4 * g + 1] = v[1]; gs[0][0][4 * g + 2] = v[2]; gs[0][0][4 * g + 3] = v[3];
                         }
                         dense<1, 1, Ops>(gs, act_lane + (b >> 1) * 32 * LD, (const frag *)a.wT_pe_skip[a.layer[l].stash] + (size_t)(b & 1) * KS * 64 + lane, KS);
@@ -723,7 +726,7 @@ __global__ __launch_bounds__(kThreads, 2) void ddf_rev_kernel(const DdfArgs a)
                     else
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
-                            f32x4v v = ysrc[((mt * NT + t) * 4 + g) * 64];
+                            f32x4v v = stream_get<L2S>(&ysrc[((mt * NT + t) * 4 + g) * 64]);
                             dst[t][4 * g] = v[0]; dst[t][4 * g + 1] = v[1]; dst[t][4 * g + 2] = v[2]; dst[t][4 * g + 3] = v[3];
                         }
                 }
@@ -809,7 +812,7 @@ __global__ __launch_bounds__(kThreads, 2) void ddf_rev_kernel(const DdfArgs a)
             if (parked) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    f32x4v v = gpe_park[(i * 4 + g) * 64];
+                    f32x4v v = stream_get<L2S>(&gpe_park[(i * 4 + g) * 64]);
                     one[0][0][4 * g] = v[0]; one[0][0][4 * g + 1] = v[1]; one[0][0][4 * g + 2] = v[2]; one[0][0][4 * g + 3] = v[3];
                 }
                 dense<1, 1, Ops>(one, act_lane + (b >> 1) * 32 * LD, (const frag *)a.wT_pe0 + (size_t)(b & 1) * KS * 64 + lane, KS);       // g_0 W_0^T
@@ -1481,7 +1484,13 @@ static void launch_ddf_rev_w(const DdfArgs &a, int grid, hipStream_t s)
     constexpr int MT = WID <= 256 ? 2 : 1;
     if (a.operands == 2) launch_ddf_rev_t<MT, OpsF16SplitT<WID>>(a, grid, s);
     else if (a.operands == 1) launch_ddf_rev_t<MT, NEDDF_BF16_REV_OPS<WID>>(a, grid, s);
-    else if (a.operands == 3) launch_ddf_rev_t<MT, OpsF32x3T<WID>>(a, grid, s);      // fp32 data, three-term bf16 products
+    else if (a.operands == 3) {      // fp32 data, three-term bf16 products; kSchedL2ModeShift: the same kernel with an L2 residency mechanism
+        const int l2 = (a.sched_flags >> kSchedL2ModeShift) & 3;
+        if (l2 == 1) launch_ddf_rev_t<MT, OpsF32x3L2T<WID, 1>>(a, grid, s);
+        else if (l2 == 2) launch_ddf_rev_t<MT, OpsF32x3L2T<WID, 2>>(a, grid, s);
+        else if (l2 == 3) launch_ddf_rev_t<MT, OpsF32x3L2T<WID, 3>>(a, grid, s);
+        else launch_ddf_rev_t<MT, OpsF32x3T<WID>>(a, grid, s);
+    }
     else launch_ddf_rev_t<MT, OpsF32T<WID>>(a, grid, s);
 }
 

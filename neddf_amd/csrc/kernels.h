@@ -14,6 +14,10 @@ constexpr int kMaxWidth = 512;
 constexpr int kMaxLayers = 12;
 constexpr int kMaxStash = 4;         // early partials per field: skip connections (+ the NeRF colour head's direction segment)
 constexpr int kSchedInts = 16;          // tile-queue head (+ padding)
+constexpr int kSchedXcd = 8, kSchedXcds = 8;     // ... and behind it one count of started tiles per XCD (tile_inputs.h l2_writeback_tick)
+// DdfArgs::sched_flags of the three-term distance kernel also carries its L2 residency mechanism (NEDDF_X3_L2; inside the flags word, so
+// that the argument block of every kernel keeps its layout): bits 4-5 the mode (1 stream, 2 wb, 3 both), bits 8-20 the write-back period
+constexpr int kSchedL2ModeShift = 4, kSchedL2PeriodShift = 8;
 constexpr int kPtAux = 16;           // floats per point handed from the distance kernel to the colour kernel
 // floats of one stash slot of one workgroup: 4 waves x (MT=4 x NT=2 x 4 float4) x 64 lanes x 4
 constexpr size_t kStashFloatsPerWg = (size_t)kWaves * (4 * 2 * 4) * 64 * 4;
@@ -94,7 +98,7 @@ struct DdfArgs {
     int ks_hidden;                        // super-steps of a width-wide product under this operand policy
     float *rev_scratch;                   // per workgroup: y' of every layer [n_layers][P][width] + encoding Jacobian, copy and parked gradient [P][192]
     int *sched;                           // [0] tile queue head (zeroed before each launch)
-    int sched_flags;                      // bit 1: dynamic tile queue (always set by the library)
+    int sched_flags;                      // bit 1: dynamic tile queue (always set by the library); operands == 3: kSchedL2* below
     float *features;                      // [n_points][feat_rows][width]
     int feat_rows;                        // 1 (value row) or 4 (value + Jacobian rows)
     float *ptaux;                         // [n_points][kPtAux]

@@ -133,6 +133,18 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
     // still prefer the large launch.  So a chunk's distance kernel runs as sub-launches of 2^20 points into the chunk's hand-off, and
     // the colour kernel once over the chunk.  With NEDDF_FIELD_CHUNK_LOG2 set, both kernels take launches of that size as before.
     const int64_t ddf_sub = (use3 && !chunk_env) ? ((int64_t)1 << 20) : ((int64_t)1 << 25);
+    // NEDDF_X3_L2 (read per call: the A/B runs flip it inside one library): an L2 residency mechanism of the three-term distance
+    // kernel (tile_engine.h OpsF32x3L2T) -- `stream` (the default: y' read back non-temporal), `wb` (a write-back every
+    // NEDDF_X3_L2_PERIOD tiles of an XCD, default 16), `both`; `0`: the plain kernel.  The sub-launches above stay: `stream` lifts a
+    // 2^23-point launch from 61 to 69 % hits, the 2^20-point ones from 77 to 82 %, and is faster with them (docs/lab_notebook.md R11.1)
+    int l2_mode = 0, l2_period = 0;
+    if (use3) {
+        const char *e = getenv("NEDDF_X3_L2");
+        l2_mode = !e ? 1 : !strcmp(e, "0") ? 0 : !strcmp(e, "wb") ? 2 : !strcmp(e, "both") ? 3 : 1;
+        const char *r = getenv("NEDDF_X3_L2_PERIOD");
+        const int v = r && *r ? atoi(r) : 16;
+        l2_period = v < 1 ? 1 : (v > 4096 ? 4096 : v);
+    }
     const int64_t chunk_cap = full ? (1 << 19) : ((int64_t)1 << chunk_log2);
     int64_t chunk = N < chunk_cap ? N : chunk_cap;
     // The hand-off of one launch (features + per-point record: 1 088 B per point eval-minimal at width 256, 9.1 GB at 2^23 points,
@@ -178,6 +190,7 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
         a.aux_grad = aux ? aux + off : nullptr;
         a.sched = (int *)ctx->sched.p;
         a.sched_flags = sched_flags();
+        if (l2_mode) a.sched_flags |= (l2_mode << kSchedL2ModeShift) | (l2_period << kSchedL2PeriodShift);
         HIPCHK(hipMemsetAsync(a.sched, 0, kSchedInts * sizeof(int), s));
         if (reverse) {          // one scalar's gradient: reverse mode, 64 or 32 points per tile (field_kernels.hip ddf_rev_kernel)
             const int pts = ddf_rev_points(dt, wid), wgs = ddf_rev_wgs_per_cu(dt, wid) * ctx->cus;

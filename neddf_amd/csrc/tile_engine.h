@@ -343,6 +343,30 @@ struct OpsF32x3T : OpsF32T<WID> {
     }
 };
 
+// The three-term policy with an L2 residency mechanism (NEDDF_X3_L2, neddf_capi.hip field_forward; docs/lab_notebook.md R11.1,
+// profiles/r11_l2_residency.txt).  Its 5.1 MB of forward + transposed weight planes share the 4 MB L2 of an XCD with the distance
+// kernel's write-once / read-once scratch traffic (y' of every layer: 448 KB per workgroup and tile):
+//   bit 0 (`stream`)  the read-back of y' and of the parked encoding gradient -- the last use of those lines -- is non-temporal
+//                     (stream_get below), so the lines leave the L2 first.  The STORES stay plain: non-temporal y' stores cost 1.5 - 2 %
+//                     of the kernel, non-temporal hand-off stores gain nothing measurable.  The weight fragments keep the default policy
+//   bit 1 (`wb`)      every NEDDF_X3_L2_PERIOD tiles of an XCD one wave writes that XCD's dirty lines back (l2_writeback_tick): measured
+//                     slower and with MORE misses; kept as the A/B partner that settles what a launch boundary's write-back is worth
+// A policy type of its own: the plain OpsF32x3T kernels and every other policy's stay instruction-identical.
+template <int WID, int L2>
+struct OpsF32x3L2T : OpsF32x3T<WID> {
+    static constexpr int kL2 = L2;
+};
+template <class Ops> constexpr int kL2Of = 0;
+template <int WID, int L2> constexpr int kL2Of<OpsF32x3L2T<WID, L2>> = L2;
+
+// 16 bytes the L2 need not keep once they are read (NT = false: the plain load, as everywhere else)
+template <bool NT>
+__device__ __forceinline__ f32x4v stream_get(const f32x4v *p)
+{
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+
 // the same policy over a narrow side tile (the encoding kept in LDS for the skip layers): 64 columns + 8 of padding per row, i.e. a row
 // stride of 36 dwords -- 16 rows x 16-byte fragments tile the 64 banks exactly
 constexpr int kEncLd = 72;

@@ -163,4 +163,16 @@ __device__ __forceinline__ int sched_next(int *sched, int flags, int64_t tile)
     return (flags & 2) ? atomicAdd(&sched[0], 1) : (int)(tile + gridDim.x);
 }
 
+// The `wb` mechanism of the three-term distance kernel (tile_engine.h OpsF32x3L2T), called once per tile and workgroup: the tiles an XCD
+// starts are counted in sched[kSchedXcd + XCC_ID] (zeroed with the queue head), and the wave whose tile completes a period of `period`
+// writes that XCD's dirty L2 lines back (an agent-scope release: buffer_wbl2 + the wave's own vmcnt wait).  Not a rendezvous: nobody
+// waits for another workgroup, and no value depends on it.
+__device__ __forceinline__ void l2_writeback_tick(int *sched, int period, int tid)
+{
+    if (tid == 0 && period > 0) {
+        const int xcc = (int)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & (kSchedXcds - 1));
+        if ((atomicAdd(&sched[kSchedXcd + xcc], 1) + 1) % period == 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    }
+}
+
 }  // namespace neddf
