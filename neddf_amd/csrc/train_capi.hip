@@ -35,7 +35,7 @@ constexpr int kLdPe = 64, kLdDir = 64, kLdNarrow = 4;      // row strides of the
 // product cut into 256 x 256 blocks instead of the 512-wide fused chains (round 5: mlp_forward_kernel / mlp_backward_kernel / mlp_backward_split_kernel
 // over the width on 32-row tiles, point-major [R, 512] matrices, one weight-gradient launch per 256 x 256 block).  Measured (NeDDF
 // 8 + 4 layers, 265 k points, forward + backward): 131 ms fused against 162 ms blocked -- after the first version, whose weight
-// gradients went through the job-parallel launch, had taken 373 ms (see wide_dw_jobs); split fp16: 71 against 124 ms.
+// gradients went through the job-parallel launch, had taken 373 ms (see add_dw); split fp16: 71 against 124 ms.
 bool wide_fused()
 {
     static const bool on = [] { const char *e = getenv("NEDDF_TRAIN_WIDE_FUSED"); return !(e && atoi(e) == 0); }();
@@ -44,10 +44,8 @@ bool wide_fused()
 
 // Weight gradients: the 256-wide routes (fp32 and split fp16) take the job-parallel launch (dw_jobs_kernel / dw_split_jobs_kernel: one launch
 // per pass; fp32 39.1 against 39.7 ms per step, split fp16 +1 %), the 512-wide fused routes one launch per 256 x 256 block (the job-parallel
-// launch measured 6x slower with their 46 blocks).  The A/B switches of rounds 4-5 left with round 6's pruning (docs/lab_notebook.md R5.18-R5.19).
-static constexpr bool dw_jobs_256() { return true; }
-static constexpr bool wide_dw_jobs() { return false; }
-static constexpr bool split_dw_jobs() { return true; }
+// launch measured 6x slower with their 46 blocks): add_dw in the NeDDF backward pass.  The A/B switches of rounds 4-5 left with round 6's
+// pruning (docs/lab_notebook.md R5.18-R5.19).
 
 // NEDDF_TRAIN_SPLIT_FUSED=0: the split-fp16 policy's backward pass as one GEMM kernel per layer on row-major matrices (rounds 1-4)
 // instead of the fused input-gradient chains on point-major ones (round 5: mlp_backward_split_kernel)
@@ -867,10 +865,13 @@ static int field_backward(neddf_ctx *ctx, int slot, const float *const *W, const
         };
         // one 256 x 256 (or K x 256) weight-gradient product: G is a 256-column block of a point-major gradient matrix
         auto add_dw = [&](const float *X, int ldx, int K, int x_pm, const float *G, const float *amax_g, float *dW, int nvalid, float *db) {
-            if (sp && (!split_dw_jobs() || WH != kWidth)) { launch_dw(1, X, ldx, K, G, WH, p.R, dW, WH, 1, nvalid, db, 4, ctx->cus, s, amax_g, am.dw_tmp, x_pm, 1); return; }
-            // 512 columns (fp32 probe route): one launch per 256 x 256 block -- the job-parallel launch spreads 46 blocks of 2.2 GB
-            // matrices over 8 workgroups each and ran at a sixth of its speed (287 ms per step against 45 ms of products)
-            if (!sp && ((WH != kWidth && !wide_dw_jobs()) || (WH == kWidth && !dw_jobs_256()))) { launch_dw(0, X, ldx, K, G, WH, p.R, dW, WH, 1, nvalid, db, 4, ctx->cus, s, nullptr, nullptr, x_pm, 1); return; }
+            // 512 columns: one launch per 256 x 256 block -- the job-parallel launch spreads 46 blocks of 2.2 GB matrices over 8 workgroups
+            // each and ran at a sixth of its speed (fp32 probe route: 287 ms per step against 45 ms of products)
+            if (WH != kWidth) {
+                if (sp) launch_dw(1, X, ldx, K, G, WH, p.R, dW, WH, 1, nvalid, db, 4, ctx->cus, s, amax_g, am.dw_tmp, x_pm, 1);
+                else launch_dw(0, X, ldx, K, G, WH, p.R, dW, WH, 1, nvalid, db, 4, ctx->cus, s, nullptr, nullptr, x_pm, 1);
+                return;
+            }
             if (dwj.n == kMaxDwJobs) { flush_dw(); dwj.n = 0; }        // (every G in the list has been produced: the jobs follow their chain)
             dwj.add(X, ldx, K, x_pm, G, WH, dW, WH, 1, nvalid, db, 4);
             dwj.job[dwj.n - 1].amax_g = amax_g;

@@ -93,15 +93,15 @@ void launch_mlp_forward(int split, const MlpForwardArgs &a, int cus, hipStream_t
 // launch_mlp_forward: the 64-row tile of gradients stays in LDS from the top layer down,
 //   dZ_{l-1} = act_backward(Z_{l-1}; dZ_l x (hidden rows of W_l)^T)          l = n_layers-1 .. 1
 // (LinearGradFunction.backward linear.py:62-74 followed by the activation's backward, e.g. tanh_exp.py:57-88), and every dZ_l
-// is left in its own [R, 256] matrix for the weight-gradient products that follow.  EVERY [R, 256] matrix of this kernel (dZtop, top_src,
+// is left in its own [R, 256] matrix for the weight-gradient products that follow.  EVERY [R, 256] matrix of this kernel (top_src,
 // top_Z, top_out, Z, dZ) is in the POINT-MAJOR layout (MlpForwardArgs.point_major).  Per row and layer the chain reads Z_{l-1}
 // and writes dZ_{l-1} (2 KB) where one GEMM kernel per layer also re-read dZ_l (3 KB), and there is no per-layer launch, fill and
 // drain.  The activation backward runs on the accumulators themselves: in the 32x32 layout a lane holds the four rows of a point
-// for one feature, and Z_{l-1} is requested in that layout before the product.  fp32 MFMA operands (the split-fp16 policy
-// keeps the per-layer route: its gradient operands are range-scaled per matrix).
+// for one feature, and Z_{l-1} is requested in that layout before the product.  fp32 MFMA operands, or (round 5) split-fp16
+// operands range-scaled per tile: see `amax_dZ` below.
 struct MlpBackwardArgs {
     int64_t R;
-    const float *dZtop;                   // [R, 256]: gradient of the top layer's pre-activations -- or NULL: formed in the kernel's prologue,
+    // the gradient of the top layer's pre-activations is formed in the kernel's prologue,
     //   dZ_top = act_backward(Z_top; top_src x top_wT + sum_c top_G[:, c] top_w[c][:])     and left in top_out for its weight gradient:
     const float *top_src, *top_wT;        // optional [R, 256] matrix and packed 256 x 256 weights (the colour trunk's gradient of the features)
     const float *top_G; int top_ldg, top_nc;              // narrow upstream gradient [R, top_ldg], top_nc <= 3 columns (the heads' raw outputs)
@@ -113,7 +113,7 @@ struct MlpBackwardArgs {
     const float *Z[kMaxLayers];           // pre-activations [R, 256]; l = 0 .. n_layers-2 are read
     float *dZ[kMaxLayers];                // outputs [R, 256], l = 0 .. n_layers-2
     int act_kind;                         // backward kind of act_grad2 (0 ReLU, 1 LeakyReLU, 2 tanhExp, 3 tanhExp as NeuS differentiates it)
-    // split-fp16 policy (launch_mlp_backward(split = 1, ...), prologue form only): top_wT / wT are split-packed, every product's gradient
+    // split-fp16 policy (launch_mlp_backward(split = 1, ...)): top_wT / wT are split-packed, every product's gradient
     // operand is range-scaled per 64-row tile inside the kernel, and each gradient matrix leaves max |dZ| in a device scalar for the
     // weight-gradient products that follow (launch_dw's amax_g); NULL slots are skipped
     float *amax_dZ[kMaxLayers];           // for dZ[l]
@@ -136,7 +136,7 @@ struct DwJob {
     float *dW; int64_t sk, sn; int nvalid;
     float *db; int bias_period;           // db[n] += sum over rows r % bias_period == 0 of G[r, n] (or NULL)
     int x_point_major;                    // X is a point-major [R, 256] matrix (MlpForwardArgs.point_major); G always is, R % 4 == 0
-    int wg0;                              // first workgroup of the product (set by launch_dw_jobs)
+    int wg0;                              // first workgroup of the product (set by dw_partition)
     // split-fp16 policy (launch_dw_split_jobs): max |G| of the gradient matrix (device scalar, or NULL) and a zeroed [256, 256] scratch
     // the range-scaled product lands in before it is added to dW divided by the scale
     const float *amax_g;
@@ -158,6 +158,34 @@ struct DwJobs {
         else overflow = true;
     }
 };
+// Relative cost of one product of K input columns, by policy.
+// fp32: matrix work ~ K, plus the streaming of G that every product pays (the constant = the staging / streaming share of a chunk,
+// ~a quarter of a 256-wide product's time; measured flat between 32 and 192)
+inline float dw_cost_f32(int K) { return 64.0f + (float)(K <= 64 ? 64 : K <= 96 ? 96 : 256); }
+// split fp16: the staging of G (256 columns split into two fp16 terms per chunk, whatever K) outweighs the matrix work: measured per
+// launch 0.226 / 0.258 / 0.346 ms for K <= 64 / <= 96 / 256 (profiles/r05_train_step_kernel_stats_f16_split_fused.csv) -- with the fp32
+// route's weights (128 : 160 : 320) the narrow products finished 1.6x late and the launch was 4.4 ms SLOWER than one launch per product
+inline float dw_cost_split(int K) { return K <= 64 ? 226.0f : K <= 96 ? 258.0f : 346.0f; }
+// The workgroups of a job-parallel launch, divided among the products in proportion to their cost: sets every job's wg0 and returns the
+// grid, max(cus, n) or less.  Every job gets at least one workgroup -- each share is clamped from below to 1 and from above to what
+// leaves one for each job still to come --, since a job without one would leave its weight gradient silently at zero
+// (tests/test_dw_partition.py sweeps the rule).
+inline int dw_partition(DwJobs &jobs, float (*cost_of)(int K), int cus)
+{
+    float cost[kMaxDwJobs], total = 0.f;
+    for (int i = 0; i < jobs.n; ++i) { cost[i] = cost_of(jobs.job[i].K); total += cost[i]; }
+    const int grid = cus > jobs.n ? cus : jobs.n;
+    int at = 0;
+    for (int i = 0; i < jobs.n; ++i) {
+        jobs.job[i].wg0 = at;
+        int share = (int)(cost[i] / total * grid + 0.5f);
+        if (share < 1) share = 1;
+        const int left = jobs.n - 1 - i;
+        if (at + share > grid - left) share = grid - left - at;
+        at += share;
+    }
+    return at;
+}
 void launch_dw_jobs(DwJobs &jobs, int cus, hipStream_t s);
 // the same list under the split-fp16 policy (round 5): three fp16 MFMAs per multiply-add on operands of two fp16 terms, G range-scaled by
 // its job's amax_g; `tmp` = jobs.n x [256, 256] floats of scratch (zeroed here), one unscale-and-add pass over all jobs at the end

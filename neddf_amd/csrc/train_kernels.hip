@@ -4,8 +4,11 @@
 // points), so that the forward pass leaves behind exactly what the hand-written
 // backward passes of the reference need (neddf/nn_module/with_grad/*.py backward
 // staticmethods).  The NeDDF forward runs its two layer stacks fused (mlp_forward_kernel,
-// round 2: the inference tile engine with side stores of Z_l / H_l); the backward pass
-// and the NeRF / NeuS fields are one kernel per layer.  All dense work -- forward layers, dX = dZ W^T and the weight
+// round 2: the inference tile engine with side stores of Z_l / H_l; NeuS' sdf trunk takes it too),
+// and the NeDDF backward pass runs one fused input-gradient chain per stack (mlp_backward_kernel,
+// round 3; mlp_backward_split_kernel, round 5) followed by the weight-gradient products.  NeRF, the
+// NeuS backward pass and the NEDDF_TRAIN_UNFUSED / _SPLIT_FUSED=0 / _WIDE_FUSED=0 routes are one
+// kernel per layer (rows_gemm_kernel).  All dense work -- forward layers, dX = dZ W^T and the weight
 // gradient dW = X^T dZ -- runs on the same fp32 MFMA tile engine as the fused
 // inference kernels; the elementwise pieces reuse device_math.h.  Training batches
 // are ~10^5 points, two orders of magnitude below a rendered frame, so the extra
@@ -22,6 +25,38 @@
 #include <type_traits>
 
 namespace neddf {
+
+// ----------------------------------------------------------------------------
+// Launch vocabulary of this file.
+// A kernel with dynamic LDS: the first launch of each instantiation (once per process) raises the kernel's limit to `lds`, which is
+// the same at every launch of that instantiation.  `lds` must be a constant of the instantiation (every caller passes a constexpr
+// of the kernel's template arguments): the limit is taken from the first call only, a later larger size would exceed it.
+template <auto Kernel, class... A>
+static void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args)
+{
+    static bool once = ((void)hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
+    (void)once;
+    hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+}
+// run-time activation kind of the backward passes (act_grad2 below: 0..3) -> f(std::integral_constant<int, kind>)
+template <class F>
+__host__ __device__ __forceinline__ void with_act_kind(int kind, F &&f)
+{
+    if (kind == 0) f(std::integral_constant<int, 0>{});
+    else if (kind == 1) f(std::integral_constant<int, 1>{});
+    else if (kind == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 3>{});
+}
+// shape of one weight-gradient product (dw_tile_rows / dw_split_rows) -> f(k-tiles that carry data, X point-major): a point-major X is
+// a hidden state, 8 k-tiles; a row-major X is a narrow first-layer input of 2 (K <= 64), 3 (K <= 96) or 8 k-tiles
+template <class F>
+__host__ __device__ __forceinline__ void with_dw_shape(int x_point_major, int K, F &&f)
+{
+    if (x_point_major) f(std::integral_constant<int, 8>{}, std::true_type{});
+    else if (K <= 64) f(std::integral_constant<int, 2>{}, std::false_type{});
+    else if (K <= 96) f(std::integral_constant<int, 3>{}, std::false_type{});
+    else f(std::integral_constant<int, 8>{}, std::false_type{});
+}
 
 // ----------------------------------------------------------------------------
 // second derivative of the hidden activations as the reference's backward passes define it
@@ -44,17 +79,34 @@ __device__ __forceinline__ void act_grad2(float x, float &dy, float &d2)
 }
 constexpr int kActTanhExpPlain2 = 3;       // backward-only kind id: tanhExp with the second derivative above
 
+// {ReLU,LeakyReLU,TanhExp}GradFunction.backward on the four rows (value, d/dx, d/dy, d/dz) of one point and feature, as the fused
+// chains hold them: elements q .. q + 3 of a 32x32 accumulator, pre-activations z, upstream gradient g -> ov
+// (dLdx = dLdy y' + sum_i dLdG_i J_i y'', dLdJ_i = dLdG_i y').  The library builds with -ffp-contract=off: this expression tree, the
+// order of the sum included, IS the result.
+template <int KIND>
+__device__ __forceinline__ void act_backward_rows(const f32x16 &z, const f32x16 &g, int q, float (&ov)[4])
+{
+    float dy, d2;
+    act_grad2<KIND>(z[q], dy, d2);
+    const float g0 = g[q], g1 = g[q + 1], g2 = g[q + 2], g3 = g[q + 3];
+    float sj = g1 * z[q + 1];
+    sj += g2 * z[q + 2];
+    sj += g3 * z[q + 3];
+    ov[0] = g0 * dy + sj * d2; ov[1] = g1 * dy; ov[2] = g2 * dy; ov[3] = g3 * dy;
+}
+
 // Backward of one activation on a 4-row group of 4 columns, in place on g (the upstream gradient of the group):
-// period 4 = {ReLU,LeakyReLU,TanhExp}GradFunction.backward (dLdx = dLdy y' + sum_i dLdG_i J_i y'', dLdJ_i = dLdG_i y');
+// period 4 = the expression tree of act_backward_rows, the kind chosen at run time;
 // period 1 = the plain activations of NeRF (F.relu / F.leaky_relu / tanhExp, nerf.py:71-79; derivative at 0 as torch's)
 __device__ __forceinline__ void act_backward_group(int kind, int period, const f32x4v (&z)[4], f32x4v (&g)[4])
 {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         if (period == 4) {
+            // (written out around the run-time dispatch: with the whole of it behind the dispatch, rows_gemm_kernel<2> spilled one
+            // register more and narrow_backward_act_kernel lost a wave of occupancy)
             float dy, d2;
-            if (kind == 0) act_grad2<0>(z[0][u], dy, d2); else if (kind == 1) act_grad2<1>(z[0][u], dy, d2);
-            else if (kind == 2) act_grad2<2>(z[0][u], dy, d2); else act_grad2<3>(z[0][u], dy, d2);
+            with_act_kind(kind, [&](auto k) { act_grad2<decltype(k)::value>(z[0][u], dy, d2); });
             float s = g[1][u] * z[1][u];
             s += g[2][u] * z[2][u];
             s += g[3][u] * z[3][u];
@@ -88,20 +140,17 @@ __device__ __forceinline__ float operand_scale_of(float amax)
     shift = shift > 100 ? 100 : (shift < -100 ? -100 : shift);
     return __builtin_bit_cast(float, (unsigned int)(127 + shift) << 23);
 }
-__device__ __forceinline__ float operand_scale(const float *amax)
-{
-    if (!amax) return 1.0f;
-    const int e = (int)((__builtin_bit_cast(unsigned int, *amax) >> 23) & 0xffu);       // biased exponent of the maximum
-    if (e == 0 || e == 255) return 1.0f;            // zero / denormal / non-finite: leave the operand alone
-    int shift = 13 + 127 - e;
-    shift = shift > 100 ? 100 : (shift < -100 ? -100 : shift);
-    return __builtin_bit_cast(float, (unsigned int)(127 + shift) << 23);
-}
+__device__ __forceinline__ float operand_scale(const float *amax) { return amax ? operand_scale_of(*amax) : 1.0f; }      // (NULL: unscaled)
 __device__ __forceinline__ float pow2_inverse(float p) { return __builtin_bit_cast(float, (254u << 23) - __builtin_bit_cast(unsigned int, p)); }
-__device__ __forceinline__ void publish_amax(float *amax_out, float lmax)       // all lanes of the wave call this
+__device__ __forceinline__ float wave_max(float v)       // all lanes of the wave call this
 {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off, 64));
+    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+__device__ __forceinline__ void publish_amax(float *amax_out, float lmax)       // all lanes of the wave call this
+{
+    lmax = wave_max(lmax);
     // Non-negative floats order like ints.  Hundreds of thousands of waves share the scalar: look first (a stale, smaller value
     // only costs an unnecessary atomic) so that all but the first few skip the same-address atomic, which serialises in L2.
     if ((threadIdx.x & 63) == 0 && lmax > *(volatile const float *)amax_out) atomicMax((int *)amax_out, __builtin_bit_cast(int, lmax));
@@ -259,18 +308,14 @@ static void launch_rows_gemm_ops(int mode, const float *X, int64_t R, int ldx, i
 {
     constexpr size_t kOpd = (size_t)64 * Ops::kLd * sizeof(typename Ops::act_t), kRes = (size_t)64 * kActLd * sizeof(float);
     constexpr size_t lds = kOpd > kRes ? kOpd : kRes;
-    static bool once = ((void)hipFuncSetAttribute((const void *)rows_gemm_kernel<0, Ops>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                        (void)hipFuncSetAttribute((const void *)rows_gemm_kernel<1, Ops>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                        (void)hipFuncSetAttribute((const void *)rows_gemm_kernel<2, Ops>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
-    (void)once;
     int64_t tiles = (R + 63) / 64;
-    int grid = (int)(tiles < 2 * cus ? tiles : 2 * cus);
+    const dim3 grid((unsigned)(tiles < 2 * cus ? tiles : 2 * cus)), block(kThreads);
     if (mode == 1)
-        hipLaunchKernelGGL((rows_gemm_kernel<1, Ops>), dim3(grid), dim3(kThreads), lds, s, X, R, ldx, kload, wp, ksteps, bias, period, Y, ldy, accumulate, act_kind, H, amax_in, amax_out);
+        launch_lds<rows_gemm_kernel<1, Ops>>(grid, block, lds, s, X, R, ldx, kload, wp, ksteps, bias, period, Y, ldy, accumulate, act_kind, H, amax_in, amax_out);
     else if (mode == 2)
-        hipLaunchKernelGGL((rows_gemm_kernel<2, Ops>), dim3(grid), dim3(kThreads), lds, s, X, R, ldx, kload, wp, ksteps, bias, period, Y, ldy, accumulate, act_kind, H, amax_in, amax_out);
+        launch_lds<rows_gemm_kernel<2, Ops>>(grid, block, lds, s, X, R, ldx, kload, wp, ksteps, bias, period, Y, ldy, accumulate, act_kind, H, amax_in, amax_out);
     else
-        hipLaunchKernelGGL((rows_gemm_kernel<0, Ops>), dim3(grid), dim3(kThreads), lds, s, X, R, ldx, kload, wp, ksteps, bias, period, Y, ldy, accumulate, -1, nullptr, amax_in, amax_out);
+        launch_lds<rows_gemm_kernel<0, Ops>>(grid, block, lds, s, X, R, ldx, kload, wp, ksteps, bias, period, Y, ldy, accumulate, -1, (float *)nullptr, amax_in, amax_out);
 }
 
 static void launch_rows_gemm_mode(int mode, int split, const float *X, int64_t R, int ldx, int kload, const float *wp, int ksteps,
@@ -480,10 +525,8 @@ static void launch_mlp_forward_ops(const MlpForwardArgs &a, int cus, hipStream_t
 {
     constexpr int ROWS = Ops::kWid <= 256 ? 64 : 32;
     constexpr size_t lds = (size_t)ROWS * Ops::kLd * sizeof(typename Ops::act_t);
-    static bool once = ((void)hipFuncSetAttribute((const void *)mlp_forward_kernel<Ops, HOLD, PM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
-    (void)once;
     const int64_t tiles = (a.R + ROWS - 1) / ROWS;
-    hipLaunchKernelGGL((mlp_forward_kernel<Ops, HOLD, PM>), dim3((unsigned)(tiles < 2 * cus ? tiles : 2 * cus)), dim3(kThreads), lds, s, a);
+    launch_lds<mlp_forward_kernel<Ops, HOLD, PM>>(dim3((unsigned)(tiles < 2 * cus ? tiles : 2 * cus)), dim3(kThreads), lds, s, a);
 }
 
 void launch_mlp_forward(int split, const MlpForwardArgs &a, int cus, hipStream_t s)
@@ -503,6 +546,59 @@ void launch_mlp_forward(int split, const MlpForwardArgs &a, int cus, hipStream_t
 // ----------------------------------------------------------------------------
 // Fused input-gradient chain of a layer stack (train_kernels.h MlpBackwardArgs): see the header.  64-row tiles, two workgroups
 // per CU, fp32 MFMA.
+
+// Two pieces of the chain's prologue and layer loop.  The split-fp16 chain below keeps its own copies inside its kernel: called from
+// there, each of these functions cost mlp_backward_split_kernel<*, 256> 3 to 10 more spilled registers, while this chain spills
+// fewer with them than with the same code written out in the kernel (profiles/r12_train_refactor.txt).
+// Z of this lane's accumulator positions: the four rows of a point for one feature = one 16-byte load in the point-major layout
+// (rows past R: zero; R is a multiple of 4)
+template <int W, int MT, int NT>
+__device__ __forceinline__ void load_z(const float *Z, int64_t r0, int64_t R, int wave, int lane, f32x16 (&zp)[MT][NT])
+{
+    const int j = lane & 31, h = lane >> 5;
+    const float *zb = Z + ((r0 >> 2) + h) * (4 * W) + (wave * NT * 32 + j) * 4;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4v v = { 0.f, 0.f, 0.f, 0.f };
+                if (r0 + mt * 32 + 8 * g + 4 * h < R) v = __builtin_nontemporal_load((const f32x4v *)(zb + (mt * 8 + 2 * g) * (4 * W) + t * 128));
+#pragma unroll
+                for (int r = 0; r < 4; ++r) zp[mt][t][4 * g + r] = v[r];
+            }
+}
+// the heads' share of the top gradient (MlpBackwardArgs top_G / top_w) on this lane's accumulator positions:
+// acc += sum_c top_G[row, c] top_w[c][feature], c in ascending order
+template <int MT, int NT>
+__device__ __forceinline__ void add_head_gradient(const MlpBackwardArgs &a, int64_t r0, int wave, int lane, f32x16 (&acc)[MT][NT])
+{
+    const int j = lane & 31, h = lane >> 5;
+    float hw[3][NT];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) hw[c][t] = c < a.top_nc ? a.top_w[c][(size_t)(wave * NT * 32 + t * 32 + j) * a.top_wstride] : 0.f;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t row = r0 + mt * 32 + 8 * g + 4 * h + r;
+                float gv[3] = { 0.f, 0.f, 0.f };
+                if (row < a.R)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        if (c < a.top_nc) gv[c] = a.top_G[row * a.top_ldg + c];
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc[mt][t][4 * g + r] = fmaf(gv[c], hw[c][t], acc[mt][t][4 * g + r]);
+            }
+}
+
 template <int KIND, int W = kWidth, int MT = 2, int NT = 2>
 __device__ __forceinline__ void mlp_backward_epilogue(const f32x16 (&acc)[MT][NT], const f32x16 (&zp)[MT][NT], float *act, float *dZl, int64_t r0,
                                                       int64_t R, int wave, int lane)
@@ -518,13 +614,8 @@ __device__ __forceinline__ void mlp_backward_epilogue(const f32x16 (&acc)[MT][NT
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 // rows 8 g + 4 h + {0, 1, 2, 3} of the tile = (value, d/dx, d/dy, d/dz) of one point, one feature
-                float dy, d2;
-                act_grad2<KIND>(zp[mt][t][4 * g], dy, d2);
-                const float g0 = acc[mt][t][4 * g], g1 = acc[mt][t][4 * g + 1], g2 = acc[mt][t][4 * g + 2], g3 = acc[mt][t][4 * g + 3];
-                float sj = g1 * zp[mt][t][4 * g + 1];
-                sj += g2 * zp[mt][t][4 * g + 2];
-                sj += g3 * zp[mt][t][4 * g + 3];
-                const float ov[4] = { g0 * dy + sj * d2, g1 * dy, g2 * dy, g3 * dy };
+                float ov[4];
+                act_backward_rows<KIND>(zp[mt][t], acc[mt][t], 4 * g, ov);
                 if (r0 + mt * 32 + 8 * g + 4 * h < R)
                     __builtin_nontemporal_store(f32x4v{ ov[0], ov[1], ov[2], ov[3] }, (f32x4v *)(gb + (mt * 8 + 2 * g) * (4 * W) + t * 128));
 #pragma unroll
@@ -544,7 +635,6 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_backward_kernel(const MlpBack
     float *act = smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float *act_lane = act_lane_ptr<Ops>(act, lane);
-    const int j = lane & 31, h = lane >> 5;
     const int64_t ntiles = (a.R + ROWS - 1) / ROWS;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t r0 = tile * ROWS;
@@ -558,29 +648,11 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_backward_kernel(const MlpBack
                 for (int q = 0; q < 4; ++q) act[(4 * p + q) * LD + c] = v[q];
             }
         };
-        // Z of this lane's accumulator positions: the four rows of a point for one feature = one 16-byte load in the point-major layout
-        auto load_z = [&](const float *Z, f32x16 (&zp)[MT][NT]) {
-            const float *zb = Z + ((r0 >> 2) + h) * (4 * W) + (wave * NT * 32 + j) * 4;
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        f32x4v v = { 0.f, 0.f, 0.f, 0.f };
-                        if (r0 + mt * 32 + 8 * g + 4 * h < a.R) v = __builtin_nontemporal_load((const f32x4v *)(zb + (mt * 8 + 2 * g) * (4 * W) + t * 128));
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) zp[mt][t][4 * g + r] = v[r];
-                    }
-        };
-        if (a.dZtop) {
-            stage(a.dZtop);
-            __syncthreads();
-        } else {
+        {
             // prologue: the top layer's gradient is formed here instead of by two more passes over HBM (a plain GEMM kernel for the
             // colour trunk's feature gradient + a kernel that adds the heads and applies the top activation's backward)
             f32x16 zp[MT][NT], acc[MT][NT];
-            load_z(a.top_Z, zp);
+            load_z<W>(a.top_Z, r0, a.R, wave, lane, zp);
             acc_init<MT, NT, false>(acc, nullptr, wave, lane);
             if (a.top_src) {
                 stage(a.top_src);
@@ -588,35 +660,14 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_backward_kernel(const MlpBack
                 dense<MT, NT, Ops>(acc, act_lane, (const frag *)a.top_wT + (size_t)wave * NT * KS * 64 + lane, KS);
                 __syncthreads();        // every wave finished reading the staged matrix
             }
-            float hw[3][NT];
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-#pragma unroll
-                for (int t = 0; t < NT; ++t) hw[c][t] = c < a.top_nc ? a.top_w[c][(size_t)(wave * NT * 32 + t * 32 + j) * a.top_wstride] : 0.f;
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int64_t row = r0 + mt * 32 + 8 * g + 4 * h + r;
-                        float gv[3] = { 0.f, 0.f, 0.f };
-                        if (row < a.R)
-#pragma unroll
-                            for (int c = 0; c < 3; ++c)
-                                if (c < a.top_nc) gv[c] = a.top_G[row * a.top_ldg + c];
-#pragma unroll
-                        for (int t = 0; t < NT; ++t)
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) acc[mt][t][4 * g + r] = fmaf(gv[c], hw[c][t], acc[mt][t][4 * g + r]);
-                    }
+            add_head_gradient(a, r0, wave, lane, acc);
             mlp_backward_epilogue<KIND, W, MT, NT>(acc, zp, act, a.top_out, r0, a.R, wave, lane);
             __syncthreads();
         }
         for (int l = a.n_layers - 1; l >= 1; --l) {
-            // Z_{l-1} of this lane's accumulator positions, requested before the product (rows past R: zero; R is a multiple of 4)
+            // Z_{l-1} of this lane's accumulator positions, requested before the product
             f32x16 zp[MT][NT];
-            load_z(a.Z[l - 1], zp);
+            load_z<W>(a.Z[l - 1], r0, a.R, wave, lane, zp);
             __builtin_amdgcn_sched_barrier(0);
             f32x16 acc[MT][NT];
             acc_init<MT, NT, false>(acc, nullptr, wave, lane);
@@ -652,11 +703,6 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_backward_split_kernel(const M
     const act_t *act_lane = act_lane_ptr<Ops>(act, lane);
     const int j = lane & 31, h = lane >> 5;
     const int64_t ntiles = (a.R + ROWS - 1) / ROWS;
-    auto wave_max = [&](float v) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-        return v;
-    };
     auto publish = [&](float *amax_out, float wmax) {       // (see publish_amax: look first, most waves skip the same-address atomic)
         if (amax_out && lane == 0 && wmax > *(volatile const float *)amax_out) atomicMax((int *)amax_out, __builtin_bit_cast(int, wmax));
     };
@@ -664,8 +710,8 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_backward_split_kernel(const M
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t r0 = tile * ROWS;
         __syncthreads();                // the previous tile is done with the LDS tile (and with smax)
-        // Z of this lane's accumulator positions: the four rows of a point for one feature = one 16-byte load in the point-major layout
-        auto load_z = [&](const float *Z, f32x16 (&zp)[MT][NT]) {
+        // this kernel's written-out copy of load_z<W, MT, NT> above (a change to either goes into both; why a copy: see there)
+        auto load_z_here = [&](const float *Z, f32x16 (&zp)[MT][NT]) {
             const float *zb = Z + ((r0 >> 2) + h) * (4 * W) + (wave * NT * 32 + j) * 4;
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
@@ -690,13 +736,8 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_backward_split_kernel(const M
                 for (int t = 0; t < NT; ++t)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        float dy, d2;
-                        act_grad2<KIND>(zp[mt][t][4 * g], dy, d2);
-                        const float g0 = acc[mt][t][4 * g], g1 = acc[mt][t][4 * g + 1], g2 = acc[mt][t][4 * g + 2], g3 = acc[mt][t][4 * g + 3];
-                        float sj = g1 * zp[mt][t][4 * g + 1];
-                        sj += g2 * zp[mt][t][4 * g + 2];
-                        sj += g3 * zp[mt][t][4 * g + 3];
-                        const float ov[4] = { g0 * dy + sj * d2, g1 * dy, g2 * dy, g3 * dy };
+                        float ov[4];
+                        act_backward_rows<KIND>(zp[mt][t], acc[mt][t], 4 * g, ov);
                         const bool in = r0 + mt * 32 + 8 * g + 4 * h < a.R;
                         if (in) __builtin_nontemporal_store(f32x4v{ ov[0], ov[1], ov[2], ov[3] }, (f32x4v *)(gb + (mt * 8 + 2 * g) * (4 * W) + t * 128));
 #pragma unroll
@@ -722,7 +763,7 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_backward_split_kernel(const M
         {
             // prologue: the top layer's gradient (MlpBackwardArgs: top_src x top_wT + the narrow heads, then the top activation's backward)
             f32x16 zp[MT][NT], acc[MT][NT];
-            load_z(a.top_Z, zp);
+            load_z_here(a.top_Z, zp);
             acc_init<MT, NT, false>(acc, nullptr, wave, lane);
             float unscale = 1.0f / Ops::kWScale;
             if (a.top_src) {
@@ -794,7 +835,7 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_backward_split_kernel(const M
         }
         for (int l = a.n_layers - 1; l >= 1; --l) {
             f32x16 zp[MT][NT];
-            load_z(a.Z[l - 1], zp);
+            load_z_here(a.Z[l - 1], zp);
             __builtin_amdgcn_sched_barrier(0);
             f32x16 acc[MT][NT];
             acc_init<MT, NT, false>(acc, nullptr, wave, lane);
@@ -819,70 +860,29 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_backward_split_kernel(const M
     }
 }
 
+// Ops: the policy at the width of the stack's matrices (tile rows, LDS tile and grid as in launch_mlp_forward_ops)
+template <class Ops>
+static void launch_mlp_backward_ops(const MlpBackwardArgs &a, int cus, hipStream_t s)
+{
+    constexpr int W = Ops::kWid, ROWS = W <= 256 ? 64 : 32;
+    constexpr bool SPLIT = Ops::kPlanes == 2;
+    constexpr size_t lds = (size_t)ROWS * Ops::kLd * sizeof(typename Ops::act_t) + (SPLIT ? 16 * sizeof(float) : 0);      // split: + smax
+    const int64_t tiles = (a.R + ROWS - 1) / ROWS;
+    const dim3 grid((unsigned)(tiles < 2 * cus ? tiles : 2 * cus));
+    with_act_kind(a.act_kind, [&](auto kind) {
+        constexpr int KIND = decltype(kind)::value;
+        if constexpr (SPLIT) launch_lds<mlp_backward_split_kernel<KIND, W>>(grid, dim3(kThreads), lds, s, a);
+        else launch_lds<mlp_backward_kernel<KIND, W>>(grid, dim3(kThreads), lds, s, a);
+    });
+}
+
 void launch_mlp_backward(int split, const MlpBackwardArgs &a, int cus, hipStream_t s)
 {
-    if (a.R <= 0 || (a.n_layers < 2 && a.dZtop)) return;         // a one-layer stack still has a prologue to run
-    if (split && a.dZtop) {             // a caller's error, not a data condition: the split chain exists in its prologue form only
-        fprintf(stderr, "neddf: launch_mlp_backward(split = 1) takes the top gradient through top_G / top_src, not dZtop\n");
-        abort();
-    }
-    if (split && a.width == 512) {      // wide fields under the split policy (round 5)
-        constexpr size_t lds5 = (size_t)32 * OpsF16SplitT<512>::kLd * sizeof(OpsF16Split::act_t) + 16 * sizeof(float);
-        static bool once5 = ((void)hipFuncSetAttribute((const void *)mlp_backward_split_kernel<0, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5),
-                             (void)hipFuncSetAttribute((const void *)mlp_backward_split_kernel<1, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5),
-                             (void)hipFuncSetAttribute((const void *)mlp_backward_split_kernel<2, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5),
-                             (void)hipFuncSetAttribute((const void *)mlp_backward_split_kernel<3, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5), true);
-        (void)once5;
-        const int64_t tiles5 = (a.R + 31) / 32;
-        const dim3 grid5((unsigned)(tiles5 < 2 * cus ? tiles5 : 2 * cus));
-        if (a.act_kind == 0) hipLaunchKernelGGL((mlp_backward_split_kernel<0, 512>), grid5, dim3(kThreads), lds5, s, a);
-        else if (a.act_kind == 1) hipLaunchKernelGGL((mlp_backward_split_kernel<1, 512>), grid5, dim3(kThreads), lds5, s, a);
-        else if (a.act_kind == 2) hipLaunchKernelGGL((mlp_backward_split_kernel<2, 512>), grid5, dim3(kThreads), lds5, s, a);
-        else hipLaunchKernelGGL((mlp_backward_split_kernel<3, 512>), grid5, dim3(kThreads), lds5, s, a);
-        return;
-    }
-    if (split) {        // (prologue form only: the NeDDF route, the one caller)
-        constexpr size_t lds = (size_t)64 * OpsF16Split::kLd * sizeof(OpsF16Split::act_t) + 16 * sizeof(float);
-        static bool once = ((void)hipFuncSetAttribute((const void *)mlp_backward_split_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                            (void)hipFuncSetAttribute((const void *)mlp_backward_split_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                            (void)hipFuncSetAttribute((const void *)mlp_backward_split_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                            (void)hipFuncSetAttribute((const void *)mlp_backward_split_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
-        (void)once;
-        const int64_t tiles = (a.R + 63) / 64;
-        const dim3 grid((unsigned)(tiles < 2 * cus ? tiles : 2 * cus));
-        if (a.act_kind == 0) hipLaunchKernelGGL(mlp_backward_split_kernel<0>, grid, dim3(kThreads), lds, s, a);
-        else if (a.act_kind == 1) hipLaunchKernelGGL(mlp_backward_split_kernel<1>, grid, dim3(kThreads), lds, s, a);
-        else if (a.act_kind == 2) hipLaunchKernelGGL(mlp_backward_split_kernel<2>, grid, dim3(kThreads), lds, s, a);
-        else hipLaunchKernelGGL(mlp_backward_split_kernel<3>, grid, dim3(kThreads), lds, s, a);
-        return;
-    }
-    if (a.width == 512) {       // wide fields (round 5): 32-row tiles of [R, 512] matrices
-        constexpr size_t lds5 = (size_t)32 * OpsF32T<512>::kLd * sizeof(float);
-        static bool once5 = ((void)hipFuncSetAttribute((const void *)mlp_backward_kernel<0, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5),
-                             (void)hipFuncSetAttribute((const void *)mlp_backward_kernel<1, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5),
-                             (void)hipFuncSetAttribute((const void *)mlp_backward_kernel<2, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5),
-                             (void)hipFuncSetAttribute((const void *)mlp_backward_kernel<3, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5), true);
-        (void)once5;
-        const int64_t tiles5 = (a.R + 31) / 32;
-        const dim3 grid5((unsigned)(tiles5 < 2 * cus ? tiles5 : 2 * cus));
-        if (a.act_kind == 0) hipLaunchKernelGGL((mlp_backward_kernel<0, 512>), grid5, dim3(kThreads), lds5, s, a);
-        else if (a.act_kind == 1) hipLaunchKernelGGL((mlp_backward_kernel<1, 512>), grid5, dim3(kThreads), lds5, s, a);
-        else if (a.act_kind == 2) hipLaunchKernelGGL((mlp_backward_kernel<2, 512>), grid5, dim3(kThreads), lds5, s, a);
-        else hipLaunchKernelGGL((mlp_backward_kernel<3, 512>), grid5, dim3(kThreads), lds5, s, a);
-        return;
-    }
-    constexpr size_t lds = (size_t)64 * OpsF32::kLd * sizeof(float);
-    static bool once = ((void)hipFuncSetAttribute((const void *)mlp_backward_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                        (void)hipFuncSetAttribute((const void *)mlp_backward_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                        (void)hipFuncSetAttribute((const void *)mlp_backward_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                        (void)hipFuncSetAttribute((const void *)mlp_backward_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
-    (void)once;
-    const int64_t tiles = (a.R + 63) / 64;
-    const dim3 grid((unsigned)(tiles < 2 * cus ? tiles : 2 * cus));
-    if (a.act_kind == 0) hipLaunchKernelGGL(mlp_backward_kernel<0>, grid, dim3(kThreads), lds, s, a);
-    else if (a.act_kind == 1) hipLaunchKernelGGL(mlp_backward_kernel<1>, grid, dim3(kThreads), lds, s, a);
-    else if (a.act_kind == 2) hipLaunchKernelGGL(mlp_backward_kernel<2>, grid, dim3(kThreads), lds, s, a);
-    else hipLaunchKernelGGL(mlp_backward_kernel<3>, grid, dim3(kThreads), lds, s, a);
+    if (a.R <= 0) return;         // (a one-layer stack still has a prologue to run)
+    if (split && a.width == 512) launch_mlp_backward_ops<OpsF16SplitT<512>>(a, cus, s);       // wide fields (round 5), either policy
+    else if (split) launch_mlp_backward_ops<OpsF16Split>(a, cus, s);
+    else if (a.width == 512) launch_mlp_backward_ops<OpsF32T<512>>(a, cus, s);
+    else launch_mlp_backward_ops<OpsF32>(a, cus, s);
 }
 
 // ----------------------------------------------------------------------------
@@ -1072,45 +1072,38 @@ __global__ __launch_bounds__(kThreads, 1) void dw_tile_kernel(const float *X, in
 // of them.  A workgroup's epilogue is 65 536 device-scope atomic adds whatever its share of rows (profiles/r03_dw_ablation.txt: 1.8 ms
 // of a step when every product is its own launch over all CUs); with the workgroups divided among the products instead of every
 // workgroup visiting every product, a pass issues one such epilogue per workgroup, not one per workgroup and product.
-__global__ __launch_bounds__(kThreads, 1) void dw_jobs_kernel(const DwJobs jobs)
+// the job of workgroup `wg` (DwJob::wg0, set by dw_partition) and its share [rb, re) of the rows: whole 32-row chunks, divided evenly
+// among the job's workgroups
+__device__ __forceinline__ const DwJob &dw_job_rows(const DwJobs &jobs, int wg, int64_t &rb, int64_t &re)
 {
     int jb = 0;
-    while (jb + 1 < jobs.n && (int)blockIdx.x >= jobs.job[jb + 1].wg0) ++jb;
+    while (jb + 1 < jobs.n && wg >= jobs.job[jb + 1].wg0) ++jb;
     const DwJob &J = jobs.job[jb];
-    const int w = (int)blockIdx.x - J.wg0, nw = (jb + 1 < jobs.n ? jobs.job[jb + 1].wg0 : (int)gridDim.x) - J.wg0;
+    const int w = wg - J.wg0, nw = (jb + 1 < jobs.n ? jobs.job[jb + 1].wg0 : (int)gridDim.x) - J.wg0;
     const int64_t chunks = (jobs.R + 31) / 32, per = (chunks + nw - 1) / nw;
-    const int64_t rb = (int64_t)w * per * 32, re_ = rb + per * 32;
-    const int64_t re = re_ < jobs.R ? re_ : jobs.R;
+    rb = (int64_t)w * per * 32;
+    const int64_t re_ = rb + per * 32;
+    re = re_ < jobs.R ? re_ : jobs.R;
+    return J;
+}
+
+__global__ __launch_bounds__(kThreads, 1) void dw_jobs_kernel(const DwJobs jobs)
+{
+    int64_t rb, re;
+    const DwJob &J = dw_job_rows(jobs, (int)blockIdx.x, rb, re);
     // G (a dZ of the fused backward chain) is point-major in every job; X is point-major when it is a hidden state (K = 256), row-major
     // when it is one of the narrow first-layer inputs
-    if (J.x_point_major) dw_tile_rows<8, 8, true, true>(J.X, J.ldx, J.K, J.G, J.ldg, rb, re, J.dW, J.sk, J.sn, J.nvalid, J.db, J.bias_period);
-    else if (J.K <= 64) dw_tile_rows<8, 2, false, true>(J.X, J.ldx, J.K, J.G, J.ldg, rb, re, J.dW, J.sk, J.sn, J.nvalid, J.db, J.bias_period);
-    else if (J.K <= 96) dw_tile_rows<8, 3, false, true>(J.X, J.ldx, J.K, J.G, J.ldg, rb, re, J.dW, J.sk, J.sn, J.nvalid, J.db, J.bias_period);
-    else dw_tile_rows<8, 8, false, true>(J.X, J.ldx, J.K, J.G, J.ldg, rb, re, J.dW, J.sk, J.sn, J.nvalid, J.db, J.bias_period);
+    with_dw_shape(J.x_point_major, J.K, [&](auto ktn, auto xpm) {
+        dw_tile_rows<8, decltype(ktn)::value, decltype(xpm)::value, true>(J.X, J.ldx, J.K, J.G, J.ldg, rb, re, J.dW, J.sk, J.sn, J.nvalid, J.db, J.bias_period);
+    });
 }
 
 void launch_dw_jobs(DwJobs &jobs, int cus, hipStream_t s)
 {
     if (jobs.n <= 0 || jobs.R <= 0) return;
-    // workgroups in proportion to the products' cost: matrix work ~ K, plus the streaming of G that every product pays
-    float cost[kMaxDwJobs], total = 0.f;
-    // (the constant = the staging / streaming share of a chunk, ~a quarter of a 256-wide product's time; measured flat between 32 and 192)
-    for (int i = 0; i < jobs.n; ++i) { const int K = jobs.job[i].K; cost[i] = 64.0f + (float)(K <= 64 ? 64 : K <= 96 ? 96 : 256); total += cost[i]; }
-    int grid = cus > jobs.n ? cus : jobs.n, at = 0;
-    for (int i = 0; i < jobs.n; ++i) {
-        jobs.job[i].wg0 = at;
-        int share = (int)(cost[i] / total * grid + 0.5f);
-        if (share < 1) share = 1;
-        const int left = jobs.n - 1 - i;
-        if (at + share > grid - left) share = grid - left - at;
-        at += share;
-    }
-    grid = at;
+    const int grid = dw_partition(jobs, dw_cost_f32, cus);
     constexpr int KP = 256, LDX = KP + 32, LDG = kWidth + 32;
-    const size_t lds = (size_t)32 * (LDX + LDG) * sizeof(float);
-    static bool once = ((void)hipFuncSetAttribute((const void *)dw_jobs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(32 * (LDX + LDG) * sizeof(float))), true);
-    (void)once;
-    hipLaunchKernelGGL(dw_jobs_kernel, dim3(grid), dim3(kThreads), lds, s, jobs);
+    launch_lds<dw_jobs_kernel>(dim3(grid), dim3(kThreads), (size_t)32 * (LDX + LDG) * sizeof(float), s, jobs);
 }
 
 template <int KT, int KTN = KT, bool XPM = false, bool GPM = false>
@@ -1119,12 +1112,10 @@ static void launch_dw_tile(const float *X, int ldx, int K, const float *G, int l
 {
     constexpr int KP = 32 * KT, LDX = ((KP + 32) % 64 == 32) ? KP + 32 : KP + 64, LDG = kWidth + 32;
     const size_t lds = (size_t)32 * (LDX + LDG) * sizeof(float);
-    static bool once = ((void)hipFuncSetAttribute((const void *)dw_tile_kernel<KT, KTN, XPM, GPM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(32 * (LDX + LDG) * sizeof(float))), true);
-    (void)once;
     int64_t chunks = (R + 31) / 32;
     int grid = (int)(chunks < cus ? chunks : cus);
     int64_t rows_per_wg = ((chunks + grid - 1) / grid) * 32;
-    hipLaunchKernelGGL((dw_tile_kernel<KT, KTN, XPM, GPM>), dim3(grid), dim3(kThreads), lds, s, X, ldx, K, G, ldg, R, rows_per_wg, dW, sk, sn, nvalid, db, bias_period);
+    launch_lds<dw_tile_kernel<KT, KTN, XPM, GPM>>(dim3(grid), dim3(kThreads), lds, s, X, ldx, K, G, ldg, R, rows_per_wg, dW, sk, sn, nvalid, db, bias_period);
 }
 
 // Heads with 1..4 output columns: dW_c[k] += sum_r X[r, k] G[r, c], db_c += sum over value rows of G[r, c].
@@ -1354,21 +1345,15 @@ __global__ __launch_bounds__(kThreads, 1) void dw_split_kernel(const float *X, i
 // of one per workgroup and product.  A job with amax_g accumulates its range-scaled product into its own dense [K, 256] scratch.
 __global__ __launch_bounds__(kThreads, 1) void dw_split_jobs_kernel(const DwJobs jobs)
 {
-    int jb = 0;
-    while (jb + 1 < jobs.n && (int)blockIdx.x >= jobs.job[jb + 1].wg0) ++jb;
-    const DwJob &J = jobs.job[jb];
-    const int w = (int)blockIdx.x - J.wg0, nw = (jb + 1 < jobs.n ? jobs.job[jb + 1].wg0 : (int)gridDim.x) - J.wg0;
-    const int64_t chunks = (jobs.R + 31) / 32, per = (chunks + nw - 1) / nw;
-    const int64_t rb = (int64_t)w * per * 32, re_ = rb + per * 32;
-    const int64_t re = re_ < jobs.R ? re_ : jobs.R;
+    int64_t rb, re;
+    const DwJob &J = dw_job_rows(jobs, (int)blockIdx.x, rb, re);
     const bool scaled = J.amax_g && J.tmp;
     float *out = scaled ? J.tmp : J.dW;
     const int64_t osk = scaled ? kWidth : J.sk, osn = scaled ? 1 : J.sn;
     const float *am = scaled ? J.amax_g : nullptr;
-    if (J.x_point_major) dw_split_rows<8, true, true, 8>(J.X, J.ldx, J.K, J.G, J.ldg, rb, re, out, osk, osn, J.nvalid, J.db, J.bias_period, am);
-    else if (J.K <= 64) dw_split_rows<8, false, true, 2>(J.X, J.ldx, J.K, J.G, J.ldg, rb, re, out, osk, osn, J.nvalid, J.db, J.bias_period, am);
-    else if (J.K <= 96) dw_split_rows<8, false, true, 3>(J.X, J.ldx, J.K, J.G, J.ldg, rb, re, out, osk, osn, J.nvalid, J.db, J.bias_period, am);
-    else dw_split_rows<8, false, true, 8>(J.X, J.ldx, J.K, J.G, J.ldg, rb, re, out, osk, osn, J.nvalid, J.db, J.bias_period, am);
+    with_dw_shape(J.x_point_major, J.K, [&](auto ktn, auto xpm) {
+        dw_split_rows<8, decltype(xpm)::value, true, decltype(ktn)::value>(J.X, J.ldx, J.K, J.G, J.ldg, rb, re, out, osk, osn, J.nvalid, J.db, J.bias_period, am);
+    });
 }
 
 // dW += tmp / scale(amax) for every scaled job of the list: block (x, y) = 256 elements x of job y
@@ -1385,28 +1370,12 @@ __global__ void dw_unscale_add_jobs_kernel(const DwJobs jobs)
 void launch_dw_split_jobs(DwJobs &jobs, float *tmp, int cus, hipStream_t s)
 {
     if (jobs.n <= 0 || jobs.R <= 0) return;
-    // workgroups in proportion to the products' cost.  Under this policy the staging of G (256 columns split into two fp16 terms per
-    // chunk, whatever K) outweighs the matrix work: measured per launch 0.226 / 0.258 / 0.346 ms for K <= 64 / <= 96 / 256
-    // (profiles/r05_train_step_kernel_stats_f16_split_fused.csv) -- with the fp32 route's weights (128 : 160 : 320) the narrow products
-    // finished 1.6x late and the launch was 4.4 ms SLOWER than one launch per product
-    float cost[kMaxDwJobs], total = 0.f;
-    for (int i = 0; i < jobs.n; ++i) { const int K = jobs.job[i].K; cost[i] = K <= 64 ? 226.0f : K <= 96 ? 258.0f : 346.0f; total += cost[i]; }
-    int grid = cus > jobs.n ? cus : jobs.n, at = 0;
-    for (int i = 0; i < jobs.n; ++i) {
-        jobs.job[i].wg0 = at;
-        int share = (int)(cost[i] / total * grid + 0.5f);
-        if (share < 1) share = 1;
-        const int left = jobs.n - 1 - i;
-        if (at + share > grid - left) share = grid - left - at;
-        at += share;
+    const int grid = dw_partition(jobs, dw_cost_split, cus);
+    for (int i = 0; i < jobs.n; ++i)
         if (jobs.job[i].amax_g) jobs.job[i].tmp = tmp + (size_t)i * kWidth * kWidth;
-    }
-    grid = at;
     (void)hipMemsetAsync(tmp, 0, (size_t)jobs.n * kWidth * kWidth * sizeof(float), s);
     constexpr size_t lds = (size_t)2 * (32 * 8 + kWidth) * 40 * sizeof(_Float16);
-    static bool once = ((void)hipFuncSetAttribute((const void *)dw_split_jobs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), true);
-    (void)once;
-    hipLaunchKernelGGL(dw_split_jobs_kernel, dim3(grid), dim3(kThreads), lds, s, jobs);
+    launch_lds<dw_split_jobs_kernel>(dim3(grid), dim3(kThreads), lds, s, jobs);
     hipLaunchKernelGGL(dw_unscale_add_jobs_kernel, dim3(kWidth * kWidth / 256, jobs.n), dim3(256), 0, s, jobs);
 }
 
@@ -1425,14 +1394,11 @@ static void launch_dw_split(const float *X, int ldx, int K, const float *G, int 
                             float *db, int bias_period, int cus, hipStream_t s, const float *amax_g)
 {
     const size_t lds = (size_t)2 * (32 * KT + kWidth) * 40 * sizeof(_Float16);
-    static bool once = ((void)hipFuncSetAttribute((const void *)dw_split_kernel<KT, XPM, GPM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)((size_t)2 * (32 * KT + kWidth) * 40 * sizeof(_Float16))), true);
-    (void)once;
     int64_t chunks = (R + 31) / 32;
     int grid = (int)(chunks < cus ? chunks : cus);
     int64_t rows_per_wg = ((chunks + grid - 1) / grid) * 32;
-    hipLaunchKernelGGL((dw_split_kernel<KT, XPM, GPM>), dim3(grid), dim3(kThreads), lds, s, X, ldx, K, G, ldg, R, rows_per_wg, dW, sk, sn, nvalid, db,
-                       bias_period, amax_g);
+    launch_lds<dw_split_kernel<KT, XPM, GPM>>(dim3(grid), dim3(kThreads), lds, s, X, ldx, K, G, ldg, R, rows_per_wg, dW, sk, sn, nvalid, db, bias_period,
+                                              amax_g);
 }
 
 // dW[k * sk + n * sn] += sum_r X[r, k] G[r, n] for k < K <= 256, n < nvalid <= 256 (G has 256 columns, the rest zero);
@@ -1442,41 +1408,27 @@ void launch_dw(int split, const float *X, int ldx, int K, const float *G, int ld
 {
     if (R <= 0 || K <= 0) return;
     if (bias_period != 1 && bias_period != 2 && bias_period != 4) return;       // the kernels test row phases with a mask
-    if (split && g_point_major) {       // round 5: the split policy's fused NeDDF route keeps its hidden states and gradients point-major
-        const bool scaled = amax_g && scaled_tmp;
-        float *out = scaled ? scaled_tmp : dW;
-        const int64_t osk = scaled ? kWidth : sk, osn = scaled ? 1 : sn;
-        if (scaled) (void)hipMemsetAsync(scaled_tmp, 0, (size_t)K * kWidth * sizeof(float), s);
-        const float *am = scaled ? amax_g : nullptr;
-        if (x_point_major) launch_dw_split<8, true, true>(X, ldx, K, G, ldg, R, out, osk, osn, nvalid, db, bias_period, cus, s, am);
-        else if (K <= 64) launch_dw_split<2, false, true>(X, ldx, K, G, ldg, R, out, osk, osn, nvalid, db, bias_period, cus, s, am);
-        else if (K <= 96) launch_dw_split<3, false, true>(X, ldx, K, G, ldg, R, out, osk, osn, nvalid, db, bias_period, cus, s, am);
-        else launch_dw_split<8, false, true>(X, ldx, K, G, ldg, R, out, osk, osn, nvalid, db, bias_period, cus, s, am);
-        if (scaled) hipLaunchKernelGGL(dw_unscale_add_kernel, dim3((K * kWidth + 255) / 256), dim3(256), 0, s, scaled_tmp, K, nvalid, dW, sk, sn, amax_g);
-        return;
-    }
-    if (split) {
-        // with a range-scaled G the product lands in a dense [K, 256] scratch first and is added to dW divided by the scale
-        const bool scaled = amax_g && scaled_tmp;
-        float *out = scaled ? scaled_tmp : dW;
-        const int64_t osk = scaled ? kWidth : sk, osn = scaled ? 1 : sn;
-        if (scaled) (void)hipMemsetAsync(scaled_tmp, 0, (size_t)K * kWidth * sizeof(float), s);
-        if (K <= 64) launch_dw_split<2>(X, ldx, K, G, ldg, R, out, osk, osn, nvalid, db, bias_period, cus, s, scaled ? amax_g : nullptr);
-        else if (K <= 96) launch_dw_split<3>(X, ldx, K, G, ldg, R, out, osk, osn, nvalid, db, bias_period, cus, s, scaled ? amax_g : nullptr);
-        else launch_dw_split<8>(X, ldx, K, G, ldg, R, out, osk, osn, nvalid, db, bias_period, cus, s, scaled ? amax_g : nullptr);
-        if (scaled) hipLaunchKernelGGL(dw_unscale_add_kernel, dim3((K * kWidth + 255) / 256), dim3(256), 0, s, scaled_tmp, K, nvalid, dW, sk, sn, amax_g);
-        return;
-    }
-    if (g_point_major) {        // (fp32, one launch per product on point-major operands: the wide fused route, whose 46 products the job-parallel launch serves badly)
-        if (x_point_major) launch_dw_tile<8, 8, true, true>(X, ldx, K, G, ldg, R, dW, sk, sn, nvalid, db, bias_period, cus, s);
-        else if (K <= 64) launch_dw_tile<8, 2, false, true>(X, ldx, K, G, ldg, R, dW, sk, sn, nvalid, db, bias_period, cus, s);
-        else if (K <= 96) launch_dw_tile<8, 3, false, true>(X, ldx, K, G, ldg, R, dW, sk, sn, nvalid, db, bias_period, cus, s);
-        else launch_dw_tile<8, 8, false, true>(X, ldx, K, G, ldg, R, dW, sk, sn, nvalid, db, bias_period, cus, s);
-        return;
-    }
-    if (K <= 64) launch_dw_tile<2>(X, ldx, K, G, ldg, R, dW, sk, sn, nvalid, db, bias_period, cus, s);
-    else if (K <= 96) launch_dw_tile<3>(X, ldx, K, G, ldg, R, dW, sk, sn, nvalid, db, bias_period, cus, s);
-    else launch_dw_tile<8>(X, ldx, K, G, ldg, R, dW, sk, sn, nvalid, db, bias_period, cus, s);
+    // split fp16 with a range-scaled G: the product lands in a dense [K, 256] scratch first and is added to dW divided by the scale
+    const bool scaled = split && amax_g && scaled_tmp;
+    float *out = scaled ? scaled_tmp : dW;
+    const int64_t osk = scaled ? kWidth : sk, osn = scaled ? 1 : sn;
+    const float *am = scaled ? amax_g : nullptr;
+    if (scaled) (void)hipMemsetAsync(scaled_tmp, 0, (size_t)K * kWidth * sizeof(float), s);
+    // Point-major operands: the split policy's fused NeDDF route (round 5) and, fp32 with one launch per product, the wide fused route,
+    // whose 46 products the job-parallel launch serves badly.  A point-major X comes with a point-major G only; row-major matrices
+    // (the per-layer routes) use the narrow products' own LDS layout and accumulator file (KT = KTN), the fp32 point-major ones that of
+    // 8 k-tiles like dw_jobs_kernel.
+    auto launch = [&](auto gpm) {
+        constexpr bool GPM = decltype(gpm)::value;
+        with_dw_shape(GPM && x_point_major, K, [&](auto ktn, auto xpm) {
+            constexpr int KTN = decltype(ktn)::value;
+            constexpr bool XPM = GPM && decltype(xpm)::value;
+            if (split) launch_dw_split<KTN, XPM, GPM>(X, ldx, K, G, ldg, R, out, osk, osn, nvalid, db, bias_period, cus, s, am);
+            else launch_dw_tile<GPM ? 8 : KTN, KTN, XPM, GPM>(X, ldx, K, G, ldg, R, dW, sk, sn, nvalid, db, bias_period, cus, s);
+        });
+    };
+    if (g_point_major) launch(std::true_type{}); else launch(std::false_type{});
+    if (scaled) hipLaunchKernelGGL(dw_unscale_add_kernel, dim3((K * kWidth + 255) / 256), dim3(256), 0, s, scaled_tmp, K, nvalid, dW, sk, sn, amax_g);
 }
 
 // ----------------------------------------------------------------------------
