@@ -144,7 +144,11 @@ int neddf_debug_check_guards(neddf_ctx *ctx, int64_t *n_bands, int64_t *n_bad_by
  *          as a 1-element weight with a dummy bias (nn.Linear layout, neus.py:80-99); desc.layer_count =
  *          sdf_layer_count, desc.col_layer_count = col_layer_count, activation ReLU or tanhExp
  * The library packs them into MFMA fragment order and uploads; the caller keeps
- * ownership of the sources. */
+ * ownership of the sources.
+ * A REFUSED call leaves the slot exactly as it was: every NEDDF_EINVAL / NEDDF_EUNSUPPORTED answer (a descriptor or an
+ * architecture the engine does not take) and a device block that cannot be allocated come before the slot is touched, so
+ * the field loaded there before keeps answering with the same results.  Only a HIP call that fails once the replacement
+ * has begun (NEDDF_EHIP from the copy) leaves the slot without a field; the next call on it then reports NEDDF_ENOFIELD. */
 int neddf_set_field(neddf_ctx *ctx, int slot, const neddf_field_desc *desc,
                     const float *const *h_weights, const float *const *h_biases, int n_tensors);
 /* Replaces NeDDF.set_iter / NeRF.set_iter (neddf.py:311-326, nerf.py:167-178):

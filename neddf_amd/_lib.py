@@ -299,11 +299,16 @@ class Context:
 
     # ------------------------------------------------------------------ fields
     def set_field(self, slot, desc, weights, biases, signature):
-        """weights/biases: lists of CPU float32 contiguous tensors in state-dict order."""
+        """weights/biases: lists of CPU float32 contiguous tensors in state-dict order.  When the call raises, nobody owns the slot
+        any more: whatever the library kept there, the next upload of any module -- the previous owner included -- goes through."""
         n = len(weights)
         wa = (_fp * n)(*[C.cast(w.data_ptr(), _fp) for w in weights])
         ba = (_fp * n)(*[C.cast(b.data_ptr(), _fp) for b in biases])
-        self.check(self.lib.neddf_set_field(self.h, slot, C.byref(desc), wa, ba, n))
+        try:
+            self.check(self.lib.neddf_set_field(self.h, slot, C.byref(desc), wa, ba, n))
+        except BaseException:
+            self.slot_owner.pop(slot, None)
+            raise
         self.slot_owner[slot] = signature
 
     def set_iter(self, slot, aux_grad_scale, distance_range_max, lowpass):

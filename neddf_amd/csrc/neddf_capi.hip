@@ -377,19 +377,37 @@ int neddf_set_field(neddf_ctx *ctx, int slot, const neddf_field_desc *desc, cons
     if (desc->activation < 0 || desc->activation > 2 || desc->density_activation < 0 || desc->density_activation > 2)
         return fail(ctx, NEDDF_EINVAL, "bad activation id");
     if (desc->weight_dtype < NEDDF_DTYPE_F32 || desc->weight_dtype > NEDDF_DTYPE_F16_SPLIT) return fail(ctx, NEDDF_EINVAL, "bad weight_dtype");
+    // Everything that can refuse the field comes BEFORE the slot is touched (include/neddf_hip.h): the packer's refusals -- it is host
+    // arithmetic into a local block -- and the allocation of a larger device block, which is made beside the old one
+    PackedField pk;
+    if (int rc = pack_field(*desc, W, B, n, pk, ctx->err)) return rc;
     Field &f = ctx->field[slot];
+    const size_t bytes = pk.blob.size() * sizeof(float);
+    DevBuf grown;
+    if (!(f.blob.cap >= bytes && !(guard_mode() && f.blob.cap != ((bytes + 15) & ~(size_t)15))))
+        if (int rc = ensure(ctx, grown, bytes)) {
+            if (grown.p) (void)hipFree(grown.base ? grown.base : grown.p);
+            return rc;
+        }
     // the packed weights of this slot are about to be overwritten: wait for the LAST launch that reads them (an event recorded
     // on its stream by field_forward), not for the whole device -- other streams and other slots keep running
-    if (f.last_use) HIPCHK(hipEventSynchronize(f.last_use));
+    if (f.last_use)
+        if (hipError_t e = hipEventSynchronize(f.last_use)) {
+            if (grown.p) (void)hipFree(grown.base ? grown.base : grown.p);
+            ctx->err = std::string("hipEventSynchronize(f.last_use): ") + hipGetErrorString(e);
+            return NEDDF_EHIP;
+        }
+    // from here on the slot holds no field until the new one is complete (only a failing HIP call can leave it that way)
     f.valid = false;
     f.has3 = false;
+    if (grown.p) {
+        if (f.blob.p) HIPCHK(hipFree(f.blob.base ? f.blob.base : f.blob.p));
+        f.blob = grown;
+    }
     f.d = *desc;
     f.aux_grad_scale = 1.1f; f.distance_range_max = 2.0f;
     for (int i = 0; i < 10; ++i) f.lowpass[i] = 1.0f;
-    PackedField pk;
-    if (int rc = pack_field(*desc, W, B, n, pk, ctx->err)) return rc;
-    if (int rc = ensure(ctx, f.blob, pk.blob.size() * sizeof(float))) return rc;
-    HIPCHK(hipMemcpy(f.blob.p, pk.blob.data(), pk.blob.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(f.blob.p, pk.blob.data(), bytes, hipMemcpyHostToDevice));
     pk.resolve((const float *)f.blob.p);
     f.ddf = pk.ddf; f.col = pk.col; f.nerf = pk.nerf;
     f.ddf3 = pk.ddf3; f.col3 = pk.col3; f.has3 = pk.has3;

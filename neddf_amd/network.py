@@ -62,6 +62,33 @@ class LinearGradLayer(nn.Module):
 
 _module_ids = itertools.count(1)
 
+
+class _Uploaded:
+    """One tensor's entry in an upload signature: (data_ptr, _version) at the time of the upload.  It also holds the storage for as
+    long as the signature owns the slot: `p.data = other` bumps no version counter, so the address is all that tells the new tensor
+    from the packed one -- and an address the allocator had got back could be handed to a later `p.data = ...` unnoticed."""
+    __slots__ = ("key", "_storage")
+
+    def __init__(self, t: Tensor) -> None:
+        self.key = (t.data_ptr(), t._version)
+        self._storage = t.detach()
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, _Uploaded) and self.key == other.key
+
+    def __ne__(self, other) -> bool:
+        return not self == other
+
+    def __hash__(self) -> int:
+        return hash(self.key)
+
+
+def _upload_signature(uid: int, slot: int, desc, tensors, epoch: int):
+    """What BaseNeuralField.upload compares with Context.slot_owner[slot]: the first three entries name module, slot and
+    architecture (all a training-mode call looks at), the rest say which values were packed."""
+    return (uid, slot, bytes(desc), tuple(_Uploaded(t) for t in tensors), epoch)
+
+
 TRAIN_ENGINE_WIDTH = 256        # hidden width of the training kernels (csrc/train_*.hip)
 
 
@@ -386,7 +413,8 @@ class BaseNeuralField(ABC, nn.Module):
         ws, bs = self._tensors() if train is None else (train[1], train[2])
         desc = self._descriptor() if train is None else train[0]
         desc.weight_dtype = DTYPE[self.weight_dtype]
-        sig = (self._uid, slot, bytes(desc), tuple((t.data_ptr(), t._version) for t in ws + bs), self._epoch)
+        # (a zero-padded training call hands over temporaries: nothing of them is worth comparing, or keeping alive)
+        sig = _upload_signature(self._uid, slot, desc, ws + bs if train is None else (), self._epoch)
         have = ctx.slot_owner.get(slot)
         if not weights and have is not None and have[:3] == sig[:3]:
             pass            # same module, same architecture: the training kernels do not read the slot's weights
@@ -698,8 +726,7 @@ class NeuS(BaseNeuralField):
         ws, bs = self._tensors() if train is None else (train[1], train[2])
         desc = self._descriptor() if train is None else train[0]
         desc.weight_dtype = DTYPE[self.weight_dtype]
-        sig = (self._uid, slot, bytes(desc), tuple((t.data_ptr(), t._version) for t in ws[:-1] + bs[:-1]), self.variance.data_ptr(),
-               self.variance._version)
+        sig = _upload_signature(self._uid, slot, desc, ws[:-1] + bs[:-1] + [self.variance] if train is None else (), self._epoch)
         have = ctx.slot_owner.get(slot)
         if not weights and have is not None and have[:3] == sig[:3]:
             return          # training step: the kernels read the live parameter tensors, the slot only describes the architecture
