@@ -62,7 +62,16 @@ enum { NEDDF_DTYPE_F32 = 0, NEDDF_DTYPE_BF16 = 1,
 enum { NEDDF_SLOT_COARSE = 0, NEDDF_SLOT_FINE = 1, NEDDF_NUM_SLOTS = 4 };
 /* uv element types accepted by neddf_raygen (the reference takes int64 in
  * render_image, int16 in training, float in its tests) */
-enum { NEDDF_UV_F32 = 0, NEDDF_UV_I64 = 1, NEDDF_UV_I32 = 2, NEDDF_UV_I16 = 3 };
+enum { NEDDF_UV_F32 = 0, NEDDF_UV_I64 = 1, NEDDF_UV_I32 = 2, NEDDF_UV_I16 = 3,
+       /* a ray bundle instead of pixels (additive to ABI v7): d_uv is float [n_rays, 6], each row the ray direction xyz followed by
+        * the ray origin xyz in world space, and h_cam is not read (it may be NULL).  neddf_raygen copies the rows to d_ray_dir /
+        * d_ray_orig bit for bit -- NaN payloads included, NO normalisation: unit length is the caller's contract, as it is for
+        * neddf_sampling -- and neddf_render_rays, _single, _surface, _single_surface, _culled and _single_culled start from the same
+        * copy; every later stage is the one the pixel types reach, and the stream contract is that of the call it rides in.
+        * Refused, with a neddf_last_error message and nothing written: params->ndc_rays != 0 (NEDDF_EUNSUPPORTED: the NDC map needs
+        * a camera's focal lengths) and neddf_raygen_backward (NEDDF_EINVAL: there is no pose to differentiate).  Any uv_type
+        * outside 0..4 is NEDDF_EINVAL in all of these calls. */
+       NEDDF_UV_RAYS = 4 };
 /* field output selection */
 enum { NEDDF_OUT_MINIMAL = 0,   /* density + color (+distance, aux_grad): what compositing consumes */
        NEDDF_OUT_FULL = 1 };    /* + fields_penalty: Jacobian through the colour trunk (neddf.py:243-300) */

@@ -6,7 +6,7 @@ this package is the thin host side.  Import is GPU-free; the library is loaded
 on first use and there is no CPU fallback."""
 from . import camera, config, dataset, logger, loss, metrics, network, nn_module, occupancy, ray, render, trace, trainer  # noqa: F401
 from ._lib import Context, NeddfError, load  # noqa: F401
-from .camera import Camera, PinholeCalib  # noqa: F401
+from .camera import Camera, OrthographicCalib, PinholeCalib  # noqa: F401
 from .network import NeDDF, NeDDFField, NeRF, NeRFField, NeuS  # noqa: F401
 from .occupancy import OccupancyGrid  # noqa: F401
 from .ray import Ray, Sampling  # noqa: F401

@@ -23,6 +23,7 @@ GRID_FIELDS = {"distance": 0, "density": 1}        # NEDDF_GRID_*
 STAGES = ("ddf", "col", "nerf", "raygen", "ndc", "sample_coarse", "sampling", "composite", "penalty", "resample", "gather")
 COMM_ID_BYTES = 128
 UV_TYPES = {torch.float32: 0, torch.int64: 1, torch.int32: 2, torch.int16: 3}
+UV_RAYS = 4         # NEDDF_UV_RAYS: float32 [n, 6] rows of (direction, origin); never inferred from a dtype or a shape
 PENALTY_KEYS = ("constraints_aux_grad", "constraints_dDdt", "range_distance", "range_aux_grad",
                 "range_color", "constraints_color")     # dict order of neddf.py:260-291
 
@@ -34,6 +35,36 @@ _dp = C.POINTER(C.c_double)
 
 class NeddfError(RuntimeError):
     pass
+
+
+def _uv_arg(uv, bundle=False):
+    """(contiguous device tensor, NEDDF_UV_* code) of a raygen / render_rays `uv` argument.  Pixels are typed by
+    their dtype (UV_TYPES; anything else becomes float32).  A ray bundle is named by the caller, never guessed from a tensor's
+    shape: either a Ray (neddf_amd.ray: ray_dir and ray_orig [n, 3], packed here) or, with bundle=True, a float32 [n, 6] tensor
+    of (direction, origin) rows."""
+    if hasattr(uv, "ray_dir") and hasattr(uv, "ray_orig"):
+        rd, ro = uv.ray_dir, uv.ray_orig
+        if rd.dim() != 2 or rd.shape[1] != 3 or ro.shape != rd.shape:
+            raise NeddfError("a ray bundle needs ray_dir and ray_orig of shape [n, 3]")
+        require_device(rd, "ray_dir")
+        require_device(ro, "ray_orig")
+        return torch.cat([rd.detach().to(torch.float32), ro.detach().to(torch.float32)], 1).contiguous(), UV_RAYS
+    require_device(uv, "uv")
+    if bundle:
+        if uv.dtype != torch.float32 or uv.dim() != 2 or uv.shape[1] != 6:
+            raise NeddfError("a ray bundle is a float32 [n, 6] tensor of (direction, origin) rows")
+        return uv.contiguous(), UV_RAYS
+    if uv.dtype not in UV_TYPES:
+        uv = uv.to(torch.float32)
+    return uv.contiguous(), UV_TYPES[uv.dtype]
+
+
+def _cam_arg(cam, uv_type):
+    if cam is None:
+        if uv_type != UV_RAYS:
+            raise NeddfError("pixel coordinates need a camera descriptor")
+        return None
+    return C.byref(cam)
 
 
 class FieldDesc(C.Structure):
@@ -316,15 +347,16 @@ class Context:
         self.check(self.lib.neddf_set_iter(self.h, slot, aux_grad_scale, distance_range_max, arr))
 
     # ------------------------------------------------------------------ stages
-    def raygen(self, uv, cam):
-        require_device(uv, "uv")
-        if uv.dtype not in UV_TYPES:
-            uv = uv.to(torch.float32)
-        uv = uv.contiguous()
+    def raygen(self, uv, cam=None, bundle=False):
+        """uv: pixels [n, 2] with a camera descriptor, or a ray bundle (a Ray, or bundle=True with float32 [n, 6] rows of
+        (direction, origin); cam may be None): the bundle's rows come back bit for bit."""
+        uv, uv_type = _uv_arg(uv, bundle)
         n = uv.shape[0]
         rd = torch.empty(n, 3, device=uv.device, dtype=torch.float32)
         ro = torch.empty_like(rd)
-        self.check(self.lib.neddf_raygen(self.h, _ptr(uv), UV_TYPES[uv.dtype], n, C.byref(cam), _ptr(rd), _ptr(ro),
+        if n == 0 and uv_type == UV_RAYS:       # an empty bundle (the pointers of empty tensors are NULL)
+            return rd, ro
+        self.check(self.lib.neddf_raygen(self.h, _ptr(uv), uv_type, n, _cam_arg(cam, uv_type), _ptr(rd), _ptr(ro),
                                          self.stream()))
         return rd, ro
 
@@ -854,14 +886,13 @@ class Context:
                                                       _ptr(out), _ptr(ids), self.stream()))
         return (out, ids) if want_ids else out
 
-    def render_rays(self, uv, cam, params, U_coarse, U_fine, outputs, single_slot=None, occupancy=None):
-        """outputs: dict name -> preallocated device tensor (subset of RenderOutputs fields, plus "normal" / "normal_coarse"
+    def render_rays(self, uv, cam, params, U_coarse, U_fine, outputs, single_slot=None, occupancy=None, bundle=False):
+        """uv: pixels [B, 2], or a ray bundle as in raygen (a Ray, or bundle=True with float32 [B, 6]; cam may then be None).
+        outputs: dict name -> preallocated device tensor (subset of RenderOutputs fields, plus "normal" / "normal_coarse"
         [B, 3]: with either present the call goes through the *_surface entry points).  occupancy: an Occupancy struct whose
         bits live on this device -- the call goes through the *_culled entry points (empty-space skipping)."""
-        require_device(uv, "uv")
-        if uv.dtype not in UV_TYPES:
-            uv = uv.to(torch.float32)
-        uv = uv.contiguous()
+        uv, uv_type = _uv_arg(uv, bundle)
+        cam_ref = _cam_arg(cam, uv_type)
         ro = RenderOutputs()
         outputs = dict(outputs)
         normal, normal_coarse = outputs.pop("normal", None), outputs.pop("normal_coarse", None)
@@ -869,28 +900,28 @@ class Context:
             setattr(ro, k, t.data_ptr())
         if occupancy is not None:
             if single_slot is None:
-                self.check(self.lib.neddf_render_rays_culled(self.h, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0], C.byref(cam),
+                self.check(self.lib.neddf_render_rays_culled(self.h, _ptr(uv), uv_type, uv.shape[0], cam_ref,
                                                              C.byref(params), _ptr(U_coarse), _ptr(U_fine), C.byref(ro),
                                                              _ptr(normal), _ptr(normal_coarse), self.stream(), C.byref(occupancy)))
             else:
-                self.check(self.lib.neddf_render_rays_single_culled(self.h, single_slot, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0],
-                                                                    C.byref(cam), C.byref(params), U_coarse.shape[1], _ptr(U_coarse),
+                self.check(self.lib.neddf_render_rays_single_culled(self.h, single_slot, _ptr(uv), uv_type, uv.shape[0],
+                                                                    cam_ref, C.byref(params), U_coarse.shape[1], _ptr(U_coarse),
                                                                     C.byref(ro), _ptr(normal), self.stream(), C.byref(occupancy)))
         elif normal is not None or normal_coarse is not None:
             if single_slot is None:
-                self.check(self.lib.neddf_render_rays_surface(self.h, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0], C.byref(cam),
+                self.check(self.lib.neddf_render_rays_surface(self.h, _ptr(uv), uv_type, uv.shape[0], cam_ref,
                                                               C.byref(params), _ptr(U_coarse), _ptr(U_fine), C.byref(ro),
                                                               _ptr(normal), _ptr(normal_coarse), self.stream()))
             else:
-                self.check(self.lib.neddf_render_rays_single_surface(self.h, single_slot, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0],
-                                                                     C.byref(cam), C.byref(params), U_coarse.shape[1], _ptr(U_coarse),
+                self.check(self.lib.neddf_render_rays_single_surface(self.h, single_slot, _ptr(uv), uv_type, uv.shape[0],
+                                                                     cam_ref, C.byref(params), U_coarse.shape[1], _ptr(U_coarse),
                                                                      C.byref(ro), _ptr(normal), self.stream()))
         elif single_slot is None:
-            self.check(self.lib.neddf_render_rays(self.h, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0], C.byref(cam),
+            self.check(self.lib.neddf_render_rays(self.h, _ptr(uv), uv_type, uv.shape[0], cam_ref,
                                                   C.byref(params), _ptr(U_coarse), _ptr(U_fine), C.byref(ro), self.stream()))
         else:
-            self.check(self.lib.neddf_render_rays_single(self.h, single_slot, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0],
-                                                         C.byref(cam), C.byref(params), U_coarse.shape[1], _ptr(U_coarse),
+            self.check(self.lib.neddf_render_rays_single(self.h, single_slot, _ptr(uv), uv_type, uv.shape[0],
+                                                         cam_ref, C.byref(params), U_coarse.shape[1], _ptr(U_coarse),
                                                          C.byref(ro), self.stream()))
 
     # ------------------------------------------------------------------ empty-space skipping
@@ -1181,17 +1212,14 @@ class Context:
                                                     radius, _ptr(g_rd), _ptr(g_ro), self.stream()))
         return g_rd, g_ro
 
-    def raygen_backward(self, uv, cam, g_ray_dir, g_ray_orig):
+    def raygen_backward(self, uv, cam, g_ray_dir, g_ray_orig, bundle=False):
         """Backward of `raygen` with respect to the pose: g_R [3, 3], g_T [3] (device tensors)."""
-        require_device(uv, "uv")
-        if uv.dtype not in UV_TYPES:
-            uv = uv.to(torch.float32)
-        uv = uv.contiguous()
+        uv, uv_type = _uv_arg(uv, bundle)        # (a bundle is refused by the library: it has no pose)
         g_rd, g_ro = f32c(g_ray_dir), f32c(g_ray_orig)
         if g_rd.shape != (uv.shape[0], 3) or g_ro.shape != (uv.shape[0], 3):
             raise NeddfError("raygen_backward: ray gradients must be [B, 3]")
         out = torch.empty(12, device=uv.device, dtype=torch.float32)
-        self.check(self.lib.neddf_raygen_backward(self.h, _ptr(uv), UV_TYPES[uv.dtype], uv.shape[0], C.byref(cam), _ptr(g_rd),
+        self.check(self.lib.neddf_raygen_backward(self.h, _ptr(uv), uv_type, uv.shape[0], _cam_arg(cam, uv_type), _ptr(g_rd),
                                                   _ptr(g_ro), _ptr(out), self.stream()))
         return out[:9].view(3, 3), out[9:]
 

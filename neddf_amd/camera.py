@@ -3,6 +3,11 @@
 Pose algebra (camera.py:66-118) stays on the host: it is a handful of 3x3
 products per view.  Pixel -> ray (camera.py:155-187, pinhole_calib.py:51-74)
 runs in the raygen HIP kernel.
+
+Any other camera model is a calib class with `unproject_local` (and, where its
+rays do not start at the camera centre, `unproject_local_origin`): Camera.create_rays
+then builds the rays in torch and the renderer takes them as a ray bundle
+(NeRFRender.render_bundle).  OrthographicCalib is the one shipped.
 """
 from typing import Optional
 
@@ -24,6 +29,10 @@ class BaseCameraCalib(nn.Module):
     @property
     def device(self) -> torch.device:
         return self.params.device
+
+    def unproject_local_origin(self, uv: Tensor) -> Tensor:
+        """pixels -> where each pixel's ray starts in the camera frame, [B,3]: the camera centre unless a model says otherwise."""
+        return torch.zeros(uv.shape[0], 3, dtype=torch.float32, device=uv.device)
 
 
 class PinholeCalib(BaseCameraCalib):
@@ -49,6 +58,36 @@ class PinholeCalib(BaseCameraCalib):
         y = (1.0 / self.fy) * (uv[:, 1] - self.cy)
         v = torch.stack([x, -y, -torch.ones_like(x)], 1)
         return nn.functional.normalize(v, p=2, dim=1)
+
+
+class OrthographicCalib(BaseCameraCalib):
+    """Parallel projection [sx, sy, cx, cy] (not a reference model): sx, sy pixels per world unit, (cx, cy) the principal point.
+    Every pixel looks along the camera's -z axis (right-up-back frame) from ((u - cx) / sx, -(v - cy) / sy, 0): exact, no
+    iteration -- the inspection view of a mesh or field viewer."""
+
+    def __init__(self, calib_param: ndarray) -> None:
+        assert np.asarray(calib_param).shape == (4,)
+        super().__init__(calib_param)
+
+    sx = property(lambda self: self.params[0])
+    sy = property(lambda self: self.params[1])
+    cx = property(lambda self: self.params[2])
+    cy = property(lambda self: self.params[3])
+
+    def project_local(self, xyz: Tensor) -> Tensor:
+        """camera-frame points -> pixels: the inverse of unproject_local_origin, whatever the depth."""
+        return torch.stack([xyz[:, 0] * self.sx + self.cx, (-xyz[:, 1]) * self.sy + self.cy], 1)
+
+    def unproject_local(self, uv: Tensor) -> Tensor:
+        """pixels -> unit camera-frame directions: (0, 0, -1) for every pixel."""
+        d = torch.zeros(uv.shape[0], 3, dtype=torch.float32, device=uv.device)
+        d[:, 2] = -1.0
+        return d
+
+    def unproject_local_origin(self, uv: Tensor) -> Tensor:
+        x = (uv[:, 0] - self.cx) / self.sx
+        y = (uv[:, 1] - self.cy) / self.sy
+        return torch.stack([x, -y, torch.zeros_like(x)], 1)
 
 
 def _hat(v: Tensor) -> Tensor:
@@ -112,7 +151,11 @@ class Camera(nn.Module):
         return 0.5 + scale * pixel_id.to(torch.float32)
 
     def descriptor(self) -> CameraDesc:
-        """POD copy of (R, T, intrinsics) for the C ABI."""
+        """POD copy of (R, T, intrinsics) for the C ABI: a pinhole camera's.  Any other calib raises -- its rays are made by
+        create_rays in torch and reach the library as a bundle."""
+        if not isinstance(self.camera_calib, PinholeCalib):
+            raise NotImplementedError("Camera.descriptor: the C ABI's camera is a pinhole; a %s makes its rays in create_rays"
+                                      % type(self.camera_calib).__name__)
         d = CameraDesc()
         d.R[:] = self.R.detach().reshape(-1).tolist()
         d.T[:] = self.T.detach().tolist()
@@ -120,8 +163,19 @@ class Camera(nn.Module):
         return d
 
     def create_rays(self, uv: Tensor) -> Ray:
-        """Pixel indices [B,2] (int64/int32/int16/float) -> rays (camera.py:155-171)."""
-        ctx = Context.get(self.device)
+        """Pixel indices [B,2] (int64/int32/int16/float) -> rays (camera.py:155-171).  A PinholeCalib goes through the raygen
+        kernel; any other calib through its unproject_local / unproject_local_origin at the pixel centres, then R and T, in fp32
+        torch ops (differentiable with respect to R and T)."""
         uv = uv.to(self.device)
+        if not isinstance(self.camera_calib, PinholeCalib):
+            centre = self.get_center_of_pixels(uv)
+            d_local = self.camera_calib.unproject_local(centre).to(torch.float32)
+            o_local = self.camera_calib.unproject_local_origin(centre).to(torch.float32)
+            R, T = self.R.to(torch.float32), self.T.to(torch.float32)
+
+            def rotate(x: Tensor) -> Tensor:        # R x per row, summed left to right as the raygen kernel does (no BLAS call)
+                return x[:, 0:1] * R[None, :, 0] + x[:, 1:2] * R[None, :, 1] + x[:, 2:3] * R[None, :, 2]
+            return Ray(rotate(d_local), rotate(o_local) + T[None, :], uv)
+        ctx = Context.get(self.device)
         rd, ro = ctx.raygen(uv, self.descriptor())
         return Ray(rd, ro, uv)

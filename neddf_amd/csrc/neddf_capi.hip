@@ -428,15 +428,17 @@ int neddf_set_iter(neddf_ctx *ctx, int slot, float aux_grad_scale, float distanc
 
 static CameraArg cam_arg(const neddf_camera *c)
 {
-    CameraArg a;
+    CameraArg a{};
+    if (!c) return a;           // NEDDF_UV_RAYS: the copy kernel reads no camera
     memcpy(a.R, c->R, sizeof(a.R)); memcpy(a.T, c->T, sizeof(a.T)); memcpy(a.calib, c->calib, sizeof(a.calib));
     return a;
 }
 
 int neddf_raygen(neddf_ctx *ctx, const void *uv, int uv_type, int64_t n, const neddf_camera *cam, float *rd, float *ro, void *stream)
 {
-    if (!ctx || !uv || !cam || !rd || !ro) return NEDDF_EINVAL;
-    if (uv_type < 0 || uv_type > 3) return fail(ctx, NEDDF_EINVAL, "bad uv_type");
+    if (!ctx || !uv || !rd || !ro) return NEDDF_EINVAL;
+    if (uv_type < 0 || uv_type > NEDDF_UV_RAYS) return fail(ctx, NEDDF_EINVAL, "bad uv_type");
+    if (!cam && uv_type != NEDDF_UV_RAYS) return NEDDF_EINVAL;
     DeviceGuard guard_(ctx->device);
     STAGE(ctx, (hipStream_t)stream, NEDDF_STAGE_RAYGEN, launch_raygen(uv, uv_type, n, cam_arg(cam), rd, ro, (hipStream_t)stream));
     HIPCHK(hipGetLastError());
@@ -677,13 +679,23 @@ static int render_pass(neddf_ctx *ctx, int slot, const float *rd, const float *r
     return 0;
 }
 
+// what the fused entry points ask of (uv_type, camera): a ray bundle (NEDDF_UV_RAYS) needs no camera and cannot be mapped to NDC
+static int check_uv(neddf_ctx *ctx, int uv_type, const neddf_camera *cam, const neddf_render_params *rp)
+{
+    if (uv_type < 0 || uv_type > NEDDF_UV_RAYS) return fail(ctx, NEDDF_EINVAL, "bad uv_type");
+    if (uv_type != NEDDF_UV_RAYS) return cam ? 0 : NEDDF_EINVAL;
+    if (rp->ndc_rays) return fail(ctx, NEDDF_EUNSUPPORTED, "NEDDF_UV_RAYS: the NDC map needs a camera's focal lengths (ndc_rays must be 0)");
+    return 0;
+}
+
 static int render_rays_impl(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, const neddf_camera *cam, const neddf_render_params *rp,
                             const float *Uc, const float *Uf, const neddf_render_outputs *out, float *normal, float *normal_coarse, void *stream,
                             const neddf_occupancy *occ = nullptr)
 {
     if (!ctx) return NEDDF_EINVAL;
     if (B <= 0) return 0;           // empty batch: nothing to do (pointers of empty tensors may be NULL)
-    if (!uv || !cam || !rp || !Uc || !Uf || !out) return NEDDF_EINVAL;
+    if (!uv || !rp || !Uc || !Uf || !out) return NEDDF_EINVAL;
+    if (int rc = check_uv(ctx, uv_type, cam, rp)) return rc;
     if (occ && !occ_ok(occ)) return fail(ctx, NEDDF_EINVAL, "render_rays_culled: the grid needs its bits and a resolution in [1, 1024]");
     if (occ && (out->fields_penalty || out->fields_penalty_coarse))
         return fail(ctx, NEDDF_EUNSUPPORTED, "render_rays_culled: no fields_penalty output with an occupancy grid (a culled sample has no penalty)");
@@ -764,7 +776,8 @@ static int render_rays_single_impl(neddf_ctx *ctx, int slot, const void *uv, int
 {
     if (!ctx) return NEDDF_EINVAL;
     if (B <= 0) return 0;
-    if (!uv || !cam || !rp || !U || !out || S1 < 2) return NEDDF_EINVAL;
+    if (!uv || !rp || !U || !out || S1 < 2) return NEDDF_EINVAL;
+    if (int rc = check_uv(ctx, uv_type, cam, rp)) return rc;
     if (occ && !occ_ok(occ)) return fail(ctx, NEDDF_EINVAL, "render_rays_single_culled: the grid needs its bits and a resolution in [1, 1024]");
     if (occ && out->fields_penalty)
         return fail(ctx, NEDDF_EUNSUPPORTED, "render_rays_single_culled: no fields_penalty output with an occupancy grid (a culled sample has no penalty)");

@@ -35,11 +35,25 @@ __global__ void raygen_kernel(const T *uv, int64_t n, CameraArg cam, float *ray_
     }
 }
 
+// NEDDF_UV_RAYS: the caller's rays, rows of (direction xyz, origin xyz).  The words are moved as integers, so every bit
+// pattern -- NaN payloads, denormals, -0 -- arrives as it left; nothing is normalised.
+__global__ void raygen_bundle_kernel(const uint32_t *rays, int64_t n, uint32_t *ray_dir, uint32_t *ray_orig)
+{
+    int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        ray_dir[3 * b + i] = rays[6 * b + i];
+        ray_orig[3 * b + i] = rays[6 * b + 3 + i];
+    }
+}
+
 void launch_raygen(const void *uv, int uv_type, int64_t n, const CameraArg &cam, float *dir, float *orig, hipStream_t s)
 {
     if (n <= 0) return;
     dim3 g((unsigned)((n + 255) / 256)), b(256);
     switch (uv_type) {
+    case 4: hipLaunchKernelGGL(raygen_bundle_kernel, g, b, 0, s, (const uint32_t *)uv, n, (uint32_t *)dir, (uint32_t *)orig); break;
     case 0: hipLaunchKernelGGL(raygen_kernel<float>, g, b, 0, s, (const float *)uv, n, cam, dir, orig); break;
     case 1: hipLaunchKernelGGL(raygen_kernel<int64_t>, g, b, 0, s, (const int64_t *)uv, n, cam, dir, orig); break;
     case 2: hipLaunchKernelGGL(raygen_kernel<int32_t>, g, b, 0, s, (const int32_t *)uv, n, cam, dir, orig); break;

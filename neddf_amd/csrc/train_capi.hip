@@ -1080,6 +1080,7 @@ int neddf_raygen_backward(neddf_ctx *ctx, const void *uv, int uv_type, int64_t n
 {
     if (!ctx) return NEDDF_EINVAL;
     // (no rays: the arrays of an empty batch may be null pointers -- the kernel reads none of them and writes zeros)
+    if (uv_type == NEDDF_UV_RAYS) return fail(ctx, NEDDF_EINVAL, "raygen_backward: a ray bundle (NEDDF_UV_RAYS) has no pose to differentiate");
     if (!cam || !g_RT || n < 0 || (n > 0 && (!uv || !g_rd || !g_ro))) return fail(ctx, NEDDF_EINVAL, "raygen_backward: bad argument");
     if (uv_type < 0 || uv_type > 3) return fail(ctx, NEDDF_EINVAL, "bad uv_type");
     DeviceGuard guard_(ctx->device);

@@ -3,7 +3,7 @@
 The arithmetic (ray.py:88-194) runs in the HIP kernels of
 csrc/render_kernels.hip; these classes only carry device tensors.
 """
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -36,12 +36,15 @@ class Sampling:
 
 
 class Ray:
-    """Batch of rays (ray.py:23-50): ray_dir/ray_orig [B,3], uv [B,2]."""
+    """Batch of rays (ray.py:23-50): ray_dir/ray_orig [B,3], uv [B,2].  uv=None (not in the reference): rays no pixel grid made --
+    a bundle assembled from several cameras or handed over by another tool (NeRFRender.render_bundle)."""
 
-    def __init__(self, ray_dir: Tensor, ray_orig: Tensor, uv: Tensor) -> None:
+    def __init__(self, ray_dir: Tensor, ray_orig: Tensor, uv: Optional[Tensor] = None) -> None:
         self.single = ray_dir.dim() == 1
         assert ray_orig.shape == ray_dir.shape
-        if self.single:
+        if uv is None:
+            pass
+        elif self.single:
             assert uv.shape == (2,)
         else:
             assert uv.shape == (ray_orig.shape[0], 2)

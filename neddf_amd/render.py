@@ -14,9 +14,10 @@ import torch
 from torch import Tensor, nn
 
 from ._lib import SLOT_COARSE, SLOT_FINE, Context, NeddfError, RenderParams
-from .camera import Camera
+from .camera import Camera, PinholeCalib
 from .config import instantiate
 from .network import BaseNeuralField, NeDDF
+from .ray import Ray
 from .rng import skip_uniforms
 
 RenderTarget = str          # Literal["color", "depth", "transmittance", "normal"]
@@ -42,6 +43,13 @@ def render_from_config(render_config: Any, **kwargs: Any) -> "NeRFRender":
     render = instantiate(cfg, **kwargs)
     render.pose_gradients = pose
     return render
+
+
+def _is_pinhole(camera: Any) -> bool:
+    """Whether `camera` goes through the raygen kernel by its descriptor(): a Camera with a PinholeCalib, or any object that only
+    offers a descriptor.  A Camera with another calib makes its rays in create_rays."""
+    calib = getattr(camera, "camera_calib", None)
+    return calib is None or isinstance(calib, PinholeCalib)
 
 
 class NeRFRender(BaseNeuralRender):
@@ -206,10 +214,14 @@ class NeRFRender(BaseNeuralRender):
             raise ValueError("the occupancy grid lives on %s, the camera on %s" % (grid.device, dev))
         return grid.descriptor()
 
-    def _render(self, ctx: Context, uv: Tensor, camera: Camera, U_c: Tensor, U_f: Tensor, full: bool, cam_desc=None,
-                nan_group: int = 0, nan_group_offset: int = 0, normal: bool = False, occupancy=None) -> Dict[str, Tensor]:
-        B = uv.shape[0]
+    def _render(self, ctx: Context, uv, camera: Optional[Camera], U_c: Tensor, U_f: Tensor, full: bool, cam_desc=None,
+                nan_group: int = 0, nan_group_offset: int = 0, normal: bool = False, occupancy=None, bundle: bool = False) -> Dict[str, Tensor]:
+        """uv: pixels [B,2] of `camera` (or of the descriptor cam_desc), or a ray bundle -- a Ray, or with bundle=True float32
+        [B,6] (direction, origin) rows -- which needs neither."""
+        B = len(uv) if isinstance(uv, Ray) else uv.shape[0]
         dev = uv.device
+        if cam_desc is None and not bundle and not isinstance(uv, Ray):
+            cam_desc = camera.descriptor()
         S2 = self.sample_coarse + self.sample_fine + 2
 
         def buf(*shape):
@@ -227,10 +239,13 @@ class NeRFRender(BaseNeuralRender):
             if full:
                 o.update(normal_coarse=buf(B, 3))
         flag = torch.zeros(1, device=dev, dtype=torch.int32)
-        ctx.render_rays(uv, camera.descriptor() if cam_desc is None else cam_desc, self._params(nan_group, nan_group_offset), U_c, U_f, dict(o, nan_flag=flag),
-                        occupancy=occupancy)
+        ctx.render_rays(uv, cam_desc, self._params(nan_group, nan_group_offset), U_c, U_f, dict(o, nan_flag=flag),
+                        occupancy=occupancy, bundle=bundle)
         o["_nan"] = flag
         return o
+
+    RAY_KEYS = ("weight", "depth", "color", "transmittance", "fields_penalty", "weight_coarse", "depth_coarse",
+                "color_coarse", "transmittance_coarse", "fields_penalty_coarse", "normal", "normal_coarse")
 
     def render_rays(self, uv: Tensor, camera: Camera) -> Dict[str, Tensor]:
         """nerf_render.py:109-188.  Keys: weight, depth, color, transmittance[, fields_penalty] + *_coarse.
@@ -238,6 +253,10 @@ class NeRFRender(BaseNeuralRender):
         docstring); the autograd path below ignores the attribute."""
         uv = uv.to(camera.device)
         B = uv.shape[0]
+        if not _is_pinhole(camera):       # any other calib makes its rays in torch
+            with torch.set_grad_enabled(torch.is_grad_enabled() and bool(self.pose_gradients)):
+                rays = camera.create_rays(uv)
+            return self.render_bundle(rays)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             return self._render_rays_with_grad(uv, camera)
         ctx = self._ctx(uv.device)
@@ -245,14 +264,11 @@ class NeRFRender(BaseNeuralRender):
         U_f = self._rand(B, self.sample_fine + 1, uv.device)
         o = self._render(ctx, uv, camera, U_c, U_f, full=True, normal=bool(self.normal_output))
         assert int(o.pop("_nan").item()) == 0, "NaN weight in integrate_volume_render"
-        order = ["weight", "depth", "color", "transmittance", "fields_penalty", "weight_coarse", "depth_coarse",
-                 "color_coarse", "transmittance_coarse", "fields_penalty_coarse", "normal", "normal_coarse"]
-        return {k: o[k] for k in order if k in o}
+        return {k: o[k] for k in self.RAY_KEYS if k in o}
 
     def _render_rays_with_grad(self, uv: Tensor, camera: Camera) -> Dict[str, Tensor]:
         """render_rays as the training step needs it (nerf_render.py:109-188 under autograd): the samplers run as in
         inference, the two field evaluations and the two volume integrals are autograd nodes (autograd.py)."""
-        from .ray import Sampling
         ctx = Context.get(uv.device)
         B = uv.shape[0]
         p = self._params()
@@ -268,65 +284,159 @@ class NeRFRender(BaseNeuralRender):
             if p.ndc_rays:
                 view = rd
                 rd, ro = ctx.rays_to_ndc(rd, ro, p.ndc_width, p.ndc_height, cam.calib[0], cam.calib[1], p.ndc_near)
-            dists_c = ctx.sample_coarse(U_c, self.dist_near, self.dist_far)
-            smp_c = Sampling(*ctx.sampling(rd, ro, dists_c, radius, view))
-        val_c = self.network_coarse(smp_c)
-        integ_c = self.integrate_volume_render(dists_c, val_c["density"], val_c["color"])
-        for key in val_c:
-            if "penalty" in key:
-                delta = dists_c[:, 1:] - dists_c[:, :-1]
-                integ_c[key] = torch.sum(delta * val_c[key].reshape(B, -1)[:, :-1], dim=1)
-        with torch.no_grad():
-            # sanitises the coarse weights in place, as the reference does under set_grad_enabled(False)
-            dists_f = ctx.importance_resample(dists_c, integ_c["weight"].detach(), U_f, True)
-            smp_f = Sampling(*ctx.sampling(rd, ro, dists_f, radius, view))
-        val_f = self.network_fine(smp_f)
-        integ = self.integrate_volume_render(dists_f, val_f["density"], val_f["color"])
-        for key in val_f:
-            if "penalty" in key:
-                delta = dists_f[:, 1:] - dists_f[:, :-1]
-                integ[key] = torch.sum(delta * val_f[key].reshape(B, -1)[:, :-1], dim=1)
-        for key in list(integ_c):
-            integ["{}_coarse".format(key)] = integ_c[key]
-        return integ
+        return self._render_generated_rays(ctx, rd, ro, radius, U_c, U_f, view=view)
 
     def _render_rays_with_pose_grad(self, ctx: Context, uv: Tensor, camera: Camera, p: RenderParams, radius, U_c: Tensor,
                                     U_f: Tensor) -> Dict[str, Tensor]:
         """_render_rays_with_grad with ray generation and both samplers as autograd nodes (autograd.py RayFunction,
         SamplingFunction): the same kernels, draws and outputs, and camera.R / camera.T (differentiable results of
         Camera.update_transform) receive their gradients."""
-        from .autograd import RayFunction, SamplingFunction
-        from .ray import Sampling
+        from .autograd import RayFunction
         if p.ndc_rays:
             raise NotImplementedError("pose_gradients: NDC rays (ray_space='ndc') are not differentiated")
+        self._check_pose_fields()
+        # (the intrinsics are not differentiated: PinholeCalib.params reaches the kernels as plain numbers and receives no gradient;
+        # NeRFTrainer refuses to put it into the optimiser together with the poses)
+        rd, ro = RayFunction.apply(ctx, uv, camera.descriptor(), camera.R, camera.T)
+        return self._render_generated_rays(ctx, rd, ro, radius, U_c, U_f, ray_graph=True)
+
+    def _check_pose_fields(self) -> None:
         from .network import NeuS
         if isinstance(self.network_coarse, NeuS) or isinstance(self.network_fine, NeuS):
             raise NotImplementedError("pose_gradients through a NeuS field need a third derivative of the sdf trunk: not implemented")
-        # (the intrinsics are not differentiated: PinholeCalib.params reaches the kernels as plain numbers and receives no gradient;
-        # NeRFTrainer refuses to put it into the optimiser together with the poses)
-        B = uv.shape[0]
-        rd, ro = RayFunction.apply(ctx, uv, camera.descriptor(), camera.R, camera.T)
+
+    def _render_generated_rays(self, ctx: Context, rd: Tensor, ro: Tensor, radius, U_c: Tensor, U_f: Tensor, view: Optional[Tensor] = None,
+                               ray_graph: bool = False) -> Dict[str, Tensor]:
+        """The training forward from the rays on, shared by the uv routes above and render_bundle: coarse distances, sampling,
+        field, volume integral, resampling, and the same again through the fine network.  ray_graph=False: the samplers run as in
+        inference (`view`: the world-space viewing direction of NDC rays); True: they are autograd nodes (SamplingFunction), so
+        gradients reach whatever rd / ro were computed from."""
+        from .autograd import SamplingFunction
+        from .ray import Sampling
+        B = rd.shape[0]
+
+        def sample(dists: Tensor) -> Sampling:
+            if ray_graph:
+                return Sampling(*SamplingFunction.apply(ctx, rd, ro, dists, radius))
+            with torch.no_grad():
+                return Sampling(*ctx.sampling(rd, ro, dists, radius, view))
+
+        def integrate(network: BaseNeuralField, smp: Sampling, dists: Tensor) -> Dict[str, Tensor]:
+            val = network(smp)
+            integ = self.integrate_volume_render(dists, val["density"], val["color"])
+            for key in val:
+                if "penalty" in key:
+                    delta = dists[:, 1:] - dists[:, :-1]
+                    integ[key] = torch.sum(delta * val[key].reshape(B, -1)[:, :-1], dim=1)
+            return integ
+
         with torch.no_grad():
             dists_c = ctx.sample_coarse(U_c, self.dist_near, self.dist_far)
-        smp_c = Sampling(*SamplingFunction.apply(ctx, rd, ro, dists_c, radius))
-        val_c = self.network_coarse(smp_c)
-        integ_c = self.integrate_volume_render(dists_c, val_c["density"], val_c["color"])
-        for key in val_c:
-            if "penalty" in key:
-                delta = dists_c[:, 1:] - dists_c[:, :-1]
-                integ_c[key] = torch.sum(delta * val_c[key].reshape(B, -1)[:, :-1], dim=1)
+        integ_c = integrate(self.network_coarse, sample(dists_c), dists_c)
         with torch.no_grad():
+            # sanitises the coarse weights in place, as the reference does under set_grad_enabled(False)
             dists_f = ctx.importance_resample(dists_c, integ_c["weight"].detach(), U_f, True)
-        smp_f = Sampling(*SamplingFunction.apply(ctx, rd, ro, dists_f, radius))
-        val_f = self.network_fine(smp_f)
-        integ = self.integrate_volume_render(dists_f, val_f["density"], val_f["color"])
-        for key in val_f:
-            if "penalty" in key:
-                delta = dists_f[:, 1:] - dists_f[:, :-1]
-                integ[key] = torch.sum(delta * val_f[key].reshape(B, -1)[:, :-1], dim=1)
+        integ = integrate(self.network_fine, sample(dists_f), dists_f)
         for key in list(integ_c):
             integ["{}_coarse".format(key)] = integ_c[key]
         return integ
+
+    # ------------------------------------------------------------------ bundles
+    def render_bundle(self, rays: Ray) -> Dict[str, Tensor]:
+        """render_rays on explicit rays (not a reference method): rays.ray_dir / rays.ray_orig [B,3] in world space, unit directions
+        by the caller's contract (nothing is normalised), rays.uv unused.  The same keys, the same uniform draw order ([B,Sc+1] then
+        [B,Sf+1]) and the same NaN assertion as render_rays; every stage after ray generation is the one render_rays runs, so a
+        bundle made from ctx.raygen(uv, camera) gives render_rays(uv, camera)'s bits.  Inference goes to the fused path
+        (NEDDF_UV_RAYS; normal_output is honoured).  Under autograd the network parameters receive gradients as in render_rays;
+        with pose_gradients set and rays.ray_dir / ray_orig requiring grad the samplers join the graph, and the gradients arrive
+        at the tensors the caller built the rays from.  ray_space='ndc' raises: the NDC map needs a camera's focal lengths."""
+        if self.ray_space == "ndc":
+            raise NotImplementedError("render_bundle: NDC rays (ray_space='ndc') need a camera's focal lengths; a bundle has none")
+        rd, ro = rays.ray_dir, rays.ray_orig
+        if rd.dim() != 2 or rd.shape[1] != 3 or ro.shape != rd.shape:
+            raise ValueError("render_bundle: ray_dir and ray_orig must be [B, 3] (got %s and %s)" % (tuple(rd.shape), tuple(ro.shape)))
+        B, dev = rd.shape[0], rd.device
+        if torch.is_grad_enabled():
+            ray_graph = bool(self.pose_gradients) and (rd.requires_grad or ro.requires_grad)
+            if ray_graph or any(p.requires_grad for p in self.parameters()):
+                ctx = Context.get(dev)
+                p = self._params()
+                U_c = self._rand(B, self.sample_coarse + 1, dev)
+                U_f = self._rand(B, self.sample_fine + 1, dev)
+                radius = p.ray_radius if p.cone_sampling else None
+                if ray_graph:
+                    self._check_pose_fields()
+                    rd, ro = rd.to(torch.float32), ro.to(torch.float32)
+                else:
+                    rd, ro = rd.detach().to(torch.float32).contiguous(), ro.detach().to(torch.float32).contiguous()
+                return self._render_generated_rays(ctx, rd, ro, radius, U_c, U_f, ray_graph=ray_graph)
+        ctx = self._ctx(dev)
+        U_c = self._rand(B, self.sample_coarse + 1, dev)       # draw order is part of the contract
+        U_f = self._rand(B, self.sample_fine + 1, dev)
+        o = self._render(ctx, rays, None, U_c, U_f, full=True, normal=bool(self.normal_output))
+        assert int(o.pop("_nan").item()) == 0, "NaN weight in integrate_volume_render"
+        return {k: o[k] for k in self.RAY_KEYS if k in o}
+
+    def render_rays_mixed(self, uv: Tensor, view_index: Tensor, cameras: List[Camera]) -> Dict[str, Tensor]:
+        """render_rays on a batch that mixes views (not a reference method): row b is pixel uv[b] of cameras[view_index[b]]
+        (uv [B,2], view_index int64 [B]).  Every camera that owns rows generates them, in batch order, with render_rays' own ray
+        generation -- one raygen launch per visited camera, RayFunction under pose_gradients so that its R / T receive gradients --
+        the rays go back to their batch positions and the batch runs as ONE bundle (render_bundle: its keys, draws and assertion).
+        A camera that owns no row costs nothing and gets no gradient; an index outside the list raises ValueError."""
+        from .autograd import RayFunction
+        if self.ray_space == "ndc":
+            raise NotImplementedError("render_rays_mixed: NDC rays (ray_space='ndc') are not supported")
+        cameras = list(cameras)
+        if not cameras:
+            raise ValueError("render_rays_mixed: no cameras")
+        dev = cameras[0].device
+        uv = uv.to(dev)
+        view_index = torch.as_tensor(view_index).to(device=dev, dtype=torch.int64)
+        if uv.dim() != 2 or uv.shape[1] != 2 or view_index.shape != (uv.shape[0],):
+            raise ValueError("render_rays_mixed: uv must be [B, 2] and view_index [B]")
+        B = uv.shape[0]
+        counts = [0] * len(cameras)
+        if B:       # one device -> host read: the smallest index, then the rows per camera
+            lowest, *counts = torch.cat([view_index.min().view(1), torch.bincount(view_index.clamp(min=0), minlength=len(cameras))]).tolist()
+            if lowest < 0 or len(counts) > len(cameras):
+                raise ValueError("render_rays_mixed: view_index must lie in [0, %d)" % len(cameras))
+        order = torch.argsort(view_index, stable=True)          # rows grouped by camera, batch order inside a group
+        graph = torch.is_grad_enabled() and bool(self.pose_gradients)
+        ctx = Context.get(dev)
+        dirs, origs, start = [], [], 0
+        for camera, count in zip(cameras, counts):
+            if not count:
+                continue
+            rows = uv[order[start:start + count]]
+            start += count
+            if not _is_pinhole(camera):
+                with torch.set_grad_enabled(graph):
+                    part = camera.create_rays(rows)
+                rd, ro = part.ray_dir, part.ray_orig
+            elif graph:
+                rd, ro = RayFunction.apply(ctx, rows, camera.descriptor(), camera.R, camera.T)
+            else:
+                with torch.no_grad():
+                    rd, ro = ctx.raygen(rows, camera.descriptor())
+            dirs.append(rd)
+            origs.append(ro)
+        if not dirs:
+            return self.render_bundle(Ray(torch.empty(0, 3, device=dev), torch.empty(0, 3, device=dev)))
+        back = torch.empty_like(order)
+        back[order] = torch.arange(B, device=dev)               # where batch row b stands in the grouped order
+        return self.render_bundle(Ray(torch.cat(dirs)[back], torch.cat(origs)[back]))
+
+    def _view_rays(self, uv: Tensor, camera: Camera):
+        """What the fused entry points take for pixels `uv` of `camera`, (uv argument, camera descriptor, bundle): the pixels and
+        the pinhole descriptor for a PinholeCalib -- the path every release took -- and otherwise the rays Camera.create_rays makes
+        in torch, as float32 [n, 6] (direction, origin) rows with no descriptor."""
+        if _is_pinhole(camera):
+            return uv, camera.descriptor(), False
+        if self.ray_space == "ndc":
+            raise NotImplementedError("NDC rays (ray_space='ndc') need a pinhole camera's focal lengths")
+        with torch.no_grad():
+            rays = camera.create_rays(uv)
+            return torch.cat([rays.ray_dir, rays.ray_orig], 1).contiguous(), None, True
 
     # ------------------------------------------------------------- render_image
     def render_image(self, width: int, height: int, camera: Camera, target_types: Iterable[RenderTarget],
@@ -361,14 +471,14 @@ class NeRFRender(BaseNeuralRender):
             flags = []
             lo, hi = (0, n) if pixel_range is None else pixel_range
 
-            cam_desc = camera.descriptor()          # three device -> host reads: once per image, not per batch
+            uv, cam_desc, bundle = self._view_rays(uv, camera)    # three device -> host reads: once per image, not per batch
             occ = self._occupancy_desc(dev)
 
             def launch(below, above, U_c, U_f):
                 # sample_pdf's NaN fallback keeps the reference's per-chunk granularity: batches start on chunk boundaries,
                 # except a slab's first batch, which may start inside a chunk another rank shares
                 o = self._render(ctx, uv[below:above], camera, U_c, U_f, full=False, cam_desc=cam_desc, nan_group=chunk,
-                                 nan_group_offset=below % chunk, normal=want_normal, occupancy=occ)
+                                 nan_group_offset=below % chunk, normal=want_normal, occupancy=occ, bundle=bundle)
                 flags.append(o["_nan"])
                 for k in target_types:
                     parts[k].append(o[k])
@@ -436,7 +546,7 @@ class NeRFRender(BaseNeuralRender):
             if normals:
                 out["normal"] = torch.empty(n, 3, device=dev)
             flag = torch.zeros(1, device=dev, dtype=torch.int32)
-            cam_desc = camera.descriptor()
+            uv, cam_desc, bundle = self._view_rays(uv, camera)
             occ = self._occupancy_desc(dev)
             for below in range(0, n, self.rays_per_call):
                 above = min(n, below + self.rays_per_call)
@@ -444,7 +554,7 @@ class NeRFRender(BaseNeuralRender):
                 # without U the uniforms are drawn per batch: in "torch_cpu" mode the host draws batch k+1 while batch k renders
                 Ub = U[below:above] if U is not None else self._rand(above - below, samples, dev)
                 ctx.render_rays(uv[below:above], cam_desc, self._params(), Ub, None,
-                                dict(o, nan_flag=flag), single_slot=SLOT_FINE, occupancy=occ)
+                                dict(o, nan_flag=flag), single_slot=SLOT_FINE, occupancy=occ, bundle=bundle)
             out["_nan"] = flag
         return out
 
@@ -490,7 +600,8 @@ class NeRFRender(BaseNeuralRender):
             uv = torch.stack([us, vs], 1)[lo:hi]
             n = uv.shape[0]
             ctx = self._ctx(dev)
-            rd, ro = ctx.raygen(uv, camera.descriptor())
+            uv, cam_desc, bundle = self._view_rays(uv, camera)
+            rd, ro = ctx.raygen(uv, cam_desc, bundle=bundle)
             st, _ = ctx.trace_field(SLOT_FINE, ro, rd, params)
             hit = st["status"] == HIT
             out: Dict[str, Tensor] = {}
@@ -582,7 +693,8 @@ class NeRFRender(BaseNeuralRender):
             lo, hi = (0, w * h) if pixel_range is None else pixel_range
             uv = torch.stack([us, vs], 1)[lo:hi]
             n = uv.shape[0]
-            rd, ro = self._ctx(dev).raygen(uv, camera.descriptor())
+            uv, cam_desc, bundle = self._view_rays(uv, camera)
+            rd, ro = self._ctx(dev).raygen(uv, cam_desc, bundle=bundle)
             order = self.tile_order(w, h, tile, dev) if tile else None
             co, cd = (ro, rd) if order is None else (ro[order].contiguous(), rd[order].contiguous())
             if bvh is not None:

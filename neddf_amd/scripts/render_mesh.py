@@ -1,5 +1,5 @@
 """`python neddf/scripts/render_mesh.py <run_dir> [--epoch 2000] [--mesh PATH.ply] [--compare-trace [THRESHOLD]] [--method grid|brute]
-[--bvh] [--tiles] [--ao [K]]` --
+[--bvh] [--tiles] [--ao [K]] [--ortho SCALE]` --
 views of an extracted mesh from the run's test cameras (no reference counterpart: the reference looks at its meshes in an Open3D
 viewer).  The run is loaded as extract_mesh.py loads it; the mesh is read with neddf_amd.mesh.read_ply, by default the newest file
 under `<run_dir>/mesh/`.  For every test camera NeRFRender.render_image_mesh casts the camera's rays -- the pixels of
@@ -10,7 +10,8 @@ the hit share and the time.  --compare-trace also sphere-traces the field at THR
 trace only, and the mean and maximum |t_mesh - t_traced| over the pixels hit by both.  --bvh casts the rays through the mesh's BVH
 (neddf_amd.bvh: the same images, bit for bit) instead of --method's route, --tiles casts them ordered by 8 x 8 pixel tiles (the same
 images again), and --ao [K] (K directions, default 16; implies --bvh) also writes `{id:03}_ao_mesh.png`, the ambient occlusion at the
-hit points: a shaded look at the mesh."""
+hit points: a shaded look at the mesh.  --ortho SCALE looks from the test cameras' poses through an orthographic camera of SCALE pixels per
+world unit (camera.OrthographicCalib, the principal point at the image centre) instead of the dataset's pinhole."""
 import re
 from argparse import ArgumentParser
 from pathlib import Path
@@ -28,6 +29,8 @@ def build_parser() -> ArgumentParser:
     parser.add_argument("--tiles", action="store_true", help="cast the rays ordered by 8 x 8 pixel tiles (the same images)")
     parser.add_argument("--ao", type=int, nargs="?", const=16, default=None, metavar="K",
                         help="also write {id:03}_ao_mesh.png: ambient occlusion from K directions (default 16); implies --bvh")
+    parser.add_argument("--ortho", type=float, default=None, metavar="SCALE",
+                        help="orthographic views from the test cameras' poses, SCALE pixels per world unit")
     return parser
 
 
@@ -75,6 +78,8 @@ def main(argv=None) -> list:
     if args.compare_trace is not None:
         threshold = threshold_of(path) if args.compare_trace != args.compare_trace else args.compare_trace
     trainer = load_trainer(load_config(output_dir), output_dir, args.epoch)
+    if args.ortho is not None:
+        trainer.use_orthographic_cameras(args.ortho)
     render = trainer.neural_render
     render.set_iter(-1)
     dev = trainer.device

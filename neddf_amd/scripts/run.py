@@ -2,7 +2,8 @@
 reference's neddf/scripts/run.py:13-40 (a hydra app over config/): the config groups of config/config.yaml's defaults
 list are composed with PyYAML, `group=name` picks another file of a group, dotted keys override single values, and --
 as hydra does -- the run executes inside a fresh outputs/<date>/<time>/ directory holding .hydra/config.yaml (which is
-what run_eval.py later reads), models/, render/ and log/."""
+what run_eval.py later reads), models/, render/ and log/.  A dotted key may also set a keyword the group's file leaves at its
+default: `trainer.batch_views=mixed` trains on batches that mix views (NeRFTrainer), `trainer.optimize_cameras=true` the poses."""
 import datetime
 import os
 import random

@@ -53,6 +53,10 @@ def build_parser() -> ArgumentParser:
                              "0.0275 for the shipped bunny) and write {id:03}_rgb_traced.png / _depth_traced.png (and _normal_traced.png "
                              "with --normals) next to the usual images; prints hit share, mean advances per ray and milliseconds per "
                              "view (not a reference option; NeDDF and NeuS fields, world-space rays, rank 0's device)")
+    parser.add_argument("--ortho", type=float, default=None, metavar="SCALE",
+                        help="render the test cameras' poses through an orthographic camera of SCALE pixels per world unit, the "
+                             "principal point at the image centre (not a reference option; an inspection view: the PSNR / SSIM "
+                             "against the dataset's perspective images then mean nothing; one device)")
     parser.add_argument("--trace-steps", type=int, default=64, metavar="N", help="marching iterations of --trace (default 64)")
     return parser
 
@@ -105,6 +109,10 @@ def main(argv=None) -> None:
         cfg["trainer"]["device"] = "cuda:%d" % local
     trainer = load_trainer(cfg, output_dir, args.epoch)
     trainer.writes_outputs = rank == 0
+    if args.ortho is not None:
+        if world > 1:
+            raise SystemExit("run_eval.py: --ortho renders ray bundles, which are not ray-sharded; run it on one device")
+        trainer.use_orthographic_cameras(args.ortho)
     save_dir = args.output_dir / "eval"
     if rank == 0:
         save_dir.mkdir(exist_ok=True)

@@ -11,7 +11,7 @@ from typing import Any, Dict, List
 import numpy as np
 import torch
 
-from .camera import Camera, PinholeCalib
+from .camera import Camera, OrthographicCalib, PinholeCalib
 from .config import instantiate, to_plain
 from .dataset import imwrite_bgr
 from .logger import ScalarLog
@@ -48,6 +48,15 @@ class BaseTrainer:
                                       for i in range(len(self.dataset))]
         loss_cfg = _get(self.config, "loss") if _has(self.config, "loss") else {"functions": []}
         self.loss_functions = [instantiate(f).to(self.device) for f in _get(loss_cfg, "functions")]     # base_trainer.py:110-113
+        self._gt_stacks: Dict[str, Any] = {}    # construct_ground_truth_mixed's device images, built on first use
+        self._view_sizes = None                 # draw_mixed_batch's per-view (w - 1, h - 1)
+
+    def use_orthographic_cameras(self, scale: float) -> None:
+        """Replaces every view's camera by an orthographic one at the same pose (not in the reference): `scale` pixels per world
+        unit, the principal point at the image centre -- the inspection views of render_mesh.py --ortho and run_eval.py --ortho."""
+        h, w = self.dataset[0]["rgb_images"].shape[:2]
+        self.camera_calib = OrthographicCalib(np.array([scale, scale, 0.5 * w, 0.5 * h], dtype=np.float32)).to(self.device)
+        self.cameras = [Camera(self.camera_calib, self.dataset[i]["camera_params"]).to(self.device) for i in range(len(self.dataset))]
 
     def load_pretrained_model(self, model_path: Path) -> None:
         """base_trainer.py:115-121"""
@@ -124,6 +133,54 @@ class BaseTrainer:
             targets["fields_penalty"] = torch.zeros(us_int.shape, dtype=torch.float32)
         return targets
 
+    def construct_ground_truth_mixed(self, view: torch.Tensor, us_int: torch.Tensor, vs_int: torch.Tensor,
+                                     loss_types: List[str]) -> Dict[str, torch.Tensor]:
+        """construct_ground_truth for a batch that mixes views: row b is pixel (us_int[b], vs_int[b]) of view[b], and holds the
+        bits construct_ground_truth(view[b], ...) gives for that pixel.  When every view has one image size the images are stacked
+        on the device once ([V,h,w,3]; masks [V,h,w]) and a step is one gather there -- x * 2^-8 is exact in fp32, so the device's
+        product is the host's; otherwise the rows are gathered per view on the host with the method above."""
+        view = torch.as_tensor(view).to(torch.int64)
+        want_color = "ColorLoss" in loss_types
+        want_mask = "MaskBCELoss" in loss_types or "MaskMSELoss" in loss_types
+        targets: Dict[str, torch.Tensor] = {}
+        stacks = self._ground_truth_stacks(want_color, want_mask)
+        if stacks is not None:
+            v, us, vs = view.to(self.device), us_int.to(self.device).to(torch.int64), vs_int.to(self.device).to(torch.int64)
+            if want_color:
+                targets["color"] = stacks["color"][v, vs, us].to(torch.float32) * (1.0 / 256)
+            if want_mask:
+                targets["mask"] = stacks["mask"][v, vs, us].to(torch.float32) * (1.0 / 256)
+        else:
+            view_host = view.cpu()
+            if want_color:
+                targets["color"] = torch.empty(view.shape[0], 3, dtype=torch.float32, device=self.device)
+            if want_mask:
+                targets["mask"] = torch.empty(view.shape[0], dtype=torch.float32, device=self.device)
+            for camera_id in torch.unique(view_host).tolist():
+                rows = (view_host == camera_id).nonzero().squeeze(1)
+                part = self.construct_ground_truth(int(camera_id), us_int.cpu()[rows], vs_int.cpu()[rows],
+                                                   [t for t in loss_types if t != "FieldsConstraintLoss"])
+                for key in part:
+                    targets[key][rows.to(self.device)] = part[key]
+        if "FieldsConstraintLoss" in loss_types:
+            targets["fields_penalty"] = torch.zeros(us_int.shape, dtype=torch.float32)
+        return targets
+
+    def _ground_truth_stacks(self, want_color: bool, want_mask: bool):
+        """The device-resident image stacks of construct_ground_truth_mixed, built on first use and kept in the images' own type
+        (uint8, or the float32 of alpha-premultiplied colours: either way the fp32 product with 2^-8 is the host's value); None
+        when the views differ in size or hold another type (the host route then reads the images as they are)."""
+        cache = self._gt_stacks
+        for key, field, want in (("color", "rgb_images", want_color), ("mask", "mask_images", want_mask)):
+            if not want or key in cache:
+                continue
+            images = [np.asarray(self.dataset[i][field]) for i in range(len(self.dataset))]
+            fits = all(im.shape == images[0].shape and im.dtype == images[0].dtype for im in images) and images[0].dtype in (np.uint8, np.float32)
+            cache[key] = torch.from_numpy(np.stack(images)).to(self.device) if fits else None
+        if (want_color and cache["color"] is None) or (want_mask and cache["mask"] is None):
+            return None
+        return cache
+
     def run_train(self) -> None:
         raise NotImplementedError()
 
@@ -136,10 +193,16 @@ class NeRFTrainer(BaseTrainer):
     Camera.params -- the SE(3) perturbation of its dataset pose -- into Adam as a second parameter group and switches the
     render's pose_gradients on; camera_lr is that group's learning rate.  The reference leaves the pose parameters out of its
     optimiser, so it has no value to follow: 1e-3 is the step of published joint pose / field optimisation (BARF, Lin et al.
-    2021, train their poses at 1e-3), twice the field's 5e-4 here, and decays with the same scheduler."""
+    2021, train their poses at 1e-3), twice the field's 5e-4 here, and decays with the same scheduler.
+    A third: batch_views.  "single" (default, the reference): a step draws all its rays from one view, an epoch visits the views in
+    a random permutation.  "mixed": every ray of a step draws its own view (run_train_step_mixed), an epoch is still len(dataset)
+    steps; with optimize_cameras every view a step visits receives a pose gradient."""
 
-    def __init__(self, optimize_cameras: bool = False, camera_lr: float = 1e-3, **kwargs: Any) -> None:
+    def __init__(self, optimize_cameras: bool = False, camera_lr: float = 1e-3, batch_views: str = "single", **kwargs: Any) -> None:
+        if batch_views not in ("single", "mixed"):
+            raise ValueError("batch_views must be 'single' or 'mixed' (got %r)" % (batch_views,))
         super().__init__(**kwargs)
+        self.batch_views = batch_views
         self.optimize_cameras, self.camera_lr = bool(optimize_cameras), float(camera_lr)
         self.neural_render = render_from_config(to_plain(_get(self.config, "render")), network_config=to_plain(_get(self.config, "network")),
                                                 _recursive_=False).to(self.device)
@@ -168,7 +231,10 @@ class NeRFTrainer(BaseTrainer):
             print("epoch: ", epoch)
             camera_ids = np.random.permutation(frame_length)
             for camera_id in camera_ids:
-                self.run_train_step(int(camera_id))
+                if self.batch_views == "mixed":     # (the permutation is drawn either way; its first view is the test render's)
+                    self.run_train_step_mixed()
+                else:
+                    self.run_train_step(int(camera_id))
                 self.neural_render.next_iter()
             self.scheduler.step()
             if not self.writes_outputs:
@@ -202,11 +268,56 @@ class NeRFTrainer(BaseTrainer):
             targets = self.construct_ground_truth(camera_id, us_int, vs_int, names)
             with torch.enable_grad():
                 rendered = self.neural_render.render_rays(torch.stack([us_int, vs_int], 1), camera)
-                terms: Dict[str, torch.Tensor] = {}
-                for f in self.loss_functions:
-                    terms.update(f(rendered, targets))
-                total = torch.stack(list(terms.values())).sum()
-                total.backward()
+                loss_value = self._finish_step(rec, rendered, targets)
+        return loss_value
+
+    def draw_mixed_batch(self):
+        """The pixel draws of a mixed-view step, on the CPU generator and in this order -- the contract of batch_views="mixed":
+
+            view = (torch.rand(B) * n_views).to(torch.int64)            each ray's view
+            us   = (torch.rand(B) * (w[view] - 1)).to(torch.int16)      then its column, scaled by ITS view's width
+            vs   = (torch.rand(B) * (h[view] - 1)).to(torch.int16)      then its row, by its view's height
+
+        (host tensors; render_rays_mixed's own draws follow).  The scale factors are fp32, as the single-view step's are."""
+        sizes = self._view_sizes
+        if sizes is None:
+            hw = [self.dataset[i]["rgb_images"].shape[:2] for i in range(len(self.dataset))]
+            sizes = self._view_sizes = (torch.tensor([s[1] - 1 for s in hw], dtype=torch.float32),
+                                        torch.tensor([s[0] - 1 for s in hw], dtype=torch.float32))
+        view = (torch.rand(self.batch_size) * len(self.dataset)).to(torch.int64)
+        us_int = (torch.rand(self.batch_size) * sizes[0][view]).to(torch.int16)
+        vs_int = (torch.rand(self.batch_size) * sizes[1][view]).to(torch.int16)
+        return view, us_int, vs_int
+
+    def run_train_step_mixed(self) -> float:
+        """run_train_step on rays drawn across all views (not a reference method).  RNG draw order: draw_mixed_batch's three
+        draws (view, u, v), then render_rays_mixed's own (render_rays' [B,Sc+1] and [B,Sf+1]).  With optimize_cameras every view
+        the step visits receives a pose gradient; a view it does not visit has none (single rank) or is reset by the all-zero
+        rule below (several ranks)."""
+        if self.logger is None:
+            self.logger = ScalarLog() if self.writes_outputs else ScalarLog(sink="null")
+        for camera in self.cameras:
+            camera.update_transform()
+        with self.logger.step() as rec:
+            self.optimizer.zero_grad()
+            view, us_int, vs_int = self.draw_mixed_batch()
+            names = [type(f).__name__ for f in self.loss_functions]
+            targets = self.construct_ground_truth_mixed(view, us_int, vs_int, names)
+            with torch.enable_grad():
+                uv = torch.stack([us_int, vs_int], 1).to(self.device)
+                rendered = self.neural_render.render_rays_mixed(uv, view.to(self.device), self.cameras)
+                loss_value = self._finish_step(rec, rendered, targets)
+        return loss_value
+
+    def _finish_step(self, rec, rendered: Dict[str, torch.Tensor], targets: Dict[str, torch.Tensor]) -> float:
+        """Losses, backward, the gradient all-reduce, the optimiser step and the log record of one training step (under
+        enable_grad, inside the logger's step)."""
+        terms: Dict[str, torch.Tensor] = {}
+        for f in self.loss_functions:
+            terms.update(f(rendered, targets))
+        total = torch.stack(list(terms.values())).sum()
+        total.backward()
+        with torch.no_grad():
             # data-parallel runs (scripts/run.py under torchrun: per-rank seed and device): one all-reduce of the gradients
             average_gradients(self.neural_render.get_parameters_list())
             if self.optimize_cameras:       # (every rank passes the same list; the ranks visit different views per step)
