@@ -18,6 +18,7 @@
 using namespace neddf;
 
 #include "capi_internal.h"
+#include "field_plan.h"
 
 // one stage launch, bracketed by a hipEvent pair while timing is on
 #define STAGE(ctx, stream, which, launch) \
@@ -69,6 +70,76 @@ static bool rays_in_field(const Field &f, bool full, bool dgrad)
     return (!rif || atoi(rif) != 0) && ddf_reverse(f, full) && f.d.kind == NEDDF_FIELD_NEDDF && !dgrad;
 }
 
+// -DNEDDF_STAMP builds (`make stamp`): the phase stamps of a field kernel.  One device block per argument type -- the distance and the
+// colour kernel each have their own -- allocated once and cleared before every launch group ...
+#ifdef NEDDF_STAMP
+constexpr size_t kStampBytes = ((size_t)kStampBlocks * 8 * kStampSlots * kStampPairTiles + 4 * kStampWgTail) * sizeof(unsigned long long);
+#endif
+template <class Args>
+static int stamp_arm(neddf_ctx *ctx, Args &a, hipStream_t s)
+{
+#ifdef NEDDF_STAMP
+    static unsigned long long *d_stamps = nullptr;
+    if (!d_stamps) HIPCHK(hipMalloc((void **)&d_stamps, kStampBytes));
+    HIPCHK(hipMemsetAsync(d_stamps, 0, kStampBytes, s));
+    a.stamps = d_stamps;
+#endif
+    return 0;
+}
+
+// ... and the LAST launch's stamps written to the path that `env` names (a diagnostic build: synchronising here is fine)
+static int stamp_dump(neddf_ctx *ctx, const unsigned long long *d_stamps, const char *env, hipStream_t s)
+{
+#ifdef NEDDF_STAMP
+    if (const char *path = getenv(env)) {
+        HIPCHK(hipStreamSynchronize(s));
+        std::vector<unsigned long long> h(kStampBytes / sizeof(unsigned long long));
+        HIPCHK(hipMemcpy(h.data(), d_stamps, kStampBytes, hipMemcpyDeviceToHost));
+        if (FILE *fp = fopen(path, "wb")) { fwrite(h.data(), 1, kStampBytes, fp); fclose(fp); }
+    }
+#endif
+    return 0;
+}
+
+// The one place that knows where a launch's pointers start.  `a` holds the whole call: its inputs and outputs at point 0, the hand-off
+// buffers at their heads.  The launch of `n` points at point `so` of the chunk at `off` reads and writes the call's arrays at off + so
+// and the chunk's hand-off at so -- whether the points come from the rays or from the sampling tensors.
+static DdfArgs ddf_at(const DdfArgs &a, int wid, int64_t off, int64_t so, int64_t n)
+{
+    DdfArgs b = a;
+    const int64_t at = off + so;
+    b.n_points = n;
+    if (a.rays.rd) b.rays.base = a.rays.base + at;
+    else { b.pos = a.pos + at * 3; b.dir = a.dir + at * 3; b.var = a.var + at * 3; }
+    if (a.features) b.features = a.features + (size_t)so * a.feat_rows * wid;
+    b.ptaux = a.ptaux + (size_t)so * kPtAux;
+    if (a.distance) b.distance = a.distance + at;
+    if (a.density) b.density = a.density + at;
+    if (a.aux_grad) b.aux_grad = a.aux_grad + at;
+    return b;
+}
+
+// the NeRF field: one kernel, one launch over all N points
+static int nerf_forward(neddf_ctx *ctx, Field &f, const float *pos, const float *dir, const float *var, int64_t N, float *density, float *color,
+                        hipStream_t s)
+{
+    NerfArgs a = f.nerf;
+    fill_enc(a.enc, f);
+    a.pos = pos; a.dir = dir; a.var = var; a.n_points = N;
+    a.scratch = (float *)ctx->scratch.p;
+    DevBuf &tmp = ctx->ptaux;   // NeRF needs no hand-off buffers; reuse ptaux for optional sinks
+    if (!density || !color) {
+        if (int rc = ensure(ctx, tmp, (size_t)N * 4 * sizeof(float))) return rc;
+    }
+    a.density = density ? density : (float *)tmp.p;
+    a.color = color ? color : (float *)tmp.p + N;
+    const int grid_cap = ctx->cus * nerf_wgs_per_cu(f.nerf.width);
+    int64_t tiles = (N + nerf_points_per_tile(f.nerf.width) - 1) / nerf_points_per_tile(f.nerf.width);
+    STAGE(ctx, s, NEDDF_STAGE_NERF, launch_nerf(a, (int)(tiles < grid_cap ? tiles : grid_cap), s));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // rays != NULL (neddf_render_rays): the N points are the [B, Se] grid of these rays' evaluated samples (Se = S unless the caller skips
 // each ray's last one, which only a rays_in_field() route can); pos / dir / var are then WORKSPACE -- filled by the sampling kernel when
 // the route cannot take its points from the rays, untouched when it can (kernels.h RaySrc)
@@ -97,21 +168,9 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
     };
     if (f.d.kind == NEDDF_FIELD_NERF) {
         if (rays) sample_now();
-        NerfArgs a = f.nerf;
-        fill_enc(a.enc, f);
-        a.pos = pos; a.dir = dir; a.var = var; a.n_points = N;
-        a.scratch = (float *)ctx->scratch.p;
-        DevBuf &tmp = ctx->ptaux;   // NeRF needs no hand-off buffers; reuse ptaux for optional sinks
-        if (!density || !color) {
-            if (int rc = ensure(ctx, tmp, (size_t)N * 4 * sizeof(float))) return rc;
-        }
-        a.density = density ? density : (float *)tmp.p;
-        a.color = color ? color : (float *)tmp.p + N;
-        int64_t tiles = (N + nerf_points_per_tile(wid) - 1) / nerf_points_per_tile(wid);
-        STAGE(ctx, s, NEDDF_STAGE_NERF, launch_nerf(a, (int)(tiles < grid_cap ? tiles : grid_cap), s));
-        HIPCHK(hipGetLastError());
-        return 0;
+        return nerf_forward(ctx, f, pos, dir, var, N, density, color, s);
     }
+    // ---- the route ----
     const bool full = (out_mode == NEDDF_OUT_FULL) && penalty && f.d.kind == NEDDF_FIELD_NEDDF;
     const int fr = full ? 4 : 1;
     const bool reverse = ddf_reverse(f, full);
@@ -121,21 +180,9 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
     if (rays && !use_rays) sample_now();
     // fp32 products as three-term bf16 splits (f32_products_split3): the reverse-mode kernel and the colour kernel behind it only
     const bool use3 = f.has3 && reverse && f.d.kind == NEDDF_FIELD_NEDDF;
-    // Points per launch of the field kernels.  Every launch boundary drains the persistent grid (workgroups finish up to one tile
-    // apart) and refills it: at 2^21 points a 65 536-ray x 128-sample call was four launch pairs, at 2^23 it is one -- fp32 +0.8 %,
-    // split fp16 +0.7 %, bf16 +2.8 % (profiles/r04_launch_size.txt).  The hand-off buffers grow with it (1 088 B per point
-    // eval-minimal: 9.1 GB at 2^23 of the 288 GB); NEDDF_FIELD_CHUNK_LOG2 overrides.
-    static const int chunk_env = [] { const char *e = getenv("NEDDF_FIELD_CHUNK_LOG2"); int v = e && *e ? atoi(e) : 0; return !v ? 0 : (v < 16 ? 16 : (v > 25 ? 25 : v)); }();
-    const int chunk_log2 = chunk_env ? chunk_env : 23;
-    // The three-term fp32 DISTANCE kernel is the exception: its L2 hit rate FALLS with the launch size (per 2^23 points: 83 % of the
-    // TCC requests hit in 2^19-point launches, 74 % at 2^21, 65 % at 2^23; fabric reads 42 / 83 / 125 M KB) and it is fastest in
-    // launches of 2^20 points (profiles/r09_alignment.txt, r09_launch_size_ab.txt).  The colour kernel behind it and every other policy
-    // still prefer the large launch.  So a chunk's distance kernel runs as sub-launches of 2^20 points into the chunk's hand-off, and
-    // the colour kernel once over the chunk.  With NEDDF_FIELD_CHUNK_LOG2 set, both kernels take launches of that size as before.
-    const int64_t ddf_sub = (use3 && !chunk_env) ? ((int64_t)1 << 20) : ((int64_t)1 << 25);
     // NEDDF_X3_L2 (read per call: the A/B runs flip it inside one library): an L2 residency mechanism of the three-term distance
     // kernel (tile_engine.h OpsF32x3L2T) -- `stream` (the default: y' read back non-temporal), `wb` (a write-back every
-    // NEDDF_X3_L2_PERIOD tiles of an XCD, default 16), `both`; `0`: the plain kernel.  The sub-launches above stay: `stream` lifts a
+    // NEDDF_X3_L2_PERIOD tiles of an XCD, default 16), `both`; `0`: the plain kernel.  The sub-launches of the plan stay: `stream` lifts a
     // 2^23-point launch from 61 to 69 % hits, the 2^20-point ones from 77 to 82 %, and is faster with them (docs/lab_notebook.md R11.1)
     int l2_mode = 0, l2_period = 0;
     if (use3) {
@@ -145,130 +192,81 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
         const int v = r && *r ? atoi(r) : 16;
         l2_period = v < 1 ? 1 : (v > 4096 ? 4096 : v);
     }
-    const int64_t chunk_cap = full ? (1 << 19) : ((int64_t)1 << chunk_log2);
-    int64_t chunk = N < chunk_cap ? N : chunk_cap;
-    // The hand-off of one launch (features + per-point record: 1 088 B per point eval-minimal at width 256, 9.1 GB at 2^23 points,
-    // twice that at engine width 512) is bounded by what the DEVICE has free, not by a constant: several contexts or ranks on one
-    // device, or a part with less HBM, get smaller launches (-0.8 .. -2.8 % each halving, profiles/r04_launch_size.txt) instead
-    // of NEDDF_EHIP -- at most a quarter of the free memory (counting what this context's own blocks give back when they grow).
-    {
-        const size_t per_point = ((size_t)fr * wid + kPtAux) * sizeof(float);
-        // a launch size settled earlier for this row size stands (the probe is a driver call: not on the hot path of every evaluation)
-        if (ctx->handoff_row == per_point && ctx->handoff_chunk > 0 && chunk > ctx->handoff_chunk) chunk = ctx->handoff_chunk;
-        if (ctx->features.cap < (size_t)chunk * fr * wid * sizeof(float) || ctx->ptaux.cap < (size_t)chunk * kPtAux * sizeof(float)) {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                free_b += ctx->features.cap + ctx->ptaux.cap;
-                const int64_t asked = chunk;
-                while (chunk > (1 << 16) && (size_t)chunk * per_point + (size_t)chunk * per_point / 8 > free_b / 4) chunk >>= 1;
-                if (chunk < asked) { ctx->handoff_row = per_point; ctx->handoff_chunk = chunk; }
-            }
-        }
-    }
+    // ---- the plan: points per launch of either kernel (field_plan.h has the rules and their reasons) ----
+    static const int chunk_env = [] { const char *e = getenv("NEDDF_FIELD_CHUNK_LOG2"); return e && *e ? atoi(e) : 0; }();
+    const FieldPlanIn in{ full, use3, N, chunk_env, (size_t)fr * wid * sizeof(float), kPtAux * sizeof(float),
+                          ctx->features.cap, ctx->ptaux.cap, ctx->handoff_row, ctx->handoff_chunk };
+    const FieldPlan plan = field_plan(in, [](size_t &free_b) { size_t total_b = 0; return hipMemGetInfo(&free_b, &total_b) == hipSuccess; });
+    if (plan.cache) { ctx->handoff_row = in.feat_row + in.aux_row; ctx->handoff_chunk = plan.chunk; }
+    // ---- the buffers ----
     // activations' element type and planes: fp32 1024 B, bf16 512 B, split bf16 (two planes) 1024 B per row
-    if (int rc = ensure(ctx, ctx->features, (size_t)chunk * fr * wid * sizeof(float))) return rc;
-    if (int rc = ensure(ctx, ctx->ptaux, (size_t)chunk * kPtAux * sizeof(float))) return rc;
+    if (int rc = ensure(ctx, ctx->features, (size_t)plan.chunk * in.feat_row)) return rc;
+    if (int rc = ensure(ctx, ctx->ptaux, (size_t)plan.chunk * in.aux_row)) return rc;
     if (int rc = ensure(ctx, ctx->sched, 2 * kSchedInts * sizeof(int))) return rc;
-    for (int64_t off = 0; off < N; off += chunk) {
-        const int64_t n = (N - off < chunk) ? N - off : chunk;
-        DdfArgs a = use3 ? f.ddf3 : f.ddf;
-        fill_enc(a.enc, f);
-        a.pos = pos + off * 3; a.dir = dir + off * 3; a.var = var + off * 3; a.n_points = n;
-        if (use_rays) {
-            a.pos = a.dir = a.var = nullptr;
-            a.rays = *rays;
-            if (!a.rays.Se) a.rays.Se = rays->S;
-            a.rays.base = rays->base + off;
-        }
-        a.aux_grad_scale = f.aux_grad_scale;
-        a.scratch = (float *)ctx->scratch.p;
-        a.features = (color || full) ? (float *)ctx->features.p : nullptr;      // no colour kernel follows: no hand-off
-        a.feat_rows = fr;
-        a.ptaux = (float *)ctx->ptaux.p;
-        a.distance = distance ? distance + off : nullptr;
-        a.density = density ? density + off : nullptr;
-        a.aux_grad = aux ? aux + off : nullptr;
-        a.sched = (int *)ctx->sched.p;
-        a.sched_flags = sched_flags();
-        if (l2_mode) a.sched_flags |= (l2_mode << kSchedL2ModeShift) | (l2_period << kSchedL2PeriodShift);
-        HIPCHK(hipMemsetAsync(a.sched, 0, kSchedInts * sizeof(int), s));
-        if (reverse) {          // one scalar's gradient: reverse mode, 64 or 32 points per tile (field_kernels.hip ddf_rev_kernel)
-            const int pts = ddf_rev_points(dt, wid), wgs = ddf_rev_wgs_per_cu(dt, wid) * ctx->cus;
-            if (int rc = ensure(ctx, ctx->rev_scratch, (size_t)wgs * ddf_rev_scratch_floats_per_wg(a.n_layers, pts, wid) * sizeof(float))) return rc;
-            a.rev_scratch = (float *)ctx->rev_scratch.p;
-#ifdef NEDDF_STAMP
-            static unsigned long long *d_stamps = nullptr;
-            const size_t stamp_bytes = ((size_t)kStampBlocks * 8 * kStampSlots * kStampPairTiles + 4 * kStampWgTail) * sizeof(unsigned long long);
-            if (!d_stamps) HIPCHK(hipMalloc((void **)&d_stamps, stamp_bytes));
-            HIPCHK(hipMemsetAsync(d_stamps, 0, stamp_bytes, s));
-            a.stamps = d_stamps;
-#endif
-            for (int64_t so = 0; so < n; so += ddf_sub) {       // (one launch, except for the three-term policy: see ddf_sub)
-                DdfArgs b = a;
-                b.n_points = n - so < ddf_sub ? n - so : ddf_sub;
-                if (so) {
-                    if (use_rays) b.rays.base = a.rays.base + so;
-                    else { b.pos = a.pos + so * 3; b.dir = a.dir + so * 3; b.var = a.var + so * 3; }
-                    if (a.features) b.features = a.features + (size_t)so * fr * wid;
-                    b.ptaux = a.ptaux + (size_t)so * kPtAux;
-                    if (a.distance) b.distance = a.distance + so;
-                    if (a.density) b.density = a.density + so;
-                    if (a.aux_grad) b.aux_grad = a.aux_grad + so;
-                    HIPCHK(hipMemsetAsync(b.sched, 0, kSchedInts * sizeof(int), s));
-                }
-                const int64_t stiles = (b.n_points + pts - 1) / pts;
-                STAGE(ctx, s, NEDDF_STAGE_DDF, launch_ddf_rev(b, (int)(stiles < wgs ? stiles : wgs), s));
-            }
-#ifdef NEDDF_STAMP
-            if (const char *path = getenv("NEDDF_STAMP_FILE")) {        // the LAST launch's stamps (a diagnostic build: synchronising here is fine)
-                HIPCHK(hipStreamSynchronize(s));
-                std::vector<unsigned long long> h((size_t)kStampBlocks * 8 * kStampSlots * kStampPairTiles + 4 * kStampWgTail);
-                HIPCHK(hipMemcpy(h.data(), d_stamps, stamp_bytes, hipMemcpyDeviceToHost));
-                if (FILE *fp = fopen(path, "wb")) { fwrite(h.data(), 1, stamp_bytes, fp); fclose(fp); }
-            }
-#endif
-        } else {
-            const int64_t tiles = (n + ddf_points_per_tile(dt, wid) - 1) / ddf_points_per_tile(dt, wid);
-            STAGE(ctx, s, NEDDF_STAGE_DDF, launch_ddf(a, (int)(tiles < grid_cap_ddf ? tiles : grid_cap_ddf), s));
-        }
+    DdfArgs a0 = use3 ? f.ddf3 : f.ddf;
+    // one scalar's gradient: reverse mode, 64 or 32 points per tile (field_kernels.hip ddf_rev_kernel)
+    const int pts = reverse ? ddf_rev_points(dt, wid) : ddf_points_per_tile(dt, wid);
+    const int wgs = reverse ? ddf_rev_wgs_per_cu(dt, wid) * ctx->cus : grid_cap_ddf;
+    if (reverse)
+        if (int rc = ensure(ctx, ctx->rev_scratch, (size_t)wgs * ddf_rev_scratch_floats_per_wg(a0.n_layers, pts, wid) * sizeof(float))) return rc;
+    // penalty requested without colour: park colour in the (already consumed) head of ptaux? no -- own sink
+    if (full && !color)
+        if (int rc = ensure(ctx, ctx->arena, (size_t)plan.chunk * 3 * sizeof(float))) return rc;
+    // ---- the whole call's arguments; every launch takes its piece of them (ddf_at) ----
+    fill_enc(a0.enc, f);
+    a0.pos = pos; a0.dir = dir; a0.var = var;
+    if (use_rays) {
+        a0.pos = a0.dir = a0.var = nullptr;
+        a0.rays = *rays;
+        if (!a0.rays.Se) a0.rays.Se = rays->S;
+    }
+    a0.aux_grad_scale = f.aux_grad_scale;
+    a0.scratch = (float *)ctx->scratch.p;
+    a0.features = (color || full) ? (float *)ctx->features.p : nullptr;      // no colour kernel follows: no hand-off
+    a0.feat_rows = fr;
+    a0.ptaux = (float *)ctx->ptaux.p;
+    if (reverse) a0.rev_scratch = (float *)ctx->rev_scratch.p;
+    a0.distance = distance; a0.density = density; a0.aux_grad = aux;
+    a0.sched = (int *)ctx->sched.p;
+    a0.sched_flags = sched_flags();
+    if (l2_mode) a0.sched_flags |= (l2_mode << kSchedL2ModeShift) | (l2_period << kSchedL2PeriodShift);
+    int rc = each_span(N, plan.chunk, [&](int64_t off, int64_t n) -> int {
+        if (reverse)
+            if (int rc = stamp_arm(ctx, a0, s)) return rc;
+        // the distance kernel (one launch per chunk, except for the three-term policy: FieldPlan::ddf_sub), each on a fresh tile queue
+        if (int rc = each_span(n, plan.ddf_sub, [&](int64_t so, int64_t n_sub) -> int {
+                const DdfArgs b = ddf_at(a0, wid, off, so, n_sub);
+                HIPCHK(hipMemsetAsync(b.sched, 0, kSchedInts * sizeof(int), s));
+                const int64_t tiles = (n_sub + pts - 1) / pts;
+                const int grid = (int)(tiles < wgs ? tiles : wgs);
+                if (reverse) STAGE(ctx, s, NEDDF_STAGE_DDF, launch_ddf_rev(b, grid, s));
+                else STAGE(ctx, s, NEDDF_STAGE_DDF, launch_ddf(b, grid, s));
+                return 0;
+            })) return rc;
+        if (reverse)
+            if (int rc = stamp_dump(ctx, a0.stamps, "NEDDF_STAMP_FILE", s)) return rc;
+        const DdfArgs a = ddf_at(a0, wid, off, 0, n);
         if (dgrad || normal)
             launch_surface_gather(a.ptaux, n, f.d.kind == NEDDF_FIELD_NEUS, dgrad ? dgrad + off * 3 : nullptr, normal ? normal + off * 3 : nullptr, s);
-        if (color || full) {
-            ColArgs c = use3 ? f.col3 : f.col;
-            fill_enc(c.enc, f);
-            c.pos = a.pos; c.dir = a.dir; c.var = a.var; c.n_points = n;
-            c.rays = use_rays ? 1 : 0;
-            c.features = a.features; c.feat_rows = fr; c.ptaux = a.ptaux;
-            c.distance_range_max = f.distance_range_max;
-            c.penalty = full ? penalty + off : nullptr;
-            if (color) c.color = color + off * 3;
-            else {      // penalty requested without colour: park colour in the (already consumed) head of ptaux? no -- own sink
-                if (int rc = ensure(ctx, ctx->arena, (size_t)chunk * 3 * sizeof(float))) return rc;
-                c.color = (float *)ctx->arena.p;
-            }
-            int ppt = col_points_per_tile(full, dt, wid);
-            int64_t ctiles = (n + ppt - 1) / ppt;
-            c.sched = (int *)ctx->sched.p + kSchedInts;
-            c.sched_flags = sched_flags();
-            HIPCHK(hipMemsetAsync(c.sched, 0, kSchedInts * sizeof(int), s));
-#ifdef NEDDF_STAMP
-            static unsigned long long *d_cstamps = nullptr;
-            const size_t cstamp_bytes = ((size_t)kStampBlocks * 8 * kStampSlots * kStampPairTiles + 4 * kStampWgTail) * sizeof(unsigned long long);
-            if (!d_cstamps) HIPCHK(hipMalloc((void **)&d_cstamps, cstamp_bytes));
-            HIPCHK(hipMemsetAsync(d_cstamps, 0, cstamp_bytes, s));
-            c.stamps = d_cstamps;
-#endif
-            STAGE(ctx, s, NEDDF_STAGE_COL, launch_col(c, (int)(ctiles < grid_cap_col ? ctiles : grid_cap_col), full, s));
-#ifdef NEDDF_STAMP
-            if (const char *path = getenv("NEDDF_STAMP_FILE_COL")) {    // the LAST colour launch's stamps (tools/stamp_timeline_col.py)
-                HIPCHK(hipStreamSynchronize(s));
-                std::vector<unsigned long long> h((size_t)kStampBlocks * 8 * kStampSlots * kStampPairTiles + 4 * kStampWgTail);
-                HIPCHK(hipMemcpy(h.data(), d_cstamps, cstamp_bytes, hipMemcpyDeviceToHost));
-                if (FILE *fp = fopen(path, "wb")) { fwrite(h.data(), 1, cstamp_bytes, fp); fclose(fp); }
-            }
-#endif
-        }
-    }
+        if (!(color || full)) return 0;
+        ColArgs c = use3 ? f.col3 : f.col;
+        fill_enc(c.enc, f);
+        c.pos = a.pos; c.dir = a.dir; c.var = a.var; c.n_points = n;
+        c.rays = use_rays ? 1 : 0;
+        c.features = a.features; c.feat_rows = fr; c.ptaux = a.ptaux;
+        c.distance_range_max = f.distance_range_max;
+        c.penalty = full ? penalty + off : nullptr;
+        c.color = color ? color + off * 3 : (float *)ctx->arena.p;
+        int ppt = col_points_per_tile(full, dt, wid);
+        int64_t ctiles = (n + ppt - 1) / ppt;
+        c.sched = (int *)ctx->sched.p + kSchedInts;
+        c.sched_flags = sched_flags();
+        HIPCHK(hipMemsetAsync(c.sched, 0, kSchedInts * sizeof(int), s));
+        if (int rc = stamp_arm(ctx, c, s)) return rc;
+        STAGE(ctx, s, NEDDF_STAGE_COL, launch_col(c, (int)(ctiles < grid_cap_col ? ctiles : grid_cap_col), full, s));
+        return stamp_dump(ctx, c.stamps, "NEDDF_STAMP_FILE_COL", s);       // (tools/stamp_timeline_col.py)
+    });
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return 0;           // (the slot is marked by `mark` on every way out)
 }
@@ -553,31 +551,29 @@ int neddf_importance_resample(neddf_ctx *ctx, const float *dists, float *weights
 
 // carve helper for the render arena
 // NEDDF_GUARD=1: a carve ends exactly at its last element and is followed by a poisoned band (capi_internal.h guard_mode)
+// p == NULL measures: the same layout function runs once on such a Carver for the byte count (`off`, no memset, no band recorded)
+// and once on the block of that size, so what is reserved is what is carved
 struct Carver {
     char *p;
-    neddf_ctx *ctx = nullptr;
+    neddf_ctx *ctx = nullptr;       // NULL: no bands between the carves
     hipStream_t s = nullptr;
     size_t off = 0;
     float *take(size_t n_floats)
     {
-        float *r = (float *)(p + off);
+        float *r = p ? (float *)(p + off) : nullptr;
+        size_t used = n_floats * sizeof(float);
         if (guard_mode() && ctx) {
-            const size_t used = (n_floats * sizeof(float) + 15) & ~(size_t)15;
-            (void)hipMemsetAsync(p + off + used, kGuardByte, kCarveGuardBytes, s);
-            ctx->carve_guards.push_back(GuardBand{ p + off + used, kCarveGuardBytes });
-            off += (used + kCarveGuardBytes + 255) & ~(size_t)255;
-            return r;
+            used = (used + 15) & ~(size_t)15;
+            if (p) {
+                (void)hipMemsetAsync(p + off + used, kGuardByte, kCarveGuardBytes, s);
+                ctx->carve_guards.push_back(GuardBand{ p + off + used, kCarveGuardBytes });
+            }
+            used += kCarveGuardBytes;
         }
-        off += (n_floats * sizeof(float) + 255) & ~(size_t)255;
+        off += (used + 255) & ~(size_t)255;
         return r;
     }
 };
-
-static size_t carve_bytes(size_t n_floats)
-{
-    if (guard_mode()) return (((n_floats * sizeof(float) + 15) & ~(size_t)15) + kCarveGuardBytes + 255) & ~(size_t)255;
-    return (n_floats * sizeof(float) + 255) & ~(size_t)255;
-}
 
 // ---- empty-space skipping: the workspace of one culled render call (carved from the arena, sized for its longest pass) ----
 struct OccWork {
@@ -589,24 +585,56 @@ struct OccWork {
     float *cdens, *ccol, *cnrm;     // [N], [N, 3], [N, 3] (cnrm only with a normal target): their results
 };
 
-static size_t occ_work_bytes(int64_t N, bool normals)
-{
-    return carve_bytes((size_t)(N + 3) / 4) + carve_bytes((size_t)N) + carve_bytes((size_t)(occ_blocks(N) + 1) * 2) + 4 * carve_bytes((size_t)N * 3) +
-           carve_bytes((size_t)N) + (normals ? carve_bytes((size_t)N * 3) : 0);
-}
+// ---- the workspace of one render call: described once, here; counted and carved by running this function twice (Carver) ----
+struct RenderWork {
+    float *rd, *ro;                         // [B, 3] the rays
+    float *nd, *no;                         // [B, 3] their NDC map (ndc_rays only)
+    float *dc, *df;                         // [B, Sc1] coarse distances (two passes only), [B, S] the last pass's
+    float *pos, *dir, *var;                 // [B, S, 3] sampling tensors of one pass
+    float *dens, *pen, *col, *nrm;          // [B, S], [B, S], [B, S, 3], [B, S, 3] (nrm only with a normal target): the field's results
+    float *wc;                              // [B, Sc1 - 1] coarse weights for the resampling
+    float *depth_c, *color_c, *trans_c;     // coarse pixels: only when the caller asked for one of them (render_rays); render_image does not
+    float *depth, *color, *trans;           // the pixels of the last pass
+    OccWork occ;
+    const OccWork *ow;                      // &occ with an occupancy grid, else NULL
+};
 
-static OccWork occ_work(Carver &cv, const neddf_occupancy *occ, int64_t N, bool normals)
+// Sc1: samples of the coarse pass of a hierarchical call, 0 for a single pass; S: samples of the last (the longest) pass.
+// A pointer the caller supplied in `out` replaces the carve.
+static void render_layout(Carver &cv, int64_t B, int Sc1, int S, const neddf_render_outputs *out, bool normals, bool ndc,
+                          const neddf_occupancy *occ, RenderWork &w)
 {
-    OccWork w{};
-    w.grid.bits = occ->d_bits; w.grid.res = occ->res;
-    for (int a = 0; a < 3; ++a) { w.grid.lo[a] = occ->lo[a]; w.grid.inv_cell[a] = occ->inv_cell[a]; }
-    w.keep = (unsigned char *)cv.take((size_t)(N + 3) / 4);
-    w.index = (int32_t *)cv.take((size_t)N);
-    w.blk = (int64_t *)cv.take((size_t)(occ_blocks(N) + 1) * 2);
-    w.cpos = cv.take((size_t)N * 3); w.cdir = cv.take((size_t)N * 3); w.cvar = cv.take((size_t)N * 3);
-    w.cdens = cv.take((size_t)N); w.ccol = cv.take((size_t)N * 3);
-    w.cnrm = normals ? cv.take((size_t)N * 3) : nullptr;
-    return w;
+    w = RenderWork{};
+    w.rd = cv.take(B * 3); w.ro = cv.take(B * 3);
+    if (Sc1) w.dc = out->dists_coarse ? out->dists_coarse : cv.take(B * Sc1);
+    w.df = out->dists_fine ? out->dists_fine : cv.take(B * S);
+    w.pos = cv.take(B * S * 3); w.dir = cv.take(B * S * 3); w.var = cv.take(B * S * 3);
+    w.dens = cv.take(B * S); w.pen = cv.take(B * S); w.col = cv.take(B * S * 3);
+    if (Sc1) {
+        w.wc = out->weight_coarse ? out->weight_coarse : cv.take(B * (Sc1 - 1));
+        const bool coarse_px = out->depth_coarse || out->color_coarse || out->transmittance_coarse || out->fields_penalty_coarse;
+        w.depth_c = out->depth_coarse ? out->depth_coarse : (coarse_px ? cv.take(B) : nullptr);
+        w.color_c = out->color_coarse ? out->color_coarse : (coarse_px ? cv.take(B * 3) : nullptr);
+        w.trans_c = out->transmittance_coarse ? out->transmittance_coarse : (coarse_px ? cv.take(B) : nullptr);
+    }
+    w.depth = out->depth ? out->depth : cv.take(B);
+    w.color = out->color ? out->color : cv.take(B * 3);
+    w.trans = out->transmittance ? out->transmittance : cv.take(B);
+    if (normals) w.nrm = cv.take(B * S * 3);           // the per-sample normals of one pass
+    if (occ) {
+        const size_t N = (size_t)B * S;
+        OccWork &o = w.occ;
+        o.grid.bits = occ->d_bits; o.grid.res = occ->res;
+        for (int a = 0; a < 3; ++a) { o.grid.lo[a] = occ->lo[a]; o.grid.inv_cell[a] = occ->inv_cell[a]; }
+        o.keep = (unsigned char *)cv.take((N + 3) / 4);
+        o.index = (int32_t *)cv.take(N);
+        o.blk = (int64_t *)cv.take((size_t)(occ_blocks(N) + 1) * 2);
+        o.cpos = cv.take(N * 3); o.cdir = cv.take(N * 3); o.cvar = cv.take(N * 3);
+        o.cdens = cv.take(N); o.ccol = cv.take(N * 3);
+        if (normals) o.cnrm = cv.take(N * 3);
+        w.ow = &w.occ;
+    }
+    if (ndc) { w.nd = cv.take(B * 3); w.no = cv.take(B * 3); }
 }
 
 static bool occ_ok(const neddf_occupancy *occ) { return occ->d_bits && occ->res >= 1 && occ->res <= kOccMaxRes; }
@@ -643,39 +671,51 @@ static int culled_field(neddf_ctx *ctx, int slot, const RaySrc &rays, int64_t B,
     return 0;
 }
 
-static int render_pass(neddf_ctx *ctx, int slot, const float *rd, const float *ro, const float *view, const float *dists, int64_t B, int S,
-                       const neddf_render_params *rp, float *pos, float *dir, float *var, float *dens, float *col, float *pen,
-                       float *w_out, float *depth, float *color, float *trans, float *pen_out, int *nan_flag, hipStream_t s,
-                       float *nrm = nullptr, float *normal_out = nullptr,      // nrm [B, S, 3] workspace, normal_out [B, 3] (the normal target)
-                       const OccWork *ow = nullptr)                            // an occupancy grid and its workspace: the culled pass
+// one pass of a render call: its rays and distances, the call's workspace, and where this pass's results go (NULL: not asked for)
+struct RenderPass {
+    const float *rd, *ro, *view;
+    const float *dists;             // [B, S]
+    int64_t B;
+    int S;
+    const RenderWork *ws;           // pos / dir / var / dens / col / pen / nrm, and ow: an occupancy grid and its workspace (the culled pass)
+    float *w, *depth, *color, *trans, *pen_out;
+    float *normal_out;              // [B, 3] (the normal target)
+    int *nan_flag;
+};
+
+static int render_pass(neddf_ctx *ctx, int slot, const neddf_render_params *rp, const RenderPass &p, hipStream_t s)
 {
+    const RenderWork &k = *p.ws;
+    const int64_t B = p.B;
+    const int S = p.S;
     RaySrc rays;
-    rays.rd = rd; rays.ro = ro; rays.view = view; rays.dists = dists; rays.S = S;
+    rays.rd = p.rd; rays.ro = p.ro; rays.view = p.view; rays.dists = p.dists; rays.S = S;
     rays.cone = rp->cone_sampling ? 1 : 0;
     rays.radius = rp->cone_sampling ? rp->ray_radius : -1.0;
     rays.r2 = (float)(rp->ray_radius * rp->ray_radius);          // launch_sampling's own (float)(radius * radius)
-    const bool want_pen = pen_out && ctx->field[slot].d.kind == NEDDF_FIELD_NEDDF;
+    const bool want_pen = p.pen_out && ctx->field[slot].d.kind == NEDDF_FIELD_NEDDF;
     // a pass whose pixels nobody asked for (the coarse pass of render_image: only its resampling weights are consumed) needs the
     // densities only -- the colour trunk is skipped (the reference evaluates and discards it)
-    const bool want_col = depth || color || trans || want_pen;
-    if (ow) {
-        if (int rc = culled_field(ctx, slot, rays, B, S, pos, dir, var, dens, want_col ? col : nullptr, normal_out ? nrm : nullptr, *ow, s)) return rc;
-        STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite(dists, dens, want_col ? col : nullptr, B, S, rp->max_dist, w_out, depth, color, trans, nan_flag, s));
-        if (normal_out) STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite_normal(dists, dens, nrm, B, S, normal_out, s));
+    const bool want_col = p.depth || p.color || p.trans || want_pen;
+    float *col = want_col ? k.col : nullptr, *nrm = p.normal_out ? k.nrm : nullptr;
+    if (k.ow) {
+        if (int rc = culled_field(ctx, slot, rays, B, S, k.pos, k.dir, k.var, k.dens, col, nrm, *k.ow, s)) return rc;
+        STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite(p.dists, k.dens, col, B, S, rp->max_dist, p.w, p.depth, p.color, p.trans, p.nan_flag, s));
+        if (nrm) STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite_normal(p.dists, k.dens, nrm, B, S, p.normal_out, s));
         return 0;
     }
-    // dens / col / nrm are workspaces of the callers (render_rays_impl, render_rays_single_impl) and the two compositors below are their only
+    // dens / col / nrm are workspaces of the caller (render_rays_body) and the two compositors below are their only
     // readers: of a ray's last sample they read the distance alone, so the field skips it where it takes its points from the rays (RaySrc::Se;
     // the arrays are then [B, S - 1] rows).  The penalty route integrates a per-sample array of its own and keeps all S samples, and so
     // does the sampling-tensor route (NeRF, NeuS, NEDDF_RAYS_IN_FIELD=0, NEDDF_DDF_REVERSE=0) and the culled pass above.
     const int Se = !want_pen && rays_in_field(ctx->field[slot], false, false) ? S - 1 : S;
     rays.Se = Se;
-    int rc = field_forward(ctx, slot, pos, dir, var, B * Se, want_pen ? NEDDF_OUT_FULL : NEDDF_OUT_MINIMAL, nullptr, dens, want_col ? col : nullptr,
-                           want_pen ? pen : nullptr, nullptr, s, &rays, nullptr, normal_out ? nrm : nullptr);
+    int rc = field_forward(ctx, slot, k.pos, k.dir, k.var, B * Se, want_pen ? NEDDF_OUT_FULL : NEDDF_OUT_MINIMAL, nullptr, k.dens, col,
+                           want_pen ? k.pen : nullptr, nullptr, s, &rays, nullptr, nrm);
     if (rc) return rc;
-    STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite(dists, dens, want_col ? col : nullptr, B, S, rp->max_dist, w_out, depth, color, trans, nan_flag, s, Se));
-    if (normal_out) STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite_normal(dists, dens, nrm, B, S, normal_out, s, Se));
-    if (want_pen) STAGE(ctx, s, NEDDF_STAGE_PENALTY, launch_integrate_penalty(dists, pen, B, S, pen_out, s));
+    STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite(p.dists, k.dens, col, B, S, rp->max_dist, p.w, p.depth, p.color, p.trans, p.nan_flag, s, Se));
+    if (nrm) STAGE(ctx, s, NEDDF_STAGE_COMPOSITE, launch_composite_normal(p.dists, k.dens, nrm, B, S, p.normal_out, s, Se));
+    if (want_pen) STAGE(ctx, s, NEDDF_STAGE_PENALTY, launch_integrate_penalty(p.dists, k.pen, B, S, p.pen_out, s));
     return 0;
 }
 
@@ -688,71 +728,70 @@ static int check_uv(neddf_ctx *ctx, int uv_type, const neddf_camera *cam, const 
     return 0;
 }
 
-static int render_rays_impl(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, const neddf_camera *cam, const neddf_render_params *rp,
-                            const float *Uc, const float *Uf, const neddf_render_outputs *out, float *normal, float *normal_coarse, void *stream,
-                            const neddf_occupancy *occ = nullptr)
+// What one fused call is, beyond the arguments every entry point shares.  A single-pass call (neddf_render_rays_single*) is the
+// hierarchical one that stops after its first pass, which then runs on the caller's slot with S1 samples and writes the final outputs.
+struct RenderCall {
+    const char *name;               // the prefix of the culled entry points' refusals
+    bool two;                       // coarse pass -> importance resampling -> fine pass
+    int slot, S1;                   // a single pass: its field and its samples per ray
+    const float *Uc, *Uf;           // [B, S] uniforms of the first draw, [B, sample_fine + 1] of the resampling (two passes)
+    float *normal, *normal_coarse;  // [B, 3] normal targets or NULL
+    const neddf_occupancy *occ;     // an occupancy grid: the culled passes
+};
+
+static int render_rays_body(neddf_ctx *ctx, const RenderCall &c, const void *uv, int uv_type, int64_t B, const neddf_camera *cam,
+                            const neddf_render_params *rp, const neddf_render_outputs *out, void *stream)
 {
+    const neddf_occupancy *occ = c.occ;
     if (!ctx) return NEDDF_EINVAL;
     if (B <= 0) return 0;           // empty batch: nothing to do (pointers of empty tensors may be NULL)
-    if (!uv || !rp || !Uc || !Uf || !out) return NEDDF_EINVAL;
+    if (!uv || !rp || !c.Uc || !out || (c.two ? !c.Uf : c.S1 < 2)) return NEDDF_EINVAL;
     if (int rc = check_uv(ctx, uv_type, cam, rp)) return rc;
-    if (occ && !occ_ok(occ)) return fail(ctx, NEDDF_EINVAL, "render_rays_culled: the grid needs its bits and a resolution in [1, 1024]");
-    if (occ && (out->fields_penalty || out->fields_penalty_coarse))
-        return fail(ctx, NEDDF_EUNSUPPORTED, "render_rays_culled: no fields_penalty output with an occupancy grid (a culled sample has no penalty)");
+    auto refuse = [&](int code, const char *why, const char *more = "") { return fail(ctx, code, std::string(c.name) + why + more); };
+    if (occ && !occ_ok(occ)) return refuse(NEDDF_EINVAL, ": the grid needs its bits and a resolution in [1, 1024]");
+    if (occ && (out->fields_penalty || (c.two && out->fields_penalty_coarse)))
+        return refuse(NEDDF_EUNSUPPORTED, ": no fields_penalty output with an occupancy grid (a culled sample has no penalty)");
     DeviceGuard guard_(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    const int Sc1 = rp->sample_coarse + 1, Sf1 = rp->sample_fine + 1, S2 = Sc1 + Sf1;
-    if (!ctx->field[NEDDF_SLOT_COARSE].valid || !ctx->field[NEDDF_SLOT_FINE].valid) return fail(ctx, NEDDF_ENOFIELD, "render_rays needs coarse and fine fields");
-    size_t need = 2 * carve_bytes(B * 3) + carve_bytes(B * Sc1) + carve_bytes(B * S2) + 3 * carve_bytes(B * S2 * 3) +
-                  2 * carve_bytes(B * S2) + carve_bytes(B * S2 * 3) + carve_bytes(B * (Sc1 - 1)) + carve_bytes(B * (S2 - 1)) +
-                  8 * carve_bytes(B * 3);
-    if (normal || normal_coarse) need += carve_bytes(B * S2 * 3);       // the per-sample normals of one pass
-    if (occ && B * S2 >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "render_rays_culled: 2^31 samples or more in one pass (compaction indices are int32)");
-    if (occ) need += occ_work_bytes(B * S2, normal || normal_coarse);
-    // the arena is also used by field_forward as a colour sink only when colour is not requested; never the case here
-    if (int rc = ensure(ctx, ctx->arena, need)) return rc;
+    // samples per ray of the first pass, of the resampling, of the last pass
+    const int Sc1 = c.two ? rp->sample_coarse + 1 : c.S1, Sf1 = rp->sample_fine + 1, S = c.two ? Sc1 + Sf1 : c.S1;
+    if (c.two) {
+        if (!ctx->field[NEDDF_SLOT_COARSE].valid || !ctx->field[NEDDF_SLOT_FINE].valid) return fail(ctx, NEDDF_ENOFIELD, "render_rays needs coarse and fine fields");
+    } else if (c.slot < 0 || c.slot >= NEDDF_NUM_SLOTS || !ctx->field[c.slot].valid) return fail(ctx, NEDDF_ENOFIELD, "no field in slot");
+    if (occ && B * S >= ((int64_t)1 << 31))
+        return refuse(NEDDF_EUNSUPPORTED, c.two ? ": 2^31 samples or more in one pass" : ": 2^31 samples or more", " (compaction indices are int32)");
+    // the workspace: measured, reserved, carved -- all by render_layout
+    // (the arena is also used by field_forward as a colour sink only when colour is not requested; never the case here)
+    RenderWork w;
+    auto layout = [&](Carver cv) { render_layout(cv, B, c.two ? Sc1 : 0, S, out, c.normal || c.normal_coarse, rp->ndc_rays != 0, occ, w); return cv.off; };
+    if (int rc = ensure(ctx, ctx->arena, layout(Carver{ nullptr, ctx, s }))) return rc;
     ctx->carve_guards.clear();
-    Carver cv{ (char *)ctx->arena.p, ctx, s };
-    float *rd = cv.take(B * 3), *ro = cv.take(B * 3);
-    float *dc = out->dists_coarse ? out->dists_coarse : cv.take(B * Sc1);
-    float *df = out->dists_fine ? out->dists_fine : cv.take(B * S2);
-    float *pos = cv.take(B * S2 * 3), *dir = cv.take(B * S2 * 3), *var = cv.take(B * S2 * 3);
-    float *dens = cv.take(B * S2), *pen = cv.take(B * S2), *col = cv.take(B * S2 * 3);
-    float *wc = out->weight_coarse ? out->weight_coarse : cv.take(B * (Sc1 - 1));
-    // coarse pixels only when the caller asked for one of them (render_rays); render_image does not
-    const bool coarse_px = out->depth_coarse || out->color_coarse || out->transmittance_coarse || out->fields_penalty_coarse;
-    float *depth_c = out->depth_coarse ? out->depth_coarse : (coarse_px ? cv.take(B) : nullptr);
-    float *color_c = out->color_coarse ? out->color_coarse : (coarse_px ? cv.take(B * 3) : nullptr);
-    float *trans_c = out->transmittance_coarse ? out->transmittance_coarse : (coarse_px ? cv.take(B) : nullptr);
-    float *depth = out->depth ? out->depth : cv.take(B);
-    float *color = out->color ? out->color : cv.take(B * 3);
-    float *trans = out->transmittance ? out->transmittance : cv.take(B);
-    float *nrm = (normal || normal_coarse) ? cv.take(B * S2 * 3) : nullptr;
-    OccWork work{};
-    if (occ) work = occ_work(cv, occ, B * S2, normal || normal_coarse);
-    const OccWork *ow = occ ? &work : nullptr;
-    int *flags = (int *)ctx->flags.p;
-    int *nan_flag = out->nan_flag ? out->nan_flag : flags;
+    layout(Carver{ (char *)ctx->arena.p, ctx, s });
+    int *nan_flag = out->nan_flag ? out->nan_flag : (int *)ctx->flags.p;
 
-    STAGE(ctx, s, NEDDF_STAGE_RAYGEN, launch_raygen(uv, uv_type, B, cam_arg(cam), rd, ro, s));
-    const float *view = nullptr;
+    STAGE(ctx, s, NEDDF_STAGE_RAYGEN, launch_raygen(uv, uv_type, B, cam_arg(cam), w.rd, w.ro, s));
+    float *d1 = c.two ? w.dc : w.df;        // the first draw
+    RenderPass p{ w.rd, w.ro, nullptr, d1, B, Sc1, &w };
     if (rp->ndc_rays) {         // positions follow the NDC ray, the field keeps the world-space viewing direction
-        float *nd = cv.take(B * 3), *no = cv.take(B * 3);
-        STAGE(ctx, s, NEDDF_STAGE_NDC, launch_ndc(rd, ro, B, (float)rp->ndc_width, (float)rp->ndc_height, cam->calib[0], cam->calib[1], rp->ndc_near, nd, no, s));
-        view = rd; rd = nd; ro = no;
+        STAGE(ctx, s, NEDDF_STAGE_NDC, launch_ndc(w.rd, w.ro, B, (float)rp->ndc_width, (float)rp->ndc_height, cam->calib[0], cam->calib[1], rp->ndc_near, w.nd, w.no, s));
+        p.view = w.rd; p.rd = w.nd; p.ro = w.no;
     }
-    STAGE(ctx, s, NEDDF_STAGE_SAMPLE_COARSE, launch_sample_coarse(Uc, B, Sc1, rp->dist_near, rp->dist_far, dc, s));
-    int rc = render_pass(ctx, NEDDF_SLOT_COARSE, rd, ro, view, dc, B, Sc1, rp, pos, dir, var, dens, col, pen, wc, depth_c, color_c,
-                         trans_c, out->fields_penalty_coarse, nan_flag, s, nrm, normal_coarse, ow);
-    if (rc) return rc;
-    // the reference takes the NaN-fallback decision of sample_pdf per render_rays call, i.e. per `chunk` rays of render_image
-    const int64_t group = rp->nan_group > 0 ? rp->nan_group : B;
-    const int64_t goff = rp->nan_group > 0 && rp->nan_group_offset > 0 ? rp->nan_group_offset % group : 0;
-    if (int rc = ensure(ctx, ctx->rflags, (size_t)((B + goff + group - 1) / group) * sizeof(int))) return rc;
-    STAGE(ctx, s, NEDDF_STAGE_RESAMPLE, launch_resample(dc, wc, Uf, B, Sc1, Sf1, 1, df, nullptr, (int *)ctx->rflags.p, group, goff, s));
-    rc = render_pass(ctx, NEDDF_SLOT_FINE, rd, ro, view, df, B, S2, rp, pos, dir, var, dens, col, pen, out->weight, depth, color, trans,
-                     out->fields_penalty, nan_flag, s, nrm, normal, ow);
-    if (rc) return rc;
+    p.nan_flag = nan_flag;
+    STAGE(ctx, s, NEDDF_STAGE_SAMPLE_COARSE, launch_sample_coarse(c.Uc, B, Sc1, rp->dist_near, rp->dist_far, d1, s));
+    if (c.two) {
+        p.w = w.wc; p.depth = w.depth_c; p.color = w.color_c; p.trans = w.trans_c;
+        p.pen_out = out->fields_penalty_coarse; p.normal_out = c.normal_coarse;
+        if (int rc = render_pass(ctx, NEDDF_SLOT_COARSE, rp, p, s)) return rc;
+        // the reference takes the NaN-fallback decision of sample_pdf per render_rays call, i.e. per `chunk` rays of render_image
+        const int64_t group = rp->nan_group > 0 ? rp->nan_group : B;
+        const int64_t goff = rp->nan_group > 0 && rp->nan_group_offset > 0 ? rp->nan_group_offset % group : 0;
+        if (int rc = ensure(ctx, ctx->rflags, (size_t)((B + goff + group - 1) / group) * sizeof(int))) return rc;
+        STAGE(ctx, s, NEDDF_STAGE_RESAMPLE, launch_resample(w.dc, w.wc, c.Uf, B, Sc1, Sf1, 1, w.df, nullptr, (int *)ctx->rflags.p, group, goff, s));
+        p.dists = w.df; p.S = S;
+    }
+    p.w = out->weight; p.depth = w.depth; p.color = w.color; p.trans = w.trans;
+    p.pen_out = out->fields_penalty; p.normal_out = c.normal;
+    if (int rc = render_pass(ctx, c.two ? NEDDF_SLOT_FINE : c.slot, rp, p, s)) return rc;
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -760,75 +799,27 @@ static int render_rays_impl(neddf_ctx *ctx, const void *uv, int uv_type, int64_t
 int neddf_render_rays(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, const neddf_camera *cam, const neddf_render_params *rp,
                       const float *Uc, const float *Uf, const neddf_render_outputs *out, void *stream)
 {
-    return render_rays_impl(ctx, uv, uv_type, B, cam, rp, Uc, Uf, out, nullptr, nullptr, stream);
+    return render_rays_body(ctx, { "render_rays_culled", true, 0, 0, Uc, Uf, nullptr, nullptr, nullptr }, uv, uv_type, B, cam, rp, out, stream);
 }
 
 int neddf_render_rays_surface(neddf_ctx *ctx, const void *uv, int uv_type, int64_t B, const neddf_camera *cam, const neddf_render_params *rp,
                               const float *Uc, const float *Uf, const neddf_render_outputs *out, float *normal, float *normal_coarse,
                               void *stream)
 {
-    return render_rays_impl(ctx, uv, uv_type, B, cam, rp, Uc, Uf, out, normal, normal_coarse, stream);
-}
-
-static int render_rays_single_impl(neddf_ctx *ctx, int slot, const void *uv, int uv_type, int64_t B, const neddf_camera *cam,
-                                   const neddf_render_params *rp, int S1, const float *U, const neddf_render_outputs *out, float *normal,
-                                   void *stream, const neddf_occupancy *occ = nullptr)
-{
-    if (!ctx) return NEDDF_EINVAL;
-    if (B <= 0) return 0;
-    if (!uv || !rp || !U || !out || S1 < 2) return NEDDF_EINVAL;
-    if (int rc = check_uv(ctx, uv_type, cam, rp)) return rc;
-    if (occ && !occ_ok(occ)) return fail(ctx, NEDDF_EINVAL, "render_rays_single_culled: the grid needs its bits and a resolution in [1, 1024]");
-    if (occ && out->fields_penalty)
-        return fail(ctx, NEDDF_EUNSUPPORTED, "render_rays_single_culled: no fields_penalty output with an occupancy grid (a culled sample has no penalty)");
-    DeviceGuard guard_(ctx->device);
-    hipStream_t s = (hipStream_t)stream;
-    if (slot < 0 || slot >= NEDDF_NUM_SLOTS || !ctx->field[slot].valid) return fail(ctx, NEDDF_ENOFIELD, "no field in slot");
-    size_t need = 2 * carve_bytes(B * 3) + carve_bytes(B * S1) + 3 * carve_bytes(B * S1 * 3) + 2 * carve_bytes(B * S1) +
-                  carve_bytes(B * S1 * 3) + 5 * carve_bytes(B * 3);
-    if (normal) need += carve_bytes(B * S1 * 3);
-    if (occ && B * S1 >= ((int64_t)1 << 31)) return fail(ctx, NEDDF_EUNSUPPORTED, "render_rays_single_culled: 2^31 samples or more (compaction indices are int32)");
-    if (occ) need += occ_work_bytes(B * S1, normal != nullptr);
-    if (int rc = ensure(ctx, ctx->arena, need)) return rc;
-    ctx->carve_guards.clear();
-    Carver cv{ (char *)ctx->arena.p, ctx, s };
-    float *rd = cv.take(B * 3), *ro = cv.take(B * 3);
-    float *dc = out->dists_fine ? out->dists_fine : cv.take(B * S1);
-    float *pos = cv.take(B * S1 * 3), *dir = cv.take(B * S1 * 3), *var = cv.take(B * S1 * 3);
-    float *dens = cv.take(B * S1), *pen = cv.take(B * S1), *col = cv.take(B * S1 * 3);
-    float *depth = out->depth ? out->depth : cv.take(B);
-    float *color = out->color ? out->color : cv.take(B * 3);
-    float *trans = out->transmittance ? out->transmittance : cv.take(B);
-    float *nrm = normal ? cv.take(B * S1 * 3) : nullptr;
-    OccWork work{};
-    if (occ) work = occ_work(cv, occ, B * S1, normal != nullptr);
-    int *nan_flag = out->nan_flag ? out->nan_flag : (int *)ctx->flags.p;
-    STAGE(ctx, s, NEDDF_STAGE_RAYGEN, launch_raygen(uv, uv_type, B, cam_arg(cam), rd, ro, s));
-    const float *view = nullptr;
-    if (rp->ndc_rays) {
-        float *nd = cv.take(B * 3), *no = cv.take(B * 3);
-        STAGE(ctx, s, NEDDF_STAGE_NDC, launch_ndc(rd, ro, B, (float)rp->ndc_width, (float)rp->ndc_height, cam->calib[0], cam->calib[1], rp->ndc_near, nd, no, s));
-        view = rd; rd = nd; ro = no;
-    }
-    STAGE(ctx, s, NEDDF_STAGE_SAMPLE_COARSE, launch_sample_coarse(U, B, S1, rp->dist_near, rp->dist_far, dc, s));
-    int rc = render_pass(ctx, slot, rd, ro, view, dc, B, S1, rp, pos, dir, var, dens, col, pen, out->weight, depth, color, trans,
-                         out->fields_penalty, nan_flag, s, nrm, normal, occ ? &work : nullptr);
-    if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    return 0;
+    return render_rays_body(ctx, { "render_rays_culled", true, 0, 0, Uc, Uf, normal, normal_coarse, nullptr }, uv, uv_type, B, cam, rp, out, stream);
 }
 
 int neddf_render_rays_single(neddf_ctx *ctx, int slot, const void *uv, int uv_type, int64_t B, const neddf_camera *cam,
                              const neddf_render_params *rp, int S1, const float *U, const neddf_render_outputs *out, void *stream)
 {
-    return render_rays_single_impl(ctx, slot, uv, uv_type, B, cam, rp, S1, U, out, nullptr, stream);
+    return render_rays_body(ctx, { "render_rays_single_culled", false, slot, S1, U, nullptr, nullptr, nullptr, nullptr }, uv, uv_type, B, cam, rp, out, stream);
 }
 
 int neddf_render_rays_single_surface(neddf_ctx *ctx, int slot, const void *uv, int uv_type, int64_t B, const neddf_camera *cam,
                                      const neddf_render_params *rp, int S1, const float *U, const neddf_render_outputs *out, float *normal,
                                      void *stream)
 {
-    return render_rays_single_impl(ctx, slot, uv, uv_type, B, cam, rp, S1, U, out, normal, stream);
+    return render_rays_body(ctx, { "render_rays_single_culled", false, slot, S1, U, nullptr, normal, nullptr, nullptr }, uv, uv_type, B, cam, rp, out, stream);
 }
 
 int neddf_op_activation(neddf_ctx *ctx, int op, const float *x, const float *J, int64_t N, int C, float *y, float *G, void *stream)
@@ -1161,14 +1152,14 @@ int neddf_render_rays_culled(neddf_ctx *ctx, const void *uv, int uv_type, int64_
                              const float *Uc, const float *Uf, const neddf_render_outputs *out, float *normal, float *normal_coarse,
                              void *stream, const neddf_occupancy *occ)
 {
-    return render_rays_impl(ctx, uv, uv_type, B, cam, rp, Uc, Uf, out, normal, normal_coarse, stream, occ);
+    return render_rays_body(ctx, { "render_rays_culled", true, 0, 0, Uc, Uf, normal, normal_coarse, occ }, uv, uv_type, B, cam, rp, out, stream);
 }
 
 int neddf_render_rays_single_culled(neddf_ctx *ctx, int slot, const void *uv, int uv_type, int64_t B, const neddf_camera *cam,
                                     const neddf_render_params *rp, int S1, const float *U, const neddf_render_outputs *out, float *normal,
                                     void *stream, const neddf_occupancy *occ)
 {
-    return render_rays_single_impl(ctx, slot, uv, uv_type, B, cam, rp, S1, U, out, normal, stream, occ);
+    return render_rays_body(ctx, { "render_rays_single_culled", false, slot, S1, U, nullptr, normal, nullptr, occ }, uv, uv_type, B, cam, rp, out, stream);
 }
 
 int neddf_cull_stats(neddf_ctx *ctx, int64_t *h_samples, int64_t *h_kept, int reset)
@@ -1380,11 +1371,15 @@ int neddf_trace_field(neddf_ctx *ctx, int slot, const float *d_ray_orig, const f
     hipStream_t s = (hipStream_t)stream;
     // workspace: index [n], points [n, 3], distances [n], and dir / var of one field chunk (at most 2^23 points, the field kernels' launch size)
     const int64_t chunk = n_rays < ((int64_t)1 << 23) ? n_rays : ((int64_t)1 << 23);
-    const size_t bytes = carve_bytes((size_t)n_rays) * 2 + carve_bytes((size_t)n_rays * 3) + 2 * carve_bytes((size_t)chunk * 3);
-    if (int rc = ensure(ctx, ctx->trace_ws, bytes)) return rc;
-    Carver cv{ (char *)ctx->trace_ws.p };          // (no bands between the carves: the block's own two stand at its ends)
-    int32_t *index = (int32_t *)cv.take((size_t)n_rays);
-    float *D = cv.take((size_t)n_rays), *pos = cv.take((size_t)n_rays * 3), *dir = cv.take((size_t)chunk * 3), *var = cv.take((size_t)chunk * 3);
+    int32_t *index;
+    float *D, *pos, *dir, *var;
+    auto layout = [&](Carver cv) {                  // (no bands between the carves: the block's own two stand at its ends)
+        index = (int32_t *)cv.take((size_t)n_rays);
+        D = cv.take((size_t)n_rays); pos = cv.take((size_t)n_rays * 3); dir = cv.take((size_t)chunk * 3); var = cv.take((size_t)chunk * 3);
+        return cv.off;
+    };
+    if (int rc = ensure(ctx, ctx->trace_ws, layout(Carver{ nullptr }))) return rc;
+    layout(Carver{ (char *)ctx->trace_ws.p });
     launch_trace_unit_inputs(dir, var, chunk, s);
     const TraceState st = trace_state(d_t, d_t_lo, d_status, d_steps, d_dist);
     launch_trace_begin(d_ray_orig, d_ray_dir, n_rays, p->t_near, st, s);

@@ -155,6 +155,33 @@ class NeRFRender(BaseNeuralRender):
             return torch.rand(rows, cols, device=device)
         raise ValueError("rng must be 'torch_cpu' or 'device'")
 
+    def _draw_pair(self, B: int, device):
+        """The uniforms of one hierarchical batch, U_c [B,Sc+1] then U_f [B,Sf+1]: draw order is part of the contract."""
+        return self._rand(B, self.sample_coarse + 1, device), self._rand(B, self.sample_fine + 1, device)
+
+    @staticmethod
+    def _pixel_grid(width: int, height: int, downsampling: int, device, pixel_range=None):
+        """(uv, w, h): every `downsampling`-th pixel as int64 rows (u, v), row-major (idx = v*w + u); pixel_range=(lo, hi): that slab."""
+        w, h = width // downsampling, height // downsampling
+        us = torch.arange(w, device=device).reshape(1, w).expand(h, w).reshape(-1) * downsampling
+        vs = torch.arange(h, device=device).reshape(h, 1).expand(h, w).reshape(-1) * downsampling
+        lo, hi = (0, w * h) if pixel_range is None else pixel_range
+        return torch.stack([us, vs], 1)[lo:hi], w, h
+
+    @staticmethod
+    def _hit_targets(hit: Tensor, t: Tensor, target_types: List[RenderTarget]) -> Dict[str, Tensor]:
+        """The targets a hit mask decides (traced and mesh views): depth = t on HIT pixels, 0 elsewhere; transmittance 0 / 1."""
+        make = dict(depth=lambda: torch.where(hit, t, torch.zeros_like(t)),
+                    transmittance=lambda: torch.where(hit, torch.zeros_like(t), torch.ones_like(t)))
+        return {k: f() for k, f in make.items() if k in target_types}
+
+    @staticmethod
+    def _as_images(out: Dict[str, Tensor], target_types: List[RenderTarget], w: int, h: int, pixel_range) -> Dict[str, Tensor]:
+        """Flat per-pixel tensors -> [h, w, 3] / [h, w] images (a slab stays flat), in the order of target_types."""
+        if pixel_range is None:
+            out = {k: v.reshape(h, w, 3) if v.dim() == 2 else v.reshape(h, w) for k, v in out.items()}
+        return {k: out[k] for k in target_types}
+
     def _has_penalty(self) -> bool:
         return isinstance(self.network_fine, NeDDF)
 
@@ -259,9 +286,12 @@ class NeRFRender(BaseNeuralRender):
             return self.render_bundle(rays)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             return self._render_rays_with_grad(uv, camera)
-        ctx = self._ctx(uv.device)
-        U_c = self._rand(B, self.sample_coarse + 1, uv.device)       # draw order is part of the contract
-        U_f = self._rand(B, self.sample_fine + 1, uv.device)
+        return self._render_rays_fused(uv, camera, B, uv.device)
+
+    def _render_rays_fused(self, uv, camera: Optional[Camera], B: int, device) -> Dict[str, Tensor]:
+        """The inference path of render_rays (uv: pixels of `camera`) and render_bundle (uv: a Ray, no camera): one fused call."""
+        ctx = self._ctx(device)
+        U_c, U_f = self._draw_pair(B, device)
         o = self._render(ctx, uv, camera, U_c, U_f, full=True, normal=bool(self.normal_output))
         assert int(o.pop("_nan").item()) == 0, "NaN weight in integrate_volume_render"
         return {k: o[k] for k in self.RAY_KEYS if k in o}
@@ -272,8 +302,7 @@ class NeRFRender(BaseNeuralRender):
         ctx = Context.get(uv.device)
         B = uv.shape[0]
         p = self._params()
-        U_c = self._rand(B, self.sample_coarse + 1, uv.device)
-        U_f = self._rand(B, self.sample_fine + 1, uv.device)
+        U_c, U_f = self._draw_pair(B, uv.device)
         radius = p.ray_radius if p.cone_sampling else None
         if self.pose_gradients:
             return self._render_rays_with_pose_grad(ctx, uv, camera, p, radius, U_c, U_f)
@@ -361,8 +390,7 @@ class NeRFRender(BaseNeuralRender):
             if ray_graph or any(p.requires_grad for p in self.parameters()):
                 ctx = Context.get(dev)
                 p = self._params()
-                U_c = self._rand(B, self.sample_coarse + 1, dev)
-                U_f = self._rand(B, self.sample_fine + 1, dev)
+                U_c, U_f = self._draw_pair(B, dev)
                 radius = p.ray_radius if p.cone_sampling else None
                 if ray_graph:
                     self._check_pose_fields()
@@ -370,12 +398,7 @@ class NeRFRender(BaseNeuralRender):
                 else:
                     rd, ro = rd.detach().to(torch.float32).contiguous(), ro.detach().to(torch.float32).contiguous()
                 return self._render_generated_rays(ctx, rd, ro, radius, U_c, U_f, ray_graph=ray_graph)
-        ctx = self._ctx(dev)
-        U_c = self._rand(B, self.sample_coarse + 1, dev)       # draw order is part of the contract
-        U_f = self._rand(B, self.sample_fine + 1, dev)
-        o = self._render(ctx, rays, None, U_c, U_f, full=True, normal=bool(self.normal_output))
-        assert int(o.pop("_nan").item()) == 0, "NaN weight in integrate_volume_render"
-        return {k: o[k] for k in self.RAY_KEYS if k in o}
+        return self._render_rays_fused(rays, None, B, dev)
 
     def render_rays_mixed(self, uv: Tensor, view_index: Tensor, cameras: List[Camera]) -> Dict[str, Tensor]:
         """render_rays on a batch that mixes views (not a reference method): row b is pixel uv[b] of cameras[view_index[b]]
@@ -459,10 +482,7 @@ class NeRFRender(BaseNeuralRender):
             self._check_normal_fields(coarse=False)
         with torch.no_grad():
             dev = camera.device
-            w, h = width // downsampling, height // downsampling
-            us = torch.arange(w, device=dev).reshape(1, w).expand(h, w).reshape(-1) * downsampling
-            vs = torch.arange(h, device=dev).reshape(h, 1).expand(h, w).reshape(-1) * downsampling
-            uv = torch.stack([us, vs], 1)
+            uv, w, h = self._pixel_grid(width, height, downsampling, dev)
             n = uv.shape[0]
             self.network_coarse.eval()
             self.network_fine.eval()
@@ -511,8 +531,7 @@ class NeRFRender(BaseNeuralRender):
                 step = max(chunk, self.rays_per_call // chunk * chunk)
                 for below in range(lo, hi, step):
                     above = min(hi, below + step)
-                    launch(below, above, self._rand(above - below, self.sample_coarse + 1, dev),
-                           self._rand(above - below, self.sample_fine + 1, dev))
+                    launch(below, above, *self._draw_pair(above - below, dev))
             assert not flags or int(torch.stack(flags).sum().item()) == 0, "NaN weight in integrate_volume_render"
             if pixel_range is None:
                 images = {k: torch.cat(parts[k], 0).reshape(h, w, -1) for k in target_types}
@@ -593,22 +612,14 @@ class NeRFRender(BaseNeuralRender):
         params = trace_params(threshold, self.dist_near, self.dist_far, max_steps, step_scale, min_step, refine)
         with torch.no_grad():
             dev = camera.device
-            w, h = width // downsampling, height // downsampling
-            us = torch.arange(w, device=dev).reshape(1, w).expand(h, w).reshape(-1) * downsampling
-            vs = torch.arange(h, device=dev).reshape(h, 1).expand(h, w).reshape(-1) * downsampling
-            lo, hi = (0, w * h) if pixel_range is None else pixel_range
-            uv = torch.stack([us, vs], 1)[lo:hi]
+            uv, w, h = self._pixel_grid(width, height, downsampling, dev, pixel_range)
             n = uv.shape[0]
             ctx = self._ctx(dev)
             uv, cam_desc, bundle = self._view_rays(uv, camera)
             rd, ro = ctx.raygen(uv, cam_desc, bundle=bundle)
             st, _ = ctx.trace_field(SLOT_FINE, ro, rd, params)
             hit = st["status"] == HIT
-            out: Dict[str, Tensor] = {}
-            if "depth" in target_types:
-                out["depth"] = torch.where(hit, st["t"], torch.zeros_like(st["t"]))
-            if "transmittance" in target_types:
-                out["transmittance"] = torch.where(hit, torch.zeros_like(st["t"]), torch.ones_like(st["t"]))
+            out = self._hit_targets(hit, st["t"], target_types)
             if "steps" in target_types:
                 out["steps"] = st["steps"]
             wide = [k for k in ("color", "normal") if k in target_types]
@@ -623,9 +634,7 @@ class NeRFRender(BaseNeuralRender):
                     o = ctx.field_forward_surface(SLOT_FINE, pos, rd[idx], torch.zeros_like(pos), OUT_MINIMAL, wide)
                     for k in wide:
                         out[k][idx] = o[k].view(-1, 3)
-            if pixel_range is None:
-                out = {k: v.reshape(h, w, 3) if v.dim() == 2 else v.reshape(h, w) for k, v in out.items()}
-        return {k: out[k] for k in target_types}
+        return self._as_images(out, target_types, w, h, pixel_range)
 
     MESH_TARGETS = ("depth", "transmittance", "triangle", "normal", "color", "ambient_occlusion")
     MESH_TILE = 8
@@ -687,11 +696,7 @@ class NeRFRender(BaseNeuralRender):
                 raise ValueError("render_image_mesh: %s must be [V, 3] like the vertices (got %s)" % (name, tuple(a.shape)))
         with torch.no_grad():
             dev = camera.device
-            w, h = width // downsampling, height // downsampling
-            us = torch.arange(w, device=dev).reshape(1, w).expand(h, w).reshape(-1) * downsampling
-            vs = torch.arange(h, device=dev).reshape(h, 1).expand(h, w).reshape(-1) * downsampling
-            lo, hi = (0, w * h) if pixel_range is None else pixel_range
-            uv = torch.stack([us, vs], 1)[lo:hi]
+            uv, w, h = self._pixel_grid(width, height, downsampling, dev, pixel_range)
             n = uv.shape[0]
             uv, cam_desc, bundle = self._view_rays(uv, camera)
             rd, ro = self._ctx(dev).raygen(uv, cam_desc, bundle=bundle)
@@ -706,11 +711,7 @@ class NeRFRender(BaseNeuralRender):
             if order is not None:
                 hits = {k: torch.empty_like(a).index_copy_(0, order, a) for k, a in hits.items()}
             hit = hits["triangle"] >= 0
-            out: Dict[str, Tensor] = {}
-            if "depth" in target_types:
-                out["depth"] = torch.where(hit, hits["t"], torch.zeros_like(hits["t"]))
-            if "transmittance" in target_types:
-                out["transmittance"] = torch.where(hit, torch.zeros_like(hits["t"]), torch.ones_like(hits["t"]))
+            out = self._hit_targets(hit, hits["t"], target_types)
             if "triangle" in target_types:
                 out["triangle"] = hits["triangle"]
             wide = [k for k in ("color", "normal", "ambient_occlusion") if k in target_types]
@@ -743,9 +744,7 @@ class NeRFRender(BaseNeuralRender):
                     if idx.shape[0]:
                         ao = bvh_module.ambient_occlusion(interpolate(vertices), nrm, vertices, triangles, n_dirs=ao_dirs, radius=ao_radius, bvh=bvh)
                         out["ambient_occlusion"][idx] = ao
-            if pixel_range is None:
-                out = {k: v.reshape(h, w, 3) if v.dim() == 2 else v.reshape(h, w) for k, v in out.items()}
-        return {k: out[k] for k in target_types}
+        return self._as_images(out, target_types, w, h, pixel_range)
 
     def render_field_slice(self, slice_t: float = 0.0, render_size: float = 1.1, render_resolution: int = 128,
                            colormap: bool = True):
