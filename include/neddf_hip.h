@@ -58,7 +58,17 @@ enum { NEDDF_DTYPE_F32 = 0, NEDDF_DTYPE_BF16 = 1,
        /* fp32 weights and activations contracted on the fp16 matrix instructions: every operand split into two fp16 terms
         * (21-22 bits), the three products above 2^-22 accumulated in fp32; weights pre-scaled by 2^10 to stay in fp16's normal
         * range.  Errors at the level of the fp32 MFMA path's own, 2.5x its throughput; operands beyond +-65504 saturate */
-       NEDDF_DTYPE_F16_SPLIT = 2 };
+       NEDDF_DTYPE_F16_SPLIT = 2,
+       /* fp16 weights + fp16 activations with fp32 accumulation on v_mfma_f32_32x32x16_f16 (additive to ABI v7): the bf16 policy's
+        * kernels and shapes with 11 significant bits per operand instead of 8, within about 4 % of bf16's speed; heads, biases,
+        * encodings stay fp32.
+        * Inference only: every entry point that evaluates a field (neddf_field_forward, _forward_surface, _grid, _grid_coarse,
+        * _bricks, the six neddf_render_rays* calls, neddf_trace_field) takes it for NeDDF, NeRF and NeuS at every width; the
+        * training entry points treat it exactly as they treat NEDDF_DTYPE_BF16 -- they do not read the packed weights at all and
+        * run fp32 MFMA products on the live fp32 tensors.  fp16 ends at +-65504: a finite OPERAND beyond that (an activation
+        * during evaluation) becomes Inf, and neddf_set_field refuses (NEDDF_EUNSUPPORTED, slot untouched) a field with a finite
+        * weight or bias beyond it; NaN and Inf weights are accepted as under every policy */
+       NEDDF_DTYPE_F16 = 3 };
 enum { NEDDF_SLOT_COARSE = 0, NEDDF_SLOT_FINE = 1, NEDDF_NUM_SLOTS = 4 };
 /* uv element types accepted by neddf_raygen (the reference takes int64 in
  * render_image, int16 in training, float in its tests) */

@@ -16,7 +16,7 @@ ABI_VERSION = 7
 
 FIELD_NEDDF, FIELD_NERF, FIELD_NEUS = 0, 1, 2
 ACT = {"ReLU": 0, "LeakyReLU": 1, "tanhExp": 2}
-DTYPE = {"fp32": 0, "bf16": 1, "f16_split": 2}
+DTYPE = {"fp32": 0, "bf16": 1, "f16_split": 2, "f16": 3}       # NEDDF_DTYPE_* (include/neddf_hip.h)
 SLOT_COARSE, SLOT_FINE, SLOT_GENERIC = 0, 1, 2
 OUT_MINIMAL, OUT_FULL = 0, 1
 GRID_FIELDS = {"distance": 0, "density": 1}        # NEDDF_GRID_*

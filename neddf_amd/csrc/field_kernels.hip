@@ -425,7 +425,7 @@ __global__ __launch_bounds__(kThreads, 2) void ddf_rev_kernel(const DdfArgs a)
     }
     // Ops::kTransposed: the two heads (neddf.py:220-230, value rows) as ONE narrow product on the matrix pipe instead of 2 x 128-term dot
     // products per thread on the vector ALU: the A operand's rows 0..2 carry w_ddf as three bf16 terms (hi + mid + lo = the fp32 weight
-    // to 2^-24: the heads stay fp32-exact on bf16 activations, as before), rows 4..6 w_aux likewise, the other rows are zero.  The
+    // to 2^-24: the heads stay fp32-exact on bf16 activations, as before; three fp16 terms under the fp16 policy), rows 4..6 w_aux likewise, the other rows are zero.  The
     // fragments of rows 0..7 are built once per workgroup into the (otherwise unused) Jacobian-factor slot of its global scratch.
     // super-steps of a 256-wide product, as a RUN-TIME value (the argument block carries it, DdfArgs::ks_hidden): with the compile-time constant hipcc
     // unrolls the reverse products completely, materialises one 64-bit address per weight fragment, spills them and reloads each
@@ -442,10 +442,10 @@ __global__ __launch_bounds__(kThreads, 2) void ddf_rev_kernel(const DdfArgs a)
                 float w = wv[Ops::kStep * S + 8 * hh + r];
                 unsigned short t16 = 0;
 #pragma unroll
-                for (int k = 0; k < 3; ++k) {       // peel hi, mid, lo: each the bf16 rounding of what the previous terms left
+                for (int k = 0; k < 3; ++k) {       // peel hi, mid, lo: each the 16-bit rounding of what the previous terms left
                     t16 = Ops::cvt(w);
                     if (k == term) break;
-                    w -= __builtin_bit_cast(float, (unsigned int)t16 << 16);
+                    w -= Ops::get(&t16);
                 }
                 bits[r] = term < 3 ? t16 : (unsigned short)0;
             }
@@ -873,11 +873,11 @@ __global__ __launch_bounds__(kThreads, 2) void ddf_rev_kernel(const DdfArgs a)
                 if (a.density) a.density[gp] = rho;
             } else {
                 float sp, dsp, t, dsg;
-                if constexpr (Ops::kFast) softplus_grad_fast(z, sp, dsp);
+                if constexpr (Ops::kFastHead) softplus_grad_fast(z, sp, dsp);
                 else softplus_grad(z, sp, dsp);          // softplus.py:38-49
                 const float D = sp + a.d_near;
                 const float dg0 = dsp * gz[0], dg1 = dsp * gz[1], dg2 = dsp * gz[2];
-                if constexpr (Ops::kFast) sigmoid_grad_fast(az, t, dsg);
+                if constexpr (Ops::kFastHead) sigmoid_grad_fast(az, t, dsg);
                 else sigmoid_grad(az, t, dsg);           // sigmoid.py:38-43
                 const float aux = a.aux_grad_scale * t;
                 const float q2 = dg0 * dg0 + dg1 * dg1 + dg2 * dg2;
@@ -1393,6 +1393,7 @@ size_t field_lds_bytes(int mt) { return lds_bytes<OpsF32>(mt); }
 //                 on (4, 2, 8); once round 6 had taken the waits out of the phases around the layers, three independent four-wave
 //                 workgroups beat two eight-wave ones in lockstep: 55.2 -> 50.4 ms per C2 step ((4, 2, 4): 52.5; (2, 2, 4): 56.6)
 //     split fp16  (2, 2, 4): two fp16 planes = the LDS bytes of fp32, same shape as fp32
+//     fp16        bf16's shapes, kernel for kernel (the same bytes and the same instruction counts; no sweep of its own)
 //   reverse-mode distance kernel: 64-point tiles, four waves, two workgroups per CU under every policy (ddf_rev_kernel)
 // Engine widths other than 256 (hidden width padded to 128 / 384 / 512; the reference's constructors take any width,
 // neddf.py:52-66, nerf.py:34-44) have ONE shape per width under every operand policy: 64-row tiles at 128 columns, 32-row tiles
@@ -1402,8 +1403,8 @@ struct Geo {
     int mt, wps, nw;
 };
 static Geo geo_w(int width) { return width == 128 ? Geo{ 2, 2, 4 } : Geo{ 1, 2, 4 }; }
-static Geo geo(int operands, int width) { return width != 256 ? geo_w(width) : (operands == 1 ? Geo{ 4, 2, 4 } : Geo{ 2, 2, 4 }); }
-static Geo geo_col(int operands, int width) { return width != 256 ? geo_w(width) : (operands == 1 ? Geo{ 2, 3, 4 } : Geo{ 2, 2, 4 }); }
+static Geo geo(int operands, int width) { return width != 256 ? geo_w(width) : (plain16(operands) ? Geo{ 4, 2, 4 } : Geo{ 2, 2, 4 }); }
+static Geo geo_col(int operands, int width) { return width != 256 ? geo_w(width) : (plain16(operands) ? Geo{ 2, 3, 4 } : Geo{ 2, 2, 4 }); }
 static Geo geo_nerf(int width) { return width == 256 ? Geo{ 2, 2, 4 } : geo_w(width); }
 int field_wgs_per_cu(int operands, int width) { return geo(operands, width).wps; }
 int col_wgs_per_cu(int operands, int width) { return geo_col(operands, width).wps; }
@@ -1445,6 +1446,7 @@ static void launch_ddf_w(const DdfArgs &a, int grid, hipStream_t s)
     constexpr int MT = WID <= 256 ? 2 : 1;
     if (a.operands == 2) launch_ddf_g<MT, 2, 4, OpsF16SplitT<WID>>(a, grid, s);
     else if (a.operands == 1) launch_ddf_g<(WID == 256 ? 4 : MT), 2, 4, OpsBF16T<WID>>(a, grid, s);
+    else if (a.operands == kOperandsH16) launch_ddf_g<(WID == 256 ? 4 : MT), 2, 4, OpsH16T<WID>>(a, grid, s);
     else launch_ddf_g<MT, 2, 4, OpsF32T<WID>>(a, grid, s);
 }
 
@@ -1484,6 +1486,7 @@ static void launch_ddf_rev_w(const DdfArgs &a, int grid, hipStream_t s)
     constexpr int MT = WID <= 256 ? 2 : 1;
     if (a.operands == 2) launch_ddf_rev_t<MT, OpsF16SplitT<WID>>(a, grid, s);
     else if (a.operands == 1) launch_ddf_rev_t<MT, NEDDF_BF16_REV_OPS<WID>>(a, grid, s);
+    else if (a.operands == kOperandsH16) launch_ddf_rev_t<MT, OpsH16RT<WID>>(a, grid, s);
     else if (a.operands == 3) {      // fp32 data, three-term bf16 products; kSchedL2ModeShift: the same kernel with an L2 residency mechanism
         const int l2 = (a.sched_flags >> kSchedL2ModeShift) & 3;
         if (l2 == 1) launch_ddf_rev_t<MT, OpsF32x3L2T<WID, 1>>(a, grid, s);
@@ -1510,6 +1513,9 @@ static void launch_col_w(const ColArgs &a, int grid, bool rows4, hipStream_t s)
     else if (a.operands == 1) {
         if constexpr (WID == 256) launch_col_g<2, 3, 4, OpsBF16>(a, grid, rows4, s);
         else launch_col_g<MT, 2, 4, OpsBF16T<WID>>(a, grid, rows4, s);
+    } else if (a.operands == kOperandsH16) {
+        if constexpr (WID == 256) launch_col_g<2, 3, 4, OpsH16T<256>>(a, grid, rows4, s);
+        else launch_col_g<MT, 2, 4, OpsH16T<WID>>(a, grid, rows4, s);
     } else if (a.operands == 3) launch_col_g<MT, 2, 4, OpsF32x3T<WID>>(a, grid, rows4, s);
     else launch_col_g<MT, 2, 4, OpsF32T<WID>>(a, grid, rows4, s);
 }
@@ -1536,6 +1542,7 @@ static void launch_nerf_w(const NerfArgs &a, int grid, hipStream_t s)
     constexpr int MT = WID <= 256 ? 2 : 1;
     if (a.operands == 2) launch_nerf_g<MT, 2, OpsF16SplitT<WID>>(a, grid, s);
     else if (a.operands == 1) launch_nerf_g<MT, 2, OpsBF16T<WID>>(a, grid, s);
+    else if (a.operands == kOperandsH16) launch_nerf_g<MT, 2, OpsH16T<WID>>(a, grid, s);
     else launch_nerf_g<MT, 2, OpsF32T<WID>>(a, grid, s);
 }
 

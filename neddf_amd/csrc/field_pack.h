@@ -27,7 +27,8 @@ struct Src {
 };
 
 // Appends to `blob` at the next 64-float boundary and returns the offset.  pack_layer: fragment-major under an operand policy (0 fp32,
-// 1 bf16, 2 split fp16, 3 fp32 as three bf16 terms; split_exact is cleared when a weight does not split exactly under 3), kmap = engine
+// 1 bf16, 2 split fp16, 3 fp32 as three bf16 terms, 4 plain fp16; split_exact is cleared when a weight does not split exactly under 3
+// or is finite and beyond fp16's range under 4), kmap = engine
 // column -> weight row (-1 = zero), nout a multiple of 32.  put: n floats, zero-padded to n_padded.
 size_t pack_layer(std::vector<float> &blob, const Src &src, std::vector<int> kmap, int nout, int operands, int *ksteps_out, bool *split_exact = nullptr);
 size_t put(std::vector<float> &blob, const float *p, size_t n, size_t n_padded = 0);

@@ -2,6 +2,7 @@
 // really differs between them (small-input maps, heads, the NeRF colour head) stays in pack_neddf / pack_neus / pack_nerf.
 #include "field_pack.h"
 
+#include <initializer_list>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -68,12 +69,17 @@ static inline bool bf16x3_split(float w, uint16_t t[3])
     return bf16_value(t[2]) == r2 && (double)bf16_value(t[0]) + (double)bf16_value(t[1]) + (double)bf16_value(t[2]) == (double)w;
 }
 
+// a finite value that fp16 rounds to infinity (NaN and Inf themselves keep their class in fp16, as under every policy)
+static inline bool beyond_f16(float v) { return isfinite(v) && fabsf(v) > 65504.0f; }
+
 // fragment-major packing, see kernels.h LayerW.  kmap is padded to a whole number of super-steps: 8 k-values for fp32 fragments
 // (4 floats per lane half), 16 for the 16-bit ones (8 per lane half).
 size_t pack_layer(std::vector<float> &blob, const Src &src, std::vector<int> kmap, int nout, int operands, int *ksteps_out, bool *split_exact)
 {
     // operands == 2 (split fp16): two fp16 planes of 2^10 w (h toward zero, m = remainder to nearest), 32 bytes per lane and super-step
     // operands == 3 (fp32 as three bf16 terms): planes hi, mid, lo of the 32x32x16 fragment, 48 bytes per lane and super-step
+    // operands == 4 (kOperandsH16, plain fp16): the bf16 fragment with every weight rounded to the nearest-even half instead; split_exact
+    // is cleared by a finite weight beyond +-65504
     const int step = operands ? 16 : 8, half = step / 2, tiles = nout / 32, planes = operands == 2 ? 2 : (operands == 3 ? 3 : 1);
     while (kmap.size() % step) kmap.push_back(-1);
     const int ks = (int)kmap.size() / step;
@@ -100,6 +106,9 @@ size_t pack_layer(std::vector<float> &blob, const Src &src, std::vector<int> kma
                         uint16_t h = f16_bits(sv, true);
                         dst16[(frag * 2 + 0) * half + r] = h;
                         dst16[(frag * 2 + 1) * half + r] = f16_bits(sv - f16_value(h), false);
+                    } else if (operands == kOperandsH16) {
+                        if (beyond_f16(v) && split_exact) *split_exact = false;
+                        dst16[frag * half + r] = f16_bits(v, false);
                     } else if (operands) dst16[frag * half + r] = bf16_bits(v);
                     else dst[frag * half + r] = v;
                 }
@@ -163,13 +172,23 @@ struct Packer {
     const float *const *W, *const *B;
     std::string &err;
     int operands;
-    bool *exact;                // pack_layer's split_exact
+    bool *exact;                // pack_layer's split_exact (fp16: cleared by a finite value beyond +-65504, in a matrix, a vector or a scalar)
     const int E = d.embed_pos_rank, Ed = d.embed_dir_rank, KH = roundup(3 * E, 4), KD = roundup(3 * Ed, 4), Cpe = 6 * E, Cdir = 6 * Ed;
     void layer(const float *&slot, const Src &src, const std::vector<int> &kmap, int nout, int *ksteps)
     {
         out.fixes.push_back({ &slot, pack_layer(out.blob, src, kmap, nout, operands, ksteps, exact) });
     }
-    void vec(const float *&slot, const float *p, size_t n, size_t n_padded = 0) { out.fixes.push_back({ &slot, put(out.blob, p, n, n_padded) }); }
+    void vec(const float *&slot, const float *p, size_t n, size_t n_padded = 0)
+    {
+        if (operands == kOperandsH16 && exact)
+            for (size_t i = 0; i < n; ++i) if (beyond_f16(p[i])) *exact = false;
+        out.fixes.push_back({ &slot, put(out.blob, p, n, n_padded) });
+    }
+    void scalars(std::initializer_list<float> v)         // the biases and the NeuS variance that travel in the argument blocks themselves
+    {
+        if (operands == kOperandsH16 && exact)
+            for (float x : v) if (beyond_f16(x)) *exact = false;
+    }
     int fail(int code, const std::string &msg) { err = msg; return code; }
 };
 
@@ -264,6 +283,7 @@ static int pack_neddf(Packer &p, DdfArgs &a, ColArgs &c)
     p.vec(a.w_ddf_out, p.W[i_ddf], Wd, WP);
     p.vec(a.w_aux_out, p.W[i_aux], Wd, WP);
     a.b_ddf_out = p.B[i_ddf][0]; a.b_aux_out = p.B[i_aux][0];
+    p.scalars({ a.b_ddf_out, a.b_aux_out, p.B[i_cout][0], p.B[i_cout][1], p.B[i_cout][2] });
     pack_transposes(p, kNeddfTrunk, a, n_trunk, Wd, WP);
     std::vector<int> ka;        // engine columns [pos sin KH | pos cos KH | dir sin KD | dir cos KD | normal 3]
     enc_map(ka, p.E, p.KH, 0);
@@ -317,6 +337,7 @@ static int pack_neus(Packer &p, DdfArgs &a, ColArgs &c)
     a.neus = 1;
     a.operands = c.operands = p.operands;
     a.neus_v10 = p.W[n_sdf + n_col + 1][0] * 10.0f;
+    p.scalars({ c.b_out[0], c.b_out[1], c.b_out[2], p.W[n_sdf + n_col + 1][0] });
     c.mode = 1;
     c.final_act = d.activation;
     return 0;
@@ -344,6 +365,7 @@ static int pack_nerf(Packer &p, NerfArgs &a)
     for (int o = 0; o < 3; ++o) memcpy(&w1[(size_t)o * HC], p.W[n + 2] + (size_t)o * Wh, (size_t)Wh * sizeof(float));
     p.vec(a.w_col1, w1.data(), w1.size());
     for (int k = 0; k < 3; ++k) a.b_col1[k] = p.B[n + 2][k];
+    p.scalars({ a.b_density, a.b_col1[0], a.b_col1[1], a.b_col1[2] });
     a.activation = d.activation;
     a.density_activation = d.density_activation;
     a.operands = p.operands;
@@ -353,7 +375,15 @@ static int pack_nerf(Packer &p, NerfArgs &a)
 
 int pack_field(const neddf_field_desc &d, const float *const *W, const float *const *B, int n_tensors, PackedField &out, std::string &err)
 {
-    Packer p{ out, d, W, B, err, d.weight_dtype, nullptr };       // 0 fp32, 1 bf16, 2 split fp16
+    // the operand policy of a weight_dtype: 0 fp32, 1 bf16, 2 split fp16 as they are; plain fp16 is kOperandsH16 (3 is the three-term packing)
+    bool in_range = true;
+    const bool h16 = d.weight_dtype == NEDDF_DTYPE_F16;
+    Packer p{ out, d, W, B, err, h16 ? kOperandsH16 : d.weight_dtype, h16 ? &in_range : nullptr };
+    const auto done = [&](int rc) {
+        if (rc == 0 && !in_range)
+            return p.fail(NEDDF_EUNSUPPORTED, "weight_dtype f16: a finite weight or bias beyond +-65504 would become Inf as an fp16 operand");
+        return rc;
+    };
     const int n = d.layer_count, n_col = d.col_layer_count;
     out.has3 = false;
     if (d.kind == NEDDF_FIELD_NEDDF) {
@@ -362,7 +392,7 @@ int pack_field(const neddf_field_desc &d, const float *const *W, const float *co
                                               "neddf.py:145: its own forward fails otherwise)");
         if (n_tensors != n + n_col + 1) return p.fail(NEDDF_EINVAL, "NeDDF: wrong tensor count");
         if (n < 2 || n - 1 > kMaxLayers || n_col < 2 || n_col - 1 > kMaxLayers) return p.fail(NEDDF_EUNSUPPORTED, "NeDDF: layer count out of range");
-        if (int rc = pack_neddf(p, out.ddf, out.col)) return rc;
+        if (int rc = done(pack_neddf(p, out.ddf, out.col))) return rc;
         // fp32 fields: the reverse-mode distance kernel and the colour kernel of the eval-minimal route take their products as three-term
         // bf16 splits (operands 3, tile_engine.h OpsF32x3T) from a second packing of the same weights; the forward-mode kernels keep the first
         if (d.weight_dtype == NEDDF_DTYPE_F32 && f32_products_split3()) {
@@ -378,13 +408,13 @@ int pack_field(const neddf_field_desc &d, const float *const *W, const float *co
     if (d.kind == NEDDF_FIELD_NERF) {
         if (n_tensors != n + 3) return p.fail(NEDDF_EINVAL, "NeRF: wrong tensor count");
         if (n < 1 || n > kMaxLayers) return p.fail(NEDDF_EUNSUPPORTED, "NeRF: layer count out of range");
-        return pack_nerf(p, out.nerf);
+        return done(pack_nerf(p, out.nerf));
     }
     if (d.kind == NEDDF_FIELD_NEUS) {
         if (n_tensors != n + n_col + 2) return p.fail(NEDDF_EINVAL, "NeuS: wrong tensor count");
         if (n < 1 || n > kMaxLayers || n_col < 1 || n_col > kMaxLayers) return p.fail(NEDDF_EUNSUPPORTED, "NeuS: layer count out of range");
         if (d.activation == NEDDF_ACT_LEAKY) return p.fail(NEDDF_EUNSUPPORTED, "NeuS: activation must be ReLU or tanhExp");
-        return pack_neus(p, out.ddf, out.col);
+        return done(pack_neus(p, out.ddf, out.col));
     }
     return p.fail(NEDDF_EINVAL, "bad field kind");
 }

@@ -64,6 +64,9 @@ struct StashW {
     int ksteps;
 };
 
+constexpr int kOperandsH16 = 4;
+inline bool plain16(int operands) { return operands == 1 || operands == kOperandsH16; }      // one 16-bit plane: bf16's tile geometry
+
 struct EncodeDesc {
     int E, Ed;             // embed_pos_rank, embed_dir_rank
     int KH, KD;            // padded half-widths: roundup(3E,4), roundup(3Ed,4)
@@ -86,7 +89,8 @@ struct DdfArgs {
     float b_ddf_out, b_aux_out;
     float d_near, aux_grad_scale;
     int operands;                         // 0 fp32 (32x32x2 f32 MFMA), 1 bf16, 2 split fp16 (three fp16 products per multiply-add), 3 fp32 with
-                                          // three-term bf16 products (OpsF32x3T: reverse-mode distance + colour kernels only), see tile_engine.h
+                                          // three-term bf16 products (OpsF32x3T: reverse-mode distance + colour kernels only), 4 = kOperandsH16
+                                          // plain fp16 (NEDDF_DTYPE_F16; the value 3 was taken), see tile_engine.h
     int neus;                             // 1: NeuS sdf trunk (neus.py:118-145): plain PE, no heads, sdf = feature 0
     float neus_v10;                       // variance * 10
     float *scratch;                       // per-workgroup stash area

@@ -154,7 +154,7 @@ static int field_forward(neddf_ctx *ctx, int slot, const float *pos, const float
     if ((dgrad || normal) && f.d.kind == NEDDF_FIELD_NERF)
         return fail(ctx, NEDDF_EUNSUPPORTED, "a NeRF field has no distance or sdf: no gradient and no normal (nerf.py:107-165)");
     UseMark mark{ ctx, f, s };
-    const int dt = f.d.weight_dtype;
+    const int dt = f.d.kind == NEDDF_FIELD_NERF ? f.nerf.operands : f.ddf.operands;      // the slot's operand policy (kernels.h DdfArgs::operands)
     const int wid = f.d.kind == NEDDF_FIELD_NERF ? f.nerf.width : f.ddf.width;        // engine width
     // persistent grids: every workgroup slot of the device filled once (all 512 are resident, two per CU: tools/residency_probe.hip)
     const int grid_cap = ctx->cus * nerf_wgs_per_cu(wid);
@@ -374,7 +374,7 @@ int neddf_set_field(neddf_ctx *ctx, int slot, const neddf_field_desc *desc, cons
     if (desc->n_skips < 0 || desc->n_skips > 8) return fail(ctx, NEDDF_EINVAL, "bad n_skips");
     if (desc->activation < 0 || desc->activation > 2 || desc->density_activation < 0 || desc->density_activation > 2)
         return fail(ctx, NEDDF_EINVAL, "bad activation id");
-    if (desc->weight_dtype < NEDDF_DTYPE_F32 || desc->weight_dtype > NEDDF_DTYPE_F16_SPLIT) return fail(ctx, NEDDF_EINVAL, "bad weight_dtype");
+    if (desc->weight_dtype < NEDDF_DTYPE_F32 || desc->weight_dtype > NEDDF_DTYPE_F16) return fail(ctx, NEDDF_EINVAL, "bad weight_dtype");
     // Everything that can refuse the field comes BEFORE the slot is touched (include/neddf_hip.h): the packer's refusals -- it is host
     // arithmetic into a local block -- and the allocation of a larger device block, which is made beside the old one
     PackedField pk;

@@ -9,7 +9,9 @@
 //   OpsF16Split  fp32 data on the fp16 matrix instructions: every operand split into two fp16 terms (21-22 bits), a.w
 //            accumulated from the three products above 2^-22 in fp32.  3 MFMAs at 1/16 of the fp32 MFMA's cost each: 5.3x
 //            the fp32 matrix rate, errors at the level of the fp32 MFMA path's own
-// Both read one 16-byte fragment per lane per super-step for A (ds_read_b128) and for B
+//   OpsH16   activations fp16 in LDS, weights fp16, v_mfma_f32_32x32x16_f16 with fp32 accumulation: the bf16 policy's geometry with
+//            11 significant bits per operand instead of 8, within ~4 % of its speed (inference only; |operand| > 65504 becomes Inf)
+// All read one 16-byte fragment per lane per super-step for A (ds_read_b128) and for B
 // (global_load_dwordx4); a super-step covers Ops::kStep values of k, lane half h = lane>>5
 // holding k = kStep*S + (kStep/2)*h ... +kStep/2-1 -- the same mapping for A and B, which is all
 // the contraction needs.
@@ -53,6 +55,7 @@ struct OpsF32T {
     static constexpr int kStep = 8;          // k values per super-step
     static constexpr int kSub = 4;           // MFMA instructions per fragment
     static constexpr bool kFast = false;     // reference-exact elementwise math
+    static constexpr bool kFastHead = kFast; // ... of the distance kernel's head tail (softplus / sigmoid) in particular
     // tanhExp in the fused kernels: the middle form (device_math.h tanhexp_grad_mid, 17 instructions: closed form where it keeps
     // relative accuracy, a fitted odd polynomial below e^x = 0.2).  Rounds 3-4 shipped the closed form alone (mode 1, 11 instructions,
     // +1.4 % rays/s: fp32 MFMA and VALU work do not overlap, so the activation is wall time); on the negative-bias stress network its
@@ -100,6 +103,7 @@ struct OpsBF16T {
     static constexpr int kStep = 16;
     static constexpr int kSub = 1;
     static constexpr bool kFast = true;      // reduced-cost elementwise math (device_math.h), invisible after bf16 rounding
+    static constexpr bool kFastHead = kFast;
     static constexpr int kActMode = 1;
     static constexpr int kPlanes = 1, kPlane = 0;
     static constexpr float kWScale = 1.0f;
@@ -189,6 +193,7 @@ struct OpsBF16RT : OpsBF16T<WID> {
 // fp16's normal range; the accumulators are scaled back (exactly) on their way into the activation.  3 MFMAs at 1/16 of
 // the fp32 MFMA's cost: 5.3x the fp32 matrix rate, errors at the fp32 MFMA path's level.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 struct hfrag2 {
     f16x8 h, m;
 };
@@ -207,6 +212,7 @@ struct OpsF16SplitT {
     static constexpr int kStep = 16;
     static constexpr int kSub = 3;
     static constexpr bool kFast = false;
+    static constexpr bool kFastHead = kFast;
     static constexpr int kActMode = NEDDF_ACT_SPLIT;      // the middle form: this policy is sold on the fp32 gates, and the closed form alone
                                                           // triples its density error where most pre-activations are very negative (profiles/r04_act_modes.txt)
     static constexpr bool kPackedRows = false;
@@ -268,6 +274,122 @@ struct OpsF16SplitT {
     }
 };
 typedef OpsF16SplitT<256> OpsF16Split;
+
+// Plain fp16 operands (weight_dtype "f16"): the bf16 policy with 11 significant bits per operand instead of 8 -- the same tile geometry,
+// LDS layout, prefetch depth and fragment order (field_pack.hip pack_layer, operands 4), v_mfma_f32_32x32x16_f16 at the bf16
+// instruction's rate, fp32 accumulation (measured 4 % slower than the bf16 kernels on C2: docs/lab_notebook.md R13.1).  What fp16 gives up is range: a finite operand beyond +-65504 becomes Inf (neddf_set_field
+// refuses such weights; the shipped trunk's largest hidden activation is 40), values below 2^-14 lose bits gradually down to 2^-24.
+// Conversions round to nearest even: v_cvt_pk_f16_f32 on gfx950, ONE instruction per pair as under bf16 (-DNEDDF_H16_RTZ=1 builds
+// v_cvt_pkrtz_f16_f32, toward zero, also one instruction, as the A/B partner).
+// Elementwise math: each of the three reduced-cost forms of the bf16 policy can be switched to the fp32 policies' form at build time
+// (`make variant NAME=<tag> DEFS="-DNEDDF_H16_ACT=2 ..."` builds a pairing, tools/time_f16_policy.py --quick measures it).  What ships
+// is the cheapest combination -- all three reduced-cost forms --, which keeps rms(f16) <= 0.5 rms(bf16) on every output of
+// tests/test_gpu_f16_policy.py; what the other pairings and the toward-zero conversion measured is in docs/lab_notebook.md R13.1.
+// (neither `OpsBF16` nor `OpsF16Split` may appear in these names: the benchmark tells the dtypes apart by those substrings)
+#ifndef NEDDF_H16_ACT
+#define NEDDF_H16_ACT 1             // tanhExp: 1 = closed form (11 instructions), 2 = the middle form of the fp32 policies (17)
+#endif
+#ifndef NEDDF_H16_FAST_ENC
+#define NEDDF_H16_FAST_ENC 1        // encodings on v_sin / v_cos / v_exp (1) or the Cody-Waite forms of the fp32 policies (0)
+#endif
+#ifndef NEDDF_H16_FAST_HEAD
+#define NEDDF_H16_FAST_HEAD 1       // softplus / sigmoid of the distance head on the raw transcendental units (1) or libm (0)
+#endif
+#ifndef NEDDF_H16_RTZ
+#define NEDDF_H16_RTZ 0
+#endif
+template <int WID>
+struct OpsH16T {
+    static constexpr int kWid = WID;
+    typedef unsigned short act_t;            // fp16 bit pattern
+    typedef f16x8 frag;
+    typedef frag afrag;
+    typedef frag bfrag;
+    static constexpr int kLd = WID + 8;
+    static constexpr int kStep = 16;
+    static constexpr int kSub = 1;
+    static constexpr bool kFast = NEDDF_H16_FAST_ENC != 0;
+    static constexpr bool kFastHead = NEDDF_H16_FAST_HEAD != 0;
+    static constexpr int kActMode = NEDDF_H16_ACT;
+    static constexpr int kPlanes = 1, kPlane = 0;
+    static constexpr float kWScale = 1.0f;   // (a 2^10 scale changed the shipped trunk's error in the fourth digit: not taken)
+    static constexpr bool kStash16 = true;
+    static constexpr bool kDeepPrefetch = true;
+    static constexpr bool kEncInLds = true;
+    static constexpr bool kTransposed = false, kStashF16 = false;
+    static constexpr bool kPackedRows = true;
+    typedef frag mfrag;
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    static __device__ __forceinline__ frag load_a(const act_t *p) { return *(const frag *)p; }
+    static __device__ __forceinline__ const mfrag &prep(const frag &a) { return a; }
+    static __device__ __forceinline__ void zero(act_t *p) { *p = 0; }
+    static __device__ __forceinline__ unsigned int cvt2(float a, float b)      // two halves in one word: a low, b high
+    {
+#if NEDDF_H16_RTZ
+        return __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_pkrtz(a, b));
+#else
+        return __builtin_bit_cast(unsigned int, __builtin_convertvector((f32x2){ a, b }, f16x2));
+#endif
+    }
+    static __device__ __forceinline__ unsigned short cvt(float v) { return (unsigned short)(cvt2(v, v) & 0xffffu); }
+    static __device__ __forceinline__ void put(act_t *p, float v) { *p = cvt(v); }
+    static __device__ __forceinline__ void put2(act_t *pa, act_t *pb, float va, float vb)
+    {
+        const unsigned int w = cvt2(va, vb);
+        *pa = (unsigned short)w; *pb = (unsigned short)(w >> 16);
+    }
+    static __device__ __forceinline__ void put_rows4(act_t *p, int ld, float v0, float v1, float v2, float v3)
+    {
+        const unsigned int a = cvt2(v0, v1), b = cvt2(v2, v3);
+        p[0] = (unsigned short)a; p[ld] = (unsigned short)(a >> 16);
+        p[2 * ld] = (unsigned short)b; p[3 * ld] = (unsigned short)(b >> 16);
+    }
+    static __device__ __forceinline__ float get(const act_t *p) { return (float)__builtin_bit_cast(_Float16, *p); }
+    // Four halves of two words, each widened by ONE v_fma_mix_f32 (half * 1 + 0: the half's value, NaN and Inf included; a half -0 comes
+    // out as +0, which no consumer tells apart -- they multiply and add it) with the half selected in the instruction -- the count of bf16's shift / mask.  Written with the instruction spelled out (half_to_float below): from
+    // `(float)bit_cast<_Float16>(v[i])` on a loaded u16x4 hipcc forms v_fma_mix_f32 itself and reads the LOW half of the first word for
+    // all four values (seen in the ISA, and as O(1) errors of every kernel with a vector-ALU head; docs/lab_notebook.md R13.1)
+    static __device__ __forceinline__ void load4(const act_t *p, float (&x)[4]);
+    static __device__ __forceinline__ f32x16 mfma(const frag &a, const frag &b, const f32x16 &c, int)
+    {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    }
+};
+template <int HI>
+__device__ __forceinline__ float half_to_float(unsigned w)
+{
+    float d;
+    if constexpr (HI) asm("v_fma_mix_f32 %0, %1, 1.0, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(w));
+    else asm("v_fma_mix_f32 %0, %1, 1.0, 0 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(w));
+    return d;
+}
+template <int WID>
+__device__ __forceinline__ void OpsH16T<WID>::load4(const act_t *p, float (&x)[4])
+{
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 v = *(const u32x2 *)p;
+    x[0] = half_to_float<0>(v[0]); x[1] = half_to_float<1>(v[0]);
+    x[2] = half_to_float<0>(v[1]); x[3] = half_to_float<1>(v[1]);
+}
+
+// ... and its reverse-mode distance kernel: transposed products, y' as fp16 pairs -- OpsBF16RT's layout, word for word
+template <int WID>
+struct OpsH16RT : OpsH16T<WID> {
+    typedef OpsH16T<WID> Base;
+    typedef typename Base::act_t act_t;
+    typedef typename Base::frag frag;
+    static constexpr bool kTransposed = true, kStashF16 = true;
+    static __device__ __forceinline__ f32x16 mfma(const frag &a, const frag &b, const f32x16 &c, int)
+    {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(b, a, c, 0, 0, 0);       // weights (b) as the A operand
+    }
+    static __device__ __forceinline__ void put4(act_t *p, float v0, float v1, float v2, float v3)      // four consecutive columns, 8-byte aligned
+    {
+        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+        u32x2 w = { Base::cvt2(v0, v1), Base::cvt2(v2, v3) };
+        *(u32x2 *)p = w;
+    }
+};
 
 // fp32 data, fp32-accurate products on the bf16 matrix instructions.  An fp32 value splits EXACTLY into three bf16 terms,
 // a = a0 + a1 + a2 (a0 = bf16_rne(a), a1 = bf16_rne(a - a0), a2 = a - a0 - a1: every remainder is exact in fp32 and the last
@@ -760,8 +882,7 @@ __device__ __forceinline__ void stash_load16(f32x16 &dst, const u32x4 *src)     
     }
 }
 
-// the same as fp16 pairs (OpsBF16RT): two packed conversions per four values, 16 bytes per lane and store
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+// the same as fp16 pairs (OpsBF16RT, OpsH16RT): two packed conversions per four values, 16 bytes per lane and store
 template <int MT, int NT>
 __device__ __forceinline__ void stash_store_f16(const f32x16 (&acc)[MT][NT], float *slot, int wave, int lane)
 {

@@ -117,7 +117,8 @@ class BaseNeuralField(ABC, nn.Module):
         self._slot = SLOT_GENERIC
         self._uid = next(_module_ids)        # identity in upload signatures (id() values are recycled by the allocator)
         # operand type of the 256-wide dense layers (not a reference keyword): "fp32" = exact fp32 MFMA, the parity path;
-        # "bf16" = bf16 weights and activations with fp32 accumulation (BASELINE.json configs[4]); NeDDF / NeuS only
+        # "bf16" = bf16 weights and activations with fp32 accumulation (BASELINE.json configs[4]); "f16" = the same kernels on fp16
+        # operands (11 significant bits instead of 8, range +-65504: inference only); "f16_split" = fp32 data as two fp16 terms
         self.weight_dtype = "fp32"
         self._epoch = 0                      # bumped by invalidate(): part of the upload signature
 
