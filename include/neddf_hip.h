@@ -79,9 +79,23 @@ enum { NEDDF_UV_F32 = 0, NEDDF_UV_I64 = 1, NEDDF_UV_I32 = 2, NEDDF_UV_I16 = 3,
         * neddf_sampling -- and neddf_render_rays, _single, _surface, _single_surface, _culled and _single_culled start from the same
         * copy; every later stage is the one the pixel types reach, and the stream contract is that of the call it rides in.
         * Refused, with a neddf_last_error message and nothing written: params->ndc_rays != 0 (NEDDF_EUNSUPPORTED: the NDC map needs
-        * a camera's focal lengths) and neddf_raygen_backward (NEDDF_EINVAL: there is no pose to differentiate).  Any uv_type
-        * outside 0..4 is NEDDF_EINVAL in all of these calls. */
+        * a camera's focal lengths) and neddf_raygen_backward (NEDDF_EINVAL: there is no pose to differentiate).  A uv_type
+        * is valid in all of these calls when it is 0..4, or 0..3 with NEDDF_UV_CAMERA_TABLE (below) OR-ed on; everything else --
+        * 5, a negative value, any other bit, the flag on NEDDF_UV_RAYS -- is NEDDF_EINVAL, and h_cam is not dereferenced. */
        NEDDF_UV_RAYS = 4 };
+/* OR-ed onto NEDDF_UV_F32 .. NEDDF_UV_I16 (additive to ABI v7): every row has its own camera.  h_cam then points to a HOST
+ * neddf_camera_table (cast to const neddf_camera *), which is read before the call returns; the arrays it names are DEVICE memory
+ * read on the stream, so the stream contract is that of the call it rides in.
+ *   neddf_raygen and the six neddf_render_rays* calls: row b carries the bits that the call gives for (uv[b], d_cameras[d_view[b]])
+ *     without the flag; every later stage is unchanged.  A row whose d_view[b] lies outside [0, n_cameras) reads no camera: its six
+ *     ray floats are quiet NaNs, which the fused calls report through nan_flag.
+ *   neddf_raygen_backward: d_g_RT is [n_cameras, 12] and EVERY row is written; row v carries the bits that the call gives without
+ *     the flag for camera v on the rows with d_view[b] == v, in batch order (+0.0 for a camera that owns no row; a row with an
+ *     invalid view belongs to no camera).  One launch, a fixed-order reduction per camera, no floating-point atomics.
+ * Refused with a neddf_last_error message before anything is written: the flag with h_cam == NULL, with a NULL array while
+ * n_rays > 0 or with n_cameras outside 1 .. 2^20 (NEDDF_EINVAL); the flag with params->ndc_rays != 0 (NEDDF_EUNSUPPORTED: the NDC
+ * map takes one camera's focal lengths). */
+enum { NEDDF_UV_CAMERA_TABLE = 0x100 };
 /* field output selection */
 enum { NEDDF_OUT_MINIMAL = 0,   /* density + color (+distance, aux_grad): what compositing consumes */
        NEDDF_OUT_FULL = 1 };    /* + fields_penalty: Jacobian through the colour trunk (neddf.py:243-300) */
@@ -118,6 +132,13 @@ typedef struct {
     float T[3];
     float calib[4];
 } neddf_camera;
+
+/* A camera per row (uv_type | NEDDF_UV_CAMERA_TABLE, above). */
+typedef struct {
+    const neddf_camera *d_cameras;   /* DEVICE [n_cameras] rows of 16 floats: R row-major, T, calib -- neddf_camera's own layout */
+    const int32_t      *d_view;      /* DEVICE [n_rays]: the camera of row b */
+    int32_t             n_cameras;   /* 1 .. 2^20 */
+} neddf_camera_table;
 
 /* NeRFRender constructor values (neddf/render/nerf_render.py:40-81). */
 typedef struct {
@@ -421,7 +442,7 @@ int neddf_sampling_backward(neddf_ctx *ctx, const float *d_g_pos, const float *d
                             void *stream);
 /* Backward of neddf_raygen with respect to the pose (Camera.create_rays camera.py:155-171: ray_dir = R c(uv), ray_orig = T):
  * d_g_RT[12] (DEVICE) = g_R [3][3] row-major = sum_b g_ray_dir[b] (x) c_b, then g_T [3] = sum_b g_ray_orig[b].  The intrinsics
- * are not differentiated. */
+ * are not differentiated.  With uv_type | NEDDF_UV_CAMERA_TABLE: d_g_RT[n_cameras][12], one such row per camera of the table. */
 int neddf_raygen_backward(neddf_ctx *ctx, const void *d_uv, int uv_type, int64_t n, const neddf_camera *cam, const float *d_g_ray_dir,
                           const float *d_g_ray_orig, float *d_g_RT, void *stream);
 /* Backward of integrate_volume_render (base_neural_render.py:148-171): gradients of weight [n_rays,S-1],

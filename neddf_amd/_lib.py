@@ -6,6 +6,7 @@ test infrastructure and is never imported from here.)
 """
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -24,6 +25,8 @@ STAGES = ("ddf", "col", "nerf", "raygen", "ndc", "sample_coarse", "sampling", "c
 COMM_ID_BYTES = 128
 UV_TYPES = {torch.float32: 0, torch.int64: 1, torch.int32: 2, torch.int16: 3}
 UV_RAYS = 4         # NEDDF_UV_RAYS: float32 [n, 6] rows of (direction, origin); never inferred from a dtype or a shape
+UV_CAMERA_TABLE = 0x100     # NEDDF_UV_CAMERA_TABLE: OR-ed onto a pixel type, a camera per row (ViewRays)
+MAX_CAMERAS = 1 << 20
 PENALTY_KEYS = ("constraints_aux_grad", "constraints_dDdt", "range_distance", "range_aux_grad",
                 "range_color", "constraints_color")     # dict order of neddf.py:260-291
 
@@ -37,11 +40,27 @@ class NeddfError(RuntimeError):
     pass
 
 
+class ViewRays(NamedTuple):
+    """Pixels with a camera per row, in place of (uv, camera): uv [n, 2] pixels, view int32 or int64 [n] the camera of row b,
+    table float32 [K, 16] the cameras (R row-major, T, calib: CameraDesc's layout).  Like a Ray it is named by the caller, never
+    guessed from shapes.  A row whose view lies outside [0, K) reads no camera and generates NaN rays."""
+    uv: torch.Tensor
+    view: torch.Tensor
+    table: torch.Tensor
+
+
 def _uv_arg(uv, bundle=False):
     """(contiguous device tensor, NEDDF_UV_* code) of a raygen / render_rays `uv` argument.  Pixels are typed by
     their dtype (UV_TYPES; anything else becomes float32).  A ray bundle is named by the caller, never guessed from a tensor's
     shape: either a Ray (neddf_amd.ray: ray_dir and ray_orig [n, 3], packed here) or, with bundle=True, a float32 [n, 6] tensor
-    of (direction, origin) rows."""
+    of (direction, origin) rows.  A ViewRays gives its pixels and their type with UV_CAMERA_TABLE set (_cam_arg takes the rest)."""
+    if isinstance(uv, ViewRays):
+        if bundle:
+            raise NeddfError("a ViewRays holds pixels, not a ray bundle")
+        t, code = _uv_arg(uv.uv)
+        if t.dim() != 2 or t.shape[1] != 2:
+            raise NeddfError("ViewRays: uv must be [n, 2]")
+        return t, code | UV_CAMERA_TABLE
     if hasattr(uv, "ray_dir") and hasattr(uv, "ray_orig"):
         rd, ro = uv.ray_dir, uv.ray_orig
         if rd.dim() != 2 or rd.shape[1] != 3 or ro.shape != rd.shape:
@@ -60,6 +79,27 @@ def _uv_arg(uv, bundle=False):
 
 
 def _cam_arg(cam, uv_type):
+    """The h_cam argument: a CameraDesc by reference, or under UV_CAMERA_TABLE the ViewRays itself, whose view and table become a
+    CameraTableDesc (the struct keeps the tensors it points to alive)."""
+    if uv_type & UV_CAMERA_TABLE:
+        if not isinstance(cam, ViewRays):
+            raise NeddfError("UV_CAMERA_TABLE needs a ViewRays")
+        n = cam.uv.shape[0]
+        view, table = cam.view, cam.table
+        require_device(view, "view")
+        require_device(table, "table")
+        if view.dtype not in (torch.int32, torch.int64) or view.dim() != 1 or view.shape[0] != n:
+            raise NeddfError("ViewRays: view must be int32 or int64 [n]")
+        if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 16 or not 1 <= table.shape[0] <= MAX_CAMERAS:
+            raise NeddfError("ViewRays: table must be float32 [K, 16] with 1 <= K <= 2^20")
+        if view.device != table.device or view.device != cam.uv.device:
+            raise NeddfError("ViewRays: uv, view and table must live on one device")
+        if view.dtype == torch.int64:       # every index beyond int32 is invalid anyway: keep it invalid through the narrowing
+            view = view.clamp(-1, 2 ** 31 - 1).to(torch.int32)
+        view, table = view.contiguous(), table.detach().contiguous()
+        desc = CameraTableDesc(table.data_ptr() or None, view.data_ptr() or None, table.shape[0])
+        desc._keep = (view, table)
+        return C.cast(C.pointer(desc), C.POINTER(CameraDesc))
     if cam is None:
         if uv_type != UV_RAYS:
             raise NeddfError("pixel coordinates need a camera descriptor")
@@ -77,6 +117,11 @@ class FieldDesc(C.Structure):
 
 class CameraDesc(C.Structure):
     _fields_ = [("R", C.c_float * 9), ("T", C.c_float * 3), ("calib", C.c_float * 4)]
+
+
+class CameraTableDesc(C.Structure):
+    """neddf_camera_table: a HOST struct naming DEVICE arrays (passed where a CameraDesc goes, under UV_CAMERA_TABLE)."""
+    _fields_ = [("d_cameras", _vp), ("d_view", _vp), ("n_cameras", C.c_int32)]
 
 
 class RenderParams(C.Structure):
@@ -349,12 +394,15 @@ class Context:
     # ------------------------------------------------------------------ stages
     def raygen(self, uv, cam=None, bundle=False):
         """uv: pixels [n, 2] with a camera descriptor, or a ray bundle (a Ray, or bundle=True with float32 [n, 6] rows of
-        (direction, origin); cam may be None): the bundle's rows come back bit for bit."""
+        (direction, origin); cam may be None): the bundle's rows come back bit for bit.  Or a ViewRays (cam is then not read):
+        row b carries the bits that (uv[b], table[view[b]]) gives through the one-camera call."""
+        if isinstance(uv, ViewRays):
+            cam = uv
         uv, uv_type = _uv_arg(uv, bundle)
         n = uv.shape[0]
         rd = torch.empty(n, 3, device=uv.device, dtype=torch.float32)
         ro = torch.empty_like(rd)
-        if n == 0 and uv_type == UV_RAYS:       # an empty bundle (the pointers of empty tensors are NULL)
+        if n == 0 and (uv_type == UV_RAYS or uv_type & UV_CAMERA_TABLE):    # an empty bundle or table batch (the pointers of empty tensors are NULL)
             return rd, ro
         self.check(self.lib.neddf_raygen(self.h, _ptr(uv), uv_type, n, _cam_arg(cam, uv_type), _ptr(rd), _ptr(ro),
                                          self.stream()))
@@ -891,6 +939,8 @@ class Context:
         outputs: dict name -> preallocated device tensor (subset of RenderOutputs fields, plus "normal" / "normal_coarse"
         [B, 3]: with either present the call goes through the *_surface entry points).  occupancy: an Occupancy struct whose
         bits live on this device -- the call goes through the *_culled entry points (empty-space skipping)."""
+        if isinstance(uv, ViewRays):        # a camera per row; cam is not read
+            cam = uv
         uv, uv_type = _uv_arg(uv, bundle)
         cam_ref = _cam_arg(cam, uv_type)
         ro = RenderOutputs()
@@ -1213,11 +1263,20 @@ class Context:
         return g_rd, g_ro
 
     def raygen_backward(self, uv, cam, g_ray_dir, g_ray_orig, bundle=False):
-        """Backward of `raygen` with respect to the pose: g_R [3, 3], g_T [3] (device tensors)."""
+        """Backward of `raygen` with respect to the pose: g_R [3, 3], g_T [3] (device tensors).  With a ViewRays (cam is then not
+        read): [K, 12], row v = (g_R row-major, g_T) of camera v over its own rows in batch order, zeros for a camera without rows."""
+        table = isinstance(uv, ViewRays)
+        if table:
+            cam = uv
         uv, uv_type = _uv_arg(uv, bundle)        # (a bundle is refused by the library: it has no pose)
         g_rd, g_ro = f32c(g_ray_dir), f32c(g_ray_orig)
         if g_rd.shape != (uv.shape[0], 3) or g_ro.shape != (uv.shape[0], 3):
             raise NeddfError("raygen_backward: ray gradients must be [B, 3]")
+        if table:
+            out = torch.empty(cam.table.shape[0], 12, device=uv.device, dtype=torch.float32)
+            self.check(self.lib.neddf_raygen_backward(self.h, _ptr(uv), uv_type, uv.shape[0], _cam_arg(cam, uv_type), _ptr(g_rd),
+                                                      _ptr(g_ro), _ptr(out), self.stream()))
+            return out
         out = torch.empty(12, device=uv.device, dtype=torch.float32)
         self.check(self.lib.neddf_raygen_backward(self.h, _ptr(uv), uv_type, uv.shape[0], _cam_arg(cam, uv_type), _ptr(g_rd),
                                                   _ptr(g_ro), _ptr(out), self.stream()))

@@ -18,7 +18,7 @@ from typing import Tuple
 import torch
 from torch import Tensor
 
-from ._lib import Context
+from ._lib import Context, ViewRays
 
 
 class FieldFunction(torch.autograd.Function):
@@ -185,3 +185,24 @@ class RayFunction(torch.autograd.Function):
         with torch.cuda.device(g_rd.device):
             g_R, g_T = ctx.hip.raygen_backward(ctx.saved_tensors[0], ctx.cam, g_rd, g_ro)
         return None, None, None, g_R, g_T
+
+
+class RayTableFunction(torch.autograd.Function):
+    """Ray generation with a camera per row (ViewRays) and every pose differentiable: (uv [B,2], view [B], table [K,16]) ->
+    (ray_dir, ray_orig) [B,3].  The gradient of `table` is [K,16]: columns 0..11 are (g_R row-major, g_T) of each camera over its
+    own rows, one launch for all cameras; columns 12..15 are zero, the intrinsics are not differentiated."""
+
+    @staticmethod
+    def forward(ctx, hip: Context, uv: Tensor, view: Tensor, table: Tensor):
+        rd, ro = hip.raygen(ViewRays(uv, view, table))
+        ctx.hip = hip
+        ctx.save_for_backward(uv, view, table)
+        return rd, ro
+
+    @staticmethod
+    def backward(ctx, g_rd, g_ro):
+        uv, view, table = ctx.saved_tensors
+        with torch.cuda.device(g_rd.device):
+            g = ctx.hip.raygen_backward(ViewRays(uv, view, table), None, g_rd, g_ro)
+        return None, None, None, torch.nn.functional.pad(g, (0, 4))
+

@@ -9,7 +9,7 @@ rays do not start at the camera centre, `unproject_local_origin`): Camera.create
 then builds the rays in torch and the renderer takes them as a ray bundle
 (NeRFRender.render_bundle).  OrthographicCalib is the one shipped.
 """
-from typing import Optional
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -179,3 +179,129 @@ class Camera(nn.Module):
         ctx = Context.get(self.device)
         rd, ro = ctx.raygen(uv, self.descriptor())
         return Ray(rd, ro, uv)
+
+
+def _hat_rows(v: Tensor) -> Tensor:
+    """_hat of every row: [K,3] -> [K,3,3]."""
+    z = torch.zeros_like(v[:, 0])
+    return torch.stack([torch.stack([z, -v[:, 2], v[:, 1]], 1), torch.stack([v[:, 2], z, -v[:, 0]], 1),
+                        torch.stack([-v[:, 1], v[:, 0], z], 1)], 1)
+
+
+def compose_poses(params: Tensor, R0: Tensor, T0: Tensor) -> Tuple[Tensor, Tensor]:
+    """Camera.update_transform for K cameras at once, differentiable with respect to `params`: params [K,6], R0 [K,3,3],
+    T0 [K,3] -> (R [K,3,3], T [K,3]).  The formula is update_transform's, term for term (its (1 - c) * ti * ti coefficient of
+    the translation map included, as the reference has it), and so is the choice between Rodrigues' form and the first-order
+    one at |rot| <= 1e-10.  Every camera starts at params == 0, so the unselected Rodrigues branch must stay finite there in the
+    BACKWARD too: its rows get a fixed unit axis in place of the zero vector before the norm and the reciprocal are taken (a
+    torch.where over 1 / theta alone would send 0 * inf = NaN into the gradient).  At a zero rotation the result carries
+    update_transform's bits (products with 0 and 1 are exact); elsewhere the two agree to rounding, not bit for bit."""
+    if params.dim() != 2 or params.shape[1] != 6 or R0.shape != (params.shape[0], 3, 3) or T0.shape != (params.shape[0], 3):
+        raise ValueError("compose_poses: params [K, 6], R0 [K, 3, 3] and T0 [K, 3] expected")
+    eye = torch.eye(3, dtype=params.dtype, device=params.device)[None]
+    rot, trans = params[:, 0:3], params[:, 3:6]
+    small = ~(torch.norm(rot.detach(), dim=1) > 1e-10)
+    axis = torch.zeros_like(rot)
+    axis[:, 0] = 1.0
+    safe = torch.where(small[:, None], axis, rot)
+    theta = torch.norm(safe, dim=1)
+    ti = 1.0 / theta
+    w = _hat_rows(ti[:, None] * safe)
+    ww = torch.matmul(w, w)
+    c, s = torch.cos(theta), torch.sin(theta)
+
+    def col(x: Tensor) -> Tensor:
+        return x[:, None, None]
+    Ri_big = eye + col(s) * w + col(1.0 - c) * ww
+    Vi_big = eye + col((1 - c) * ti * ti) * w + col((theta - s) * ti * ti * ti) * ww
+    Ri_small = eye + _hat_rows(rot)
+    Ri = torch.where(col(small), Ri_small, Ri_big)
+    Vi = torch.where(col(small), Ri_small, Vi_big)
+    R = torch.matmul(Ri, R0)
+    T = (torch.matmul(Vi, trans[:, :, None]) + torch.matmul(Ri, T0[:, :, None]))[:, :, 0]
+    return R, T
+
+
+class CameraSet:
+    """The cameras of a training set as one device-resident table: [K,16] rows of (R row-major, T, calib), what
+    NeRFRender.render_rays_views and the library's per-row-camera ray generation read.  The initial poses (one scipy call per
+    camera) and the intrinsics are stacked once; a table is then one batched pose composition (compose_poses) whatever K is.
+    Every camera must be a pinhole; the cameras' own R / T attributes are not touched (Camera.update_transform still owns them)."""
+
+    def __init__(self, cameras: Sequence[Camera]) -> None:
+        self.cameras: List[Camera] = list(cameras)
+        if not self.cameras:
+            raise ValueError("CameraSet: no cameras")
+        for camera in self.cameras:
+            if not isinstance(camera.camera_calib, PinholeCalib):
+                raise NotImplementedError("CameraSet: the camera table holds pinhole cameras; a %s makes its rays in create_rays"
+                                          % type(camera.camera_calib).__name__)
+        self.device = self.cameras[0].device
+        initial = np.stack([np.asarray(c.initial_params_np, dtype=np.float64).reshape(6) for c in self.cameras])
+        # (the same scipy call and fp32 rounding as Camera.R0 / Camera.T0, once)
+        self.R0 = torch.from_numpy(Rotation.from_rotvec(initial[:, :3]).as_matrix().astype(np.float32)).to(self.device)
+        self.T0 = torch.from_numpy(np.stack([np.asarray(c.initial_params_np)[3:6].astype(np.float32) for c in self.cameras])).to(self.device)
+        self._cached: Optional[Tensor] = None
+        self._key: Optional[tuple] = None
+        self.rebuilds = 0               # how often the cached table was composed (the cache's own test reads it)
+
+    def __len__(self) -> int:
+        return len(self.cameras)
+
+    def _state(self) -> tuple:
+        return tuple(c.params._version for c in self.cameras) + tuple(c.camera_calib.params._version for c in self.cameras)
+
+    def _calib(self, indices: Optional[Sequence[int]]) -> Tensor:
+        cams = self.cameras if indices is None else [self.cameras[i] for i in indices]
+        first = cams[0].camera_calib
+        if all(c.camera_calib is first for c in cams):      # one calib shared by every view, as the trainer builds them
+            return first.params.detach().to(torch.float32)[None, :].expand(len(cams), 4)
+        return torch.stack([c.camera_calib.params.detach().to(torch.float32) for c in cams])
+
+    def table(self, indices: Optional[Sequence[int]] = None, grad: bool = False) -> Tensor:
+        """[K,16] rows of the cameras `indices` (all of them: None), at their current `params`.  grad=False: no graph; the table
+        of all cameras is cached and composed again only after a camera's (or a calib's) parameters changed in place.  grad=True:
+        composed from torch.stack of the selected cameras' `params`, so each of them receives its own gradient through the table
+        and a camera that was not selected receives none."""
+        if indices is not None:
+            indices = [int(i) for i in indices]
+            for i in indices:
+                if not 0 <= i < len(self.cameras):
+                    raise ValueError("CameraSet: camera index %d outside [0, %d)" % (i, len(self.cameras)))
+            if not indices:
+                raise ValueError("CameraSet: an empty selection has no table")
+        if not grad:
+            key = self._state()
+            if self._cached is None or key != self._key:
+                with torch.no_grad():
+                    self._cached = self._compose(None)
+                self._key = key
+                self.rebuilds += 1
+            return self._cached if indices is None else self._cached[torch.as_tensor(indices, device=self.device)]
+        return self._compose(indices)
+
+    def _compose(self, indices: Optional[Sequence[int]]) -> Tensor:
+        cams = self.cameras if indices is None else [self.cameras[i] for i in indices]
+        params = torch.stack([c.params for c in cams])
+        if indices is None:
+            R0, T0 = self.R0, self.T0
+        else:
+            at = torch.as_tensor(indices, device=self.device)
+            R0, T0 = self.R0[at], self.T0[at]
+        R, T = compose_poses(params, R0, T0)
+        return torch.cat([R.reshape(-1, 9), T, self._calib(indices)], 1)
+
+    def select(self, view: Tensor) -> Tuple[List[int], Tensor]:
+        """A HOST view draw [B] -> (the cameras it visits, ascending; the draw renumbered to positions in that list, int32):
+        what table(visited, grad=True) and its rays need.  No device is read.  An index outside the set raises ValueError."""
+        self.check_view(view)
+        visited, local = torch.unique(view.to(torch.int64), sorted=True, return_inverse=True)
+        return visited.tolist(), local.to(torch.int32)
+
+    def check_view(self, view: Tensor) -> None:
+        """ValueError unless every entry of the HOST view draw names a camera of the set."""
+        if view.device.type != "cpu":
+            raise ValueError("CameraSet: the view draw is validated on the host (got a %s tensor)" % view.device.type)
+        if view.numel() and (int(view.min()) < 0 or int(view.max()) >= len(self.cameras)):
+            raise ValueError("CameraSet: view must lie in [0, %d)" % len(self.cameras))
+

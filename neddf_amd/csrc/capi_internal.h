@@ -163,6 +163,29 @@ static inline int fail(neddf_ctx *ctx, int code, const std::string &msg)
     return code;
 }
 
+// uv_type as the ray-generating calls take it (neddf_raygen, the six neddf_render_rays*, neddf_raygen_backward): an element type
+// 0..4, and under NEDDF_UV_CAMERA_TABLE (element types 0..3 only) h_cam is a HOST neddf_camera_table naming a camera per row.
+// Everything is checked here, before the caller writes anything.
+struct UvSpec {
+    int elem;                       // NEDDF_UV_F32 .. NEDDF_UV_RAYS
+    neddf::CameraTableArg table;    // cameras == nullptr: no table
+};
+static inline int parse_uv(neddf_ctx *ctx, int uv_type, int64_t n, const neddf_camera *cam, bool ndc, UvSpec *u)
+{
+    u->elem = uv_type & ~(int)NEDDF_UV_CAMERA_TABLE;
+    u->table = neddf::CameraTableArg{ nullptr, nullptr, 0 };
+    if (uv_type < 0 || u->elem > NEDDF_UV_RAYS) return fail(ctx, NEDDF_EINVAL, "bad uv_type");
+    if (!(uv_type & NEDDF_UV_CAMERA_TABLE)) return 0;
+    if (u->elem == NEDDF_UV_RAYS) return fail(ctx, NEDDF_EINVAL, "bad uv_type: NEDDF_UV_CAMERA_TABLE goes with the pixel types, a ray bundle has no camera");
+    if (!cam) return fail(ctx, NEDDF_EINVAL, "NEDDF_UV_CAMERA_TABLE: h_cam must point to a neddf_camera_table");
+    const neddf_camera_table *t = (const neddf_camera_table *)cam;
+    if (t->n_cameras < 1 || t->n_cameras > (1 << 20)) return fail(ctx, NEDDF_EINVAL, "NEDDF_UV_CAMERA_TABLE: n_cameras must be in 1 .. 2^20");
+    if (n > 0 && (!t->d_cameras || !t->d_view)) return fail(ctx, NEDDF_EINVAL, "NEDDF_UV_CAMERA_TABLE: d_cameras and d_view must not be NULL");
+    if (ndc) return fail(ctx, NEDDF_EUNSUPPORTED, "NEDDF_UV_CAMERA_TABLE: the NDC map takes one camera's focal lengths (ndc_rays must be 0)");
+    u->table = neddf::CameraTableArg{ (const float *)t->d_cameras, t->d_view, t->n_cameras };
+    return 0;
+}
+
 static inline int ensure(neddf_ctx *ctx, DevBuf &b, size_t bytes)
 {
     if (b.cap >= bytes && !(guard_mode() && b.cap != ((bytes + 15) & ~(size_t)15))) return 0;

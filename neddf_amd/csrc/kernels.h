@@ -173,6 +173,13 @@ struct NerfArgs {
 struct CameraArg {
     float R[9], T[3], calib[4];
 };
+// NEDDF_UV_CAMERA_TABLE: a camera per row.  cameras [n_cameras] rows of 16 floats in CameraArg's own layout, view [n] the camera
+// of row b -- both DEVICE memory.  cameras == nullptr: no table, the call has one camera (or a ray bundle).
+struct CameraTableArg {
+    const float *cameras;
+    const int32_t *view;
+    int32_t n_cameras;
+};
 
 size_t field_lds_bytes(int mt);
 void launch_ddf(const DdfArgs &a, int grid, hipStream_t s);
@@ -189,7 +196,9 @@ int nerf_wgs_per_cu(int width);
 int field_wgs_per_cu(int operands, int width);
 int col_wgs_per_cu(int operands, int width);
 
-void launch_raygen(const void *uv, int uv_type, int64_t n, const CameraArg &cam, float *dir, float *orig, hipStream_t s);
+// uv_type: the element type 0..4 (the table flag already taken off); with a table (element types 0..3) cam is not read
+void launch_raygen(const void *uv, int uv_type, int64_t n, const CameraArg &cam, const CameraTableArg &table, float *dir, float *orig,
+                   hipStream_t s);
 void launch_sample_coarse(const float *U, int64_t n, int S1, float near_, float far_, float *dists, hipStream_t s);
 void launch_sampling(const float *rd, const float *ro, const float *view, const float *dists, int64_t n, int S, double radius,
                      float *pos, float *dir, float *var, hipStream_t s);

@@ -435,10 +435,12 @@ static CameraArg cam_arg(const neddf_camera *c)
 int neddf_raygen(neddf_ctx *ctx, const void *uv, int uv_type, int64_t n, const neddf_camera *cam, float *rd, float *ro, void *stream)
 {
     if (!ctx || !uv || !rd || !ro) return NEDDF_EINVAL;
-    if (uv_type < 0 || uv_type > NEDDF_UV_RAYS) return fail(ctx, NEDDF_EINVAL, "bad uv_type");
-    if (!cam && uv_type != NEDDF_UV_RAYS) return NEDDF_EINVAL;
+    UvSpec u;
+    if (int rc = parse_uv(ctx, uv_type, n, cam, false, &u)) return rc;
+    if (!cam && u.elem != NEDDF_UV_RAYS) return NEDDF_EINVAL;
     DeviceGuard guard_(ctx->device);
-    STAGE(ctx, (hipStream_t)stream, NEDDF_STAGE_RAYGEN, launch_raygen(uv, uv_type, n, cam_arg(cam), rd, ro, (hipStream_t)stream));
+    STAGE(ctx, (hipStream_t)stream, NEDDF_STAGE_RAYGEN,
+          launch_raygen(uv, u.elem, n, cam_arg(u.table.cameras ? nullptr : cam), u.table, rd, ro, (hipStream_t)stream));
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -719,11 +721,12 @@ static int render_pass(neddf_ctx *ctx, int slot, const neddf_render_params *rp, 
     return 0;
 }
 
-// what the fused entry points ask of (uv_type, camera): a ray bundle (NEDDF_UV_RAYS) needs no camera and cannot be mapped to NDC
-static int check_uv(neddf_ctx *ctx, int uv_type, const neddf_camera *cam, const neddf_render_params *rp)
+// what the fused entry points ask of (uv_type, camera): a ray bundle (NEDDF_UV_RAYS) needs no camera and cannot be mapped to NDC,
+// and neither can a camera table (NEDDF_UV_CAMERA_TABLE)
+static int check_uv(neddf_ctx *ctx, int uv_type, int64_t B, const neddf_camera *cam, const neddf_render_params *rp, UvSpec *u)
 {
-    if (uv_type < 0 || uv_type > NEDDF_UV_RAYS) return fail(ctx, NEDDF_EINVAL, "bad uv_type");
-    if (uv_type != NEDDF_UV_RAYS) return cam ? 0 : NEDDF_EINVAL;
+    if (int rc = parse_uv(ctx, uv_type, B, cam, rp->ndc_rays != 0, u)) return rc;
+    if (u->elem != NEDDF_UV_RAYS) return cam ? 0 : NEDDF_EINVAL;
     if (rp->ndc_rays) return fail(ctx, NEDDF_EUNSUPPORTED, "NEDDF_UV_RAYS: the NDC map needs a camera's focal lengths (ndc_rays must be 0)");
     return 0;
 }
@@ -746,7 +749,8 @@ static int render_rays_body(neddf_ctx *ctx, const RenderCall &c, const void *uv,
     if (!ctx) return NEDDF_EINVAL;
     if (B <= 0) return 0;           // empty batch: nothing to do (pointers of empty tensors may be NULL)
     if (!uv || !rp || !c.Uc || !out || (c.two ? !c.Uf : c.S1 < 2)) return NEDDF_EINVAL;
-    if (int rc = check_uv(ctx, uv_type, cam, rp)) return rc;
+    UvSpec u;
+    if (int rc = check_uv(ctx, uv_type, B, cam, rp, &u)) return rc;
     auto refuse = [&](int code, const char *why, const char *more = "") { return fail(ctx, code, std::string(c.name) + why + more); };
     if (occ && !occ_ok(occ)) return refuse(NEDDF_EINVAL, ": the grid needs its bits and a resolution in [1, 1024]");
     if (occ && (out->fields_penalty || (c.two && out->fields_penalty_coarse)))
@@ -769,7 +773,7 @@ static int render_rays_body(neddf_ctx *ctx, const RenderCall &c, const void *uv,
     layout(Carver{ (char *)ctx->arena.p, ctx, s });
     int *nan_flag = out->nan_flag ? out->nan_flag : (int *)ctx->flags.p;
 
-    STAGE(ctx, s, NEDDF_STAGE_RAYGEN, launch_raygen(uv, uv_type, B, cam_arg(cam), w.rd, w.ro, s));
+    STAGE(ctx, s, NEDDF_STAGE_RAYGEN, launch_raygen(uv, u.elem, B, cam_arg(u.table.cameras ? nullptr : cam), u.table, w.rd, w.ro, s));
     float *d1 = c.two ? w.dc : w.df;        // the first draw
     RenderPass p{ w.rd, w.ro, nullptr, d1, B, Sc1, &w };
     if (rp->ndc_rays) {         // positions follow the NDC ray, the field keeps the world-space viewing direction

@@ -4,11 +4,13 @@
 //   enc_input_grad_kernel     dZ of the layers that read an encoding  ->  g_pos, g_dir, g_var [N, 3]
 //   sampling_backward_kernel  g_pos, g_dir, g_var [B, S, 3]           ->  g_ray_dir, g_ray_orig [B, 3]
 //   raygen_backward_kernel    g_ray_dir, g_ray_orig [B, 3]            ->  g_R [3, 3], g_T [3]
+//   raygen_table_backward_kernel   the same per camera of a camera table ->  [n_cameras] rows of g_R, g_T
 //
 // Operand policy: fp32 MFMA (v_mfma_f32_32x32x2_f32) for the products, whatever the field's policy; the C ABI refuses the
 // split-fp16 policy for these outputs rather than mixing the two.  Every reduction runs in a fixed order (LDS / wave trees, no
 // floating-point atomics): the outputs are bitwise repeatable.
 #include "train_kernels.h"
+#include "block_scan.h"
 #include "device_math.h"
 #include <math.h>
 
@@ -227,32 +229,33 @@ void launch_sampling_backward(const float *g_pos, const float *g_dir, const floa
 // the pixel (pinhole_calib.py:51-74; the intrinsics are not differentiated):
 //   g_R[i][j] = sum_b g_ray_dir[b][i] c_b[j]        g_T[i] = sum_b g_ray_orig[b][i]
 // One workgroup: every thread sums its rays b = tid, tid + 256, .. in order, then an LDS tree over the 256 partial sums.
+//
+// one ray's terms added to a thread's 12 partial sums (raygen_backward_kernel and raygen_table_backward_kernel)
 template <typename T>
-__global__ __launch_bounds__(256) void raygen_backward_kernel(const T *uv, int64_t n, CameraArg cam, const float *g_rd, const float *g_ro, float *out)
+__device__ __forceinline__ void raygen_backward_row(const T *uv, int64_t b, float fx, float fy, float cx, float cy, const float *g_rd,
+                                                    const float *g_ro, float (&acc)[12])
 {
-    __shared__ float red[12][256];
-    const int tid = threadIdx.x;
-    const float fx = cam.calib[0], fy = cam.calib[1], cx = cam.calib[2], cy = cam.calib[3];
-    float acc[12];
+    float u = 0.5f + 1.0f * (float)uv[2 * b + 0];
+    float v = 0.5f + 1.0f * (float)uv[2 * b + 1];
+    float x = (1.0f / fx) * (u - cx);
+    float y = (1.0f / fy) * (v - cy);
+    float c[3] = { x, -y, -1.0f };
+    float nrm = sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+    nrm = nrm < 1e-12f ? 1e-12f : nrm;
+    c[0] /= nrm; c[1] /= nrm; c[2] /= nrm;
 #pragma unroll
-    for (int k = 0; k < 12; ++k) acc[k] = 0.f;
-    for (int64_t b = tid; b < n; b += 256) {
-        float u = 0.5f + 1.0f * (float)uv[2 * b + 0];
-        float v = 0.5f + 1.0f * (float)uv[2 * b + 1];
-        float x = (1.0f / fx) * (u - cx);
-        float y = (1.0f / fy) * (v - cy);
-        float c[3] = { x, -y, -1.0f };
-        float nrm = sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-        nrm = nrm < 1e-12f ? 1e-12f : nrm;
-        c[0] /= nrm; c[1] /= nrm; c[2] /= nrm;
+    for (int i = 0; i < 3; ++i) {
+        const float gi = g_rd[3 * b + i];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float gi = g_rd[3 * b + i];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc[3 * i + j] += gi * c[j];
-            acc[9 + i] += g_ro[3 * b + i];
-        }
+        for (int j = 0; j < 3; ++j) acc[3 * i + j] += gi * c[j];
+        acc[9 + i] += g_ro[3 * b + i];
     }
+}
+
+// the tree over the 256 threads' partial sums; out[12] = g_R | g_T
+__device__ __forceinline__ void raygen_backward_tree(const float (&acc)[12], float (*red)[256], float *out)
+{
+    const int tid = threadIdx.x;
 #pragma unroll
     for (int k = 0; k < 12; ++k) red[k][tid] = acc[k];
     __syncthreads();
@@ -265,6 +268,19 @@ __global__ __launch_bounds__(256) void raygen_backward_kernel(const T *uv, int64
     if (tid < 12) out[tid] = red[tid][0];
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void raygen_backward_kernel(const T *uv, int64_t n, CameraArg cam, const float *g_rd, const float *g_ro, float *out)
+{
+    __shared__ float red[12][256];
+    const int tid = threadIdx.x;
+    const float fx = cam.calib[0], fy = cam.calib[1], cx = cam.calib[2], cy = cam.calib[3];
+    float acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) acc[k] = 0.f;
+    for (int64_t b = tid; b < n; b += 256) raygen_backward_row(uv, b, fx, fy, cx, cy, g_rd, g_ro, acc);
+    raygen_backward_tree(acc, red, out);
+}
+
 void launch_raygen_backward(const void *uv, int uv_type, int64_t n, const CameraArg &cam, const float *g_rd, const float *g_ro, float *out,
                             hipStream_t s)
 {
@@ -274,6 +290,59 @@ void launch_raygen_backward(const void *uv, int uv_type, int64_t n, const Camera
     case 1: hipLaunchKernelGGL(raygen_backward_kernel<int64_t>, g, b, 0, s, (const int64_t *)uv, n, cam, g_rd, g_ro, out); break;
     case 2: hipLaunchKernelGGL(raygen_backward_kernel<int32_t>, g, b, 0, s, (const int32_t *)uv, n, cam, g_rd, g_ro, out); break;
     default: hipLaunchKernelGGL(raygen_backward_kernel<int16_t>, g, b, 0, s, (const int16_t *)uv, n, cam, g_rd, g_ro, out); break;
+    }
+}
+
+// NEDDF_UV_CAMERA_TABLE: one workgroup per camera v = blockIdx.x, out[v][12] = what raygen_backward_kernel gives for camera v on
+// the rows with view[b] == v, taken in batch order -- the same bits, because every add happens in the same place: that kernel hands
+// the camera's k-th row to thread k mod 256, each thread adds its rows in increasing k, then the tree runs.  Here the batch is walked
+// in chunks of 256 rows; a lane whose row belongs to v has rank k = (rows of v in earlier chunks) + (rows of v at lower lanes of this
+// chunk) and drops its lane number into LDS slot k mod 256 -- the ranks of one chunk are at most 256 consecutive numbers, so no two
+// share a slot -- and after the barrier thread t adds the row in slot t, if any.  Chunks run in order, so every thread meets its
+// rows in increasing k.  No sort, no workspace, no atomic; a view outside [0, n_cameras) equals no blockIdx.x and belongs to no
+// camera; a camera without rows sums nothing and writes +0.0.  Every workgroup reads the whole view array: O(n_cameras * n) 4-byte
+// reads out of L2, nothing next to the field kernels at training sizes.
+template <typename T>
+__global__ __launch_bounds__(256) void raygen_table_backward_kernel(const T *uv, int64_t n, CameraTableArg table, const float *g_rd,
+                                                                    const float *g_ro, float *out)
+{
+    __shared__ float red[12][256];
+    __shared__ int slot[256];
+    __shared__ int waves[4];
+    const int tid = threadIdx.x;
+    const int32_t cam = (int32_t)blockIdx.x;            // < n_cameras: the grid is n_cameras workgroups
+    float fx = 1.f, fy = 1.f, cx = 0.f, cy = 0.f;
+    if (n > 0) {                                        // (an empty batch may come without a table to read)
+        const float *calib = table.cameras + 16 * (int64_t)cam + 12;
+        fx = calib[0]; fy = calib[1]; cx = calib[2]; cy = calib[3];
+    }
+    float acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) acc[k] = 0.f;
+    unsigned before = 0;                                // the camera's rows in earlier chunks, mod 2^32 (only mod 256 is used)
+    for (int64_t c0 = 0; c0 < n; c0 += 256) {
+        slot[tid] = -1;                                 // (this thread alone read slot[tid] in the last round)
+        const int64_t b = c0 + tid;
+        const bool mine = b < n && table.view[b] == cam;
+        const int rank = block_rank(mine, waves);       // barrier: every slot is cleared, the wave counts are in
+        if (mine) slot[(before + (unsigned)rank) & 255u] = tid;
+        before += (unsigned)(waves[0] + waves[1] + waves[2] + waves[3]);
+        __syncthreads();                                // the slots are filled; the wave counts are read
+        const int lane = slot[tid];
+        if (lane >= 0) raygen_backward_row(uv, c0 + lane, fx, fy, cx, cy, g_rd, g_ro, acc);
+    }
+    raygen_backward_tree(acc, red, out + 12 * (int64_t)cam);
+}
+
+void launch_raygen_table_backward(const void *uv, int uv_type, int64_t n, const CameraTableArg &table, const float *g_rd, const float *g_ro,
+                                  float *out, hipStream_t s)
+{
+    dim3 g((unsigned)table.n_cameras), b(256);
+    switch (uv_type) {
+    case 0: hipLaunchKernelGGL(raygen_table_backward_kernel<float>, g, b, 0, s, (const float *)uv, n, table, g_rd, g_ro, out); break;
+    case 1: hipLaunchKernelGGL(raygen_table_backward_kernel<int64_t>, g, b, 0, s, (const int64_t *)uv, n, table, g_rd, g_ro, out); break;
+    case 2: hipLaunchKernelGGL(raygen_table_backward_kernel<int32_t>, g, b, 0, s, (const int32_t *)uv, n, table, g_rd, g_ro, out); break;
+    default: hipLaunchKernelGGL(raygen_table_backward_kernel<int16_t>, g, b, 0, s, (const int16_t *)uv, n, table, g_rd, g_ro, out); break;
     }
 }
 

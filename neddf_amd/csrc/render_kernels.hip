@@ -14,11 +14,11 @@ namespace neddf {
 
 // ----------------------------------------------------------------------------
 // Camera.create_rays camera.py:155-171 (+ :173-187, pinhole_calib.py:51-74)
+// one ray: raygen_kernel (the call's camera, from the kernel arguments) and raygen_table_kernel (the row's camera, loaded from the
+// table) both run exactly these operations, so row b of either carries the same bits for the same (uv[b], camera)
 template <typename T>
-__global__ void raygen_kernel(const T *uv, int64_t n, CameraArg cam, float *ray_dir, float *ray_orig)
+__device__ __forceinline__ void raygen_row(const T *uv, int64_t b, const CameraArg &cam, float *ray_dir, float *ray_orig)
 {
-    int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= n) return;
     const float fx = cam.calib[0], fy = cam.calib[1], cx = cam.calib[2], cy = cam.calib[3];
     float u = 0.5f + 1.0f * (float)uv[2 * b + 0];
     float v = 0.5f + 1.0f * (float)uv[2 * b + 1];
@@ -35,6 +35,39 @@ __global__ void raygen_kernel(const T *uv, int64_t n, CameraArg cam, float *ray_
     }
 }
 
+template <typename T>
+__global__ void raygen_kernel(const T *uv, int64_t n, CameraArg cam, float *ray_dir, float *ray_orig)
+{
+    int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    raygen_row(uv, b, cam, ray_dir, ray_orig);
+}
+
+// NEDDF_UV_CAMERA_TABLE: row b takes camera view[b] of the table.  A view outside [0, n_cameras) is never turned into an address:
+// its row becomes six quiet NaNs, which the renderer's NaN flag reports.
+template <typename T>
+__global__ void raygen_table_kernel(const T *uv, int64_t n, CameraTableArg table, float *ray_dir, float *ray_orig)
+{
+    int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    const int32_t v = table.view[b];
+    if ((uint32_t)v >= (uint32_t)table.n_cameras) {
+        const float q = __builtin_nanf("");
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { ray_dir[3 * b + i] = q; ray_orig[3 * b + i] = q; }
+        return;
+    }
+    const float *row = table.cameras + 16 * (int64_t)v;
+    CameraArg cam;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) cam.R[i] = row[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) cam.T[i] = row[9 + i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cam.calib[i] = row[12 + i];
+    raygen_row(uv, b, cam, ray_dir, ray_orig);
+}
+
 // NEDDF_UV_RAYS: the caller's rays, rows of (direction xyz, origin xyz).  The words are moved as integers, so every bit
 // pattern -- NaN payloads, denormals, -0 -- arrives as it left; nothing is normalised.
 __global__ void raygen_bundle_kernel(const uint32_t *rays, int64_t n, uint32_t *ray_dir, uint32_t *ray_orig)
@@ -48,10 +81,20 @@ __global__ void raygen_bundle_kernel(const uint32_t *rays, int64_t n, uint32_t *
     }
 }
 
-void launch_raygen(const void *uv, int uv_type, int64_t n, const CameraArg &cam, float *dir, float *orig, hipStream_t s)
+void launch_raygen(const void *uv, int uv_type, int64_t n, const CameraArg &cam, const CameraTableArg &table, float *dir, float *orig,
+                   hipStream_t s)
 {
     if (n <= 0) return;
     dim3 g((unsigned)((n + 255) / 256)), b(256);
+    if (table.cameras) {
+        switch (uv_type) {
+        case 0: hipLaunchKernelGGL(raygen_table_kernel<float>, g, b, 0, s, (const float *)uv, n, table, dir, orig); break;
+        case 1: hipLaunchKernelGGL(raygen_table_kernel<int64_t>, g, b, 0, s, (const int64_t *)uv, n, table, dir, orig); break;
+        case 2: hipLaunchKernelGGL(raygen_table_kernel<int32_t>, g, b, 0, s, (const int32_t *)uv, n, table, dir, orig); break;
+        default: hipLaunchKernelGGL(raygen_table_kernel<int16_t>, g, b, 0, s, (const int16_t *)uv, n, table, dir, orig); break;
+        }
+        return;
+    }
     switch (uv_type) {
     case 4: hipLaunchKernelGGL(raygen_bundle_kernel, g, b, 0, s, (const uint32_t *)uv, n, (uint32_t *)dir, (uint32_t *)orig); break;
     case 0: hipLaunchKernelGGL(raygen_kernel<float>, g, b, 0, s, (const float *)uv, n, cam, dir, orig); break;

@@ -1082,8 +1082,14 @@ int neddf_raygen_backward(neddf_ctx *ctx, const void *uv, int uv_type, int64_t n
     // (no rays: the arrays of an empty batch may be null pointers -- the kernel reads none of them and writes zeros)
     if (uv_type == NEDDF_UV_RAYS) return fail(ctx, NEDDF_EINVAL, "raygen_backward: a ray bundle (NEDDF_UV_RAYS) has no pose to differentiate");
     if (!cam || !g_RT || n < 0 || (n > 0 && (!uv || !g_rd || !g_ro))) return fail(ctx, NEDDF_EINVAL, "raygen_backward: bad argument");
-    if (uv_type < 0 || uv_type > 3) return fail(ctx, NEDDF_EINVAL, "bad uv_type");
+    UvSpec u;
+    if (int rc = parse_uv(ctx, uv_type, n, cam, false, &u)) return rc;
     DeviceGuard guard_(ctx->device);
+    if (uv_type & NEDDF_UV_CAMERA_TABLE) {      // g_RT [n_cameras, 12]; an empty batch may come with NULL arrays and still zeroes every row
+        launch_raygen_table_backward(uv, u.elem, n, u.table, g_rd, g_ro, g_RT, (hipStream_t)stream);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
     CameraArg c;
     memcpy(c.R, cam->R, sizeof(c.R)); memcpy(c.T, cam->T, sizeof(c.T)); memcpy(c.calib, cam->calib, sizeof(c.calib));
     launch_raygen_backward(uv, uv_type, n, c, g_rd, g_ro, g_RT, (hipStream_t)stream);

@@ -282,5 +282,8 @@ void launch_sampling_backward(const float *g_pos, const float *g_dir, const floa
 // out[12] = g_R[9] (row-major) | g_T[3]
 void launch_raygen_backward(const void *uv, int uv_type, int64_t n, const CameraArg &cam, const float *g_rd, const float *g_ro, float *out,
                             hipStream_t s);
+// out[n_cameras][12]: row v as launch_raygen_backward writes it for camera v on that camera's rows in batch order; every row written
+void launch_raygen_table_backward(const void *uv, int uv_type, int64_t n, const CameraTableArg &table, const float *g_rd, const float *g_ro,
+                                  float *out, hipStream_t s);
 
 }  // namespace neddf

@@ -13,7 +13,7 @@ import os
 import torch
 from torch import Tensor, nn
 
-from ._lib import SLOT_COARSE, SLOT_FINE, Context, NeddfError, RenderParams
+from ._lib import SLOT_COARSE, SLOT_FINE, Context, NeddfError, RenderParams, ViewRays
 from .camera import Camera, PinholeCalib
 from .config import instantiate
 from .network import BaseNeuralField, NeDDF
@@ -245,9 +245,10 @@ class NeRFRender(BaseNeuralRender):
                 nan_group: int = 0, nan_group_offset: int = 0, normal: bool = False, occupancy=None, bundle: bool = False) -> Dict[str, Tensor]:
         """uv: pixels [B,2] of `camera` (or of the descriptor cam_desc), or a ray bundle -- a Ray, or with bundle=True float32
         [B,6] (direction, origin) rows -- which needs neither."""
-        B = len(uv) if isinstance(uv, Ray) else uv.shape[0]
-        dev = uv.device
-        if cam_desc is None and not bundle and not isinstance(uv, Ray):
+        views = isinstance(uv, ViewRays)        # a camera per row: the table travels inside `uv`
+        B = len(uv) if isinstance(uv, Ray) else uv.uv.shape[0] if views else uv.shape[0]
+        dev = uv.uv.device if views else uv.device
+        if cam_desc is None and not bundle and not views and not isinstance(uv, Ray):
             cam_desc = camera.descriptor()
         S2 = self.sample_coarse + self.sample_fine + 2
 
@@ -400,13 +401,53 @@ class NeRFRender(BaseNeuralRender):
                 return self._render_generated_rays(ctx, rd, ro, radius, U_c, U_f, ray_graph=ray_graph)
         return self._render_rays_fused(rays, None, B, dev)
 
+    def render_rays_views(self, uv: Tensor, view_index: Tensor, table: Tensor) -> Dict[str, Tensor]:
+        """render_rays on a batch in which every row has its own camera (not a reference method): row b is pixel uv[b] of the
+        camera in row view_index[b] of `table` (uv [B,2]; view_index int32 or int64 [B]; table float32 [K,16] rows of R row-major,
+        T, calib -- CameraSet.table builds them).  ONE ray-generation launch whatever K is, then render_bundle's stages, draws
+        and keys.  Inference is the fused call with the library's camera-table flag: no ray tensor is made.  Under autograd the
+        network parameters receive gradients as in render_rays, and with pose_gradients set and `table` requiring grad ray
+        generation is RayTableFunction: one backward launch fills the [K,16] gradient (intrinsics columns zero).  Nothing here
+        reads the device, so view_index is the caller's to validate (CameraSet.select / check_view on the host draw): a row
+        whose index lies outside [0, K) reads no camera and renders NaN, which the inference path's assertion reports."""
+        from .autograd import RayTableFunction
+        if self.ray_space == "ndc":
+            raise NotImplementedError("render_rays_views: NDC rays (ray_space='ndc') take one camera's focal lengths")
+        dev = table.device
+        uv = uv.to(dev)
+        view_index = torch.as_tensor(view_index).to(dev)
+        if view_index.dtype not in (torch.int32, torch.int64):
+            view_index = view_index.to(torch.int64)
+        if uv.dim() != 2 or uv.shape[1] != 2 or view_index.shape != (uv.shape[0],):
+            raise ValueError("render_rays_views: uv must be [B, 2] and view_index [B]")
+        if table.dim() != 2 or table.shape[1] != 16 or table.shape[0] < 1:
+            raise ValueError("render_rays_views: table must be [K, 16] with K >= 1")
+        B = uv.shape[0]
+        if torch.is_grad_enabled():
+            graph = bool(self.pose_gradients) and table.requires_grad
+            if graph or any(p.requires_grad for p in self.parameters()):
+                ctx = Context.get(dev)
+                p = self._params()
+                U_c, U_f = self._draw_pair(B, dev)
+                radius = p.ray_radius if p.cone_sampling else None
+                if graph:
+                    self._check_pose_fields()
+                    rd, ro = RayTableFunction.apply(ctx, uv, view_index, table.to(torch.float32))
+                else:
+                    with torch.no_grad():
+                        rd, ro = ctx.raygen(ViewRays(uv, view_index, table.detach().to(torch.float32)))
+                return self._render_generated_rays(ctx, rd, ro, radius, U_c, U_f, ray_graph=graph)
+        return self._render_rays_fused(ViewRays(uv, view_index, table.detach().to(torch.float32)), None, B, dev)
+
     def render_rays_mixed(self, uv: Tensor, view_index: Tensor, cameras: List[Camera]) -> Dict[str, Tensor]:
         """render_rays on a batch that mixes views (not a reference method): row b is pixel uv[b] of cameras[view_index[b]]
-        (uv [B,2], view_index int64 [B]).  Every camera that owns rows generates them, in batch order, with render_rays' own ray
-        generation -- one raygen launch per visited camera, RayFunction under pose_gradients so that its R / T receive gradients --
-        the rays go back to their batch positions and the batch runs as ONE bundle (render_bundle: its keys, draws and assertion).
-        A camera that owns no row costs nothing and gets no gradient; an index outside the list raises ValueError."""
-        from .autograd import RayFunction
+        (uv [B,2], view_index int64 [B]).  The visited cameras' R / T / intrinsics AS THEY STAND are stacked into a camera table
+        (under pose_gradients with their graph, so that each visited camera's R / T receive gradients) and the batch goes through
+        render_rays_views: one ray-generation launch and one backward launch whatever the number of views, no descriptor read.
+        Its keys, draws and assertion are render_bundle's, and every output carries the bits of generating each camera's rows
+        with render_rays' own ray generation.  A camera that owns no row costs nothing and gets no gradient; an index outside
+        the list raises ValueError (the one device -> host read).  If a VISITED camera is not a pinhole the batch takes the
+        per-camera route instead (_render_rays_mixed_per_camera): its rays are made in torch."""
         if self.ray_space == "ndc":
             raise NotImplementedError("render_rays_mixed: NDC rays (ray_space='ndc') are not supported")
         cameras = list(cameras)
@@ -423,6 +464,29 @@ class NeRFRender(BaseNeuralRender):
             lowest, *counts = torch.cat([view_index.min().view(1), torch.bincount(view_index.clamp(min=0), minlength=len(cameras))]).tolist()
             if lowest < 0 or len(counts) > len(cameras):
                 raise ValueError("render_rays_mixed: view_index must lie in [0, %d)" % len(cameras))
+        visited = [i for i, count in enumerate(counts) if count]
+        if not visited:
+            return self.render_bundle(Ray(torch.empty(0, 3, device=dev), torch.empty(0, 3, device=dev)))
+        if not all(_is_pinhole(cameras[i]) for i in visited):
+            return self._render_rays_mixed_per_camera(uv, view_index, cameras, counts)
+        graph = torch.is_grad_enabled() and bool(self.pose_gradients)
+        with torch.set_grad_enabled(graph):
+            table = torch.cat([torch.stack([cameras[i].R.to(torch.float32).reshape(9) for i in visited]),
+                               torch.stack([cameras[i].T.to(torch.float32) for i in visited]),
+                               torch.stack([cameras[i].camera_calib.params.detach().to(torch.float32) for i in visited])], 1)
+        local = view_index
+        if len(visited) != len(cameras):        # positions in the visited list
+            lut = torch.full((len(cameras),), -1, dtype=torch.int64)
+            lut[visited] = torch.arange(len(visited))
+            local = lut.to(dev)[view_index]
+        return self.render_rays_views(uv, local, table)
+
+    def _render_rays_mixed_per_camera(self, uv: Tensor, view_index: Tensor, cameras: List[Camera], counts: List[int]) -> Dict[str, Tensor]:
+        """render_rays_mixed where a visited camera is not a pinhole: every camera that owns rows generates them, in batch order,
+        with render_rays' own ray generation (a launch, or Camera.create_rays in torch, per visited camera), the rays go back to
+        their batch positions and the batch runs as one bundle."""
+        from .autograd import RayFunction
+        dev, B = uv.device, uv.shape[0]
         order = torch.argsort(view_index, stable=True)          # rows grouped by camera, batch order inside a group
         graph = torch.is_grad_enabled() and bool(self.pose_gradients)
         ctx = Context.get(dev)
@@ -443,8 +507,6 @@ class NeRFRender(BaseNeuralRender):
                     rd, ro = ctx.raygen(rows, camera.descriptor())
             dirs.append(rd)
             origs.append(ro)
-        if not dirs:
-            return self.render_bundle(Ray(torch.empty(0, 3, device=dev), torch.empty(0, 3, device=dev)))
         back = torch.empty_like(order)
         back[order] = torch.arange(B, device=dev)               # where batch row b stands in the grouped order
         return self.render_bundle(Ray(torch.cat(dirs)[back], torch.cat(origs)[back]))

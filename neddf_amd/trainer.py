@@ -11,7 +11,7 @@ from typing import Any, Dict, List
 import numpy as np
 import torch
 
-from .camera import Camera, OrthographicCalib, PinholeCalib
+from .camera import Camera, CameraSet, OrthographicCalib, PinholeCalib
 from .config import instantiate, to_plain
 from .dataset import imwrite_bgr
 from .logger import ScalarLog
@@ -50,6 +50,7 @@ class BaseTrainer:
         self.loss_functions = [instantiate(f).to(self.device) for f in _get(loss_cfg, "functions")]     # base_trainer.py:110-113
         self._gt_stacks: Dict[str, Any] = {}    # construct_ground_truth_mixed's device images, built on first use
         self._view_sizes = None                 # draw_mixed_batch's per-view (w - 1, h - 1)
+        self._camera_set = None                 # run_train_step_mixed's camera table (CameraSet), built on first use
 
     def use_orthographic_cameras(self, scale: float) -> None:
         """Replaces every view's camera by an orthographic one at the same pose (not in the reference): `scale` pixels per world
@@ -289,15 +290,28 @@ class NeRFTrainer(BaseTrainer):
         vs_int = (torch.rand(self.batch_size) * sizes[1][view]).to(torch.int16)
         return view, us_int, vs_int
 
+    def camera_set(self):
+        """The CameraSet of `cameras` (built once per camera list), or None where a camera is not a pinhole."""
+        held = self._camera_set
+        if held is None or held[0] is not self.cameras:
+            pinholes = all(isinstance(c.camera_calib, PinholeCalib) for c in self.cameras)
+            held = self._camera_set = (self.cameras, CameraSet(self.cameras) if pinholes else None)
+        return held[1]
+
     def run_train_step_mixed(self) -> float:
         """run_train_step on rays drawn across all views (not a reference method).  RNG draw order: draw_mixed_batch's three
-        draws (view, u, v), then render_rays_mixed's own (render_rays' [B,Sc+1] and [B,Sf+1]).  With optimize_cameras every view
-        the step visits receives a pose gradient; a view it does not visit has none (single rank) or is reset by the all-zero
-        rule below (several ranks)."""
+        draws (view, u, v), then the renderer's own (render_rays' [B,Sc+1] and [B,Sf+1]).  The cameras reach ray generation as a
+        device-resident table (CameraSet, NeRFRender.render_rays_views): no work per view on the host, one ray-generation launch.
+        Without optimize_cameras that is the cached table of all views.  With it the table is composed, with its graph, from the
+        parameters of the views the HOST draw visits: every view the step visits receives a pose gradient from one backward
+        launch; a view it does not visit has none (single rank) or is reset by the all-zero rule of _finish_step (several ranks).
+        Cameras that are not pinholes keep the per-camera route (render_rays_mixed)."""
         if self.logger is None:
             self.logger = ScalarLog() if self.writes_outputs else ScalarLog(sink="null")
-        for camera in self.cameras:
-            camera.update_transform()
+        cams = self.camera_set()
+        if cams is None:
+            for camera in self.cameras:
+                camera.update_transform()
         with self.logger.step() as rec:
             self.optimizer.zero_grad()
             view, us_int, vs_int = self.draw_mixed_batch()
@@ -305,7 +319,14 @@ class NeRFTrainer(BaseTrainer):
             targets = self.construct_ground_truth_mixed(view, us_int, vs_int, names)
             with torch.enable_grad():
                 uv = torch.stack([us_int, vs_int], 1).to(self.device)
-                rendered = self.neural_render.render_rays_mixed(uv, view.to(self.device), self.cameras)
+                if cams is None:
+                    rendered = self.neural_render.render_rays_mixed(uv, view.to(self.device), self.cameras)
+                elif self.optimize_cameras:
+                    visited, local = cams.select(view)      # (validated and renumbered on the host: the draw never left it)
+                    rendered = self.neural_render.render_rays_views(uv, local.to(self.device), cams.table(visited, grad=True))
+                else:
+                    cams.check_view(view)
+                    rendered = self.neural_render.render_rays_views(uv, view.to(self.device), cams.table())
                 loss_value = self._finish_step(rec, rendered, targets)
         return loss_value
 
@@ -325,9 +346,11 @@ class NeRFTrainer(BaseTrainer):
                 # the all-reduce hands every camera a gradient tensor, zeros for the views no rank visited; Adam would then step
                 # those too (a view visited once would keep drifting on its decaying first moment).  As in a single-rank run a
                 # view nobody visited has no gradient: same decision on every rank, since the averaged values are the same
-                for p in self.camera_parameters():
-                    if p.grad is not None and not bool(p.grad.any()):
-                        p.grad = None
+                held = [p for p in self.camera_parameters() if p.grad is not None]
+                if held:        # one device -> host read for all cameras
+                    for p, moved in zip(held, torch.stack([p.grad for p in held]).ne(0).any(dim=1).tolist()):
+                        if not moved:
+                            p.grad = None
             self.optimizer.step()
             mse = float(torch.mean(torch.square(rendered["color"].detach() - targets["color"])).item())
             loss_value = float(total.item())

@@ -3,15 +3,20 @@
 64 x 64 RGBA views on a ring around the origin), the shipped bunny_smoke network (65 coarse + 194 fine cone samples, fp32 operands),
 1024 rays, ColorLoss + MaskBCELoss + FieldsConstraintLoss.  A step is the whole run_train_step / run_train_step_mixed -- host draws, ground
 truth, forward, backward, Adam -- timed with the host clock between two device synchronises; per configuration `--warmup` steps, then
-the median of `--reps`.  Records, to profiles/mixed_batch_cost.json:
+the median of `--reps`.  Records, to profiles/view_table_cost.json (profiles/mixed_batch_cost.json is the record of the tree before the
+camera table and stays as it is):
 
     single_ms                   batch_views="single" on this tree, and with --parent PATH on that checkout of the parent commit (a child
-                                process that imports the package from PATH and runs this file's single-view timing)
-    mixed_ms[views][poses]      batch_views="mixed" over 1, 10 and 100 views, optimize_cameras off and on
-    image_ms                    render_image, 800 x 800, colour, rng="device": a pinhole camera through the uv path, and the same camera as
-                                a calib class that makes the same rays in torch (the bundle path)
+                                process that imports the package from PATH and runs this file's step timings)
+    mixed_ms[views][poses]      batch_views="mixed" over 1, 10 and 100 views, optimize_cameras off and on; under "parent" the same six
+                                from the parent checkout, in the same session
+    views_do_not_matter         the soft criterion: the 100-view fields-only median lies inside the min..max of the 1-view one
+    table_kernels_ms            the camera-table ray generation and its backward alone (device events around 20 launches) at
+                                (rays, cameras) = (1024, 100) and (65536, 1000)
+    image_ms                    with --images: render_image, 800 x 800, colour, rng="device": a pinhole camera through the uv path, and the
+                                same camera as a calib class that makes the same rays in torch (the bundle path)
 
-    python tools/time_mixed_batch.py [--parent PATH] [--rays 1024] [--reps 5] [--warmup 3]
+    python tools/time_mixed_batch.py [--parent PATH] [--rays 1024] [--reps 5] [--warmup 3] [--images]
 """
 import argparse
 import json
@@ -85,6 +90,46 @@ def time_single(args):
     return median_ms(lambda: tr.run_train_step(next(views) % 10), args.warmup, args.reps)
 
 
+def time_mixed(args):
+    out = {}
+    for n_views in (1, 10, 100):
+        row = out["%d_views" % n_views] = {}
+        for poses in (False, True):
+            tr = make_trainer(n_views, args.rays, batch_views="mixed", optimize_cameras=poses)
+            row["optimize_cameras" if poses else "fields_only"] = median_ms(tr.run_train_step_mixed, args.warmup, args.reps)
+            del tr
+    return out
+
+
+def time_table_kernels():
+    """The two camera-table launches alone: device events around 20 launches after a warm-up, ms per launch."""
+    import torch
+    from neddf_amd._lib import Context, ViewRays
+    dev = torch.device("cuda:0")
+    ctx = Context.get(dev)
+    gen = torch.Generator().manual_seed(5)
+    out = {}
+    for rays, cams in ((1024, 100), (65536, 1000)):
+        table = torch.rand(cams, 16, generator=gen).to(dev) + 0.5
+        uv = (torch.rand(rays, 2, generator=gen) * 63).to(torch.int16).to(dev)
+        view = (torch.rand(rays, generator=gen) * cams).to(torch.int32).to(dev)
+        g_rd, g_ro = torch.randn(rays, 3, generator=gen).to(dev), torch.randn(rays, 3, generator=gen).to(dev)
+        arg = ViewRays(uv, view, table)
+        row = out["%d_rays_%d_cameras" % (rays, cams)] = {}
+        for name, fn in (("raygen", lambda: ctx.raygen(arg)), ("raygen_backward", lambda: ctx.raygen_backward(arg, None, g_rd, g_ro))):
+            for _ in range(3):
+                fn()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            for _ in range(20):
+                fn()
+            b.record()
+            b.synchronize()
+            row[name] = a.elapsed_time(b) / 20
+    return out
+
+
 def time_images(args):
     import torch
     from torch import nn
@@ -123,40 +168,42 @@ def main():
     ap.add_argument("--rays", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--parent", default=None, help="a checkout of the parent commit, built: its single-view step is timed in a child process")
+    ap.add_argument("--parent", default=None, help="a checkout of the parent commit, built: its steps are timed in a child process")
     ap.add_argument("--tree", default=HERE, help="the checkout whose package is imported (default: this one)")
-    ap.add_argument("--single-only", action="store_true", help="time the single-view step, print it as JSON and stop (the --parent child)")
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "mixed_batch_cost.json"))
+    ap.add_argument("--steps-only", action="store_true", help="time the single-view and the mixed steps, print them as JSON and stop (the --parent child)")
+    ap.add_argument("--images", action="store_true", help="also time render_image through the uv path and as a bundle")
+    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "view_table_cost.json"))
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.tree))
     import torch
 
     import neddf_amd
     assert os.path.abspath(os.path.dirname(os.path.dirname(neddf_amd.__file__))) == os.path.abspath(args.tree), neddf_amd.__file__
-    if args.single_only:
-        print("SINGLE " + json.dumps(time_single(args)))
+    if args.steps_only:
+        print("STEPS " + json.dumps({"single_ms": time_single(args), "mixed_ms": time_mixed(args)}))
         return
     rec = {"workload": "training step (host draws, ground truth, forward, backward, Adam), %d rays x 259 samples, NeDDF fp32, shipped "
                        "bunny_smoke weights, %d x %d views; host clock between device synchronises" % (args.rays, SIZE, SIZE),
            "reps": args.reps, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
     rec["single_ms"] = {"this_tree": time_single(args)}
+    rec["mixed_ms"] = time_mixed(args)
     if args.parent:
-        child = subprocess.run([sys.executable, os.path.abspath(__file__), "--single-only", "--tree", os.path.abspath(args.parent), "--rays",
+        child = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps-only", "--tree", os.path.abspath(args.parent), "--rays",
                                 str(args.rays), "--reps", str(args.reps), "--warmup", str(args.warmup)], cwd=os.path.abspath(args.parent),
-                               capture_output=True, text=True, timeout=600)
-        lines = [l for l in child.stdout.splitlines() if l.startswith("SINGLE ")]
+                               capture_output=True, text=True, timeout=900)
+        lines = [l for l in child.stdout.splitlines() if l.startswith("STEPS ")]
         if child.returncode or not lines:
             raise SystemExit("the parent's timing failed:\n" + child.stdout[-2000:] + child.stderr[-2000:])
-        rec["single_ms"]["parent"] = json.loads(lines[-1][len("SINGLE "):])
-    rec["mixed_ms"] = {}
-    for n_views in (1, 10, 100):
-        row = rec["mixed_ms"]["%d_views" % n_views] = {}
-        for poses in (False, True):
-            tr = make_trainer(n_views, args.rays, batch_views="mixed", optimize_cameras=poses)
-            row["optimize_cameras" if poses else "fields_only"] = median_ms(tr.run_train_step_mixed, args.warmup, args.reps)
-            del tr
-    rec["image_ms"] = dict(time_images(args), what="render_image 800 x 800, colour, rng='device': the uv path against the same rays made in "
-                                                   "torch and rendered as a bundle")
+        parent = json.loads(lines[-1][len("STEPS "):])
+        rec["single_ms"]["parent"] = parent["single_ms"]
+        rec["mixed_ms"]["parent"] = parent["mixed_ms"]
+    one, hundred = rec["mixed_ms"]["1_views"]["fields_only"], rec["mixed_ms"]["100_views"]["fields_only"]
+    rec["views_do_not_matter"] = {"criterion": "fields only: the 100-view median inside the min..max of the 1-view step, same process",
+                                  "holds": one["min"] <= hundred["median"] <= one["max"]}
+    rec["table_kernels_ms"] = dict(time_table_kernels(), what="ray generation with a camera per row and its pose backward alone, ms per launch")
+    if args.images:
+        rec["image_ms"] = dict(time_images(args), what="render_image 800 x 800, colour, rng='device': the uv path against the same rays made "
+                                                       "in torch and rendered as a bundle")
     json.dump(rec, open(args.out, "w"), indent=1)
     print(json.dumps(rec))
 
